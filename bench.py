@@ -9,8 +9,14 @@ are resident in HBM (torch tensors, device-pointer C-ABI entry mcq_eval_batch_de
 rank evaluates its own shard and one RCCL all-reduce of the integer tally matrix closes the step (weak
 scaling: per-GPU work is fixed).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line; everything that takes runs of its own (the
+side configurations, the oracle spot check, the CPU baselines, the all-reduce timed alone) runs only with --full.
+--dump-outputs DIR writes the tally matrix of the last timed step (the [states, 13] mcq_result rows the path hands
+its caller, float64, exact) to DIR/tallies.npy; beyond 64 MB a fixed, seeded sample of its rows, whose indices go to
+DIR/tallies_rows.npy.  The inputs are fixed by the arguments, so two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
   roofline      VALU integer issue roofline of the evaluation kernel (this path is integer/branch work, neither
@@ -20,6 +26,8 @@ Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
                 on the launch stream inside the timed region; `frac` = achieved / the 2-cycle wave64 issue
                 peak, <= 1 by construction.  SURVEY 8(d)'s a-priori cost model is reported beside it as
                 `model` (it over-counts this kernel's instructions 2.3x, so it is not a fraction of anything)
+and with --full also
+  other_configs the side configurations (BASELINE configs[1]-[4], parity mode, ranges, exact, showdown, table driver)
   cpu_baseline  the oracle (a C port of tools/montecarlo_python.py, bit-exact to it) timed on this host
   parity_spot_check  rows of the LAST timed launch compared with the oracle (outside the timed region); a
                 mismatch makes the process exit non-zero
@@ -160,6 +168,23 @@ CONFIGS3 = {"states": 65536, "players": 6, "iters": 20000}
 METRIC = "Monte Carlo hand evals/sec @100k iters, 6-max preflop"
 METRIC_CONFIGS3 = ("Monte Carlo hand evals/sec, BASELINE configs[3]: 65 536 mixed flop/turn states x 6 players x 20k iters, "
                    "sharded over the GPUs, one tally all-reduce")
+DUMP_MAX_BYTES = 64 << 20
+SEED = 20261004  # step i of a run (warm-up steps first) runs on seed SEED + i
+
+
+def dump_outputs(out_dir, t):
+    """--dump-outputs: the last timed step's tally matrix t ([rows, 13] uint64) as DIR/tallies.npy in float64 (the
+    counts are far below 2^53, so exact); above DUMP_MAX_BYTES a fixed, seeded sample of the rows, their indices in
+    DIR/tallies_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    t = np.asarray(t)
+    row_bytes = t.shape[1] * 8
+    if t.nbytes > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 4096) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(len(t), keep, replace=False))
+        np.save(os.path.join(out_dir, "tallies_rows.npy"), rows.astype(np.float64))
+        t = t[rows]
+    np.save(os.path.join(out_dir, "tallies.npy"), t.astype(np.float64))
 
 
 def cpu_baseline(n_players, runs, seconds=12.0, threads=None):
@@ -250,7 +275,7 @@ def native_multi(args):
     d_q = [torch.from_numpy(raw[B * s // k:B * (s + 1) // k].copy()).to("cuda:%d" % d) for s, d in enumerate(devices)]
     d_res = [torch.zeros((B, 13), dtype=torch.int64, device="cuda:%d" % d) for d in devices]
     qp, rp = [t.data_ptr() for t in d_q], [t.data_ptr() for t in d_res]
-    seed = 20261004
+    seed = SEED
 
     def fence():
         for d in set(devices):
@@ -271,6 +296,8 @@ def native_multi(args):
     t = d_res[0].cpu().numpy().view(np.uint64)
     assert (t[:, 0] == runs).all() and np.array_equal(t[:, 2] + t[:, 3], t[:, 4:].sum(1))
     assert all(torch.equal(d_res[0].cpu(), r.cpu()) for r in d_res[1:]), "the shards' matrices differ after the all-reduce"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, t)
     evals = float(B) * runs * N
     info = me.info
     kernel_ms = float(np.mean(kmax))
@@ -324,9 +351,15 @@ def main():
                     help="headline: --states preflop states PER GPU x 6 players x 100k iterations (weak scaling). configs3: "
                          "BASELINE configs[3], 65 536 flop/turn states x 6 players x 20k iterations IN ALL, block-sharded over "
                          "the --gpus ranks (strong scaling), one all-reduce of the [65536,13] tally matrix")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run what takes runs of its own: the side configurations "
+                    "(other_configs), the oracle spot check of the last timed launch, the CPU baselines, the all-reduce "
+                    "timed alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no spot check, no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no side configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's tally matrix to DIR/tallies.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.workload == "configs3":
         args.players, args.iters = CONFIGS3["players"], CONFIGS3["iters"]
 
@@ -388,7 +421,7 @@ def main():
     tallies = torch.zeros((total, 13), dtype=torch.int64, device=dev)  # mcq_result rows of the whole job
     mine = tallies[first_qid:first_qid + B]
     stream = torch.cuda.current_stream()
-    seed = 20261004
+    seed = SEED
 
     def step(i):
         if grouped:
@@ -426,9 +459,11 @@ def main():
     t = tallies.cpu().numpy().view(np.uint64)
     assert (t[:, 0] == runs).all(), "runs column wrong"
     assert np.array_equal(t[:, 2] + t[:, 3], t[:, 4:].sum(1)), "sum(by_type) != win + tie"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, t)
 
     ar_ms = None
-    if grouped and args.backend == "nccl":   # the collective alone (outside the timed region): same key as --native-multi
+    if args.full and grouped and args.backend == "nccl":   # the collective alone (outside the timed region): same key as --native-multi
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(5):
@@ -492,7 +527,7 @@ def main():
         out["collective"] = {"all_reduce_ms": ar_ms, "bytes": total * 104, "ranks": world,
                              "backend": "RCCL (torch.distributed nccl)" if args.backend == "nccl" else args.backend}
     side_counters = (profile_counters()[0] or {}).get("side_kernels", {})  # PMC passes of tools/side_kernels.py's workloads
-    if world == 1 and not args.no_extras and not configs3:  # single-GPU side measurements; never delay the other ranks' teardown
+    if args.full and world == 1 and not args.no_extras and not configs3:  # single-GPU side measurements; never delay the other ranks' teardown
         extras = {}
 
         def side_measurements():  # a failure here must never cost the headline line
@@ -733,7 +768,7 @@ def main():
             extras["error"] = "%s: %s" % (type(e).__name__, e)
         out["other_configs"] = extras
     spot_ok = True
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             # Parity spot check of the LAST TIMED launch: its rows are still in `tallies`; the oracle (MCQ-CTR mode:
             # the same specification as the production kernel, montecarlo_python.py:223-250 for what a row means)

@@ -948,13 +948,48 @@ def test_bench_rccl_branch_runs_on_this_gpu():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
                           "--gpus", "1", "--steps", "2", "--warmup", "1", "--states", "256", "--iters", "3000",
-                          "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, cwd=root)
+                          "--full", "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [x for x in out.stdout.splitlines() if x.startswith("{")]
     assert len(line) == 1, out.stdout
     d = _json.loads(line[0])
     assert d["n_gpus"] == 1 and "RCCL all-reduce" in d["config"]["workload"] and d["value"] > 0
     assert d["collective"]["ranks"] == 1 and d["collective"]["all_reduce_ms"] > 0 and "roofline" in d
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py` run (no --full) prints the contract's keys and nothing that takes runs of its own;
+    --dump-outputs writes the last timed step's tally matrix, the same in two runs with the same arguments and equal,
+    row for row, to the oracle's MCQ-CTR tallies of that step's seed."""
+    import json as _json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup, states, iters = 3, 2, 256, 3000
+    dumps = []
+    for k in range(2):
+        d_out = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                              "--warmup", str(warmup), "--states", str(states), "--iters", str(iters),
+                              "--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = [x for x in out.stdout.splitlines() if x.startswith("{")]
+        assert len(line) == 1, out.stdout
+        d = _json.loads(line[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0 and d["value"] > 0
+        assert not {"other_configs", "parity_spot_check", "cpu_baseline"} & set(d), sorted(d)
+        assert sorted(os.listdir(d_out)) == ["tallies.npy"]
+        t = np.load(d_out / "tallies.npy")
+        assert t.dtype == np.float64 and t.shape == (states, 13)
+        dumps.append(t)
+    assert np.array_equal(dumps[0], dumps[1])
+    hole, board = bench.make_states(states, 0)
+    raw = npa.pack_queries(hole, board, 6, iters).view(np.uint8).reshape(states, 16)
+    exp = O.run_batch(O.MODE_CTR, raw, bench.SEED + warmup + steps - 1, 0)
+    assert np.array_equal(dumps[0], exp.astype(np.float64))
 
 
 def test_bench_native_multi_prints_the_same_keys():

@@ -186,19 +186,23 @@ def test_uniform_law_exact_and_reference_cpp_expectations():
 
 
 def test_reference_cpp_agrees_with_uniform_law():
-    """oracle/_ref/ref_mc is the reference's own C++ variant compiled from /root/reference (make -C oracle ref);
-    it shuffles uniformly, so it must estimate the exact UNIFORM expectation (and not the Python law's)."""
+    """The reference's own C++ variant shuffles uniformly, so it must estimate the exact UNIFORM expectation (and
+    not the Python law's).  tests/golden/ref_cpp_equity.json holds recorded runs of it (oracle/ref_driver.cpp);
+    where `make -C oracle ref` has built oracle/_ref/ref_mc from the reference's sources, one live run as well."""
     import subprocess
-    exe = os.path.join(os.path.dirname(O.__file__), "_ref", "ref_mc")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref/ref_mc not built (needs /root/reference)")
-    hero, board = ["TC", "TH"], ["4D", "QD", "KC", "2S"]
-    w, t, _ = O.exact(hero, board, 2, uniform=True)
-    out = subprocess.run([exe, "equity", hero[0], hero[1], "2", "40000"] + board, capture_output=True, text=True,
-                         check=True).stdout.split()
-    eq = float(out[0])
+    row = jload("ref_cpp_equity.json")
+    hero, board, runs = row["hero"], row["board"], row["iterations"]
+    w, t, _ = O.exact(hero, board, row["n_players"], uniform=True)
     p = w + t
-    assert abs(eq - p) < 5 * (p * (1 - p) / 40000) ** 0.5, (eq, p)
+    estimates = list(row["equity"])
+    exe = os.path.join(os.path.dirname(O.__file__), "_ref", "ref_mc")
+    if os.path.exists(exe):
+        out = subprocess.run([exe, "equity", hero[0], hero[1], str(row["n_players"]), str(runs)] + board,
+                             capture_output=True, text=True, check=True).stdout.split()
+        estimates.append(float(out[0]))
+    assert len(estimates) >= 3
+    for eq in estimates:
+        assert abs(eq - p) < 5 * (p * (1 - p) / runs) ** 0.5, (eq, p)
 
 
 def _ext_range(row):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # On the GPU box: the round's evidence in one go -> gpurun_out/<TAG>_*  (copy what is to be judged into profiles/)
 TAG=${1:-rXX}; O=gpurun_out; mkdir -p $O
-timeout -k 10 300 python bench.py > $O/${TAG}_bench_full.json 2> $O/${TAG}_bench_full.err; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full > $O/${TAG}_bench_full.json 2> $O/${TAG}_bench_full.err; echo "bench rc=$?"
 timeout -k 10 200 python tools/small_probe.py > $O/${TAG}_small_probe.txt 2>&1; echo "small rc=$?"
 timeout -k 10 200 python tools/ext_probe.py > $O/${TAG}_ext_speed.txt 2>&1; echo "ext rc=$?"
 timeout -k 10 100 python tools/ext_latency_probe.py > $O/${TAG}_ext_latency.txt 2>&1; echo "extlat rc=$?"

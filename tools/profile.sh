@@ -24,7 +24,7 @@ rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/spmc2 -o p
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/spmc3 -o p -- $S > $OUT/spmc3.log 2>&1 || exit 1
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE SQ_LDS_IDX_ACTIVE --output-format csv -d $OUT/spmc4 -o p -- $S > $OUT/spmc4.log 2>&1 || exit 1
 # the side configurations (configs[1]-[4], parity mode, multi-GPU entry, table driver) under the kernel trace
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_extras -o p -- python3 $R/bench.py --no-cpu-baseline --steps 3 --warmup 1 > $OUT/kt_extras.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_extras -o p -- python3 $R/bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > $OUT/kt_extras.log 2>&1 || exit 1
 python3 - <<PY
 import csv, collections, glob, json, re, sys
 sys.path.insert(0, "$R")
