@@ -31,7 +31,7 @@ extern "C" {
 #endif
 
 #define MCQ_VERSION_MAJOR 0
-#define MCQ_VERSION_MINOR 3
+#define MCQ_VERSION_MINOR 4
 #define MCQ_VERSION_PATCH 0
 
 /* error codes */
@@ -192,6 +192,30 @@ MCQ_API int mcq_eval_batch_part(mcq_ctx *ctx, const mcq_query *q, size_t n, uint
  * the outcomes (integers; equity = (win + tie) / runs exactly), passes = 0.  Preflop heads-up = 2.1e9 hand
  * evaluations, three players preflop = 1.2e12 pair comparisons. */
 MCQ_API int mcq_exact_batch(mcq_ctx *ctx, const mcq_query *q, size_t n, int law, mcq_result *out);
+
+/* Exact enumeration of EXTENDED queries (SURVEY 8f-3 with 8f-2): hand against hand(s), ghost cards, opponents holding a
+ * range.  Accepted: hero given as two cards, 0..9 further known hands each given as two cards (is_range == 0), optional
+ * ghost cards, 0, 1 or 2 random opponents (n_players - 1 - n_known) drawn from opp_range, both laws.  Refused with
+ * MCQ_EINVAL, nothing launched: whatever mcq_eval_batch_ext refuses, hero_is_range, a known hand given as a range, more
+ * than two random opponents, and a range that cannot be dealt on some branch of positive probability.  A hero range (an
+ * outer sum over the hero's hands: out of reach preflop) and ranged known hands (the reference's pop-by-value quirk,
+ * montecarlo_python.py:154-161) are left out on purpose.
+ * MCQ_LAW_REFERENCE: every ordered pair (A, B) of the current deck is equally likely provided A != B, B is not the
+ * deck's highest card and class(A, B) is allowed; A is dealt, then B if B < A, else the card that follows B
+ * (montecarlo_python.py:165-181); a table card is never the highest card left.  MCQ_LAW_UNIFORM: every allowed
+ * unordered hand still in the deck and every table completion equally likely.
+ * prob[i] is always filled.  weights (may be NULL) gets integer weights as mcq_exact_batch writes them (runs = total
+ * weight, passes = 0, prob = weight / runs) whenever one common total exists: without a range, or with at most one
+ * random opponent.  With a range and two random opponents the second opponent's normaliser depends on the first
+ * opponent's hand; that row of weights is zeroed.  Deterministic: sums in integers per first opponent hand, combined
+ * on the host in a fixed order.  A record that restricts nothing gives mcq_exact_batch's weights bit for bit. */
+typedef struct mcq_exact_prob {
+    double win;        /* P(hero strictly best) */
+    double tie;        /* P(hero best together with at least one other hand; credited to hero, as the reference does) */
+    double by_type[9]; /* P(hero wins or ties holding hand type t); sums to win + tie */
+} mcq_exact_prob;      /* 88 bytes */
+MCQ_API int mcq_exact_batch_ext(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                                mcq_exact_prob *prob, mcq_result *weights);
 
 /* Select the dealing law used by MCQ_MODE_PHILOX on this context (MCQ_LAW_*). */
 MCQ_API int mcq_set_dealing_law(mcq_ctx *ctx, int law);

@@ -28,7 +28,8 @@ TABLES_CONFIG_DTYPE = np.dtype([("n_tables", "<u4"), ("n_seats", "<u4"), ("runs"
                                 ("initial_stacks", "<f8"), ("small_blind", "<f8"), ("big_blind", "<f8"),
                                 ("seed", "<u8"), ("seat_kind", "u1", (10,)), ("reserved", "u1", (6,)),
                                 ("min_call_equity", "<f8", (10,)), ("min_bet_equity", "<f8", (10,))])
-assert TABLES_CONFIG_DTYPE.itemsize == 224
+EXACT_PROB_DTYPE = np.dtype([("win", "<f8"), ("tie", "<f8"), ("by_type", "<f8", (9,))])
+assert TABLES_CONFIG_DTYPE.itemsize == 224 and EXACT_PROB_DTYPE.itemsize == 88
 assert QUERY_DTYPE.itemsize == 16 and RESULT_DTYPE.itemsize == 104 and QUERY_EXT_DTYPE.itemsize == 304
 ALL_CLASSES = np.array([0xFFFFFFFF] * 5 + [0x1FF], np.uint32)  # 169 bits
 
@@ -106,6 +107,8 @@ def load_library():
         L.mcq_showdown.restype = C.c_int
         L.mcq_exact_batch.argtypes = [vp, vp, sz, C.c_int, vp]
         L.mcq_exact_batch.restype = C.c_int
+        L.mcq_exact_batch_ext.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
+        L.mcq_exact_batch_ext.restype = C.c_int
         L.mcq_set_dealing_law.argtypes = [vp, C.c_int]
         L.mcq_set_dealing_law.restype = C.c_int
         L.mcq_set_kernel_timing.argtypes = [vp, C.c_int]
@@ -322,6 +325,25 @@ class Engine:
         if rc:
             _raise(rc)
         return out
+
+    def exact_ext(self, queries, ext, law="reference"):
+        """Exact enumeration of extended queries (mcq_exact_batch_ext: further known hands, ghost cards, an opponent range;
+        at most two random opponents).  -> (prob, weights): EXACT_PROB_DTYPE rows (win, tie, by_type) and RESULT_DTYPE
+        rows of integer weights -- zeroed for a query with a range and two random opponents (no common total)."""
+        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
+        if code is None:
+            raise ValueError("law must be 'reference' or 'uniform'")
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        prob = np.zeros(len(q), EXACT_PROB_DTYPE)
+        weights = np.zeros(len(q), RESULT_DTYPE)
+        rc = self._lib.mcq_exact_batch_ext(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, prob.ctypes.data,
+                                           weights.ctypes.data)
+        if rc:
+            _raise(rc)
+        return prob, weights
 
     def eval_batch_ext(self, queries, ext, seed, first_query_id=0, mode=MODE_PHILOX):
         """queries with one QUERY_EXT_DTYPE record each (ranges, hero range, ghost cards, second known hand)."""

@@ -18,6 +18,7 @@
 
 #include "mcq_ctx.hpp"
 #include "mcq_device.hpp"
+#include "mcq_exact_ext.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt_blocks.hpp"
 #include "mcq_replay.hpp"
@@ -1183,6 +1184,90 @@ int mcq_exact_batch(mcq_ctx *c, const mcq_query *q, size_t n, int law, mcq_resul
     memcpy(out, c->h_res.p, n * sizeof(mcq_result));
     return MCQ_OK;
     ABI_GUARD_END("mcq_exact_batch")
+}
+
+int mcq_exact_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, mcq_exact_prob *prob,
+                        mcq_result *weights) {
+    ABI_GUARD_BEGIN
+    static const char *who = "mcq_exact_batch_ext";
+    if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
+    if (n == 0) return MCQ_OK;
+    if (!q || !ext || !prob) return mcq_fail(MCQ_EINVAL, who, "null buffer");
+    if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return mcq_fail(MCQ_EINVAL, who, "bad law");
+    if (n > 65535u) return mcq_fail(MCQ_EINVAL, who, "at most 65535 queries per call");
+    /* validation first: nothing is launched for a batch with one query that cannot be enumerated */
+    std::vector<McqExactExtQuery> xq(n);
+    std::vector<uint8_t> rid(n * 64u);
+    uint64_t h1_words = 0;
+    for (size_t i = 0; i < n; i++) {
+        const McqExtRec er = {reinterpret_cast<const uint32_t *>(&ext[i])};
+        const int why = mcq_exact_ext_query(mcq_query_words(q[i]), er, law, xq[i]);
+        char buf[200];
+        if (why != MCQ_XX_OK) {
+            static const char *const reason[] = {
+                "", "invalid extended query (as mcq_eval_batch_ext: distinct card ids < 52, at most 9 known hands, used ranges not empty)",
+                "a hero range is not enumerated (rotate a known hand into the hero's seat)",
+                "a known hand given as a range is not enumerated", "at most two random opponents"};
+            snprintf(buf, sizeof buf, "query %zu: %s", i, reason[why]);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+        mcq_exact_ext_r_ids(xq[i], &rid[64u * i]);
+        if (!mcq_exact_ext_dealable(xq[i], &rid[64u * i])) {
+            snprintf(buf, sizeof buf, "query %zu: the opponents' range cannot be dealt from the remaining cards", i);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+        if (xq[i].b.n_opp == 2u) h1_words += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
+    }
+    MCQ_ENTER(c, who);
+    McqDeviceScope dev_(c->device);
+    HIP_TRY(dev_.err);
+    HIP_TRY(c->d_res.reserve(n * sizeof(mcq_result)));
+    c->res_clean = 0;
+    HIP_TRY(c->h_res.reserve(n * sizeof(mcq_result) + h1_words * 8u));
+    HIP_TRY(hipMemsetAsync(c->d_res.p, 0, n * sizeof(mcq_result), c->stream));
+    /* the per-first-hand sums of the two-opponent queries: the parity mode's draw buffer is free during this call */
+    if (h1_words) {
+        HIP_TRY(c->d_draws.reserve(h1_words * 8u));
+        HIP_TRY(hipMemsetAsync(c->d_draws.p, 0, h1_words * 8u, c->stream));
+    }
+    /* jobs and extension records travel in pinned memory, the jobs grouped by kind */
+    const size_t job_bytes = (n * sizeof(McqExactExtJob) + 255u) & ~(size_t)255u;
+    HIP_TRY(c->h_misc.reserve(job_bytes + n * sizeof(mcq_query_ext)));
+    McqExactExtJob *jobs = static_cast<McqExactExtJob *>(c->h_misc.p);
+    const McqExactExtJob *d_jobs = static_cast<const McqExactExtJob *>(c->h_misc.dev);
+    memcpy(static_cast<uint8_t *>(c->h_misc.p) + job_bytes, ext, n * sizeof(mcq_query_ext));
+    const uint32_t *d_ext = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(c->h_misc.dev) + job_bytes);
+    std::vector<uint64_t> h1_off(n, 0);
+    size_t at = 0;
+    uint64_t off = 0;
+    for (uint32_t kind = 0; kind < 3u; kind++) {
+        const size_t first = at;
+        uint32_t max_grid = 0;
+        for (size_t i = 0; i < n; i++) {
+            if (xq[i].b.n_opp != kind) continue;
+            h1_off[i] = off;
+            const uint32_t g = mcq_exact_ext_plan(&q[i], (uint32_t)i, (uint32_t)i, kind, xq[i].b.L, (uint32_t)off,
+                                                  (uint32_t)c->n_cu, &jobs[at++]);
+            max_grid = g > max_grid ? g : max_grid;
+            if (kind == 2u) off += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
+        }
+        HIP_TRY(mcq_launch_exact_ext(d_jobs + first, (uint32_t)(at - first), max_grid, kind, d_ext, law, (mcq_result *)c->d_res.p,
+                                     (unsigned long long *)c->d_draws.p, c->d_luts, c->stream));
+    }
+    uint8_t *hr = static_cast<uint8_t *>(c->h_res.p);
+    HIP_TRY(hipMemcpyAsync(hr, c->d_res.p, n * sizeof(mcq_result), hipMemcpyDeviceToHost, c->stream));
+    if (h1_words)
+        HIP_TRY(hipMemcpyAsync(hr + n * sizeof(mcq_result), c->d_draws.p, h1_words * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const unsigned long long *h1 = reinterpret_cast<const unsigned long long *>(hr + n * sizeof(mcq_result));
+    for (size_t i = 0; i < n; i++) {
+        mcq_result w;
+        memcpy(&w, hr + i * sizeof(mcq_result), sizeof w);
+        mcq_exact_ext_finish(xq[i], &rid[64u * i], h1 + h1_off[i], w, prob[i]);
+        if (weights) weights[i] = w;
+    }
+    return MCQ_OK;
+    ABI_GUARD_END("mcq_exact_batch_ext")
 }
 
 }  // extern "C"

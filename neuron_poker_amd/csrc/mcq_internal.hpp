@@ -22,6 +22,20 @@ struct McqExactJob {
     uint32_t n_boards, slices, row, grid;   /* table completions, cuts of the first-opponent loop, result row, blocks that work */
 };
 void mcq_exact_plan(const mcq_query *q, uint32_t row, uint32_t n_cu, McqExactJob *job);
+/* exact enumeration of extended queries (mcq_exact_ext.hpp): one job per query, one launch per kind = random opponents
+ * (0, 1, 2); the extension records lie in device-visible memory, 76 words each.  Kinds 0 and 1 add into the zeroed row
+ * d_rows[job.row], kind 2 into the zeroed per-first-hand sums d_h1[h1_off + 12 * hand] (hand < C(L, 2)). */
+struct McqExactExtJob {
+    uint32_t rec[4];                      /* the 16-byte query record */
+    uint32_t ext, n_boards, row, grid;    /* its extension record, table completions, result row, blocks that work */
+    uint32_t groups, h1_off, pad_[2];     /* kind 2: blocks per completion (1024 first hands each), offset of its sums */
+};
+/* plan of one job (L = |R|, the cards the opponents are dealt from) -> its grid */
+uint32_t mcq_exact_ext_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t kind, uint32_t L, uint32_t h1_off,
+                            uint32_t n_cu, McqExactExtJob *job);
+hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, uint32_t kind,
+                                const uint32_t *d_ext, int law, mcq_result *d_rows, unsigned long long *d_h1,
+                                const McqTables *d_luts, hipStream_t s);
 hipError_t mcq_launch_exact(const McqExactJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, bool two_opp, int law,
                             mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
 /* hands / winner / wtype / keys: device-visible memory (pinned host memory or HBM), 16-byte aligned and padded to whole

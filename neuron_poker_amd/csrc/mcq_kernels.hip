@@ -16,6 +16,7 @@
 
 #include "mcq_device.hpp"
 #include "mcq_exact.hpp"
+#include "mcq_exact_ext.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt.hpp"
 #include "mcq_mt_ext.hpp"
@@ -1783,6 +1784,149 @@ __global__ __launch_bounds__(TWO_OPP ? 384 : 1024) void mcq_exact_kernel(const M
     if (lane < 13u && sum != 0ull) atomicAdd(reinterpret_cast<unsigned long long *>(row) + lane, sum);
 }
 
+// ---------------------------------------------------------------------------------------------- exact enumeration, extended
+// SURVEY 8f-3 x 8f-2, see mcq_exact_ext.hpp; one job per query (blockIdx.y), all of one KIND = random opponents:
+//   0  a lane per table completion (hand against known hands: C(48, 5) completions preflop, nothing else to do);
+//   1  a wave per completion, lanes over the candidate hands, as mcq_exact_kernel<false>;
+//   2  a BLOCK per completion: its 1024 threads make the candidate keys once (LDS), then thread t owns first hand
+//      group * 1024 + t (an R-pair: fixed across completions) and walks every second hand; its sums stay in registers
+//      until the block's last completion and go to h1_sums[job.h1_off + 12 * hand] (integer atomics: deterministic).
+//      LDS: 97 KB of tables + 10 KB of keys and records, one block of 16 waves per CU.
+// Kinds 0 and 1 add into the zeroed row rows[job.row] by lane roles as mcq_exact_kernel does.
+template <uint32_t KIND>
+__global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
+                                                             int law, mcq_result *__restrict__ rows,
+                                                             unsigned long long *__restrict__ h1_sums,
+                                                             const McqTables *__restrict__ g_tab) {
+    const McqExactExtJob job = jobs[blockIdx.y];
+    if (blockIdx.x >= job.grid) return;
+    constexpr uint32_t kWaves = 16u, kRem = KIND == 1u ? kWaves : 1u;
+    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ uint16_t pair_xy[MCQ_EXACT_PAIRS + 2];
+    __shared__ uint32_t xw[MCQ_EXT_WORDS];
+    __shared__ McqExactExtQuery xq;
+    __shared__ uint8_t r_id[64];
+    __shared__ uint8_t cb_tab[KIND != 0u ? MCQ_XX_MAX_RP : 1u];
+    __shared__ McqCard rem_card_all[kRem][64];
+    __shared__ uint32_t rem_pos_all[kRem][64];
+    __shared__ uint32_t keys[KIND == 2u ? MCQ_EXACT_PAIRS + 2 : 1u];
+    __shared__ uint32_t recs[KIND == 2u ? MCQ_EXACT_PAIRS + 2 : 1u];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
+    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
+    for (uint32_t i = tid; i < MCQ_EXACT_PAIRS; i += blockDim.x) {
+        uint32_t x, y;
+        mcq_exact_pair_xy(i, x, y);
+        pair_xy[i] = (uint16_t)(x | (y << 8));
+    }
+    load_tables(tab, g_tab); /* ends with a barrier */
+    if (tid == 0) {
+        const McqExtRec er = {xw};
+        (void)mcq_exact_ext_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, law, xq); /* validated by the host */
+        mcq_exact_ext_r_ids(xq, r_id);
+    }
+    __syncthreads();
+    const McqExactExtQuery &e = xq;
+    if (KIND != 0u) {
+        mcq_exact_ext_cb_table(e, r_id, tid, blockDim.x, cb_tab);
+        __syncthreads();
+    }
+    const uint32_t n_boards = job.n_boards;
+
+    if (KIND == 0u) {
+        McqExactAcc acc = {0, 0, 0};
+        uint32_t by_type[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t idx = blockIdx.x * blockDim.x + tid; idx < n_boards; idx += job.grid * blockDim.x) {
+            McqExactAcc a = {0, 0, 0};
+            const uint32_t t = mcq_exact_ext_lone(e, idx, tab.sel8, g_tab->tf, tab.tops, tab.sd, a);
+            acc.win += a.win;
+            acc.tie += a.tie;
+            acc.tot += a.tot;
+#pragma unroll
+            for (uint32_t j = 0; j < 9; j++) by_type[j] += j == t ? a.win + a.tie : 0u;
+        }
+        uint32_t mine = 0; /* lane roles as mcq_exact_kernel: 0 total, 2 wins, 3 ties, 4 + t type t */
+        const uint32_t tot = wave_sum(acc.tot), win = wave_sum(acc.win), tie = wave_sum(acc.tie);
+        mine = lane == 0u ? tot : lane == 2u ? win : lane == 3u ? tie : 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 9; j++) {
+            const uint32_t v = wave_sum(by_type[j]);
+            mine = lane == 4u + j ? v : mine;
+        }
+        if (lane < 13u && mine != 0u) atomicAdd(reinterpret_cast<unsigned long long *>(rows + job.row) + lane, (unsigned long long)mine);
+    } else if (KIND == 1u) {
+        McqCard *rem_card = rem_card_all[wib];
+        uint32_t *rem_pos = rem_pos_all[wib];
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wib), n_waves = job.grid * kWaves;
+        unsigned long long sum = 0;
+        for (uint32_t board = wave; board < n_boards; board += n_waves) {
+            uint32_t pos[5];
+            mcq_exact_unrank(board, e.b.L, e.b.k, pos);
+            McqExactBoard bd;
+            mcq_exact_board(e.b, pos, tab.sel8, g_tab->tf, tab.tops, tab.sd, bd);
+            const uint32_t kb = mcq_exact_ext_known_best(e, bd, g_tab->tf, tab.tops, tab.sd);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* the previous completion's reads are done (same wave) */
+            if (lane < e.m) {
+                const uint32_t rp = mcq_exact_rem_pos(pos, lane);
+                rem_pos[lane] = rp;
+                rem_card[lane] = mcq_card(r_id[rp]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            McqExactAcc acc = {0, 0, 0};
+            mcq_exact_ext_pass_a(e, bd, kb, lane, 64u, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, nullptr,
+                                 nullptr, acc);
+            const uint32_t win = wave_sum(acc.win), tie = wave_sum(acc.tie), tot = wave_sum(acc.tot);
+            const uint32_t type = mcq_key_type(bd.hero_key);
+            if (lane == 0u) sum += tot;
+            if (lane == 2u) sum += win;
+            if (lane == 3u) sum += tie;
+            if (lane == 4u + type) sum += win + tie;
+        }
+        if (lane < 13u && sum != 0ull) atomicAdd(reinterpret_cast<unsigned long long *>(rows + job.row) + lane, sum);
+    } else {
+        McqCard *rem_card = rem_card_all[0];
+        uint32_t *rem_pos = rem_pos_all[0];
+        const uint32_t groups = job.groups, group = blockIdx.x % groups, h = group * blockDim.x + tid;
+        const bool own = h < e.n_rp;
+        uint32_t qa = 0, qb = 1;
+        if (own) mcq_exact_pair_xy(h, qa, qb);
+        McqExactExtSums s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+        for (uint32_t board = blockIdx.x / groups; board < n_boards; board += job.grid / groups) {
+            uint32_t pos[5];
+            mcq_exact_unrank(board, e.b.L, e.b.k, pos);
+            McqExactBoard bd;
+            mcq_exact_board(e.b, pos, tab.sel8, g_tab->tf, tab.tops, tab.sd, bd);
+            const uint32_t kb = mcq_exact_ext_known_best(e, bd, g_tab->tf, tab.tops, tab.sd);
+            __syncthreads(); /* the previous completion's pass B is done with keys and records */
+            if (tid < e.m) {
+                const uint32_t rp = mcq_exact_rem_pos(pos, tid);
+                rem_pos[tid] = rp;
+                rem_card[tid] = mcq_card(r_id[rp]);
+            }
+            __syncthreads();
+            McqExactAcc unused = {0, 0, 0};
+            mcq_exact_ext_pass_a(e, bd, kb, tid, blockDim.x, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, keys,
+                                 recs, unused);
+            __syncthreads();
+            const uint32_t mi = own ? mcq_exact_ext_m_index(e, pos, qa, qb) : e.n_pairs;
+            if (mi < e.n_pairs) {
+                McqExactAcc acc = {0, 0, 0};
+                mcq_exact_ext_pass_b(e, bd, qa, qb, mi, keys, recs, acc);
+                mcq_exact_ext_add(s, acc, mcq_key_type(bd.hero_key));
+            }
+        }
+        if (own) {
+            unsigned long long *dst = h1_sums + job.h1_off + (size_t)h * MCQ_XX_SUMS;
+            if (s.win) atomicAdd(dst + 0, s.win);
+            if (s.tie) atomicAdd(dst + 1, s.tie);
+            if (s.tot) atomicAdd(dst + 2, s.tot);
+#pragma unroll
+            for (uint32_t t = 0; t < 9; t++)
+                if (s.type[t]) atomicAdd(dst + 3 + t, s.type[t]);
+        }
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- launchers
@@ -1992,6 +2136,45 @@ hipError_t mcq_launch_exact(const McqExactJob *d_jobs, uint32_t n_jobs, uint32_t
         hipLaunchKernelGGL(mcq_exact_kernel<true>, dim3(max_grid, n_jobs), dim3(384), 0, s, d_jobs, law, d_rows, d_luts);
     else
         hipLaunchKernelGGL(mcq_exact_kernel<false>, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, law, d_rows, d_luts);
+    return hipGetLastError();
+}
+
+uint32_t mcq_exact_ext_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t kind, uint32_t L, uint32_t h1_off,
+                            uint32_t n_cu, McqExactExtJob *job) {
+    __builtin_memcpy(job->rec, q, 16);
+    const uint32_t k = 5u - q->n_board, n_rp = L * (L - 1u) / 2u;
+    job->ext = ext;
+    job->n_boards = mcq_exact_binom(L, k);
+    job->row = row;
+    job->h1_off = h1_off;
+    job->groups = 1u;
+    if (kind == 0u) {
+        const uint32_t blocks = (job->n_boards + 1023u) / 1024u;
+        job->grid = blocks < n_cu ? blocks : n_cu;
+    } else if (kind == 1u) {
+        const uint32_t blocks = (job->n_boards + 15u) / 16u;
+        job->grid = blocks < n_cu ? blocks : n_cu;
+    } else {
+        job->groups = (n_rp + 1023u) / 1024u;
+        uint32_t per = n_cu / job->groups;
+        if (per < 1u) per = 1u;
+        if (per > job->n_boards) per = job->n_boards;
+        job->grid = per * job->groups;
+    }
+    return job->grid;
+}
+
+hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, uint32_t kind,
+                                const uint32_t *d_ext, int law, mcq_result *d_rows, unsigned long long *d_h1,
+                                const McqTables *d_luts, hipStream_t s) {
+    if (n_jobs == 0) return hipSuccess;
+    if (n_jobs > 65535u || max_grid == 0 || kind > 2u) return hipErrorInvalidValue;
+    if (kind == 0u)
+        hipLaunchKernelGGL(mcq_exact_ext_kernel<0u>, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, d_rows, d_h1, d_luts);
+    else if (kind == 1u)
+        hipLaunchKernelGGL(mcq_exact_ext_kernel<1u>, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, d_rows, d_h1, d_luts);
+    else
+        hipLaunchKernelGGL(mcq_exact_ext_kernel<2u>, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, d_rows, d_h1, d_luts);
     return hipGetLastError();
 }
 

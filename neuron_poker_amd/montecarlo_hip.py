@@ -179,7 +179,12 @@ class MonteCarlo(object):
 
     def run_montecarlo(self, original_player_card_list, original_table_card_list, player_amount, ui, maxRuns,
                        timeout, ghost_cards, opponent_range=1, *, mode=None, seed=None):
+        """mode: None (the configured one), 'philox', 'replay', or 'exact' (the exact probabilities the Monte-Carlo modes
+        converge to: see _run_exact)."""
         eng = self._engine or _lib.default_engine()
+        if mode == "exact":
+            return self._run_exact(eng, original_player_card_list, original_table_card_list, player_amount, ghost_cards,
+                                   opponent_range)
         m = _state["mode"] if mode is None else _MODES[mode]
         players = list(original_player_card_list)
         if not 1 <= len(players) <= 1 + _lib.MAX_KNOWN:
@@ -216,6 +221,33 @@ class MonteCarlo(object):
         self.winTypesDict = self.winnerCardTypeList.items()          # :248
         self.runs = runs                                             # :249
         self.passes = int(res["passes"])                             # :250
+        return self.equity, self.winTypesDict
+
+    def _run_exact(self, eng, original_player_card_list, original_table_card_list, player_amount, ghost_cards,
+                   opponent_range):
+        """mode='exact': what run_montecarlo converges to, by enumeration (mcq_exact_batch_ext under the reference's law):
+        equity and winTypesDict are the exact probabilities, result the row of integer weights (zero when there is
+        none: a range with two random opponents), runs and passes 0.  Known hands are two cards each; a hero range,
+        ranged known hands and more than two random opponents raise ValueError."""
+        players = list(original_player_card_list)
+        if not 1 <= len(players) <= 1 + _lib.MAX_KNOWN:
+            raise ValueError("between one and ten known hands")
+        if isinstance(players[0], (set, frozenset)):
+            raise ValueError("mode='exact' needs the hero's two cards, not a range")
+        for h in players[1:]:
+            if isinstance(h, (set, frozenset)) or len(h) != 2:
+                raise ValueError("mode='exact' needs every known hand as two cards")
+        opp_bits = _opponent_range_bits(opponent_range)
+        q = _query(list(players[0]), list(original_table_card_list), player_amount, 1)
+        ext = _ext_record(list(players[0]), False, players[1:], ghost_cards, opponent_range, opp_bits)
+        prob, weights = eng.exact_ext(q, ext, "reference")
+        p = prob[0]
+        self.result = weights[0]
+        self.equity = float(p["win"] + p["tie"])
+        self.winnerCardTypeList = Counter({TYPES[t]: float(v) for t, v in enumerate(p["by_type"]) if v})
+        self.winTypesDict = self.winnerCardTypeList.items()
+        self.runs = 0
+        self.passes = 0
         return self.equity, self.winTypesDict
 
 
@@ -313,12 +345,28 @@ def get_equity_batch(hole, board, n_players, runs, seed=None, first_query_id=0, 
     return equity, tallies
 
 
-def get_equity_exact(player_cards, table_cards, players, dealing="reference", engine=None):
+def get_equity_exact(player_cards, table_cards, players, dealing="reference", engine=None, *, known_hands=(),
+                     ghost_cards='', opponent_range=1):
     """The number get_equity() converges to, by exhaustive enumeration on the GPU (1 to 3 players).
 
     dealing='reference': the exact expectation of tools/montecarlo_python.py's dealing (index bias included);
     'uniform': every remaining card equally likely (what montecarlo_cython.pyx / Montecarlo.cpp intend and
-    tools/montecarlo_cpp/Test.cpp:176-217 checks within 1 %).  -> (equity, result row of integer weights)."""
+    tools/montecarlo_cpp/Test.cpp:176-217 checks within 1 %).  -> (equity, result row of integer weights).
+
+    known_hands (further hands of two cards, in the order of original_player_card_list after the hero), ghost_cards and
+    opponent_range follow run_montecarlo's conventions; `players` counts them all, and at most two of them may be random
+    opponents (mcq_exact_batch_ext).  The row of weights is zero for a range with two random opponents: those outcomes
+    have no common integer total, the equity is exact all the same."""
+    opp_bits = _opponent_range_bits(opponent_range)
+    known_hands = [list(h) for h in known_hands]
     q = _query(list(player_cards), list(table_cards), players, 1)
-    res = (engine or _lib.default_engine()).exact(q, dealing)[0]
-    return (int(res["win"]) + int(res["tie"])) / int(res["runs"]), res
+    eng = engine or _lib.default_engine()
+    if not known_hands and opp_bits is None and (ghost_cards == '' or ghost_cards is None):
+        res = eng.exact(q, dealing)[0]
+        return (int(res["win"]) + int(res["tie"])) / int(res["runs"]), res
+    for h in known_hands:
+        if isinstance(h, (set, frozenset)) or len(h) != 2:
+            raise ValueError("a known hand is two cards here (ranged known hands are not enumerated)")
+    ext = _ext_record(list(player_cards), False, known_hands, ghost_cards, opponent_range, opp_bits)
+    prob, weights = eng.exact_ext(q, ext, dealing)
+    return float(prob[0]["win"] + prob[0]["tie"]), weights[0]
