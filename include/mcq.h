@@ -141,7 +141,8 @@ MCQ_API int mcq_eval_one(mcq_ctx *ctx, const mcq_query *q, uint64_t seed, int mo
  * range excludes) -- `passes` counts these trials, not the reference's.  Streams (MCQ-CTR v5x): as mcq_eval_batch,
  * sixteen iterations each, but two for a query that draws from a list and has at most 8192 iterations.
  * Up to eight queries of at most 8192 iterations (six candidate lists) per call take ONE kernel launch: the call
- * pattern of the reference's agents, one ranged query per decision -- 25 us per call. */
+ * pattern of the reference's agents, one ranged query per decision -- 25 us per call.
+ * MCQ_MODE_PHILOX follows MCQ_LAW_REFERENCE only: on a context set to MCQ_LAW_UNIFORM it gives MCQ_EINVAL. */
 MCQ_API int mcq_eval_batch_ext(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
                        uint64_t first_query_id, int mode, mcq_result *out);
 
@@ -217,7 +218,8 @@ typedef struct mcq_exact_prob {
 MCQ_API int mcq_exact_batch_ext(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
                                 mcq_exact_prob *prob, mcq_result *weights);
 
-/* Select the dealing law used by MCQ_MODE_PHILOX on this context (MCQ_LAW_*). */
+/* Select the dealing law used by MCQ_MODE_PHILOX on this context (MCQ_LAW_*).  Extended queries
+ * (mcq_eval_batch_ext) are dealt by the reference's law only: under MCQ_LAW_UNIFORM that call gives MCQ_EINVAL. */
 MCQ_API int mcq_set_dealing_law(mcq_ctx *ctx, int law);
 
 /* Kernel timing (off by default: a timestamped launch costs a small query about 6 us of its call time).  When on,

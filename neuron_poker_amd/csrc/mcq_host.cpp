@@ -930,6 +930,10 @@ int mcq_eval_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext,
     if (!c) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: null context");
     if (!q || !ext || !out) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: null buffer");
     if (n > 0x7fffffffu) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: n too large");
+    /* the extended kernels deal the reference's law only: refuse rather than deal it under the uniform law's name */
+    if (mode == MCQ_MODE_PHILOX && c->law == MCQ_LAW_UNIFORM)
+        return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: the uniform dealing law is not available for extended queries "
+                                    "(exact enumeration has it: mcq_exact_batch_ext)");
     uint64_t total_tasks = 0;
     uint32_t lists_stride = 1; /* candidate lists per query of the production mode: the batch's maximum */
     uint32_t most_tasks = 0;

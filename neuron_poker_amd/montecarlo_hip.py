@@ -66,7 +66,8 @@ def seed(s):
 def configure(mode=None, couple_numpy=None, dealing=None):
     """mode: 'philox' (default, production) or 'replay' (bit-exact MT19937 replay of the reference).
     dealing: 'reference' (default: the Python reference's law incl. its index bias) or 'uniform' (unbiased, what
-    the reference's Cython/C++ variants deal; production mode only) -- applied to every thread's default engine and
+    the reference's Cython/C++ variants deal; production mode and plain queries only: an extended query -- a range,
+    ghost cards, further known hands -- raises ValueError under it) -- applied to every thread's default engine and
     to the multi-GPU engines of get_equity_batch(n_gpus=...); call it while no equity call is running.
     couple_numpy=True (replay mode only): draw from numpy's GLOBAL random state and advance it exactly as the
     reference does, so that code sharing np.random with the equity call (gym_env/env.py:142,680,686 deals with
