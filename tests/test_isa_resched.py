@@ -1,6 +1,7 @@
 """tools/isa_resched.py -- the pass every kernel's assembly goes through on its way into libmcq_hip.so (csrc/Makefile).
 CPU tests of its three parts: the opcode rewrite, the re-ordering inside a run of vector instructions, and the hazard
-distances of gfx950 that the re-ordering must keep (checked on the build's own text when it is there)."""
+distances of gfx950 that the re-ordering must keep (checked on the build's own text when it is there); inline-asm
+regions pass through untouched."""
 import os
 import sys
 
@@ -80,10 +81,64 @@ def test_hazard_rules():
     assert X.fix_hazards(body, {}) == body
 
 
+def function(body, name="_Z1kv"):
+    """a function of assembly text around body (lines without their leading tab)"""
+    return ["\t.type\t%s,@function\n" % name, "%s:\n" % name] + ["\t%s\n" % b for b in body] + \
+        ["\ts_endpgm\n", ".Lfunc_end0:\n", "\t.size\t%s, .Lfunc_end0-%s\n" % (name, name)]
+
+
+def wait_states(lines, first, second):
+    """wait states between the instruction lines first and second (s_nop N = N + 1, comments none)"""
+    i, j = lines.index(first), lines.index(second)
+    n = 0
+    for l in lines[i + 1:j]:
+        w = l.split()
+        if l.startswith("\t") and w and not w[0].startswith((";", ".")):
+            n += int(w[1]) + 1 if w[0] == "s_nop" else 1
+    return n
+
+
+def test_hazard_across_an_asm_marker_pair_gets_padded():
+    """the small-batch kernels' stream-key set-up as the compiler wrote it: the read of s1 two wait states behind its
+    write, an `asm volatile("")` barrier (a ;;#ASMSTART / ;;#ASMEND comment pair) in between.  The re-ordering still
+    puts the fast v_xor ahead of the slow v_mad, and the function-wide padding makes up the wait state it took away."""
+    body = ["v_readlane_b32 s1, v127, 45", ";;#ASMSTART", ";;#ASMEND", "s_nop 0",
+            "v_mad_u64_u32 v[2:3], s[24:25], v5, s7, 0", "v_xor_b32_e32 v4, s1, v4", "s_add_i32 s1, s20, 1"]
+    src = function(body)
+    assert wait_states(src, "\tv_readlane_b32 s1, v127, 45\n", "\tv_xor_b32_e32 v4, s1, v4\n") == 2
+    out, st = X.process_file(src, ["_Z1k"], bitop3=True, reorder=True, sep=True)
+    ops = [l.split()[0] for l in out if l.startswith("\t") and not l.startswith("\t.")]
+    assert ops.index("v_xor_b32_e32") < ops.index("v_mad_u64_u32") and st["moved"] == 1
+    assert wait_states(out, "\tv_readlane_b32 s1, v127, 45\n", "\tv_xor_b32_e32 v4, s1, v4\n") >= 2
+    assert st["hazard_nops"] == 1
+    # nothing left to pad, and the marker pair is still there
+    assert X.process_file(out, [], bitop3=False, reorder=True, check_only=True)[1].get("hazard_nops", 0) == 0
+    assert "\t;;#ASMSTART\n" in out and "\t;;#ASMEND\n" in out
+
+
+def test_inline_asm_region_comes_out_byte_for_byte():
+    """nothing between ;;#ASMSTART and ;;#ASMEND is rewritten, re-ordered or padded, though the same instructions
+    outside a region are; a hazard into the region is padded in front of it"""
+    region = ["\t;;#ASMSTART\n", "\tv_readfirstlane_b32 s20, v10\n", "\tv_or3_b32 v1, v2, v3, v4\n",
+              "\tv_bcnt_u32_b32  v5, v6, 0\t; as the author wrote it\n", "\tv_add_u32_e32 v7, v8, v9\n", "\t;;#ASMEND\n"]
+    outside = ["\tv_or3_b32 v1, v2, v3, v4\n", "\tv_bcnt_u32_b32 v5, v6, 0\n", "\tv_add_u32_e32 v7, v8, v9\n"]
+    src = function([])
+    src[2:2] = outside + ["\ts_waitcnt vmcnt(0)\n", "\tv_add_u32_e32 v10, v11, v12\n"] + region
+    out, st = X.process_file(src, ["_Z1k"], bitop3=True, reorder=True, sep=True)
+    i = out.index(region[0])
+    assert out[i:i + len(region)] == region
+    assert st["bitop3"] == 1 and st["moved"] == 1   # the copy outside the region
+    assert "\tv_or3_b32 v1, v2, v3, v4\n" not in out[:i]
+    # the VALU write of v10 right in front of the region, read by v_readfirstlane inside it: padded before the region
+    assert out[i - 2:i] == ["\tv_add_u32_e32 v10, v11, v12\n", "\ts_nop 0\n"]
+    assert st["hazard_nops"] == 1
+
+
 @pytest.mark.skipif(not os.path.exists(os.path.join(BUILD, "mcq_kernels.s")), reason="the library has not been built here")
 def test_build_texts_need_no_padding():
     """the rules ask for nothing the compiler has not already provided (so they are not stricter than the hardware's
-    documented ones), and the text that went into the library satisfies them too"""
+    documented ones), and the text that went into the library satisfies them too -- over whole functions, across the
+    comment lines of inline-asm markers, labels and directives (process_file's function-wide pass)"""
     for name in ("mcq_kernels.s", "mcq_kernels.post.s"):
         with open(os.path.join(BUILD, name)) as f:
             lines = f.readlines()

@@ -15,7 +15,7 @@ instructions (the fast class) at the slow cadence.
 So: behind every slow-class VALU instruction whose successor is another VALU instruction this pass puts an `s_nop 0`
 (one SALU issue slot of the wave; free for the SIMD while other waves have vector work).  Only inside the functions
 named by --only (substring match on the symbol; default: every kernel), only between instructions of one basic block
-(labels, directives and comments end a pair), never inside an inline-asm region that declares itself with ';APP'.
+(labels, directives and comments end a pair), never inside an inline-asm region (;;#ASMSTART .. ;;#ASMEND).
 Wait states only ever get longer by an s_nop, so every hazard the compiler has padded for stays padded.
 
     python tools/isa_cadence.py in.s out.s [--only mcq_eval_kernel --only mcq_eval_ext_kernel] [--stats]
@@ -27,6 +27,8 @@ import sys
 FAST = {"v_add_u32", "v_sub_u32", "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_not_b32", "v_mov_b32",
         "v_lshrrev_b32", "v_ashrrev_i32", "v_bitop3_b32", "v_addc_co_u32", "v_nop", "v_add_f32", "v_mul_f32", "v_sub_f32"}
 INS = re.compile(r"^\t([a-z_][a-z0-9_]*)\b(.*)$")
+# the AMDGPU backend brackets every inline-asm statement (an empty `asm volatile("")` barrier too) with these comments
+ASM_START, ASM_END = ";;#ASMSTART", ";;#ASMEND"
 
 
 def base_of(op):
@@ -61,9 +63,9 @@ def process(lines, only, sep):
         if s.startswith("\t.type") and "@function" in s:
             func = s.split()[1].split(",")[0]
             active = (not only) or any(o in func for o in only)
-        if ";APP" in s:
+        if ASM_START in s:
             in_app = True
-        if ";NO_APP" in s:
+        if ASM_END in s:
             in_app = False
         if m and not s.lstrip().startswith(("." , ";")):
             op, args = m.group(1), m.group(2)

@@ -25,6 +25,7 @@ import sys
 import isa_cadence
 
 INS = isa_cadence.INS
+ASM_START, ASM_END = isa_cadence.ASM_START, isa_cadence.ASM_END
 BITOP3 = {"v_or3_b32": "0xfe", "v_and_or_b32": "0xec", "v_bfi_b32": "0xca"}
 # truth tables (a = 0xf0, b = 0xcc, c = 0xaa): a | b | c; (a & b) | c; (a & b) | (~a & c)
 assert (0xF0 | 0xCC | 0xAA) == 0xFE and ((0xF0 & 0xCC) | 0xAA) == 0xEA and ((0xF0 & 0xCC) | (0x0F & 0xAA)) == 0xCA
@@ -263,8 +264,9 @@ def transform(body, bitop3=True, reorder=True, sep=False, split=False, sink=Fals
 #   a VALU instruction writes a VGPR           -> v_readlane / v_readfirstlane reads it:                            1
 #   a VALU instruction writes a VGPR           -> a DPP instruction reads it:                                       2
 #   a transcendental instruction, or an SDWA one with dst_sel other than DWORD, writes a VGPR -> a VALU instruction reads it: 1
-# fix_hazards() walks a block and pads (s_nop) wherever the text in front of it has fewer; on the compiler's own output it
-# must find nothing to do (checked by `--check`).
+# fix_hazards() walks a block and pads (s_nop) wherever the text in front of it has fewer; pad_function() runs it once
+# more over each whole function.  On the compiler's own output it must find nothing to do (checked by `--check`), and
+# tools/isa_audit.py checks the code object the build produces against a rule table of its own.
 TRANS = ("v_rcp", "v_rsq", "v_sqrt", "v_exp", "v_log", "v_sin", "v_cos")
 VMEM = ("global_", "buffer_", "flat_", "scratch_", "tbuffer_")
 
@@ -295,11 +297,13 @@ def rw_loose(op, args):
     return reads, writes
 
 
-def fix_hazards(body, stats=None):
+def fix_hazards(body, stats=None, pads=None):
+    """body padded where the rules above ask for more wait states; pads, when given, receives (index into body, wait
+    states added in front of that instruction)"""
     out = []
     ws = 0                      # wait states issued so far
     w_sgpr, w_vgpr, w_fwd = {}, {}, {}   # register -> wait-state index of the VALU instruction that wrote it last
-    for op, args in body:
+    for k, (op, args) in enumerate(body):
         need = 0
         if op.startswith("v_"):
             reads, writes = rw_loose(op, args)
@@ -324,6 +328,8 @@ def fix_hazards(body, stats=None):
             ws += need
             if stats is not None:
                 stats["hazard_nops"] = stats.get("hazard_nops", 0) + 1
+            if pads is not None:
+                pads.append((k, need))
         out.append((op, args))
         if op == "s_nop":
             m = re.match(r"\s*(\d+)", args)
@@ -417,11 +423,41 @@ def sink_pass(segs):
     return sunk
 
 
+def pad_function(lines, stats):
+    """One hazard-padding pass over the whole instruction stream of one function (its text lines, already transformed):
+    unlike the padding inside transform(), which sees one block at a time, it keeps the hazard state across comments,
+    inline-asm markers, labels and directives.  Every `asm volatile("")` barrier is a ;;#ASMSTART / ;;#ASMEND pair of
+    comment lines, and a write in front of one with a read behind it is a hazard all the same.  Padding never goes inside
+    an inline-asm region: an instruction there is padded in front of its region's first line (which does not help when
+    its writer is in the same region; the audit of the build's code object would then fail)."""
+    body, at = [], []  # the instructions, and the line each one's padding goes in front of
+    region = None
+    for i, line in enumerate(lines):
+        s = line.rstrip("\n")
+        if ASM_START in s:
+            region = i
+        elif ASM_END in s:
+            region = None
+        else:
+            m = INS.match(s)
+            if m and not s.lstrip().startswith((".", ";")):
+                body.append((m.group(1), re.sub(r"\s*;.*$", "", m.group(2))))
+                at.append(i if region is None else region)
+    pads = []
+    fix_hazards(body, stats, pads)
+    for k, need in reversed(pads):
+        lines.insert(at[k], "\ts_nop %d\n" % (need - 1))
+    return lines
+
+
 def process_file(lines, only, bitop3=False, **kw):
     """bitop3: everywhere; the other transforms: only inside the functions --only names (substring of the symbol; none
-    given: everywhere).  Never inside an inline-asm region (;APP .. ;NO_APP); labels, directives and comments end a block."""
+    given: everywhere).  Never inside an inline-asm region (;;#ASMSTART .. ;;#ASMEND): its lines come out as they went
+    in.  Labels, directives and comments end a block for the transforms; the hazard padding then runs once over each
+    whole function (pad_function)."""
     out, total = [], {}
     func, active, in_app = None, False, False
+    fstart = None  # where the current function's lines begin in out
     block = []
 
     def flush():
@@ -433,13 +469,21 @@ def process_file(lines, only, bitop3=False, **kw):
             out.extend("\t%s %s\n" % (o, a.strip()) if a.strip() else "\t%s\n" % o for o, a in new)
             block = []
 
+    def end_function():
+        nonlocal fstart
+        if fstart is not None:
+            out[fstart:] = pad_function(out[fstart:], total)
+        fstart = None
+
     for line in lines:
         s = line.rstrip("\n")
         if s.startswith("\t.type") and "@function" in s:
             flush()
+            end_function()
+            fstart = len(out)
             func = s.split()[1].split(",")[0]
             active = (not only) or any(o in func for o in only)
-        if ";APP" in s:
+        if ASM_START in s:
             flush()
             in_app = True
         m = INS.match(s)
@@ -448,9 +492,10 @@ def process_file(lines, only, bitop3=False, **kw):
         else:
             flush()
             out.append(line)
-        if ";NO_APP" in s:
+        if ASM_END in s:
             in_app = False
     flush()
+    end_function()
     return out, total
 
 
