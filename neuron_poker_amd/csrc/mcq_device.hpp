@@ -113,6 +113,17 @@ MCQ_HD uint32_t mcq_opaque_uniform(uint32_t x) {
 #endif
     return x;
 }
+// Keeps a value alive without an instruction.  Used on the one field of a 16-byte card that an opponent's hole does not
+// need: with all four fields live the card is ONE ds_read_b128 (64 banks, 16 lanes per LDS cycle); without it the
+// compiler reads ds_read_b32 + ds_read_b64, and the lone first dwords of the 16-byte entries share 8 of the 32 banks
+// that instruction has.
+MCQ_HD void mcq_keep(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : : "v"(x));
+#else
+    (void)x;
+#endif
+}
 MCQ_HD uint32_t mcq_bfe(uint32_t x, uint32_t off, uint32_t width) { /* (x >> off) & ((1 << width) - 1), off + width <= 32 */
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_ubfe(x, off, width);
@@ -126,6 +137,27 @@ MCQ_HD uint32_t mcq_sad_u8(uint32_t bytes, uint32_t acc) { /* acc + sum of the f
 #else
     return acc + (bytes & 0xFFu) + ((bytes >> 8) & 0xFFu) + ((bytes >> 16) & 0xFFu) + (bytes >> 24);
 #endif
+}
+MCQ_HD uint32_t mcq_perm(uint32_t hi, uint32_t lo, uint32_t sel) { /* v_perm_b32: result byte i = byte sel_i of hi:lo
+                                                                      (0-3 lo, 4-7 hi), 0 for sel_i = 0x0C */
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t v = ((uint64_t)hi << 32) | lo;
+    uint32_t r = 0;
+    for (uint32_t i = 0; i < 4; i++) {
+        const uint32_t k = (sel >> (8u * i)) & 0xFFu;
+        if (k < 8u) r |= (uint32_t)((v >> (8u * k)) & 0xFFu) << (8u * i);
+    }
+    return r;
+#endif
+}
+MCQ_HD uint32_t mcq_bfi(uint32_t mask, uint32_t a, uint32_t b) { /* (mask & a) | (~mask & b): one v_bfi_b32 */
+    return (mask & a) | (~mask & b);
+}
+MCQ_HD uint32_t mcq_max3(uint32_t a, uint32_t b, uint32_t c) { /* one v_max3_u32 */
+    const uint32_t m = a > b ? a : b;
+    return m > c ? m : c;
 }
 MCQ_HD uint32_t mcq_splat_byte(uint32_t x) { /* x < 256 -> x in all four bytes */
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -157,9 +189,15 @@ MCQ_HD uint32_t mcq_straight_runs(uint32_t m) {
 // ------------------------------------------------------------------------------------------ lookup tables (LDS)
 // sel8: only for laying out the per-query base deck (once per wave task).
 // All mask-indexed tables are addressed with x4-domain masks (m4 = m << 2):
-//   tops[m] (u32, byte offset m4):  top two set bits of m (x4 domain, 0 if fewer than two) | top bit << 16
+//   tops[m] (u32, byte offset m4):  the two-pair / full-house family (F2 in mcq_eval_key) reads it twice.  Bits 2..14:
+//           the top set bit of m (x4 domain) -- the family's kicker when m is what the pairs leave over.  Bits 15..30:
+//           the upper half of a finished TwoPair key when m is the mask of the ranks held at least twice: the top two
+//           set bits of m << 15 | MCQ_C_TWOPAIR << 28; with fewer than two bits in m these are 0 and bit 31 is set
+//           instead (never part of a key: it only makes the entry compare above every entry of the trips table below)
 //   sd[m]   (u32, byte offset m4):  (straight ? 0x80 | top position 1..10 : 0) << 23, i.e. the complete
-//           Straight key (0 without a straight)
+//           Straight key (0 without a straight); masks of at most four ranks cannot hold a straight and carry the
+//           FourOfAKind key's field instead: the top two set bits of m (x4 domain, 0 if fewer than two) -- below every
+//           key such a hand can have (at most four ranks in seven cards: two pairs at least) until the quads bit joins it
 //   sd[8192 + m] ("kc", byte offset 32768 + m4, folded into the read instruction's offset field): the low part of
 //           the HighCard / Pair / ThreeOfAKind key when m is the mask of the ranks held exactly once: m without
 //           its two lowest set bits (the kickers that count) | the type code << 28, which the number of kickers
@@ -176,8 +214,9 @@ struct McqTables { /* order matters on the device: the first 64 KB are reachable
                      the sparsest, is the one that costs least there (measured) */
     uint32_t tops[8192];
     uint32_t sd[16384]; /* [0, 8192) sd, [8192, 16384) kc */
-    uint32_t tf[16384]; /* [0, 8192) tf, [8192, 16384) a second copy of tops for the lookup that goes through
-                           global memory with tf (tops[ge3], see mcq_eval_key) */
+    uint32_t tf[16384]; /* [0, 8192) tf, [8192, 16384) the trips table, read through global memory with tf: for the mask
+                           m of the ranks held at least three times the upper half of a finished FullHouse key, top
+                           set bit of m << 15 | MCQ_C_FULL << 28, and 0 for m = 0 (see mcq_eval_key) */
     uint32_t sel8[256];
 };
 #define MCQ_KC_BYTE_OFFSET 32768u /* kc relative to sd */
@@ -198,12 +237,12 @@ static inline void mcq_fill_tables(McqTables *t) {
         uint32_t n = (uint32_t)__builtin_popcount(m);
         uint32_t d2 = m & (m - 1);
         d2 &= d2 - 1; /* m == 0 stays 0 */
-        t->sd[m] = st << 23;
-        t->sd[8192 + m] = (d2 << 2) | ((n == 5 ? (uint32_t)MCQ_C_PAIR : n == 4 ? (uint32_t)MCQ_C_TRIPS : 0u) << MCQ_KEY_SHIFT);
         uint32_t hi1 = m ? 0x80000000u >> __builtin_clz(m) : 0, hi2 = 0;
         if (n >= 2) hi2 = hi1 | (0x80000000u >> __builtin_clz(m ^ hi1));
-        t->tops[m] = (hi2 << 2) | (hi1 << 18);
-        t->tf[8192 + m] = t->tops[m];
+        t->sd[m] = n <= 4 ? hi2 << 2 : st << 23;
+        t->sd[8192 + m] = (d2 << 2) | ((n == 5 ? (uint32_t)MCQ_C_PAIR : n == 4 ? (uint32_t)MCQ_C_TRIPS : 0u) << MCQ_KEY_SHIFT);
+        t->tops[m] = (hi1 << 2) | (n >= 2 ? (hi2 << 15) | ((uint32_t)MCQ_C_TWOPAIR << MCQ_KEY_SHIFT) : 0x80000000u);
+        t->tf[8192 + m] = m ? (hi1 << 15) | ((uint32_t)MCQ_C_FULL << MCQ_KEY_SHIFT) : 0u;
         uint32_t key = 0;
         if (n >= 5) {
             if (runs) {
@@ -464,16 +503,17 @@ struct McqHole { /* two hole cards: B = r1 | r2, P = r1 & r2 (pocket pair) */
 };
 
 // Only a suit with at least three table cards can make a flush, and five table cards hold at most one such
-// suit.  use_hi / sh locate that suit's 16-bit field in the (los, his) pairs, bfl4 is the table's mask in it.
-// Without such a suit the fields of clubs are taken: table + hole then hold fewer than five bits and tf[] = 0.
+// suit.  psel is the byte selector (mcq_perm) that takes that suit's 16-bit field out of a (his, los) pair -- clubs
+// bytes 0-1 of los, diamonds 2-3, hearts bytes 0-1 of his, spades 2-3 -- in ONE instruction per hand; bfl4 is the
+// table's mask in it.  Without such a suit the field of clubs is taken: table + hole then hold fewer than five bits
+// and tf[] = 0.
 struct McqFlushSel {
-    bool use_hi;
-    uint32_t sh, bfl4;
+    uint32_t psel, bfl4;
     MCQ_HDM void from_board(const McqBoard &b) {
         const uint32_t f = (b.cnt + 0x5555u) & 0x8888u; /* bit 4s+3 <=> suit s has >= 3 table cards */
-        use_hi = (f & 0x8800u) != 0;                     /* hearts or spades */
-        sh = (f & 0x8080u) != 0 ? 16u : 0u;              /* diamonds or spades: upper half-word */
-        bfl4 = mcq_bfe(use_hi ? b.his : b.los, sh, 16);
+        psel = 0x0C0C0100u + ((f & 0x8800u) != 0 ? 0x0404u : 0u) /* hearts or spades: his */
+               + ((f & 0x8080u) != 0 ? 0x0202u : 0u);            /* diamonds or spades: upper half-word */
+        bfl4 = mcq_perm(b.his, b.los, psel);
     }
 };
 
@@ -481,20 +521,31 @@ struct McqFlushSel {
 MCQ_HD uint32_t mcq_ld_u32(const uint32_t *t, uint32_t byte_off) {
     return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(t) + byte_off);
 }
+MCQ_HD uint32_t mcq_ld_lo16(const uint32_t *t, uint32_t byte_off) { /* the entry's low half-word, zero-extended */
+    /* (opaque: told that the upper half is zero, the compiler narrows the masks of the bit-field insert that takes
+     * this value and emits three instructions for it) */
+    return mcq_opaque(*reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(t) + byte_off));
+}
 
-// Key of table + hole.  Branch-free: every family of hand types yields a candidate key that is 0 when the
-// family does not apply or carries a lower code than the true type; the key is their maximum.
+// Key of table + hole = the maximum of four candidate keys (mcq_eval_cands).  Branch-free: every family of hand
+// types yields a candidate that is the hand's key when the family applies and a smaller number when it does not:
 //   F1  HighCard / Pair / ThreeOfAKind: (pair or trips rank) then the kickers = all other ranks minus the two
 //       lowest (hand_evaluator.py:104-106, 110-115)
 //   F2  TwoPair (two best pairs, kicker = best of the rest incl. a third pair, :39-42, 107-109) and
 //       FullHouse (trips, best remaining pair or second trips, :36-38)
-//   straight (top rank decides, wheel lowest, :52-58), flush / straight flush (table tf), and
-//   FoufOfAKind = the two highest distinct ranks of all seven cards (:43-46).
+//   flush / straight flush (table tf)
+//   straight (top rank decides, wheel lowest, :52-58) and FourOfAKind = the two highest distinct ranks of all
+//       seven cards (:43-46): one candidate, because seven cards with quads hold four ranks at most and no straight.
+// No condition is tested that a table entry already decides (see McqTables): F2 has one compare, between the entries
+// of its two first lookups, and no candidate is cleared -- what a family leaves when it does not apply stays below
+// 2^15, under every key of seven cards, or carries a code below the hand's true one.
 // All masks below are x4-domain.
-MCQ_HD uint32_t mcq_eval_key(const McqBoard &b, const McqFlushSel &fs, const McqHole &h, const uint32_t *tf,
-                             const uint32_t *tops, const uint32_t *sd) {
+MCQ_HD void mcq_eval_cands(const McqBoard &b, const McqFlushSel &fs, const McqHole &h, const uint32_t *tf,
+                           const uint32_t *tops, const uint32_t *sd, uint32_t (&cand)[4]) {
 #ifdef MCQ_ABLATE_EVAL /* diagnostic timing build: wrong results */
-    return (b.any ^ h.B ^ (h.los >> 3)) | (1u << MCQ_KEY_SHIFT);
+    cand[0] = (b.any ^ h.B ^ (h.los >> 3)) | (1u << MCQ_KEY_SHIFT);
+    cand[1] = cand[2] = cand[3] = 0u;
+    return;
 #endif
     const uint32_t any = b.any | h.B;
     const uint32_t ge2 = b.ge2 | (b.any & h.B) | h.P;
@@ -503,37 +554,36 @@ MCQ_HD uint32_t mcq_eval_key(const McqBoard &b, const McqFlushSel &fs, const Mcq
 
     /* lookups first: their latency overlaps the arithmetic below */
     const uint32_t e_ge2 = mcq_ld_u32(tops, ge2);
-    /* tops[ge3] from the copy of tops behind tf: in the kernels tf is the GLOBAL image, and the vector-memory
-     * path takes this second sparse lookup off the LDS pipe as well (ge3 is zero for 19 hands in 20: one cache
-     * line); measured 7.17 -> 7.04 ms, a third lookup there loses */
+    /* the trips table lies behind tf: in the kernels tf is the GLOBAL image, and the vector-memory path takes this
+     * second sparse lookup off the LDS pipe as well (ge3 is zero for 19 hands in 20: one cache line); measured
+     * 7.17 -> 7.04 ms, a third lookup there loses */
     const uint32_t e_ge3 = mcq_ld_u32(tf + 8192, ge3);
     const uint32_t d_any = mcq_ld_u32(sd, any);
     const uint32_t d_kick = mcq_ld_u32(sd, (any ^ ge2) + MCQ_KC_BYTE_OFFSET); /* kickers | type code of family F1 */
-    const uint32_t key_f = mcq_ld_u32(tf, fs.bfl4 | mcq_bfe(fs.use_hi ? h.his : h.los, fs.sh, 16)); /* tf: LDS or global */
+    cand[2] = mcq_ld_u32(tf, fs.bfl4 | mcq_perm(h.his, h.los, fs.psel)); /* tf: LDS or global */
 
-    const uint32_t key_s = d_any;
-    const uint32_t key1 = (ge2 << 13) | d_kick;
+    cand[0] = (ge2 << 13) | d_kick;
 
-    const bool fh = ge3 != 0;
-    const uint32_t H = fh ? (e_ge3 >> 16) : (e_ge2 & 0xFFFFu);
-    const uint32_t R = (fh ? ge2 : any) ^ H;
-    const uint32_t kick2 = mcq_ld_u32(tops, R) >> 16;
-    uint32_t key2 = (H << 13) | kick2 |
-                    (fh ? (uint32_t)MCQ_C_FULL << MCQ_KEY_SHIFT : (uint32_t)MCQ_C_TWOPAIR << MCQ_KEY_SHIFT);
-    key2 = (H != 0 && R != 0) ? key2 : 0u;
+    /* F2.  e_ge3 > e_ge2 <=> trips AND a second rank held twice (0 < TwoPair entries < FullHouse entries < entries
+     * of fewer than two ranks): the full house.  Either entry's bits 15..30 are the key's upper half and its first
+     * field H; the kicker is the top of what H leaves of the ranks held twice (full house) or at all (two pairs).
+     * Neither: e_ge2 has no upper half, and the candidate is one rank bit in the lower field. */
+    const bool fh = e_ge3 > e_ge2;
+    const uint32_t e_H = fh ? e_ge3 : e_ge2;
+    const uint32_t R = (fh ? ge2 : any) ^ ((e_H >> 13) & 0x7FFCu);
+    cand[1] = mcq_bfi(0x7FFF8000u, e_H, mcq_ld_lo16(tops, R)); /* (a 16-bit read: bit 31 of that entry stays out) */
 
-#ifdef MCQ_ABLATE_QUADS /* diagnostic timing build: wrong results */
-    (void)eq4;
-    return (key1 > key2 ? key1 : key2) > (key_s > key_f ? key_s : key_f) ? (key1 > key2 ? key1 : key2) : (key_s > key_f ? key_s : key_f);
-#endif
-    /* quads (0.17 % of hands), without a branch: a vote of the wave in front of this lookup cost as many instructions as
-     * the lookup itself and cut the straight-line iteration into seven blocks */
-    const uint32_t key4 = eq4 != 0 ? ((mcq_ld_u32(tops, any) & 0xFFFFu) | ((uint32_t)MCQ_C_QUADS << MCQ_KEY_SHIFT)) : 0u;
+    /* quads (0.17 % of hands) cost two instructions and no lookup of their own: bit 31 = MCQ_C_QUADS << 28 is the
+     * sign of -eq4, and sd[any] is the rest of that key whenever eq4 != 0 */
+    cand[3] = ((0u - eq4) & ((uint32_t)MCQ_C_QUADS << MCQ_KEY_SHIFT)) | d_any;
+}
 
-    uint32_t k = key1 > key2 ? key1 : key2;
-    k = k > key_s ? k : key_s;
-    uint32_t k2 = key_f > key4 ? key_f : key4;
-    return k > k2 ? k : k2;
+MCQ_HD uint32_t mcq_eval_key(const McqBoard &b, const McqFlushSel &fs, const McqHole &h, const uint32_t *tf,
+                             const uint32_t *tops, const uint32_t *sd) {
+    uint32_t c[4];
+    mcq_eval_cands(b, fs, h, tf, tops, sd, c);
+    const uint32_t k = mcq_max3(c[0], c[1], c[2]);
+    return k > c[3] ? k : c[3];
 }
 
 // ------------------------------------------------------------------------------------------ one query, one lane
@@ -674,10 +724,6 @@ MCQ_HD void mcq_hole_reg(uint32_t rb, uint32_t &h, uint32_t &k) {
     h = h + f - 0x01010101u;                          /* every other hole moves down by one */
 }
 
-MCQ_HD uint32_t mcq_bfi(uint32_t mask, uint32_t a, uint32_t b) { /* (mask & a) | (~mask & b): one v_bfi_b32 */
-    return (mask & a) | (~mask & b);
-}
-
 // Store t = r in byte SLOT.  rb7 = r (optionally with bit 7 set) in every byte, as the scan needs it anyway, so
 // the insertion is a single bit-field insert of the low seven bits (the slot's bit 7 is always clear).
 template <int SLOT>
@@ -780,6 +826,7 @@ MCQ_HD void mcq_iteration(const McqQueryCtx &qc, Draws &dr, const McqCard *base1
         dr.template pair<P>(L, r1, r2); /* r1 in [0,L-1], r2 in [0,L-2], r1 != r2 (l.167-176), both | 0x80 */  \
         const McqCard c1 = base128[mcq_draw_opp<2 * P>(r1, H)];     /* deck.pop(r1) (l.178) */                 \
         const McqCard c2 = base128[mcq_draw_opp<2 * P + 1>(r2, H)]; /* deck.pop(r2), shrunk list (l.179) */    \
+        mcq_keep(c1.cnt); /* (the first card of the pair only: with both, the 6-max iteration spills registers) */ \
         opp[P].set(c1, c2);                                                                                    \
         L -= 2;                                                                                                \
     }
@@ -801,10 +848,11 @@ MCQ_HD void mcq_iteration(const McqQueryCtx &qc, Draws &dr, const McqCard *base1
     const uint32_t hk = mcq_eval_key(b, fs, qc.hero, tf, tops, sd);
     uint32_t best = 0;
     const uint32_t n_opp_e = NOPP >= 0 ? (uint32_t)NOPP : mcq_opaque_uniform(qc.n_opp); /* a fresh scalar compare per block, see mcq_opaque_uniform */
-#define MCQ_EVAL(P)                                                        \
+#define MCQ_EVAL(P) /* the opponents' best key straight from the candidates: two v_max3_u32 per hand */ \
     if (P < n_opp_e) {                                                     \
-        const uint32_t k = mcq_eval_key(b, fs, opp[P], tf, tops, sd);     \
-        best = k > best ? k : best;                                        \
+        uint32_t c[4];                                                     \
+        mcq_eval_cands(b, fs, opp[P], tf, tops, sd, c);                    \
+        best = mcq_max3(mcq_max3(best, c[0], c[1]), c[2], c[3]);           \
     }
     MCQ_EVAL(0) MCQ_EVAL(1) MCQ_EVAL(2) MCQ_EVAL(3) MCQ_EVAL(4) MCQ_EVAL(5) MCQ_EVAL(6) MCQ_EVAL(7) MCQ_EVAL(8)
 #undef MCQ_EVAL

@@ -8,7 +8,7 @@ hardware (tools/ubench -> profiles/r01_ubench*.txt, profiles/r06_vcc_probe.txt, 
 What it does: unbundles the gfx950 code object (clang-offload-bundler), disassembles it (llvm-objdump -d), takes the
 kernel whose mangled name contains --kernel, finds its loops (backward branches) and picks the straight-line iteration
 of `nopp` opponents and `ndeal` table cards to come: the innermost loop WITHOUT any other branch inside whose signature
-fits -- 2 * nopp + ndeal card reads (ds_read_b128) and 3 * nopp + ndeal + ceil(ndeal / 2) 64-bit multiply-adds
+fits -- nopp + ndeal whole card records (ds_read_b128) and 3 * nopp + ndeal + ceil(ndeal / 2) 64-bit multiply-adds
 (one per random word, one per bounded draw; mcq_device.hpp: McqCtrDrawsT, McqMwc64x).  Every instruction of that loop
 is put into an issue class:
 
@@ -257,11 +257,13 @@ def signature(body):
 
 
 def pick_loop(ins, nopp, ndeal, rng_stub=False):
-    """The straight-line iteration of `nopp` opponents and `ndeal` table cards: ndeal whole card records (ds_read_b128;
-    an opponent's card is read as b32 + b64: the evaluator needs three of its four words) and one 64-bit multiply-add
+    """The straight-line iteration of `nopp` opponents and `ndeal` table cards: ndeal whole card records (ds_read_b128)
+    for the table and one per opponent (the evaluator needs three of the four words of an opponent's card: the first
+    of a pair is read whole, the second as b32 + b64 -- mcq_keep in mcq_device.hpp), and one 64-bit multiply-add
     per random word (nopp + ceil(ndeal / 2)) and per bounded draw (2 * nopp + ndeal)."""
     words = nopp + (ndeal + 1) // 2
-    want = (ndeal, (0 if rng_stub else words) + 2 * nopp + ndeal)
+    mads = (0 if rng_stub else words) + 2 * nopp + ndeal
+    want = (nopp + ndeal, mads)
     found = [(j, i) for j, i in loops_of(ins) if signature(ins[j:i + 1]) == want]
     if not found:
         raise SystemExit("no straight-line loop with %d card records and %d multiply-adds (nopp %d, ndeal %d)"
@@ -321,7 +323,7 @@ def main():
                 best = None
                 for vj, vi in loops_of(vins):
                     vb = vins[vj:vi + 1]
-                    if sum(1 for _, o, _ in vb if o == "ds_read_b128") == 2 * a.nopp + a.ndeal:
+                    if a.ndeal <= sum(1 for _, o, _ in vb if o == "ds_read_b128") <= 2 * a.nopp + a.ndeal:
                         vh = histogram(vb, a.vcc_window)
                         if best is None or abs(vh["valu"] - full_valu) < abs(best["valu"] - full_valu):
                             best = vh
