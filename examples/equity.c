@@ -14,6 +14,7 @@
 /* the record layouts the Python binding (neuron_poker_amd/_lib.py) and the kernels rely on */
 typedef char query_is_16_bytes[sizeof(mcq_query) == 16 ? 1 : -1];
 typedef char result_is_104_bytes[sizeof(mcq_result) == 104 ? 1 : -1];
+typedef char result_ways_is_176_bytes[sizeof(mcq_result_ways) == 176 && offsetof(mcq_result_ways, tie_ways) == 104 ? 1 : -1];
 typedef char ext_is_304_bytes[sizeof(mcq_query_ext) == 304 && sizeof(mcq_known_hand) == 28 ? 1 : -1];
 typedef char config_is_224_bytes[sizeof(mcq_tables_config) == 224 ? 1 : -1];
 typedef char runs_at_12[offsetof(mcq_query, runs) == 12 ? 1 : -1];
@@ -27,11 +28,17 @@ int main(int argc, char **argv) {
     mcq_ctx *ctx;
     mcq_query q;
     mcq_result r;
-    int rc;
+    mcq_result_ways w;
+    double share;
+    int rc, k;
     if (argc > 1 && strcmp(argv[1], "--layout") == 0) { /* used by tests/test_abi.py: no GPU needed */
         printf("%d %d %d %d %d %d %d\n", (int)sizeof(mcq_query), (int)sizeof(mcq_result), (int)sizeof(mcq_query_ext),
                (int)sizeof(mcq_tables_config), (int)offsetof(mcq_tables_config, seed),
                (int)offsetof(mcq_tables_config, seat_kind), (int)offsetof(mcq_tables_config, min_call_equity));
+        return 0;
+    }
+    if (argc > 1 && strcmp(argv[1], "--layout-ways") == 0) { /* likewise, for the split-pot rows */
+        printf("%d\n", (int)sizeof(mcq_result_ways));
         return 0;
     }
     ctx = mcq_create(0, 0);
@@ -88,6 +95,18 @@ int main(int argc, char **argv) {
                (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2]);
         mcq_tables_destroy(t);
     }
+    /* six players: ties are no longer all two-way, and crediting them to hero in full overstates his share of the pot
+     * (printed last: the lines above are what callers of this example already read) */
+    q.n_players = 6;
+    rc = mcq_eval_batch_ways(ctx, &q, 1, /*seed*/ 1, /*first_query_id*/ 0, MCQ_MODE_PHILOX, &w);
+    if (rc) {
+        fprintf(stderr, "mcq_eval_batch_ways: %d %s\n", rc, mcq_last_error());
+        return 1;
+    }
+    share = (double)w.r.win;
+    for (k = 2; k <= 10; k++) share += (double)w.tie_ways[k - 2] / (double)k;
+    printf("AhKh six-handed: equity %.4f (ties credited to hero), pot share %.4f\n",
+           (double)(w.r.win + w.r.tie) / (double)w.r.runs, share / (double)w.r.runs);
     mcq_destroy(ctx);
     return 0;
 }

@@ -31,7 +31,7 @@ extern "C" {
 #endif
 
 #define MCQ_VERSION_MAJOR 0
-#define MCQ_VERSION_MINOR 4
+#define MCQ_VERSION_MINOR 5
 #define MCQ_VERSION_PATCH 0
 
 /* error codes */
@@ -75,6 +75,19 @@ typedef struct mcq_result {
     uint64_t tie; /* hero best together with at least one opponent (credited to hero by the reference) */
     uint64_t by_type[9];
 } mcq_result;
+
+/* Per-query tallies with the ties split by how many hands share the pot (176 bytes).  `r` is exactly what
+ * mcq_eval_batch writes for the same (query, seed, query id, mode, dealing law).  tie_ways[k - 2] counts the iterations in
+ * which hero is best together with k - 1 opponents, k = 2..10: sum(tie_ways) == r.tie, and tie_ways[k - 2] == 0 for
+ * k > n_players.  The reference credits a tied pot to hero in full (equity = (win + tie) / runs); hero's expected SHARE of
+ * the pot is
+ *     (r.win + sum_k tie_ways[k - 2] / k) / r.runs.
+ * "Equal" means equal ranking key, the reference's own comparison with its quirks (hand_evaluator.py:9-24): a board that
+ * plays for everybody does not always tie every hand there.  All counters are integers and add across shards. */
+typedef struct mcq_result_ways {
+    mcq_result r;
+    uint64_t tie_ways[9];
+} mcq_result_ways;
 
 /* Optional extension of a query (304 bytes) for the rest of run_montecarlo's arguments:
  * ghost_cards (tools/montecarlo_python.py:206-208), any number of further known hands (collusion players, :133-163),
@@ -170,6 +183,19 @@ MCQ_API int mcq_eval_batch_device(mcq_ctx *ctx, const void *d_queries, size_t n,
  * one ordinary call on the context. */
 MCQ_API int mcq_eval_batch_device_small(mcq_ctx *ctx, const void *d_queries, size_t n, uint64_t seed, uint64_t first_query_id,
                                         void *d_results, void *hip_stream);
+
+/* mcq_eval_batch / mcq_eval_batch_device writing mcq_result_ways rows (the split-pot tallies above); every contract of
+ * those two entries holds: validation first and MCQ_EINVAL touches nothing (host entry), MCQ_EBUSY, an invalid device query
+ * gets runs = 0, passes = UINT64_MAX and zeros behind them, sharding by first_query_id, the context's dealing law, kernel
+ * timing.  The host entry takes both modes and keeps the one-launch path for small batches (parity mode always walks
+ * the streams with a pair of waves per query).  The device entry (MCQ_MODE_PHILOX, asynchronous) cannot see the queries:
+ * it prices them on the device and runs the evaluation kernel, cut finer for up to 1024 small queries, whatever their
+ * size; d_results -> mcq_result_ways[n].
+ * Extended queries, the exact enumerations and mcq_multi_* have no split-pot form. */
+MCQ_API int mcq_eval_batch_ways(mcq_ctx *ctx, const mcq_query *q, size_t n, uint64_t seed, uint64_t first_query_id, int mode,
+                                mcq_result_ways *out);
+MCQ_API int mcq_eval_batch_device_ways(mcq_ctx *ctx, const void *d_queries, size_t n, uint64_t seed, uint64_t first_query_id,
+                                       void *d_results, void *hip_stream);
 
 /* Showdown with the same device evaluator (tools/hand_evaluator.py:9-24 get_winner / eval_best_hand):
  * hands = n_tables x n_players x 7 card ids (host); winner[t] = index of the best hand (first of equals),

@@ -20,6 +20,8 @@ QUERY_DTYPE = np.dtype([("hole", "u1", (2,)), ("board", "u1", (5,)), ("n_board",
                         ("reserved", "u1", (3,)), ("runs", "<u4")])
 RESULT_DTYPE = np.dtype([("runs", "<u8"), ("passes", "<u8"), ("win", "<u8"), ("tie", "<u8"),
                          ("by_type", "<u8", (9,))])
+# mcq_result_ways: the same 13 counters, then tie_ways[k - 2] = iterations in which k hands share the pot, k = 2..10
+RESULT_WAYS_DTYPE = np.dtype(RESULT_DTYPE.descr + [("tie_ways", "<u8", (9,))])
 KNOWN_HAND_DTYPE = np.dtype([("cards", "u1", (2,)), ("is_range", "u1"), ("reserved", "u1"), ("range", "<u4", (6,))])
 MAX_KNOWN = 9
 QUERY_EXT_DTYPE = np.dtype([("ghost", "u1", (2,)), ("hero_is_range", "u1"), ("n_known", "u1"), ("opp_range", "<u4", (6,)),
@@ -31,6 +33,7 @@ TABLES_CONFIG_DTYPE = np.dtype([("n_tables", "<u4"), ("n_seats", "<u4"), ("runs"
 EXACT_PROB_DTYPE = np.dtype([("win", "<f8"), ("tie", "<f8"), ("by_type", "<f8", (9,))])
 assert TABLES_CONFIG_DTYPE.itemsize == 224 and EXACT_PROB_DTYPE.itemsize == 88
 assert QUERY_DTYPE.itemsize == 16 and RESULT_DTYPE.itemsize == 104 and QUERY_EXT_DTYPE.itemsize == 304
+assert RESULT_WAYS_DTYPE.itemsize == 176
 ALL_CLASSES = np.array([0xFFFFFFFF] * 5 + [0x1FF], np.uint32)  # 169 bits
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -101,6 +104,10 @@ def load_library():
         L.mcq_eval_batch_numpy_stream.restype = C.c_int
         L.mcq_eval_batch_device.argtypes = [vp, vp, sz, u64, u64, vp, vp]
         L.mcq_eval_batch_device.restype = C.c_int
+        L.mcq_eval_batch_ways.argtypes = [vp, vp, sz, u64, u64, C.c_int, vp]
+        L.mcq_eval_batch_ways.restype = C.c_int
+        L.mcq_eval_batch_device_ways.argtypes = [vp, vp, sz, u64, u64, vp, vp]
+        L.mcq_eval_batch_device_ways.restype = C.c_int
         L.mcq_eval_batch_device_small.argtypes = [vp, vp, sz, u64, u64, vp, vp]
         L.mcq_eval_batch_device_small.restype = C.c_int
         L.mcq_showdown.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp]
@@ -186,6 +193,17 @@ def pack_queries(hole, board, n_players, runs):
         raise ValueError("runs out of range")
     q["runs"] = r.astype(np.uint32)
     return q
+
+
+def pot_share(rows):
+    """Hero's expected share of the pot, float64 [n], from rows of RESULT_WAYS_DTYPE (or an [n, 22] integer matrix):
+    (win + sum_k tie_ways[k - 2] / k) / runs, k = 2..10 hands sharing the pot.  The reference's equity credits every tie
+    to hero in full: (win + tie) / runs."""
+    t = np.ascontiguousarray(rows)
+    if t.dtype == RESULT_WAYS_DTYPE:
+        t = t.view(np.uint64)
+    t = t.reshape(-1, 22).astype(np.float64)
+    return (t[:, 2] + (t[:, 13:22] / np.arange(2, 11, dtype=np.float64)).sum(1)) / np.maximum(t[:, 0], 1.0)
 
 
 def pack_query_one(hole, board, n_players, runs):
@@ -313,6 +331,18 @@ class Engine:
             _raise(rc)
         return out
 
+    def eval_batch_ways(self, queries, seed, first_query_id=0, mode=MODE_PHILOX):
+        """eval_batch with the ties split by the number of hands that share the pot (mcq_eval_batch_ways).
+        -> array of RESULT_WAYS_DTYPE: the fields of RESULT_DTYPE exactly as eval_batch returns them, then tie_ways[9];
+        pot_share(rows) is hero's expected share of the pot."""
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        out = np.empty(len(q), RESULT_WAYS_DTYPE)   # every row is written by the library on success; on failure we raise
+        rc = self._lib.mcq_eval_batch_ways(self._ctx, q.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
+                                           int(first_query_id) & (2 ** 64 - 1), int(mode), out.ctypes.data)
+        if rc:
+            _raise(rc)
+        return out
+
     def exact(self, queries, law="reference"):
         """Exact enumeration (1..3 players; `runs` of the queries is ignored).  -> RESULT_DTYPE rows of integer
         weights: runs = total weight, equity = (win + tie) / runs exactly."""
@@ -379,6 +409,14 @@ class Engine:
         rc = self._lib.mcq_eval_batch_device(self._ctx, int(d_queries), int(n), int(seed) & (2 ** 64 - 1),
                                              int(first_query_id) & (2 ** 64 - 1), int(d_results),
                                              int(stream) if stream else None)
+        if rc:
+            _raise(rc)
+
+    def eval_batch_device_ways(self, d_queries, n, seed, d_results, first_query_id=0, stream=None):
+        """eval_batch_device writing mcq_result_ways rows: d_results -> n x 22 uint64 (176 bytes per query)."""
+        rc = self._lib.mcq_eval_batch_device_ways(self._ctx, int(d_queries), int(n), int(seed) & (2 ** 64 - 1),
+                                                  int(first_query_id) & (2 ** 64 - 1), int(d_results),
+                                                  int(stream) if stream else None)
         if rc:
             _raise(rc)
 

@@ -180,4 +180,5 @@ int mcq_run_slice(mcq_ctx *c, int mode, const mcq_query *d_q, uint32_t n, mcq_re
                   uint64_t first_qid, uint64_t total_tasks, const uint8_t *d_draws, const uint64_t *d_off, hipStream_t s,
                   bool timed, uint64_t max_tasks = 0, uint32_t part = 0, uint32_t n_parts = 1,
                   const uint32_t *mt_seed32 = nullptr, const uint64_t *d_prefix_ready = nullptr,
-                  const struct McqMtbLaunch *mtb = nullptr);
+                  const struct McqMtbLaunch *mtb = nullptr,
+                  uint32_t row_words = 13 /* 22: d_res holds mcq_result_ways rows (not with mtb) */);

@@ -696,9 +696,22 @@ MCQ_HD McqCard mcq_base_entry(const McqQueryCtx &qc, uint32_t l, const uint32_t 
 }
 
 struct McqLaneAcc {
+    static constexpr bool kWays = false;
     uint64_t types; /* MCQ_N_CODES fields of 6 bits: hero's winning hand codes (<= 16 per lane per task) */
     uint32_t tie;
     uint32_t passes;
+};
+// The accumulator type is the compile-time switch of mcq_iteration / mcq_iterations: with this one every opponent's
+// key is materialised and the iterations hero does not lose are split by how many hands share the pot
+// (mcq_result_ways).  Packed as `types` is: field e (6 bits, <= 16 per lane per task) counts the iterations in which
+// hero is best together with e opponents, e = 0..9; field 0 repeats the strict wins and is not stored.
+#define MCQ_N_WAYS 9u /* tie_ways[k - 2], k = 2..10 hands sharing the pot */
+// (No `tie` here: it is the sum of fields 1..9, taken when the lanes are added up -- a register the iteration keeps.)
+struct McqLaneAccWays {
+    static constexpr bool kWays = true;
+    uint64_t types;
+    uint32_t passes;
+    uint64_t ways;
 };
 
 // ------------------------------------------------------------------------------------------ dealing without search
@@ -812,10 +825,11 @@ MCQ_HD void mcq_deal_table(const McqQueryCtx &qc, Draws &dr, const McqCard *base
 // NOPP / NDEAL >= 0: the number of opponents / of table cards to come is known at compile time (it must equal
 // qc.n_opp / qc.n_deal): the iteration is ONE basic block, which lets the compiler send lookups early and wait late
 // across hands and draws -- the wave-uniform branches of the general form are scheduling barriers.
-template <class Draws, int NOPP = -1, int NDEAL = -1>
+// Acc = McqLaneAccWays: the split-pot form (see there); McqLaneAcc: the code is what it was before that form existed.
+template <class Draws, int NOPP = -1, int NDEAL = -1, class Acc = McqLaneAcc>
 // base128 = (base deck table) - 128 entries: draw indices carry a bias of 128 (r | 0x80), folded into the pointer.
 MCQ_HD void mcq_iteration(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const uint32_t *tf,
-                          const uint32_t *tops, const uint32_t *sd, McqLaneAcc &acc) {
+                          const uint32_t *tops, const uint32_t *sd, Acc &acc) {
     uint32_t H[5] = {MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL};
     uint32_t L = qc.L0;
     McqHole opp[MCQ_MAX_OPP];
@@ -847,52 +861,61 @@ MCQ_HD void mcq_iteration(const McqQueryCtx &qc, Draws &dr, const McqCard *base1
     fs.from_board(b);
     const uint32_t hk = mcq_eval_key(b, fs, qc.hero, tf, tops, sd);
     uint32_t best = 0;
+    uint32_t n_equal = 0; /* (split-pot form only) opponents whose key equals hero's */
     const uint32_t n_opp_e = NOPP >= 0 ? (uint32_t)NOPP : mcq_opaque_uniform(qc.n_opp); /* a fresh scalar compare per block, see mcq_opaque_uniform */
 #define MCQ_EVAL(P) /* the opponents' best key straight from the candidates: two v_max3_u32 per hand */ \
     if (P < n_opp_e) {                                                     \
         uint32_t c[4];                                                     \
         mcq_eval_cands(b, fs, opp[P], tf, tops, sd, c);                    \
-        best = mcq_max3(mcq_max3(best, c[0], c[1]), c[2], c[3]);           \
+        if (Acc::kWays) { /* the hand's own key: max3, max, compare, add with carry, max */ \
+            const uint32_t k3 = mcq_max3(c[0], c[1], c[2]);                \
+            const uint32_t k = k3 > c[3] ? k3 : c[3];                      \
+            n_equal += k == hk ? 1u : 0u;                                  \
+            best = k > best ? k : best;                                    \
+        } else {                                                           \
+            best = mcq_max3(mcq_max3(best, c[0], c[1]), c[2], c[3]);       \
+        }                                                                  \
     }
     MCQ_EVAL(0) MCQ_EVAL(1) MCQ_EVAL(2) MCQ_EVAL(3) MCQ_EVAL(4) MCQ_EVAL(5) MCQ_EVAL(6) MCQ_EVAL(7) MCQ_EVAL(8)
 #undef MCQ_EVAL
     uint64_t won = hk >= best ? 1u : 0u; /* ties go to hero (hand_evaluator.py:23) */
     acc.types += won << (6u * (hk >> MCQ_KEY_SHIFT));
-    acc.tie += hk == best ? 1u : 0u;
+    if constexpr (Acc::kWays) acc.ways += won << (6u * n_equal); /* pot shared by 1 + n_equal hands */
+    else acc.tie += hk == best ? 1u : 0u;
 }
 
 // `cnt` iterations of one lane.  STRAIGHT: by the (wave-uniform) number of opponents, and before the flop also by the
 // number of table cards, the loop body is a specialisation of mcq_iteration without branches -- one basic block, in
 // which the compiler sends lookups early and waits late across hands and draws (6-max before the flop: 6.37 -> 6.00 ms;
 // the general form's wave-uniform branches are scheduling barriers).  Same arithmetic, same results.
-template <bool STRAIGHT, class Draws>
+template <bool STRAIGHT, class Draws, class Acc>
 MCQ_HD void mcq_iterations(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const uint32_t *tf,
-                                               const uint32_t *tops, const uint32_t *sd, McqLaneAcc &acc, uint32_t cnt) {
+                                               const uint32_t *tops, const uint32_t *sd, Acc &acc, uint32_t cnt) {
     if (STRAIGHT) {
 #define MCQ_STRAIGHT(N)                                                                                   \
     case N:                                                                                               \
-        if (qc.n_deal == 5u)                                                                              \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, 5>(qc, dr, base128, tf, tops, sd, acc); \
+        if (qc.n_deal == 5u)                                                                          \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, 5, Acc>(qc, dr, base128, tf, tops, sd, acc); \
         else if (qc.n_deal == 2u)                                                                         \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, 2>(qc, dr, base128, tf, tops, sd, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, 2, Acc>(qc, dr, base128, tf, tops, sd, acc); \
         else if (qc.n_deal == 1u)                                                                         \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, 1>(qc, dr, base128, tf, tops, sd, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, 1, Acc>(qc, dr, base128, tf, tops, sd, acc); \
         else                                                                                              \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, -1>(qc, dr, base128, tf, tops, sd, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, -1, Acc>(qc, dr, base128, tf, tops, sd, acc); \
         return;
         switch (qc.n_opp) {
             MCQ_STRAIGHT(1) MCQ_STRAIGHT(2) MCQ_STRAIGHT(3) MCQ_STRAIGHT(4) MCQ_STRAIGHT(5) MCQ_STRAIGHT(6) MCQ_STRAIGHT(7)
             case 8: /* (only the form with the table cards counted at run time: the others spill registers) */
-                for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, 8, -1>(qc, dr, base128, tf, tops, sd, acc);
+                for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, 8, -1, Acc>(qc, dr, base128, tf, tops, sd, acc);
                 return;
             case 9:
-                for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, 9, -1>(qc, dr, base128, tf, tops, sd, acc);
+                for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, 9, -1, Acc>(qc, dr, base128, tf, tops, sd, acc);
                 return;
             default: break; /* hero alone: the general form */
         }
 #undef MCQ_STRAIGHT
     }
-    for (uint32_t j = 0; j < cnt; j++) mcq_iteration(qc, dr, base128, tf, tops, sd, acc);
+    for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, -1, -1, Acc>(qc, dr, base128, tf, tops, sd, acc);
 }
 
 // ================================================================================================ extended queries

@@ -31,6 +31,13 @@ thread_local std::string g_err;
 
 constexpr size_t kReplayChunkBytes = 256u << 20;  /* draw bytes staged per launch by the host walk (numpy-stream entry) */
 constexpr uint32_t kBlock = 1024;                /* threads per block of the evaluation kernels */
+/* 64-bit words of a result row: mcq_result, or mcq_result_ways (the *_ways entries).  The staging code below handles rows
+ * as `rw` words; row i of a buffer starts rw * 8 * i bytes in. */
+constexpr uint32_t kPlainWords = sizeof(mcq_result) / 8u, kWaysWords = sizeof(mcq_result_ways) / 8u;
+static_assert(kPlainWords == 13u && kWaysWords == 22u && sizeof(mcq_result_ways) % 16u == 0u, "result rows");
+inline mcq_result *row_at(void *rows, size_t i, uint32_t rw) { /* (the first 13 words of either row are an mcq_result) */
+    return reinterpret_cast<mcq_result *>(static_cast<char *>(rows) + i * rw * 8u);
+}
 
 }  // namespace
 
@@ -128,8 +135,10 @@ int scratch_for(mcq_ctx *c, hipStream_t s, size_t bytes, bool capturing, mcq_ctx
 int mcq_run_slice(mcq_ctx *c, int mode, const mcq_query *d_q, uint32_t n, mcq_result *d_res, uint64_t seed,
                   uint64_t first_qid, uint64_t total_tasks, const uint8_t *d_draws, const uint64_t *d_off, hipStream_t s,
                   bool timed, uint64_t max_tasks, uint32_t part, uint32_t n_parts, const uint32_t *mt_seed32,
-                  const uint64_t *d_prefix_ready, const McqMtbLaunch *mtb) {
+                  const uint64_t *d_prefix_ready, const McqMtbLaunch *mtb, uint32_t row_words) {
     if (mode == MCQ_MODE_PHILOX && c->law == MCQ_LAW_UNIFORM) mode = MCQ_INTERNAL_MODE_UNIFORM;
+    const bool ways = row_words == kWaysWords;
+    if ((!ways && row_words != kPlainWords) || (ways && mtb)) return mcq_fail(MCQ_EINVAL, "mcq: internal: bad result row length");
     const bool capturing = stream_capturing(s);
     if (capturing || !c->timing) timed = false; /* events recorded inside a capture cannot be read back */
     mcq_ctx::Scratch *sc = nullptr;
@@ -138,7 +147,8 @@ int mcq_run_slice(mcq_ctx *c, int mode, const mcq_query *d_q, uint32_t n, mcq_re
         int rc = scratch_for(c, s, ((size_t)n + 3) * sizeof(uint64_t), capturing, &sc);
         if (rc) return rc;
         d_prefix = (const uint64_t *)sc->prefix.p;
-        HIP_TRY(mcq_launch_prep(d_q, n, d_res, (uint64_t *)sc->prefix.p, part, n_parts, (uint32_t)c->n_cu, c->split_max, s));
+        HIP_TRY(mcq_launch_prep(d_q, n, d_res, (uint64_t *)sc->prefix.p, part, n_parts, (uint32_t)c->n_cu, c->split_max, s,
+                                row_words));
     }
     uint32_t grid, block, split, work_wpb;
     pick_geometry(c, mode, total_tasks, &grid, &block, &split, max_tasks, &work_wpb);
@@ -160,10 +170,10 @@ int mcq_run_slice(mcq_ctx *c, int mode, const mcq_query *d_q, uint32_t n, mcq_re
         else
             HIP_TRY(mcq_launch_mt_parse(d_q, n, *mt_seed32, const_cast<uint8_t *>(d_draws), d_off, d_res,
                                         const_cast<uint32_t *>(reinterpret_cast<const uint32_t *>(d_prefix + n + 2)),
-                                        (uint32_t)c->n_cu, s));
+                                        (uint32_t)c->n_cu, s, row_words));
     }
     HIP_TRY(mcq_launch_eval(mode, d_q, n, d_prefix, d_res, seed, first_qid, c->d_luts, d_draws, d_off, grid, block, split,
-                            part, n_parts, s, t0, t1, work_wpb));
+                            part, n_parts, s, t0, t1, work_wpb, ways));
     if (timed) c->n_timed++;
     /* a caller's stream may run on while another stream's call takes over the scratch: mark its last reader.  The
      * context's own stream (slot 0) is synchronised by every host entry before it returns. */
@@ -210,8 +220,9 @@ namespace {
  * repeated with the serial walk. */
 constexpr size_t kMtbQueries = 64;
 constexpr uint64_t kMtbMinBlocks = 64, kMtbMaxBlocks = 1u << 18; /* (2.7 KB of scratch per block) */
-int replay_batch_device(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed, uint64_t first_query_id, mcq_result *out,
-                        bool allow_blocks = true) {
+int replay_batch_device(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed, uint64_t first_query_id, void *out,
+                        uint32_t rw, bool allow_blocks = true) {
+    if (rw != kPlainWords) allow_blocks = false; /* the block-parallel walk writes 13-word rows only: the serial walk serves */
     HIP_TRY(c->h_off.reserve(n * sizeof(uint64_t)));
     HIP_TRY(c->d_off.reserve(n * sizeof(uint64_t)));
     uint64_t *off = (uint64_t *)c->h_off.p;
@@ -301,9 +312,9 @@ int replay_batch_device(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed,
             }
         }
         int rc = mcq_run_slice(c, MCQ_MODE_REPLAY_MT19937, (const mcq_query *)c->d_q.p + ch.a, (uint32_t)m,
-                               (mcq_result *)c->d_res.p + ch.a, seed, first_query_id + ch.a, ch.tasks ? ch.tasks : 1,
+                               row_at(c->d_res.p, ch.a, rw), seed, first_query_id + ch.a, ch.tasks ? ch.tasks : 1,
                                (const uint8_t *)c->d_draws.p, (const uint64_t *)c->d_off.p + ch.a, c->stream, true,
-                               ch.max_tasks, 0, 1, &seed32, nullptr, mtb.d_blk_off ? &mtb : nullptr);
+                               ch.max_tasks, 0, 1, &seed32, nullptr, mtb.d_blk_off ? &mtb : nullptr, rw);
         if (rc) return rc;
     }
     if (by_blocks && n <= c->publish_max_rows) {
@@ -317,15 +328,15 @@ int replay_batch_device(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed,
         rc = wait_ticket(c, ticket, nullptr, 0.0);
         if (rc) return rc;
     } else {
-        HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * sizeof(mcq_result), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * rw * 8u, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     if (by_blocks) { /* a stream that ran past its estimated blocks (never seen; the margin is eight blocks): the serial walk */
         const mcq_result *hr = (const mcq_result *)c->h_res.p;
         for (size_t i = 0; i < n; i++)
-            if (hr[i].passes == ~0ull) return replay_batch_device(c, q, n, seed, first_query_id, out, false);
+            if (hr[i].passes == ~0ull) return replay_batch_device(c, q, n, seed, first_query_id, out, rw, false);
     }
-    memcpy(out, c->h_res.p, n * sizeof(mcq_result));
+    memcpy(out, c->h_res.p, n * rw * 8u);
     float total = 0.f;
     const int launched = (int)(c->n_timed - timed0);
     if (launched > 0 && launched <= mcq_ctx::kRing) {
@@ -341,8 +352,9 @@ int replay_batch_device(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed,
  * share numpy's global state (mcq_eval_batch_numpy_stream): a serial walk by construction, done on the host
  * (mcq_replay.hpp); chunks of queries whose draw bytes fit the staging budget. */
 int replay_batch(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed, uint64_t first_query_id, McqMt19937 *stream,
-                 mcq_result *out) {
-    if (!stream) return replay_batch_device(c, q, n, seed, first_query_id, out);
+                 mcq_result *out, uint32_t rw = kPlainWords) {
+    if (!stream) return replay_batch_device(c, q, n, seed, first_query_id, out, rw);
+    if (rw != kPlainWords) return mcq_fail(MCQ_EINVAL, "mcq: internal: the numpy-stream walk writes mcq_result rows");
     std::vector<uint64_t> passes(n, 0);
     float replay_ms = 0.f;
     size_t a = 0;
@@ -391,7 +403,7 @@ int replay_batch(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed, uint64
 }
 
 /* validation + query upload shared by the host entry points (the caller has selected the context's device) */
-int stage_queries(mcq_ctx *c, const mcq_query *q, size_t n, mcq_result *out, const char *who) {
+int stage_queries(mcq_ctx *c, const mcq_query *q, size_t n, const void *out, const char *who, uint32_t rw = kPlainWords) {
     if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
     if (!q || !out) return mcq_fail(MCQ_EINVAL, who, "null buffer");
     if (n > 0x7fffffffu) return mcq_fail(MCQ_EINVAL, who, "n too large");
@@ -401,9 +413,9 @@ int stage_queries(mcq_ctx *c, const mcq_query *q, size_t n, mcq_result *out, con
     for (size_t i = 0; i < n; i++) total_tasks += tasks_of(q[i]);
     if (total_tasks > 0xfffffff0ull) return mcq_fail(MCQ_EINVAL, who, "too many iterations in one call");
     HIP_TRY(c->h_q.reserve(n * sizeof(mcq_query)));
-    HIP_TRY(c->h_res.reserve((n + (n & 1u)) * sizeof(mcq_result))); /* (whole 16-byte words: mcq_publish_kernel) */
+    HIP_TRY(c->h_res.reserve((n + (n & 1u)) * rw * 8u)); /* (whole 16-byte words: mcq_publish_kernel) */
     HIP_TRY(c->d_q.reserve(n * sizeof(mcq_query)));
-    HIP_TRY(c->d_res.reserve((n + (n & 1u)) * sizeof(mcq_result)));
+    HIP_TRY(c->d_res.reserve((n + (n & 1u)) * rw * 8u));
     c->res_clean = 0; /* these entries zero their rows in the prep kernel and leave them filled */
     memcpy(c->h_q.p, q, n * sizeof(mcq_query));
     HIP_TRY(hipMemcpyAsync(c->d_q.p, c->h_q.p, n * sizeof(mcq_query), hipMemcpyHostToDevice, c->stream));
@@ -632,6 +644,25 @@ int mcq_eval_batch_device(mcq_ctx *c, const void *d_queries, size_t n, uint64_t 
     ABI_GUARD_END("mcq_eval_batch_device")
 }
 
+/* The same with mcq_result_ways rows: the prep kernel clears 22 words per row, the evaluation kernel is the instantiation
+ * that splits the ties (for up to 1024 small queries the finer cut the prep kernel picks). */
+int mcq_eval_batch_device_ways(mcq_ctx *c, const void *d_queries, size_t n, uint64_t seed, uint64_t first_query_id,
+                               void *d_results, void *hip_stream) {
+    ABI_GUARD_BEGIN
+    if (!c) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_device_ways: null context");
+    if (n == 0) return MCQ_OK;
+    if (!d_queries || !d_results) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_device_ways: null buffer");
+    if (n > 0x7fffffffu) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_device_ways: n too large");
+    MCQ_ENTER(c, "mcq_eval_batch_device_ways");
+    McqDeviceScope dev_(c->device);
+    HIP_TRY(dev_.err);
+    c->last_ms = 0.f;
+    return mcq_run_slice(c, MCQ_MODE_PHILOX, (const mcq_query *)d_queries, (uint32_t)n, (mcq_result *)d_results, seed,
+                         first_query_id, 0, nullptr, nullptr, (hipStream_t)hip_stream, true, 0, 0, 1, nullptr, nullptr, nullptr,
+                         kWaysWords);
+    ABI_GUARD_END("mcq_eval_batch_device_ways")
+}
+
 /* Small queries resident in HBM -- the reference's call pattern (gym_env/env.py:22,261-262: 1000 runs per query) for a
  * caller whose states already live on the GPU: ONE kernel launch and nothing else (mcq_eval_direct_kernel in its device
  * mode): no prep kernel, no cost prefix, no atomics -- every query is owned by 2^lg waves of one block, lg chosen from
@@ -734,13 +765,14 @@ static double cost_to_us(const mcq_ctx *c, uint64_t cost) { return (double)cost 
  * pattern, thousands of 1000-run queries (gym_env/env.py:22,261-262).  `runs` (and nothing else) of a row is the
  * host's to fill in. */
 static int eval_host_philox(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed, uint64_t first_query_id, uint32_t part,
-                            uint32_t n_parts, mcq_result *out, const char *who) {
+                            uint32_t n_parts, void *out, const char *who, uint32_t rw) {
+    const bool ways = rw == kWaysWords;
     if (!q || !out) return mcq_fail(MCQ_EINVAL, who, "null buffer");
     if (n > 0x7fffffffu) return mcq_fail(MCQ_EINVAL, who, "n too large");
     int rc = validate(q, n);
     if (rc) return rc;
-    const size_t q_bytes = n * sizeof(mcq_query), p_bytes = (n + 3) * sizeof(uint64_t), r_bytes = n * sizeof(mcq_result);
-    const size_t r_pad = (n + (n & 1u)) * sizeof(mcq_result); /* whole 16-byte words (mcq_publish_kernel) */
+    const size_t q_bytes = n * sizeof(mcq_query), p_bytes = (n + 3) * sizeof(uint64_t), r_bytes = n * rw * 8u;
+    const size_t r_pad = (n + (n & 1u)) * rw * 8u; /* whole 16-byte words (mcq_publish_kernel) */
     /* behind the records: the cost prefix, then (one-launch path) the wave layout: at most n + 2 * 16 * n_cu waves, dealt
      * to the blocks in whole rounds */
     const size_t a_off = (q_bytes + p_bytes + 15u) & ~(size_t)15u, a_cap = n + 96u * (size_t)c->n_cu + 64u; /* waves */
@@ -788,7 +820,7 @@ static int eval_host_philox(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t s
             HIP_TRY(mcq_launch_eval_direct((int)mode, c->h_q.dev, nullptr, rounds, lg ? 1u : 0u, (mcq_result *)c->h_res.dev, seed,
                                            first_query_id, c->d_luts, grid, (uint32_t *)c->d_done.p, (uint32_t *)c->h_flag.dev,
                                            ticket, c->stream, c->timing ? c->ev0[slot] : nullptr,
-                                           c->timing ? c->ev1[slot] : nullptr, nullptr, (uint32_t)n, lg));
+                                           c->timing ? c->ev1[slot] : nullptr, nullptr, (uint32_t)n, lg, ways));
             if (c->timing) c->n_timed++;
             rc = wait_ticket(c, ticket, nullptr);
             if (rc) return rc;
@@ -832,7 +864,7 @@ static int eval_host_philox(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t s
                                        lay.merge ? 1u : 0u, (mcq_result *)c->h_res.dev, seed, first_query_id, c->d_luts, grid,
                                        (uint32_t *)c->d_done.p, (uint32_t *)c->h_flag.dev, ticket, c->stream,
                                        timed ? c->ev0[slot] : nullptr, timed ? c->ev1[slot] : nullptr,
-                                       by_karg ? &karg : nullptr));
+                                       by_karg ? &karg : nullptr, 0, 0, ways));
         if (timed) c->n_timed++;
         const auto t1 = std::chrono::steady_clock::now();
         bool seen = false; /* the last block raises the flag once every row is out */
@@ -862,7 +894,7 @@ static int eval_host_philox(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t s
     if (total_tasks) {
         rc = mcq_run_slice(c, MCQ_MODE_PHILOX, (const mcq_query *)c->d_q.p, (uint32_t)n, (mcq_result *)c->d_res.p, seed,
                            first_query_id, total_tasks, nullptr, nullptr, c->stream, true, max_tasks, part, n_parts, nullptr,
-                           reinterpret_cast<const uint64_t *>(static_cast<const char *>(c->d_q.p) + q_bytes));
+                           reinterpret_cast<const uint64_t *>(static_cast<const char *>(c->d_q.p) + q_bytes), nullptr, rw);
         if (rc) return rc;
     }
     if (n <= c->publish_max_rows) {
@@ -872,7 +904,7 @@ static int eval_host_philox(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t s
         if (rc) return rc;
         const uint32_t ticket = next_ticket(c);
         HIP_TRY(mcq_launch_publish((mcq_result *)c->d_res.p, (mcq_result *)c->h_res.dev, n + (n & 1u), (uint32_t *)c->d_done.p,
-                                   (uint32_t *)c->h_flag.dev, ticket, c->stream));
+                                   (uint32_t *)c->h_flag.dev, ticket, c->stream, rw * 8u));
         rc = wait_ticket(c, ticket, nullptr, cost_to_us(c, cost));
         if (rc) return rc;
     } else {
@@ -883,12 +915,12 @@ static int eval_host_philox(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t s
     c->res_clean = r_pad;
     if (!total_tasks || !c->timing || kernel_times_impl(c, &c->last_ms, 1) != 1) c->last_ms = 0.f;
     memcpy(out, c->h_res.p, r_bytes);
-    for (size_t i = 0; i < n; i++) out[i].runs = mcq_part(tasks_of(q[i]), q[i].runs, part, n_parts).runs;
+    for (size_t i = 0; i < n; i++) row_at(out, i, rw)->runs = mcq_part(tasks_of(q[i]), q[i].runs, part, n_parts).runs;
     return MCQ_OK;
 }
 
 static int eval_batch_impl(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed, uint64_t first_query_id, int mode,
-                           uint32_t part, uint32_t n_parts, mcq_result *out, const char *who) {
+                           uint32_t part, uint32_t n_parts, void *out, const char *who, uint32_t rw = kPlainWords) {
     if (mode != MCQ_MODE_PHILOX && mode != MCQ_MODE_REPLAY_MT19937) return mcq_fail(MCQ_EINVAL, who, "bad mode");
     if (n_parts == 0 || part >= n_parts) return mcq_fail(MCQ_EINVAL, who, "part must be < n_parts");
     if (n_parts > 1 && mode != MCQ_MODE_PHILOX)
@@ -898,10 +930,10 @@ static int eval_batch_impl(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t se
     MCQ_ENTER(c, who);
     McqDeviceScope dev_(c->device);
     HIP_TRY(dev_.err);
-    if (mode == MCQ_MODE_PHILOX) return eval_host_philox(c, q, n, seed, first_query_id, part, n_parts, out, who);
-    int rc = stage_queries(c, q, n, out, who);
+    if (mode == MCQ_MODE_PHILOX) return eval_host_philox(c, q, n, seed, first_query_id, part, n_parts, out, who, rw);
+    int rc = stage_queries(c, q, n, out, who, rw);
     if (rc) return rc;
-    return replay_batch(c, q, n, seed, first_query_id, nullptr, out);
+    return replay_batch(c, q, n, seed, first_query_id, nullptr, static_cast<mcq_result *>(out), rw);
 }
 
 int mcq_eval_batch(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed, uint64_t first_query_id, int mode,
@@ -909,6 +941,13 @@ int mcq_eval_batch(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed, uint
     ABI_GUARD_BEGIN
     return eval_batch_impl(c, q, n, seed, first_query_id, mode, 0, 1, out, "mcq_eval_batch");
     ABI_GUARD_END("mcq_eval_batch")
+}
+
+int mcq_eval_batch_ways(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed, uint64_t first_query_id, int mode,
+                        mcq_result_ways *out) {
+    ABI_GUARD_BEGIN
+    return eval_batch_impl(c, q, n, seed, first_query_id, mode, 0, 1, out, "mcq_eval_batch_ways", kWaysWords);
+    ABI_GUARD_END("mcq_eval_batch_ways")
 }
 
 int mcq_eval_batch_part(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t seed, uint64_t first_query_id,

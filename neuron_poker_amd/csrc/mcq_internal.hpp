@@ -10,11 +10,13 @@ struct McqTables;
 #define MCQ_INTERNAL_MODE_UNIFORM 2 /* MCQ_MODE_PHILOX with the context's dealing law set to MCQ_LAW_UNIFORM */
 
 hipError_t mcq_launch_prep(const mcq_query *d_q, uint32_t n, mcq_result *d_res, uint64_t *d_prefix, uint32_t part,
-                           uint32_t n_parts, uint32_t n_cu, uint32_t split_max, hipStream_t s);
+                           uint32_t n_parts, uint32_t n_cu, uint32_t split_max, hipStream_t s,
+                           uint32_t row_words = 13 /* 64-bit words per result row: 22 for mcq_result_ways rows */);
 hipError_t mcq_launch_eval(int mode, const mcq_query *d_q, uint32_t n, const uint64_t *d_prefix, mcq_result *d_res,
                            uint64_t seed, uint64_t first_qid, const McqTables *d_luts, const uint8_t *d_draws,
                            const uint64_t *d_draw_off, uint32_t grid, uint32_t block, uint32_t split, uint32_t part,
-                           uint32_t n_parts, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr, uint32_t work_wpb = 0);
+                           uint32_t n_parts, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr, uint32_t work_wpb = 0,
+                           bool ways = false /* d_res holds mcq_result_ways rows: the instantiation that splits the ties */);
 /* exact enumeration (n_players <= 3), any number of queries per launch: one job per query (blockIdx.y), all of the same
  * kind -- two opponents or fewer; every job adds into its zeroed row d_rows[job.row] */
 struct McqExactJob {
@@ -72,13 +74,13 @@ hipError_t mcq_launch_eval_ext(int mode, const mcq_query *d_q, const mcq_query_e
 /* host-buffer calls with few rows: d_rows[0..n_rows) -> pinned host memory (device address h_rows_dev), d_rows zeroed,
  * then *done_flag = ticket; n_rows even (buffers hold the odd row's neighbour), d_done a zeroed device word */
 hipError_t mcq_launch_publish(mcq_result *d_rows, mcq_result *h_rows_dev, uint64_t n_rows, uint32_t *d_done,
-                              uint32_t *done_flag, uint32_t ticket, hipStream_t s);
+                              uint32_t *done_flag, uint32_t ticket, hipStream_t s, uint32_t row_bytes = sizeof(mcq_result));
 /* dst[i] += src[i], i < n (tally matrices of two shards on one device, both 16-byte aligned) */
 hipError_t mcq_launch_add_u64(uint64_t *d_dst, const uint64_t *d_src, uint64_t n, hipStream_t s);
 /* parity mode: one wave per query parses np.random.seed(seed32 + i)'s MT19937 stream into d_draws (+ passes into the
  * result rows); d_counter must be zero (the prep kernel leaves one behind the cost prefix) */
 hipError_t mcq_launch_mt_parse(const mcq_query *d_q, uint32_t n, uint32_t seed32, uint8_t *d_draws, const uint64_t *d_draw_off,
-                               mcq_result *d_res, uint32_t *d_counter, uint32_t n_cu, hipStream_t s);
+                               mcq_result *d_res, uint32_t *d_counter, uint32_t n_cu, hipStream_t s, uint32_t row_words = 13);
 /* ... for few long queries (mcq_mt_blocks.hpp): the state blocks of a query side by side.  d_blk_off[q] .. d_blk_off[q + 1]:
  * the query's blocks in d_raw (624 state words each), d_exits (MCQ_MTB_LANES words each), d_entries (8 B each); max_blocks = the most
  * blocks of one query; d_grp_off likewise for the query's groups of MCQ_MTB_GROUP blocks in d_gword / d_gits (MCQ_MTB_LANES
@@ -110,4 +112,5 @@ hipError_t mcq_launch_eval_direct(int mode, const void *work_rec, const uint32_t
                                   uint32_t *d_done, uint32_t *done_flag, uint32_t ticket, hipStream_t s, hipEvent_t t0,
                                   hipEvent_t t1, const McqDirectKarg *karg /* or null: read work_rec / work_qi */,
                                   uint32_t dev_n = 0 /* != 0: work_rec is the caller's mcq_query[dev_n] in HBM, work_qi null: */,
-                                  uint32_t dev_lg = 0 /* every query 2^dev_lg waves; validated on the device */);
+                                  uint32_t dev_lg = 0 /* every query 2^dev_lg waves; validated on the device */,
+                                  bool ways = false /* res holds mcq_result_ways rows */);

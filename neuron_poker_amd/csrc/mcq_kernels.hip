@@ -106,6 +106,8 @@ __device__ __forceinline__ uint64_t block_exclusive_scan_1024(uint64_t v, uint64
 // One block.  Validates every query, zeroes its result row and builds the exclusive prefix of the queries'
 // scheduling cost (tasks x weight; prefix[n] = total).  Invalid queries cost nothing and get runs = 0,
 // passes = UINT64_MAX.
+// ROW_WORDS: 64-bit words of a result row, 13 (mcq_result) or 22 (mcq_result_ways).
+template <uint32_t ROW_WORDS>
 __global__ __launch_bounds__(1024) void mcq_prep_kernel(const mcq_query *__restrict__ q, uint32_t n,
                                                         mcq_result *__restrict__ res, uint64_t *__restrict__ prefix,
                                                         uint32_t part_idx, uint32_t n_parts, uint32_t n_cu,
@@ -133,12 +135,13 @@ __global__ __launch_bounds__(1024) void mcq_prep_kernel(const mcq_query *__restr
             const McqPart pt = mcq_part(mcq_task_count(qq), qq.runs(), part_idx, n_parts);
             cost = ok ? (uint64_t)(pt.t_hi - pt.t_lo) * mcq_task_weight(qq) : 0ull;
             my_tasks = ok ? pt.t_hi - pt.t_lo : 0u;
-            uint64_t *r = reinterpret_cast<uint64_t *>(res + i);
+            uint64_t *r = ROW_WORDS == 13u ? reinterpret_cast<uint64_t *>(res + i)
+                                           : reinterpret_cast<uint64_t *>(res) + (size_t)i * ROW_WORDS;
             r[0] = ok ? pt.runs : 0ull;
             r[1] = ok || part_idx != 0u ? 0ull : ~0ull; /* the marker of an invalid query: from ONE share only, so that the
                                                           * sum of the shares (same-device add, all-reduce) still shows it */
 #pragma unroll
-            for (int k = 2; k < 13; k++) r[k] = 0;
+            for (int k = 2; k < (int)ROW_WORDS; k++) r[k] = 0;
         }
         if (n <= 1024u) { /* a possible small batch: what mcq_pick_split needs (below); one atomic per wave */
             const uint32_t ws = wave_sum(my_tasks);
@@ -204,7 +207,8 @@ __device__ __forceinline__ void mcq_mt_next_block(McqMtPairWave &, McqMtState &s
 __global__ __launch_bounds__(kMtBlock) void mcq_mt_parse_kernel(const mcq_query *__restrict__ queries, uint32_t n,
                                                                 uint32_t seed32, uint8_t *__restrict__ draws,
                                                                 const uint64_t *__restrict__ draw_off,
-                                                                mcq_result *__restrict__ res, uint32_t *__restrict__ counter) {
+                                                                mcq_result *__restrict__ res, uint32_t *__restrict__ counter,
+                                                                uint32_t row_words) {
     __shared__ __attribute__((aligned(16))) McqMtPairWave w;
     __shared__ __attribute__((aligned(16))) McqMtProducer prod;
     const uint32_t lane = threadIdx.x & 63u;
@@ -242,7 +246,7 @@ __global__ __launch_bounds__(kMtBlock) void mcq_mt_parse_kernel(const mcq_query 
                                    ((uint64_t)runs + 63u) & ~63ull);
                 /* every lane stores the same word: a store under `lane == 0` here would be a divergent branch in front of
                  * the barrier */
-                reinterpret_cast<unsigned long long *>(res + qi)[1] = st.passes;
+                reinterpret_cast<unsigned long long *>(res)[(size_t)qi * row_words + 1u] = st.passes;
                 if (lane == 0) w.stop_at = st.blocks + 1u; /* the producer is filling one more block: it leaves behind the next barrier */
                 __syncthreads();
             }
@@ -798,7 +802,114 @@ struct WaveTally { /* per-lane running sums of the current (wave, query) pair */
     }
 };
 
-template <int MODE, bool SPLIT>
+/* The split-pot rows (mcq_result_ways): tie_ways[k - 2] in lane 12 + (k - 2) = word 13 + (k - 2) of the 22-word row, the
+ * same reductions and, on the one-launch path, the same two-per-word packing.  The evaluation kernels run at the register
+ * limit, so the nine counters cost two registers, not nine: a lane keeps them as 10-bit fields, three per register -- a
+ * task adds at most 16 to a field, so the tally is flushed after MCQ_WAYS_TALLY_TASKS tasks (the row's counters are
+ * atomic sums: a flush in the middle of a query changes nothing) -- and `tie` is not kept at all: it is their sum. */
+#define MCQ_WAYS_TALLY_TASKS 63u
+struct WaveTallyWays {
+    uint32_t code[MCQ_N_CODES], passes, way3[3];
+    uint32_t n_add; /* tasks added since the last flush (wave-uniform) */
+    bool dirty;
+    static_assert(16u * MCQ_WAYS_TALLY_TASKS < 1024u && MCQ_DIRECT_TASKS_LIMIT <= MCQ_WAYS_TALLY_TASKS, "10-bit fields");
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int c = 0; c < MCQ_N_CODES; c++) code[c] = 0;
+        way3[0] = way3[1] = way3[2] = 0;
+        passes = 0;
+        n_add = 0;
+        dirty = false;
+    }
+    __device__ __forceinline__ void add(const McqLaneAccWays &a) {
+#pragma unroll
+        for (int c = 0; c < MCQ_N_CODES; c++)
+            if (c != 5) code[c] += (uint32_t)(a.types >> (6 * c)) & 63u;
+#pragma unroll
+        for (uint32_t k = 0; k < MCQ_N_WAYS; k++)
+            way3[k / 3u] += ((uint32_t)(a.ways >> (6u * (k + 1u))) & 63u) << (10u * (k % 3u));
+        passes += a.passes;
+        n_add++;
+        dirty = true;
+    }
+    __device__ __forceinline__ bool full() const { return n_add >= MCQ_WAYS_TALLY_TASKS; }
+    __device__ __forceinline__ uint32_t way(uint32_t k) const { return (way3[k / 3u] >> (10u * (k % 3u))) & 1023u; }
+    /* as WaveTally::row_words, lanes 12..20: tie_ways */
+    __device__ __forceinline__ unsigned long long row_words(uint32_t lane) {
+        static_assert(64u * 16u * MCQ_DIRECT_TASKS_LIMIT < 65536u, "two counters per 32-bit reduction");
+        uint32_t wins = 0, ties = 0;
+        unsigned long long mine = 0;
+#pragma unroll
+        for (uint32_t c = 0; c < MCQ_N_CODES; c += 2) {
+            const uint32_t hi = c + 1 < MCQ_N_CODES ? code[c + 1] : 0u;
+            const uint32_t v = wave_sum_dpp(code[c] | (hi << 16));
+            const uint32_t s0 = v & 0xFFFFu, s1 = v >> 16;
+            wins += s0 + s1; /* (code 5 is never counted: zero) */
+            if (c != 5 && lane == 3u + mcq_code_to_type(c)) mine = s0;
+            if (c + 1 != 5 && c + 1 < MCQ_N_CODES && lane == 3u + mcq_code_to_type(c + 1)) mine = s1;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < MCQ_N_WAYS; k += 2) {
+            const uint32_t hi = k + 1 < MCQ_N_WAYS ? way(k + 1) : 0u;
+            const uint32_t v = wave_sum_dpp(way(k) | (hi << 16));
+            ties += (v & 0xFFFFu) + (v >> 16);
+            if (lane == 12u + k) mine = v & 0xFFFFu;
+            if (k + 1 < MCQ_N_WAYS && lane == 13u + k) mine = v >> 16;
+        }
+        const uint32_t pass = wave_sum_dpp(passes);
+        if (lane == 0) mine = pass;
+        if (lane == 1) mine = wins - ties;
+        if (lane == 2) mine = ties;
+        return mine;
+    }
+    __device__ __forceinline__ uint64_t row_value(uint32_t lane) {
+        uint32_t wins = 0, ties = 0;
+        uint64_t mine = 0;
+#pragma unroll
+        for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
+            if (c == 5) continue;
+            const uint32_t v = wave_sum(code[c]);
+            wins += v;
+            if (lane == 3u + mcq_code_to_type(c)) mine = v;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < MCQ_N_WAYS; k++) {
+            const uint32_t v = wave_sum(way(k));
+            ties += v;
+            if (lane == 12u + k) mine = v;
+        }
+        const uint32_t pass = wave_sum(passes);
+        if (lane == 0) mine = pass;
+        if (lane == 1) mine = wins - ties;
+        if (lane == 2) mine = ties;
+        return mine;
+    }
+    __device__ __forceinline__ void flush(unsigned long long *row, uint32_t lane) {
+        if (!dirty) return;
+        const uint64_t mine = row_value(lane);
+        if (lane < 12u + MCQ_N_WAYS && mine != 0) atomicAdd(row + 1 + lane, (unsigned long long)mine);
+        clear();
+    }
+};
+/* what a kernel instantiation works with: the lane accumulator, the wave tally, the row's length in 64-bit words and the
+ * lanes that hold one word of it each (every word but `runs`) */
+template <bool WAYS> struct McqRowKind {
+    typedef McqLaneAcc Acc;
+    typedef WaveTally Tally;
+    static constexpr uint32_t kWords = 13u, kLanes = 12u;
+    static __device__ __forceinline__ mcq_result *row(mcq_result *res, uint32_t i) { return res + i; }
+};
+template <> struct McqRowKind<true> {
+    typedef McqLaneAccWays Acc;
+    typedef WaveTallyWays Tally;
+    static constexpr uint32_t kWords = 13u + MCQ_N_WAYS, kLanes = 12u + MCQ_N_WAYS;
+    static __device__ __forceinline__ unsigned long long *row(mcq_result *res, uint32_t i) {
+        return reinterpret_cast<unsigned long long *>(res) + (size_t)i * kWords;
+    }
+};
+static_assert(McqRowKind<true>::kWords * 8u == sizeof(mcq_result_ways), "row of mcq_result_ways");
+
+template <int MODE, bool SPLIT, bool WAYS>
 __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__restrict__ queries, uint32_t n,
                                                              const uint64_t *__restrict__ prefix,
                                                              mcq_result *__restrict__ res, uint64_t seed,
@@ -819,11 +930,13 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
      * single long query is hundreds of waves, and twelve atomics per wave on ONE row serialise (a 100 000-run query: 392
      * waves, 18 us where the arithmetic takes 6) -- and the last wave sends the sum: s_key = that query (claimed by the
      * first wave to finish), s_done = waves that have finished */
-    __shared__ unsigned long long s_row[12];
+    typedef McqRowKind<WAYS> Row; /* WAYS: 22-word rows with the ties split by the hands that share the pot */
+    constexpr uint32_t kLanes = Row::kLanes;
+    __shared__ unsigned long long s_row[kLanes];
     __shared__ uint32_t s_key, s_done;
     if (SPLIT) {
-        if (threadIdx.x < 12u) s_row[threadIdx.x] = 0ull;
-        if (threadIdx.x == 12u) {
+        if (threadIdx.x < kLanes) s_row[threadIdx.x] = 0ull;
+        if (threadIdx.x == kLanes) {
             s_key = 0xFFFFFFFFu;
             s_done = 0u;
         }
@@ -851,7 +964,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
     uint32_t task = 0, task0 = 0, n_tasks = 0, weight = 1; /* tasks [task0, n_tasks) of the query are this launch's */
     uint64_t pfx = 0;
     McqQueryCtx qc;
-    WaveTally tally;
+    typename Row::Tally tally;
     tally.clear();
     bool fresh = true; /* query record qi not loaded yet */
     for (; lo < hi;) { /* (a wave without a slice goes straight to the end: the work-group counts it there) */
@@ -877,14 +990,14 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
             }
         }
         if (task >= n_tasks) {
-            tally.flush(res + qi, lane);
+            tally.flush(Row::row(res, qi), lane);
             qi++;
             fresh = true;
             continue;
         }
         if (pfx + (uint64_t)(task - task0) * weight >= hi) break;
 
-        McqLaneAcc acc = {0, 0, 0};
+        typename Row::Acc acc = {};
         if (MODE != MCQ_MODE_REPLAY_MT19937) {
             const uint32_t stream = (task >> split) * MCQ_WAVE + lane, sub = task & sub_mask;
             const uint64_t it0 = (uint64_t)stream * MCQ_STREAM_ITERS + sub * chunk;
@@ -919,10 +1032,13 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
                              * of mcq_eval_batch_numpy_stream patches it in afterwards) */
         }
         tally.add(acc);
+        if constexpr (WAYS) {
+            if (tally.full()) tally.flush(Row::row(res, qi), lane); /* its packed counters are about to overflow */
+        }
         task++;
     }
     if (!SPLIT) {
-        if (qi < n) tally.flush(res + qi, lane);
+        if (qi < n) tally.flush(Row::row(res, qi), lane);
         return;
     }
     const bool have = qi < n && tally.dirty; /* (wave-uniform) */
@@ -932,9 +1048,9 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
         if (lane == 0) key = atomicCAS(&s_key, 0xFFFFFFFFu, qi);
         key = __builtin_amdgcn_readfirstlane(key);
         if (key == 0xFFFFFFFFu || key == qi) {
-            if (lane < 12u && mine != 0) atomicAdd(&s_row[lane], (unsigned long long)mine);
-        } else if (lane < 12u && mine != 0) { /* another query's tail: straight to its row */
-            atomicAdd(reinterpret_cast<unsigned long long *>(res + qi) + 1 + lane, (unsigned long long)mine);
+            if (lane < kLanes && mine != 0) atomicAdd(&s_row[lane], (unsigned long long)mine);
+        } else if (lane < kLanes && mine != 0) { /* another query's tail: straight to its row */
+            atomicAdd(reinterpret_cast<unsigned long long *>(Row::row(res, qi)) + 1 + lane, (unsigned long long)mine);
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); /* the sums are in LDS before this wave counts as finished */
@@ -944,9 +1060,9 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
     if (done + 1u == waves_per_block) { /* the last wave of the work-group */
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         const uint32_t key = *(volatile uint32_t *)&s_key;
-        if (key != 0xFFFFFFFFu && lane < 12u) {
+        if (key != 0xFFFFFFFFu && lane < kLanes) {
             const unsigned long long v = *(volatile unsigned long long *)&s_row[lane];
-            if (v != 0) atomicAdd(reinterpret_cast<unsigned long long *>(res + key) + 1 + lane, v);
+            if (v != 0) atomicAdd(reinterpret_cast<unsigned long long *>(Row::row(res, key)) + 1 + lane, v);
         }
     }
 }
@@ -990,6 +1106,7 @@ extern "C" __attribute__((visibility("default"))) int mcq_debug_read_stamps(unsi
 // or has more than MCQ_DIRECT_DEV_TASKS tasks gets runs = 0, passes = UINT64_MAX and no work, one without iterations a
 // row of zeros (the slot of its first wave writes it).
 #define MCQ_DIRECT_DEV_TASKS 8u
+template <uint32_t ROW_WORDS>
 __device__ __forceinline__ void mcq_direct_fetch_dev(const uint4 *__restrict__ queries, size_t at, uint32_t n, uint32_t lg,
                                                      mcq_result *__restrict__ res, uint32_t &qi, uint4 &rec) {
     const uint32_t q = (uint32_t)(at >> lg), sub = (uint32_t)at & ((1u << lg) - 1u);
@@ -1002,15 +1119,15 @@ __device__ __forceinline__ void mcq_direct_fetch_dev(const uint4 *__restrict__ q
         qi = q;
         rec.z |= (lg << 8) | (sub << 16); /* reserved[0], reserved[1]: as the host's layout writes them */
     } else if (sub == 0u) {
-        unsigned long long *r = reinterpret_cast<unsigned long long *>(res + q);
+        unsigned long long *r = reinterpret_cast<unsigned long long *>(res) + (size_t)q * ROW_WORDS;
         r[0] = 0ull;
         r[1] = ok ? 0ull : ~0ull;
 #pragma unroll
-        for (int k = 2; k < 13; k++) r[k] = 0ull;
+        for (int k = 2; k < (int)ROW_WORDS; k++) r[k] = 0ull;
     }
 }
 
-template <int MODE>
+template <int MODE, bool WAYS>
 __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 *__restrict__ work_rec,
                                                                     const uint32_t *__restrict__ work_qi, uint32_t rounds,
                                                                     uint32_t merge, mcq_result *__restrict__ res, uint64_t seed,
@@ -1020,7 +1137,9 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
     constexpr uint32_t kWaves = kMaxBlock / 64, kStage = MCQ_DIRECT_STAGE_ROUNDS * kWaves;
     __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
     __shared__ McqCard base_tab[kMaxBlock];
-    __shared__ unsigned long long partial[2][kWaves][12]; /* [round parity][wave][passes, win, tie, by_type[9]] */
+    typedef McqRowKind<WAYS> Row; /* WAYS: 22-word rows, tie_ways[9] behind by_type[9] */
+    constexpr uint32_t kLanes = Row::kLanes;
+    __shared__ unsigned long long partial[2][kWaves][kLanes]; /* [round parity][wave][passes, win, tie, by_type[9](, tie_ways[9])] */
     __shared__ uint4 s_rec[kStage];
     __shared__ uint32_t s_qi[kStage];
 
@@ -1051,7 +1170,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
             pre_qi = karg.qi[at];
             pre_rec = make_uint4(karg.rec[at][0], karg.rec[at][1], karg.rec[at][2], karg.rec[at][3]);
         } else if (use_karg == 2u) {
-            mcq_direct_fetch_dev(work_rec, at, karg.qi[0], karg.qi[1], res, pre_qi, pre_rec);
+            mcq_direct_fetch_dev<Row::kWords>(work_rec, at, karg.qi[0], karg.qi[1], res, pre_qi, pre_rec);
         } else {
             pre_qi = work_qi[at];
             pre_rec = work_rec[at];
@@ -1106,7 +1225,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
                 if (r < rounds) {
                     const size_t at = ((size_t)r * gridDim.x + blockIdx.x) * kWaves + threadIdx.x % kWaves;
                     if (use_karg == 2u) {
-                        mcq_direct_fetch_dev(work_rec, at, karg.qi[0], karg.qi[1], res, pre_qi, pre_rec);
+                        mcq_direct_fetch_dev<Row::kWords>(work_rec, at, karg.qi[0], karg.qi[1], res, pre_qi, pre_rec);
                     } else {
                         pre_qi = work_qi[at];
                         pre_rec = work_rec[at];
@@ -1140,11 +1259,11 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 MCQ_STAMP(3);
-                WaveTally tally;
+                typename Row::Tally tally;
                 tally.clear();
                 const uint32_t tasks = mcq_task_count(q);
                 for (uint32_t task = 0; task < tasks; task++) {
-                    McqLaneAcc acc = {0, 0, 0};
+                    typename Row::Acc acc = {};
                     const uint32_t stream = task * MCQ_WAVE + lane;
                     const uint64_t it0 = (uint64_t)stream * MCQ_STREAM_ITERS + sub * chunk;
                     if (it0 < qc.runs) {
@@ -1169,13 +1288,13 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
             /* Row word w = min(lane, 12): lanes 13..63 repeat lane 12's store (same address, same value) so that no
              * branch on the lane number stands in front of the loop's back edge -- the wave stays whole for the
              * cross-lane steps of the next round. */
-            const uint32_t w = lane < 12u ? lane : 12u;
+            const uint32_t w = lane < kLanes ? lane : kLanes;
             if (!merge) { /* no query of this launch has more than one wave: a wave's sums are the row */
                 const unsigned long long up = __shfl(mine, (int)((w + 63u) & 63u), 64); /* every lane takes part */
-                if (work) reinterpret_cast<unsigned long long *>(res + qi)[w] = w == 0u ? (unsigned long long)runs : up;
+                if (work) reinterpret_cast<unsigned long long *>(Row::row(res, qi))[w] = w == 0u ? (unsigned long long)runs : up;
                 continue;
             }
-            if (lane < 12u) partial[round & 1u][wib][lane] = mine;
+            if (lane < kLanes) partial[round & 1u][wib][lane] = mine;
             MCQ_STAMP(8);
             __syncthreads(); /* every wave of the block, every round; two buffers: a wave may run one round ahead */
             if (work && sub == 0u) {
@@ -1184,7 +1303,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
                     v = 0;
                     for (uint32_t k = 0; k < wpq; k++) v += partial[round & 1u][wib + k][w - 1u];
                 }
-                reinterpret_cast<unsigned long long *>(res + qi)[w] = v;
+                reinterpret_cast<unsigned long long *>(Row::row(res, qi))[w] = v;
             }
             MCQ_STAMP(9);
         }
@@ -1931,9 +2050,12 @@ __global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJo
 
 // ---------------------------------------------------------------------------------------------- launchers
 hipError_t mcq_launch_prep(const mcq_query *d_q, uint32_t n, mcq_result *d_res, uint64_t *d_prefix, uint32_t part,
-                           uint32_t n_parts, uint32_t n_cu, uint32_t split_max, hipStream_t s) {
-    if (n_parts == 0 || part >= n_parts) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mcq_prep_kernel, dim3(1), dim3(1024), 0, s, d_q, n, d_res, d_prefix, part, n_parts, n_cu, split_max);
+                           uint32_t n_parts, uint32_t n_cu, uint32_t split_max, hipStream_t s, uint32_t row_words) {
+    if (n_parts == 0 || part >= n_parts || (row_words != 13u && row_words != 22u)) return hipErrorInvalidValue;
+    if (row_words == 13u)
+        hipLaunchKernelGGL(mcq_prep_kernel<13u>, dim3(1), dim3(1024), 0, s, d_q, n, d_res, d_prefix, part, n_parts, n_cu, split_max);
+    else
+        hipLaunchKernelGGL(mcq_prep_kernel<22u>, dim3(1), dim3(1024), 0, s, d_q, n, d_res, d_prefix, part, n_parts, n_cu, split_max);
     return hipGetLastError();
 }
 
@@ -1942,29 +2064,35 @@ hipError_t mcq_launch_prep(const mcq_query *d_q, uint32_t n, mcq_result *d_res, 
 hipError_t mcq_launch_eval(int mode, const mcq_query *d_q, uint32_t n, const uint64_t *d_prefix, mcq_result *d_res,
                            uint64_t seed, uint64_t first_qid, const McqTables *d_luts, const uint8_t *d_draws,
                            const uint64_t *d_draw_off, uint32_t grid, uint32_t block, uint32_t split, uint32_t part,
-                           uint32_t n_parts, hipStream_t s, hipEvent_t t0, hipEvent_t t1, uint32_t work_wpb) {
+                           uint32_t n_parts, hipStream_t s, hipEvent_t t0, hipEvent_t t1, uint32_t work_wpb, bool ways) {
     if ((split > 4 && split != MCQ_SPLIT_FROM_PREP) || n_parts == 0 || part >= n_parts) return hipErrorInvalidValue;
     if (mode == MCQ_MODE_REPLAY_MT19937 && split > 2) return hipErrorInvalidValue; /* its lanes take four iterations at a time */
-#define MCQ_LAUNCH_EVAL(M)                                                                                          \
+#define MCQ_LAUNCH_EVAL_W(M, W)                                                                                     \
     do {                                                                                                            \
         if (split)                                                                                                  \
-            MCQ_LAUNCH_TIMED((mcq_eval_kernel<M, true>), grid, block, d_q, n,     \
+            MCQ_LAUNCH_TIMED((mcq_eval_kernel<M, true, W>), grid, block, d_q, n,     \
                                   d_prefix, d_res, seed, first_qid, d_luts, d_draws, d_draw_off, split, part, n_parts, work_wpb); \
         else                                                                                                        \
-            MCQ_LAUNCH_TIMED((mcq_eval_kernel<M, false>), grid, block, d_q, n,    \
+            MCQ_LAUNCH_TIMED((mcq_eval_kernel<M, false, W>), grid, block, d_q, n,    \
                                   d_prefix, d_res, seed, first_qid, d_luts, d_draws, d_draw_off, 0u, part, n_parts, work_wpb); \
+    } while (0)
+#define MCQ_LAUNCH_EVAL(M)                        \
+    do {                                          \
+        if (ways) MCQ_LAUNCH_EVAL_W(M, true);     \
+        else MCQ_LAUNCH_EVAL_W(M, false);         \
     } while (0)
     if (mode == MCQ_MODE_PHILOX) MCQ_LAUNCH_EVAL(MCQ_MODE_PHILOX);
     else if (mode == MCQ_INTERNAL_MODE_UNIFORM) MCQ_LAUNCH_EVAL(MCQ_INTERNAL_MODE_UNIFORM);
     else MCQ_LAUNCH_EVAL(MCQ_MODE_REPLAY_MT19937);
 #undef MCQ_LAUNCH_EVAL
+#undef MCQ_LAUNCH_EVAL_W
     return hipGetLastError();
 }
 
 hipError_t mcq_launch_eval_direct(int mode, const void *work_rec, const uint32_t *work_qi, uint32_t rounds, uint32_t merge,
                                   mcq_result *res, uint64_t seed, uint64_t first_qid, const McqTables *d_luts, uint32_t grid,
                                   uint32_t *d_done, uint32_t *done_flag, uint32_t ticket, hipStream_t s, hipEvent_t t0,
-                                  hipEvent_t t1, const McqDirectKarg *karg, uint32_t dev_n, uint32_t dev_lg) {
+                                  hipEvent_t t1, const McqDirectKarg *karg, uint32_t dev_n, uint32_t dev_lg, bool ways) {
     if (grid == 0 || rounds == 0) return hipErrorInvalidValue;
     if (karg && (uint64_t)grid * rounds * (kMaxBlock / 64) > MCQ_DIRECT_KARG_SLOTS) return hipErrorInvalidValue;
     if (karg && rounds > MCQ_DIRECT_STAGE_ROUNDS) return hipErrorInvalidValue; /* the kernel reads them in its first stage only */
@@ -1976,22 +2104,27 @@ hipError_t mcq_launch_eval_direct(int mode, const void *work_rec, const uint32_t
     dev.qi[1] = dev_lg;
     const uint32_t use = dev_n ? 2u : karg ? 1u : 0u;
     const McqDirectKarg &ka = dev_n ? dev : karg ? *karg : none;
-    if (mode == MCQ_INTERNAL_MODE_UNIFORM)
-        MCQ_LAUNCH_TIMED((mcq_eval_direct_kernel<MCQ_INTERNAL_MODE_UNIFORM>), grid, kMaxBlock, rec,
-                              work_qi, rounds, merge, res, seed, first_qid, d_luts, d_done, done_flag, ticket, use, ka);
-    else
-        MCQ_LAUNCH_TIMED((mcq_eval_direct_kernel<MCQ_MODE_PHILOX>), grid, kMaxBlock, rec, work_qi,
-                              rounds, merge, res, seed, first_qid, d_luts, d_done, done_flag, ticket, use, ka);
+#define MCQ_LAUNCH_DIRECT(M, W)                                                                                  \
+    MCQ_LAUNCH_TIMED((mcq_eval_direct_kernel<M, W>), grid, kMaxBlock, rec, work_qi, rounds, merge, res, seed, first_qid, \
+                     d_luts, d_done, done_flag, ticket, use, ka)
+    if (mode == MCQ_INTERNAL_MODE_UNIFORM) {
+        if (ways) MCQ_LAUNCH_DIRECT(MCQ_INTERNAL_MODE_UNIFORM, true);
+        else MCQ_LAUNCH_DIRECT(MCQ_INTERNAL_MODE_UNIFORM, false);
+    } else {
+        if (ways) MCQ_LAUNCH_DIRECT(MCQ_MODE_PHILOX, true);
+        else MCQ_LAUNCH_DIRECT(MCQ_MODE_PHILOX, false);
+    }
+#undef MCQ_LAUNCH_DIRECT
     return hipGetLastError();
 }
 
 hipError_t mcq_launch_mt_parse(const mcq_query *d_q, uint32_t n, uint32_t seed32, uint8_t *d_draws, const uint64_t *d_draw_off,
-                               mcq_result *d_res, uint32_t *d_counter, uint32_t n_cu, hipStream_t s) {
+                               mcq_result *d_res, uint32_t *d_counter, uint32_t n_cu, hipStream_t s, uint32_t row_words) {
     if (n == 0) return hipSuccess;
     uint32_t blocks = n; /* one pair of waves per query */
     if (blocks > 16u * n_cu) blocks = 16u * n_cu; /* what a CU holds at once: 16 work-groups */
     hipLaunchKernelGGL(mcq_mt_parse_kernel, dim3(blocks), dim3(kMtBlock), 0, s, d_q, n, seed32, d_draws, d_draw_off, d_res,
-                       d_counter);
+                       d_counter, row_words);
     return hipGetLastError();
 }
 
@@ -2044,10 +2177,10 @@ hipError_t mcq_launch_mt_parse_ext(const mcq_query *d_q, const mcq_query_ext *d_
 }
 
 hipError_t mcq_launch_publish(mcq_result *d_rows, mcq_result *h_rows_dev, uint64_t n_rows, uint32_t *d_done,
-                              uint32_t *done_flag, uint32_t ticket, hipStream_t s) {
+                              uint32_t *done_flag, uint32_t ticket, hipStream_t s, uint32_t row_bytes) {
     static_assert(sizeof(mcq_result) % 16 == 8, "13 x 8 bytes");
     if (n_rows == 0 || (n_rows & 1ull)) return hipErrorInvalidValue; /* whole 16-byte words: the caller rounds the rows up */
-    const uint64_t words = n_rows * sizeof(mcq_result) / 16u;
+    const uint64_t words = n_rows * row_bytes / 16u;
     uint64_t blocks = (words + 1023u) / 1024u; /* four words per thread */
     if (blocks > 64u) blocks = 64u;
     hipLaunchKernelGGL(mcq_publish_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, reinterpret_cast<ulonglong2 *>(d_rows),
@@ -2180,9 +2313,9 @@ hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, u
 
 hipError_t mcq_eval_occupancy(int mode, int block, int *blocks_per_cu) {
     if (mode == MCQ_MODE_PHILOX)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, mcq_eval_kernel<MCQ_MODE_PHILOX, false>, block, 0);
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, mcq_eval_kernel<MCQ_MODE_PHILOX, false, false>, block, 0);
     if (mode == MCQ_INTERNAL_MODE_UNIFORM)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, mcq_eval_kernel<MCQ_INTERNAL_MODE_UNIFORM, false>,
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, mcq_eval_kernel<MCQ_INTERNAL_MODE_UNIFORM, false, false>,
                                                             block, 0);
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, mcq_eval_kernel<MCQ_MODE_REPLAY_MT19937, false>, block, 0);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, mcq_eval_kernel<MCQ_MODE_REPLAY_MT19937, false, false>, block, 0);
 }

@@ -34,7 +34,7 @@ import numpy as np
 from . import _lib
 from .cards import TYPES, card_id
 
-__all__ = ["get_equity", "get_equity_batch", "get_equity_exact", "MonteCarlo", "seed", "configure"]
+__all__ = ["get_equity", "get_pot_equity", "get_equity_batch", "get_equity_exact", "MonteCarlo", "seed", "configure"]
 
 _state = {"couple_numpy": False,
           "mode": _lib.MODE_REPLAY_MT19937 if os.environ.get("MCQ_MODE", "philox").lower() == "replay"
@@ -294,11 +294,24 @@ def get_equity(player_cards, table_cards, players, runs):
     return (out[2] + out[3]) / out[0]
 
 
+def get_pot_equity(player_cards, table_cards, players, runs):
+    """get_equity's sibling: hero's expected SHARE of the pot, a tie among k hands counting 1/k (mcq_eval_batch_ways),
+    where get_equity -- as the reference, tools/hand_evaluator.py:23 -- credits a tied pot to hero in full.  Same
+    arguments, same seed()/stream state (a call takes one query id, as a get_equity call does) and the same configure()
+    switches: mode and dealing law; couple_numpy has no split-pot form and raises ValueError."""
+    if _state["couple_numpy"] and _state["mode"] == _lib.MODE_REPLAY_MT19937:
+        raise ValueError("get_pot_equity: configure(couple_numpy=True) has no split-pot form")
+    q = _query(list(player_cards), list(table_cards), players, runs)
+    s, first = _take_ids(1)
+    rows = _lib.default_engine().eval_batch_ways(q, s, first_query_id=first, mode=_state["mode"])
+    return float(_lib.pot_share(rows)[0])
+
+
 _MULTI = {}   # tuple of device ordinals -> MultiEngine (made at first use, kept; its callers take turns on its lock)
 
 
 def get_equity_batch(hole, board, n_players, runs, seed=None, first_query_id=0, mode=None, engine=None, n_gpus=None,
-                     devices=None):
+                     devices=None, ties="hero"):
     """Many states in one launch.
 
     hole [B,2] u8 card ids, board [B,5] u8 (0xFF = empty), n_players scalar or [B], runs scalar or [B].
@@ -309,11 +322,18 @@ def get_equity_batch(hole, board, n_players, runs, seed=None, first_query_id=0, 
     all-reduce of the integer tallies; production mode only); the tallies are the same integers as on one GPU, under the
     dealing law configure(dealing=...) has set.  devices=[...] names the shards' devices explicitly instead (one
     ordinal per shard, repeats allowed: several shards on one GPU).
+    ties="split": the returned equity is hero's expected share of the pot (a tie among k hands counts 1/k) and the
+    tallies are [B,22]: nine more columns, tie_ways[k - 2] for k = 2..10 hands sharing the pot (one GPU only).  The
+    default "hero" credits ties to hero in full, as the reference does.
     STATUS of n_gpus > 1: untested on more than one distinct device (no multi-GPU node was reachable; the partitions,
     the same-device add and a one-rank RCCL communicator are tested on one GPU with devices=[0, 0, ...]).
     """
+    if ties not in ("hero", "split"):
+        raise ValueError("ties must be 'hero' or 'split'")
     q = _lib.pack_queries(hole, board, n_players, runs)
     m = _state["mode"] if mode is None else _MODES[mode]
+    if ties == "split" and (devices is not None or (n_gpus is not None and int(n_gpus) > 1)):
+        raise ValueError("ties='split' runs on one GPU (the multi-GPU entry has no split-pot rows)")
     if seed is None:
         s, base = _take_ids(len(q))
         first_query_id = base + first_query_id
@@ -339,6 +359,10 @@ def get_equity_batch(hole, board, n_players, runs, seed=None, first_query_id=0, 
             res = me.eval_batch(q, s, first_query_id=first_query_id)
     else:
         eng = engine or _lib.default_engine()
+        if ties == "split":
+            res = eng.eval_batch_ways(q, s, first_query_id=first_query_id, mode=m)
+            tallies = res.view(np.uint64).reshape(len(q), 22)
+            return _lib.pot_share(tallies), tallies
         res = eng.eval_batch(q, s, first_query_id=first_query_id, mode=m)
     tallies = res.view(np.uint64).reshape(len(q), 13)
     runs_f = np.maximum(tallies[:, 0], 1).astype(np.float64)

@@ -12,6 +12,8 @@ hole [B,2] uint8 card ids, board [B,5] uint8 (255 = empty slot, any position), n
 runs int or [B] int32 -- all on the same CUDA (HIP) device.  equity: float64 [B]; tallies: int64 [B,13] with
 columns runs, passes, win, tie, by_type[9] (include/mcq.h mcq_result).  Query i runs under id first_query_id + i:
 the numbers equal Engine.eval_batch / get_equity_batch on the same inputs, bit for bit.
+ties="split": equity is hero's expected share of the pot (a tie among k hands counts 1/k), tallies int64 [B,22] with
+nine more columns tie_ways[k - 2], k = 2..10 (mcq_result_ways) -- both computed on the device.
 """
 import torch
 
@@ -48,11 +50,21 @@ def pack_queries_torch(hole, board, n_players, runs):
     return q
 
 
-def get_equity_batch_torch(hole, board, n_players, runs, seed=0, first_query_id=0, engine=None):
+def get_equity_batch_torch(hole, board, n_players, runs, seed=0, first_query_id=0, engine=None, ties="hero"):
+    if ties not in ("hero", "split"):
+        raise ValueError("ties must be 'hero' or 'split'")
     if not hole.is_cuda:
         raise ValueError("the tensors must live on the GPU (use get_equity_batch for host arrays)")
     eng = engine or _engine(hole.device.index if hole.device.index is not None else torch.cuda.current_device())
     q = pack_queries_torch(hole, board, n_players, runs)
+    if ties == "split":
+        out = torch.empty((q.shape[0], 22), dtype=torch.int64, device=q.device)
+        eng.eval_batch_device_ways(q.data_ptr(), q.shape[0], seed, out.data_ptr(), first_query_id=first_query_id,
+                                   stream=torch.cuda.current_stream(q.device).cuda_stream)
+        q.record_stream(torch.cuda.current_stream(q.device))
+        k = torch.arange(2, 11, dtype=torch.float64, device=q.device)
+        share = out[:, 2].to(torch.float64) + (out[:, 13:22].to(torch.float64) / k).sum(1)
+        return share / out[:, 0].clamp(min=1).to(torch.float64), out
     out = torch.empty((q.shape[0], 13), dtype=torch.int64, device=q.device)
     eng.eval_batch_device(q.data_ptr(), q.shape[0], seed, out.data_ptr(), first_query_id=first_query_id,
                           stream=torch.cuda.current_stream(q.device).cuda_stream)

@@ -2,7 +2,7 @@
 """Opcode histogram of a hot loop of libmcq_hip.so's gfx950 code object, priced with the issue costs measured on the
 hardware (tools/ubench -> profiles/r01_ubench*.txt, profiles/r06_vcc_probe.txt, profiles/r07_issue_probe.txt).
 
-    python tools/isa_hist.py [--lib neuron_poker_amd/libmcq_hip.so] [--kernel mcq_eval_kernelILi0ELb0] \
+    python tools/isa_hist.py [--lib neuron_poker_amd/libmcq_hip.so] [--kernel mcq_eval_kernelILi0ELb0ELb0 | --ways] \
                              [--nopp 5 --ndeal 5] [--json profiles/<tag>_isa_hist.json] [--dump loop.s]
 
 What it does: unbundles the gfx950 code object (clang-offload-bundler), disassembles it (llvm-objdump -d), takes the
@@ -292,7 +292,9 @@ def kernel_sources_sha256():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=os.path.join(ROOT, "neuron_poker_amd", "libmcq_hip.so"))
-    ap.add_argument("--kernel", default="mcq_eval_kernelILi0ELb0")
+    ap.add_argument("--kernel", default="mcq_eval_kernelILi0ELb0ELb0")
+    ap.add_argument("--ways", action="store_true", help="the bulk kernel's split-pot instantiation (mcq_result_ways rows: "
+                    "mcq_eval_kernel<MCQ_MODE_PHILOX, false, true>) instead of the plain one")
     ap.add_argument("--nopp", type=int, default=5)
     ap.add_argument("--ndeal", type=int, default=5)
     ap.add_argument("--vcc-window", type=int, default=2)
@@ -300,6 +302,8 @@ def main():
     ap.add_argument("--dump", help="write the loop's disassembly here")
     ap.add_argument("--roles", action="store_true", help="split by role through the MCQ_ABLATE_* builds (three compiles)")
     a = ap.parse_args()
+    if a.ways:
+        a.kernel = "mcq_eval_kernelILi0ELb0ELb1"
     with tempfile.TemporaryDirectory() as wd:
         co = code_object(a.lib, wd)
         name, ins = kernel_instructions(disassemble(co), a.kernel)

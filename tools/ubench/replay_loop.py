@@ -599,7 +599,7 @@ int main(int argc, char **argv) {
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=os.path.join(isa_hist.ROOT, "neuron_poker_amd", "libmcq_hip.so"))
-    ap.add_argument("--kernel", default="mcq_eval_kernelILi0ELb0")
+    ap.add_argument("--kernel", default="mcq_eval_kernelILi0ELb0ELb0")
     ap.add_argument("--nopp", type=int, default=5)
     ap.add_argument("--ndeal", type=int, default=5)
     ap.add_argument("--out", required=True)
