@@ -458,6 +458,51 @@ int mcqo_compare(const uint8_t *a, const uint8_t *b) {
 
 int mcqo_best_hand(const uint8_t *hands, int n, int *type, int *tie) { return best_hand(hands, n, type, tie); }
 
+/* Batch form of calc_score for sweeps over many 7-card hands: one ORDER-PRESERVING 64-bit score per hand.
+ * Bits 32..35 hold the type; below it the card_ranks tuple, entry i as (rank + 1) in the 4-bit field at bit
+ * 28 - 4 i (the wheel's -1 becomes 0), zero-padded on the right.  The longest tuple has 8 entries (straight flushes:
+ * 5 to 8, hand_evaluator.py:68-76).  The type follows the score tuple's python order ((1,) < (2,1,1) < (2,2,1) <
+ * (3,1) < (3,1,2) < (3,1,3) < (3,2) < (4,) < (5,)), so score_cmp(a, b) and the integers' order agree: a proper prefix
+ * is smaller than its extensions, and a field of zero can only be the wheel's closing -1, which a tuple carries
+ * exactly when it starts with the ace -- no tuple and its extension by -1 both occur.  A hand without a valid type
+ * scores UINT64_MAX. */
+static uint64_t pack_score(const score_t *s) {
+    if (s->type < 0 || s->nranks > 8) return ~0ull;
+    uint64_t v = (uint64_t)s->type << 32;
+    for (int i = 0; i < s->nranks; i++) v |= (uint64_t)(s->ranks[i] + 1) << (28 - 4 * i);
+    return v;
+}
+
+typedef struct {
+    const uint8_t *cards;
+    size_t begin, end;
+    uint64_t *out;
+} score_job_t;
+
+static void *score_worker(void *p) {
+    score_job_t *j = (score_job_t *)p;
+    score_t s;
+    for (size_t i = j->begin; i < j->end; i++) {
+        calc_score(j->cards + 7 * i, 7, &s);
+        j->out[i] = pack_score(&s);
+    }
+    return 0;
+}
+
+/* cards[n][7] -> out[n]; threads >= 1 (pthreads, contiguous shares), at most 64 */
+void mcqo_calc_score_batch(const uint8_t *cards, size_t n, uint64_t *out, int threads) {
+    if (threads < 1) threads = 1;
+    if (threads > 64) threads = 64;
+    pthread_t th[64];
+    score_job_t jobs[64];
+    for (int t = 0; t < threads; t++) {
+        jobs[t] = (score_job_t){cards, n * (size_t)t / (size_t)threads, n * (size_t)(t + 1) / (size_t)threads, out};
+        if (t > 0) pthread_create(&th[t], 0, score_worker, &jobs[t]);
+    }
+    score_worker(&jobs[0]);
+    for (int t = 1; t < threads; t++) pthread_join(th[t], 0);
+}
+
 /* mode 0: np.random.seed((uint32)seed) then the reference loop; mode 1: MCQ-CTR v5 with query id qid.
  * trace (optional): first `keep` iterations' hands [keep][n_players][7]; words (optional, mode 0): MT words
  * per kept iteration; total_words (optional). Returns 0, or -1 on invalid input. */

@@ -57,6 +57,8 @@ def lib():
         L.mcqo_ctr_stream.restype = None
         L.mcqo_calc_score.argtypes = [u8p, C.c_int, i32p]
         L.mcqo_calc_score.restype = None
+        L.mcqo_calc_score_batch.argtypes = [u8p, C.c_size_t, u64p, C.c_int]
+        L.mcqo_calc_score_batch.restype = None
         L.mcqo_compare.argtypes = [u8p, u8p]
         L.mcqo_compare.restype = C.c_int
         L.mcqo_best_hand.argtypes = [u8p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -122,6 +124,28 @@ def calc_score(cards):
     out = np.zeros(15, np.int32)
     lib().mcqo_calc_score(_p(c, C.c_uint8), len(c), _p(out, C.c_int32))
     return tuple(int(x) for x in out[1:1 + out[0]]), tuple(int(x) for x in out[5:5 + out[4]]), int(out[14])
+
+
+def pack_score(typ, ranks):
+    """The order-preserving integer of (type index, card_ranks tuple) that mcqo_calc_score_batch returns: the type at
+    bit 32, below it entry i as rank + 1 in the 4-bit field at bit 28 - 4 i, zero-padded on the right."""
+    assert 0 <= typ < len(TYPES) and len(ranks) <= 8 and all(-1 <= r <= 12 for r in ranks)
+    v = typ << 32
+    for i, r in enumerate(ranks):
+        v |= (r + 1) << (28 - 4 * i)
+    return v
+
+
+def score_type(scores):
+    return (np.asarray(scores, np.uint64) >> np.uint64(32)).astype(np.uint32)
+
+
+def score_batch(cards, threads=1):
+    """cards [n, 7] -> uint64 [n]: pack_score of every hand's calc_score, `threads` (at most 16) host threads."""
+    c = np.ascontiguousarray(cards, np.uint8).reshape(-1, 7)
+    out = np.zeros(len(c), np.uint64)
+    lib().mcqo_calc_score_batch(_p(c, C.c_uint8), len(c), _p(out, C.c_uint64), max(1, min(int(threads), 16)))
+    return out
 
 
 def compare(a, b):

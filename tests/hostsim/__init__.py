@@ -23,7 +23,7 @@ def lib():
     global _lib
     if _lib is None:
         if "MCQ_HOSTSIM_SO" not in os.environ and (not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS)):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized", "-shared", "-fPIC", "-o", _SO, _SRCS[0]])
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized", "-shared", "-fPIC", "-pthread", "-o", _SO, _SRCS[0]])
         L = C.CDLL(_SO)
         L.hs_select_pop.restype = C.c_uint32
         _lib = L
@@ -39,6 +39,16 @@ def eval7(cards):
     keys = np.zeros(len(cards), np.uint32)
     lib().hs_eval7(_p(cards, C.c_uint8), C.c_size_t(len(cards)), _p(keys, C.c_uint32))
     return keys
+
+
+def eval7_splits(cards, threads=1):
+    """Keys of 7-card hands evaluated under all 21 (hole, table) splits -> (keys [n] of the split eval7 takes, index of
+    the first hand whose splits disagree or None)."""
+    cards = np.ascontiguousarray(cards, np.uint8).reshape(-1, 7)
+    keys = np.zeros(len(cards), np.uint32)
+    lib().hs_eval7_splits.restype = C.c_size_t
+    bad = lib().hs_eval7_splits(_p(cards, C.c_uint8), C.c_size_t(len(cards)), _p(keys, C.c_uint32), C.c_int(threads))
+    return keys, (None if bad == len(cards) else int(bad))
 
 
 def key_type(keys):

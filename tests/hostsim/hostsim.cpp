@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <atomic>
+#include <thread>
 #include <vector>
 
 #include "../../neuron_poker_amd/csrc/mcq_device.hpp"
@@ -61,6 +63,48 @@ void hs_eval7(const uint8_t *cards, size_t n, uint32_t *keys) {
     }
 }
 uint32_t hs_key_type(uint32_t key) { return mcq_key_type(key); }
+
+// ... and of every hand under ALL 21 splits into (two hole cards, five table cards): keys[i] = the key of the split
+// hs_eval7 takes (hole = cards 0 and 1).  Returns the index of the first hand one of whose other twenty splits gives
+// a different key, n when there is none.  `threads` host threads (1..16) over contiguous shares.
+size_t hs_eval7_splits(const uint8_t *cards, size_t n, uint32_t *keys, int threads) {
+    const McqTables &t = luts(); /* filled before the threads start */
+    if (threads < 1) threads = 1;
+    if (threads > 16) threads = 16;
+    std::atomic<size_t> bad(n);
+    auto work = [&](size_t begin, size_t end) {
+        for (size_t i = begin; i < end; i++) {
+            McqCard c[7];
+            for (int k = 0; k < 7; k++) c[k] = mcq_card(cards[7 * i + k]);
+            uint32_t first = 0;
+            bool same = true;
+            for (int x = 0; x < 6; x++)
+                for (int y = x + 1; y < 7; y++) {
+                    McqBoard b;
+                    b.clear();
+                    for (int k = 0; k < 7; k++)
+                        if (k != x && k != y) b.add(c[k]);
+                    McqHole h;
+                    h.set(c[x], c[y]);
+                    McqFlushSel fs;
+                    fs.from_board(b);
+                    const uint32_t key = mcq_eval_key(b, fs, h, t.tf, t.tops, t.sd);
+                    if (x == 0 && y == 1) first = key;
+                    else same = same && key == first;
+                }
+            keys[i] = first;
+            if (!same) {
+                size_t cur = bad.load();
+                while (i < cur && !bad.compare_exchange_weak(cur, i)) {}
+            }
+        }
+    };
+    std::vector<std::thread> th;
+    for (int k = 1; k < threads; k++) th.emplace_back(work, n * (size_t)k / (size_t)threads, n * (size_t)(k + 1) / (size_t)threads);
+    work(0, n / (size_t)threads);
+    for (auto &x : th) x.join();
+    return bad.load();
+}
 
 uint32_t hs_select_pop(uint32_t *dlo, uint32_t *dhi, uint32_t k) { return mcq_select_pop(*dlo, *dhi, k, luts().sel8); }
 

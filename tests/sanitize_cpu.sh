@@ -40,13 +40,22 @@ for ret, name, args in decls:
 open(T + "/stub.cpp", "w").write("\n".join(out) + "\n}\n")
 PY
 gcc $F -o $T/libmcq_oracle.so $R/oracle/mcq_oracle.c -lpthread
-g++ $F -std=c++17 -Wno-unknown-pragmas -o $T/libmcq_hostsim.so $R/tests/hostsim/hostsim.cpp
+g++ $F -std=c++17 -Wno-unknown-pragmas -pthread -o $T/libmcq_hostsim.so $R/tests/hostsim/hostsim.cpp
 g++ $F -std=c++17 -Wno-unknown-pragmas -I$R/include -o $T/libmcq_san.so $T/stub.cpp $R/neuron_poker_amd/csrc/mcq_tables.cpp -lpthread
 cd $R
 LD_PRELOAD="$(gcc -print-file-name=libasan.so) $(gcc -print-file-name=libubsan.so)" ASAN_OPTIONS=detect_leaks=0 \
 MCQ_ORACLE_SO=$T/libmcq_oracle.so MCQ_HOSTSIM_SO=$T/libmcq_hostsim.so MCQ_LIBRARY=$T/libmcq_san.so MCQ_SAN_STUB=1 \
-python3 -m pytest tests/test_oracle_golden.py tests/test_lane_arithmetic_host.py tests/test_table_driver.py -x -q \
-  -k "not three_players_on_the_turn" -p no:cacheprovider "$@"
+python3 -m pytest tests/test_oracle_golden.py tests/test_lane_arithmetic_host.py tests/test_table_driver.py \
+  tests/test_evaluator_exhaustive_host.py tests/test_hot_boards_host.py -x -q \
+  -k "not three_players_on_the_turn and not every_hand_in_every_split" -p no:cacheprovider "$@"
+# (of the evaluator's sweep only test_a_slice_under_threads: six chunks, 2.3 M of the 133.8 M hands, a REDUCED slice)
+# ThreadSanitizer over the threaded sweep entries (hs_eval7_splits, mcqo_calc_score_batch), the same reduced slice
+FT="-O1 -g -fsanitize=thread -fno-omit-frame-pointer -shared -fPIC"
+gcc $FT -o $T/libmcq_oracle_tsan.so $R/oracle/mcq_oracle.c -lpthread
+g++ $FT -std=c++17 -Wno-unknown-pragmas -pthread -o $T/libmcq_hostsim_tsan.so $R/tests/hostsim/hostsim.cpp
+LD_PRELOAD="$(gcc -print-file-name=libtsan.so)" TSAN_OPTIONS="report_signal_unsafe=0 exitcode=66" \
+MCQ_ORACLE_SO=$T/libmcq_oracle_tsan.so MCQ_HOSTSIM_SO=$T/libmcq_hostsim_tsan.so \
+python3 -m pytest tests/test_evaluator_exhaustive_host.py -x -q -k "slice_under_threads" -p no:cacheprovider
 # ThreadSanitizer over the driver's threads (helper thread of the two-stream schedule, thread pool)
 g++ -O1 -g -fsanitize=thread -fno-omit-frame-pointer -shared -fPIC -std=c++17 -Wno-unknown-pragmas -I$R/include \
     -o $T/libmcq_tsan.so $T/stub.cpp $R/neuron_poker_amd/csrc/mcq_tables.cpp -lpthread

@@ -29,16 +29,44 @@ def u64(r):
     return r.view(np.uint64).reshape(-1, 13)
 
 
-def batch(runs, rng):
-    """one query per run count: players 1 + i % 10, street i % 4 (preflop, flop, turn, river)"""
+GRID = {(p, nb) for p in range(1, 11) for nb in (0, 3, 4, 5)}    # 40 (players, table cards) pairs = kernel instances
+
+
+def pair(g):
+    """grid cell g (mod 40): players 1 + g % 10 on street g // 10 -- unlike (1 + i % 10, i % 4), whose two coordinates
+    share the parity of i and so reach only 20 of the 40 cells"""
+    return 1 + g % 10, [0, 3, 4, 5][g // 10 % 4]
+
+
+def batch(runs, rng, cells=None):
+    """one query per run count; query i sits in grid cell cells[i] (default: i)"""
     hole, board, npl = [], [], []
     for i in range(len(runs)):
-        nb = [0, 3, 4, 5][i % 4]
+        p, nb = pair(i if cells is None else cells[i])
         c = rng.permutation(52)[:2 + nb]
         hole.append(c[:2])
         board.append(list(c[2:]) + [255] * (5 - nb))
-        npl.append(1 + i % 10)
-    return npa.pack_queries(hole, board, npl, list(runs))
+        npl.append(p)
+    q = npa.pack_queries(hole, board, npl, list(runs))
+    assert_grid(q)
+    return q
+
+
+def assert_grid(q):
+    """every batch of this file visits ALL 40 instances, each of them once with more than one task and once with a run
+    count that leaves a partly filled stream (not a multiple of 16)"""
+    raw = q.view(np.uint8).reshape(-1, 16)
+    cells = list(zip(raw[:, 8].tolist(), raw[:, 7].tolist()))
+    assert set(cells) == GRID, sorted(GRID - set(cells))
+    runs = q["runs"].astype(np.int64)
+    assert {c for c, r in zip(cells, runs) if r > 1024} == GRID
+    assert {c for c, r in zip(cells, runs) if r % 16} == GRID
+
+
+def grid_runs(extra, shift):
+    """-> (runs, cells): every cell with 1025 iterations (two tasks, the second one a single iteration), then the run
+    counts `extra` on cells spread over the grid (7 is coprime to 40) from `shift` on"""
+    return [1025] * 40 + list(extra), list(range(40)) + [(shift + 7 * j) % 40 for j in range(len(extra))]
 
 
 def tasks(q):
@@ -79,10 +107,12 @@ def test_general_path_at_every_cut_under_both_laws(monkeypatch):
     """mcq_eval_kernel<0|2, false> (MCQ_SPLIT_MAX=0) and <0|2, true> at the cuts 1 to 4, host and device entries; each
     query alone too, which the finest cut reaches whatever its run count"""
     rng = np.random.default_rng(2024)
-    q = batch(RUNS * 3, rng)                     # 36 queries, 99 tasks
+    runs, cells = grid_runs(RUNS + RUNS[:9], 3)  # 61 queries, 122 tasks: every cell, every run count of RUNS
+    q = batch(runs, rng, cells)
+    assert set(RUNS) <= set(runs) and int(tasks(q).sum()) == 122
     cus = n_cu()
     assert pick_split(q, cus, 4) == 4            # so MCQ_SPLIT_MAX=s really gives the cut s
-    assert all(pick_split(q[i:i + 1], cus, 4) == 4 for i in range(len(RUNS)))
+    assert all(pick_split(q[i:i + 1], cus, 4) == 4 for i in range(len(q)))
     want = {law: oracle(om, q, SEED) for law, om in LAWS}
     monkeypatch.setenv("MCQ_DIRECT_MAX_TASKS", "0")
     for s in range(5):
@@ -93,11 +123,11 @@ def test_general_path_at_every_cut_under_both_laws(monkeypatch):
                 e.set_dealing_law(law)
                 assert np.array_equal(u64(e.eval_batch(q, SEED, first_query_id=FQ)), want[law]), (s, law)
                 assert np.array_equal(device_entry(e, q, SEED), want[law]), (s, law, "device")
-                for i in range(len(RUNS)):
+                for i in range(len(q)):
                     got = u64(e.eval_batch(q[i:i + 1], SEED, first_query_id=FQ + i))
-                    assert np.array_equal(got, want[law][i:i + 1]), (s, law, RUNS[i])
+                    assert np.array_equal(got, want[law][i:i + 1]), (s, law, runs[i], pair(cells[i]))
                     got = device_entry(e, q[i:i + 1], SEED, FQ + i)
-                    assert np.array_equal(got, want[law][i:i + 1]), (s, law, RUNS[i], "device")
+                    assert np.array_equal(got, want[law][i:i + 1]), (s, law, runs[i], pair(cells[i]), "device")
         finally:
             e.close()
 
@@ -105,7 +135,9 @@ def test_general_path_at_every_cut_under_both_laws(monkeypatch):
 def test_replay_at_every_cut(monkeypatch):
     """mcq_eval_kernel<1, false> and <1, true>: replay mode's lanes take four iterations at a time, so its cut stops at 2"""
     rng = np.random.default_rng(77)
-    q = batch(RUNS * 3, rng)
+    runs, cells = grid_runs(RUNS + RUNS[:9], 5)
+    q = batch(runs, rng, cells)
+    assert set(RUNS) <= set(runs)
     want = oracle(O.MODE_MT, q, MT_SEED)
     monkeypatch.setenv("MCQ_DIRECT_MAX_TASKS", "0")
     for s in range(3):
@@ -114,9 +146,9 @@ def test_replay_at_every_cut(monkeypatch):
         try:
             got = u64(e.eval_batch(q, MT_SEED, first_query_id=FQ, mode=npa.MODE_REPLAY_MT19937))
             assert np.array_equal(got, want), s
-            for i in range(len(RUNS)):
+            for i in range(len(q)):
                 got = u64(e.eval_batch(q[i:i + 1], MT_SEED, first_query_id=FQ + i, mode=npa.MODE_REPLAY_MT19937))
-                assert np.array_equal(got, want[i:i + 1]), (s, RUNS[i])
+                assert np.array_equal(got, want[i:i + 1]), (s, runs[i], pair(cells[i]))
         finally:
             e.close()
 
@@ -126,6 +158,7 @@ def test_bulk_batches_under_both_laws(monkeypatch):
     rng = np.random.default_rng(5)
     runs = rng.choice(RUNS[:10], 1100)
     runs[::97] = 4097
+    runs[1000:1040] = 1025                       # query i sits in cell i % 40: every cell once with two tasks
     q = batch(runs, rng)
     monkeypatch.setenv("MCQ_DIRECT_MAX_TASKS", "0")
     e = npa.Engine(0)
@@ -147,8 +180,12 @@ def test_one_launch_kernel_under_both_laws(monkeypatch):
     monkeypatch.delenv("MCQ_SPLIT_MAX", raising=False)
     rng = np.random.default_rng(31)
     short = [r for r in RUNS if r <= 8 * 1024] + [8192]
-    few = batch(short * 3, rng)
-    many = batch(rng.choice(short, 200), rng)
+    runs, cells = grid_runs(short * 2, 11)       # 64 queries: laid out by the host
+    few = batch(runs, rng, cells)
+    runs_many = rng.choice(short, 200)
+    runs_many[160:200] = 1025
+    many = batch(runs_many, rng)
+    assert set(short) <= set(runs) and len(few) < 128 <= len(many)
     assert int(tasks(few).max()) <= 8 and int(tasks(many).max()) <= 8
     e = npa.Engine(0)
     try:
@@ -158,8 +195,8 @@ def test_one_launch_kernel_under_both_laws(monkeypatch):
                 want = oracle(om, q, SEED)
                 assert np.array_equal(u64(e.eval_batch(q, SEED, first_query_id=FQ)), want), (law, len(q))
             want = oracle(om, few, SEED)
-            for i in range(len(short)):
+            for i in range(len(few)):
                 got = u64(e.eval_batch(few[i:i + 1], SEED, first_query_id=FQ + i))
-                assert np.array_equal(got, want[i:i + 1]), (law, short[i])
+                assert np.array_equal(got, want[i:i + 1]), (law, runs[i], pair(cells[i]))
     finally:
         e.close()
