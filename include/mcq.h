@@ -159,6 +159,16 @@ MCQ_API int mcq_eval_one(mcq_ctx *ctx, const mcq_query *q, uint64_t seed, int mo
 MCQ_API int mcq_eval_batch_ext(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
                        uint64_t first_query_id, int mode, mcq_result *out);
 
+/* mcq_eval_batch_ext writing mcq_result_ways rows: out[i].r is bit for bit what mcq_eval_batch_ext writes for the same
+ * arguments, and tie_ways[k - 2] counts the iterations in which hero is best together with k - 1 OTHER hands -- further
+ * known hands, hands drawn from a range and random opponents alike, each compared by its ranking key (a known hand that
+ * lost a card to an earlier ranged hand, montecarlo_python.py:154-161, is evaluated with the cards it names, as the
+ * credited tallies evaluate it).  Every contract of mcq_eval_batch_ext holds: both modes, validation first and MCQ_EINVAL
+ * leaves out untouched, MCQ_EBUSY, the undealable range, the refusal under MCQ_LAW_UNIFORM, sharding by first_query_id,
+ * the one-launch path for up to eight small queries. */
+MCQ_API int mcq_eval_batch_ext_ways(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
+                                    uint64_t first_query_id, int mode, mcq_result_ways *out);
+
 /* Parity mode coupled to numpy's GLOBAL random state, as consecutive reference calls are: the n
  * queries consume ONE MT19937 stream in order.  mt_key[624] / *mt_pos are numpy's state words and position
  * (np.random.get_state()[1], [2]); on return they hold the state after the last query, so
@@ -191,7 +201,8 @@ MCQ_API int mcq_eval_batch_device_small(mcq_ctx *ctx, const void *d_queries, siz
  * the streams with a pair of waves per query).  The device entry (MCQ_MODE_PHILOX, asynchronous) cannot see the queries:
  * it prices them on the device and runs the evaluation kernel, cut finer for up to 1024 small queries, whatever their
  * size; d_results -> mcq_result_ways[n].
- * Extended queries, the exact enumerations and mcq_multi_* have no split-pot form. */
+ * Extended queries have their own split-pot entries, mcq_eval_batch_ext_ways and mcq_exact_batch_ext_ways (below).  The
+ * plain exact enumeration, the extended one with two random opponents and mcq_multi_* have no split-pot form. */
 MCQ_API int mcq_eval_batch_ways(mcq_ctx *ctx, const mcq_query *q, size_t n, uint64_t seed, uint64_t first_query_id, int mode,
                                 mcq_result_ways *out);
 MCQ_API int mcq_eval_batch_device_ways(mcq_ctx *ctx, const void *d_queries, size_t n, uint64_t seed, uint64_t first_query_id,
@@ -243,6 +254,20 @@ typedef struct mcq_exact_prob {
 } mcq_exact_prob;      /* 88 bytes */
 MCQ_API int mcq_exact_batch_ext(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
                                 mcq_exact_prob *prob, mcq_result *weights);
+
+/* The same enumeration with the ties split by how many hands share the pot, for records with AT MOST ONE random
+ * opponent (hand against known hands; one opponent, ranged or not): prob[i].p is what mcq_exact_batch_ext returns,
+ * prob[i].tie_ways[k - 2] = P(hero is best together with k - 1 other hands), k = 2..10, and hero's exact pot share is
+ * p.win + sum_k tie_ways[k - 2] / k.  weights (may be NULL) is always defined here -- one random opponent at most means
+ * one common total -- as mcq_result_ways rows: r as mcq_exact_batch_ext's weights, sum(tie_ways) == r.tie exactly.
+ * Refused with MCQ_EINVAL, nothing launched: whatever mcq_exact_batch_ext refuses, and TWO random opponents (the
+ * per-first-hand normalisers of that enumeration would each need nine more sums). */
+typedef struct mcq_exact_prob_ways {
+    mcq_exact_prob p;
+    double tie_ways[9];
+} mcq_exact_prob_ways; /* 160 bytes */
+MCQ_API int mcq_exact_batch_ext_ways(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                                     mcq_exact_prob_ways *prob, mcq_result_ways *weights);
 
 /* Select the dealing law used by MCQ_MODE_PHILOX on this context (MCQ_LAW_*).  Extended queries
  * (mcq_eval_batch_ext) are dealt by the reference's law only: under MCQ_LAW_UNIFORM that call gives MCQ_EINVAL. */

@@ -34,6 +34,9 @@ EXACT_PROB_DTYPE = np.dtype([("win", "<f8"), ("tie", "<f8"), ("by_type", "<f8", 
 assert TABLES_CONFIG_DTYPE.itemsize == 224 and EXACT_PROB_DTYPE.itemsize == 88
 assert QUERY_DTYPE.itemsize == 16 and RESULT_DTYPE.itemsize == 104 and QUERY_EXT_DTYPE.itemsize == 304
 assert RESULT_WAYS_DTYPE.itemsize == 176
+# mcq_exact_prob_ways: mcq_exact_prob, then tie_ways[k - 2] = P(k hands share the pot)
+EXACT_PROB_WAYS_DTYPE = np.dtype([("p", EXACT_PROB_DTYPE), ("tie_ways", "<f8", (9,))])
+assert EXACT_PROB_WAYS_DTYPE.itemsize == 160
 ALL_CLASSES = np.array([0xFFFFFFFF] * 5 + [0x1FF], np.uint32)  # 169 bits
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -108,6 +111,10 @@ def load_library():
         L.mcq_eval_batch_ways.restype = C.c_int
         L.mcq_eval_batch_device_ways.argtypes = [vp, vp, sz, u64, u64, vp, vp]
         L.mcq_eval_batch_device_ways.restype = C.c_int
+        L.mcq_eval_batch_ext_ways.argtypes = [vp, vp, vp, sz, u64, u64, C.c_int, vp]
+        L.mcq_eval_batch_ext_ways.restype = C.c_int
+        L.mcq_exact_batch_ext_ways.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
+        L.mcq_exact_batch_ext_ways.restype = C.c_int
         L.mcq_eval_batch_device_small.argtypes = [vp, vp, sz, u64, u64, vp, vp]
         L.mcq_eval_batch_device_small.restype = C.c_int
         L.mcq_showdown.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp]
@@ -195,11 +202,18 @@ def pack_queries(hole, board, n_players, runs):
     return q
 
 
-def pot_share(rows):
+def pot_share(rows, exact=False):
     """Hero's expected share of the pot, float64 [n], from rows of RESULT_WAYS_DTYPE (or an [n, 22] integer matrix):
     (win + sum_k tie_ways[k - 2] / k) / runs, k = 2..10 hands sharing the pot.  The reference's equity credits every tie
-    to hero in full: (win + tie) / runs."""
+    to hero in full: (win + tie) / runs.  The rows may be Monte-Carlo tallies or the integer weights of
+    Engine.exact_ext_ways; exact=True returns a list of fractions.Fraction instead, exact for such weights."""
     t = np.ascontiguousarray(rows)
+    if exact:
+        from fractions import Fraction
+        if t.dtype == RESULT_WAYS_DTYPE:
+            t = t.view(np.uint64)
+        return [(int(r[2]) + sum(Fraction(int(r[13 + j]), j + 2) for j in range(9))) / max(int(r[0]), 1)
+                for r in t.reshape(-1, 22)]
     if t.dtype == RESULT_WAYS_DTYPE:
         t = t.view(np.uint64)
     t = t.reshape(-1, 22).astype(np.float64)
@@ -374,6 +388,39 @@ class Engine:
         if rc:
             _raise(rc)
         return prob, weights
+
+    def exact_ext_ways(self, queries, ext, law="reference"):
+        """exact_ext with the ties split by the hands that share the pot (mcq_exact_batch_ext_ways; at most ONE random
+        opponent).  -> (prob, weights): EXACT_PROB_WAYS_DTYPE rows (p as exact_ext's prob, tie_ways[9]) and
+        RESULT_WAYS_DTYPE rows of integer weights, always defined; pot_share(weights, exact=True) is the exact share."""
+        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
+        if code is None:
+            raise ValueError("law must be 'reference' or 'uniform'")
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        prob = np.zeros(len(q), EXACT_PROB_WAYS_DTYPE)
+        weights = np.zeros(len(q), RESULT_WAYS_DTYPE)
+        rc = self._lib.mcq_exact_batch_ext_ways(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, prob.ctypes.data,
+                                                weights.ctypes.data)
+        if rc:
+            _raise(rc)
+        return prob, weights
+
+    def eval_batch_ext_ways(self, queries, ext, seed, first_query_id=0, mode=MODE_PHILOX):
+        """eval_batch_ext with the ties split by the hands that share the pot (mcq_eval_batch_ext_ways).  -> array of
+        RESULT_WAYS_DTYPE: the fields of RESULT_DTYPE exactly as eval_batch_ext returns them, then tie_ways[9]."""
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        out = np.zeros(len(q), RESULT_WAYS_DTYPE)
+        rc = self._lib.mcq_eval_batch_ext_ways(self._ctx, q.ctypes.data, e.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
+                                               int(first_query_id) & (2 ** 64 - 1), int(mode), out.ctypes.data)
+        if rc:
+            _raise(rc)
+        return out
 
     def eval_batch_ext(self, queries, ext, seed, first_query_id=0, mode=MODE_PHILOX):
         """queries with one QUERY_EXT_DTYPE record each (ranges, hero range, ghost cards, second known hand)."""

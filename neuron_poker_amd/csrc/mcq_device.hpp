@@ -1187,10 +1187,19 @@ struct McqExtReplayDraws { /* accepted draws from the host, all in list.pop orde
 // hands; cards: the 52-entry card table; wc.list: the query's candidate lists,
 // wc: the known hands and the list sizes.  Returns false when a range could not be dealt within
 // MCQ_EXT_MAX_TRIALS attempts.
-template <class Draws, bool LDS_LIST = false /* the candidate lists lie in LDS: see mcq_iteration_ext_fast */>
+// Acc = McqLaneAccWays: the split-pot form, as in mcq_iteration -- the iterations hero does not lose are split by how many
+// OTHER hands (known, ranged or random alike, each by its key) equal hero's.  A stream of the extended path holds
+// sixteen or two iterations (mcq_ext_stream_iters), and a lane runs one stream per task: a 6-bit field never overflows.
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(MCQ_EXT_DEAL_HOOK)
+#define MCQ_EXT_DEALT(h, c1, c2) MCQ_EXT_DEAL_HOOK(h, c1, c2) /* host test builds only: the hands of the iteration */
+#else
+#define MCQ_EXT_DEALT(h, c1, c2) ((void)0)
+#endif
+template <class Draws, bool LDS_LIST = false /* the candidate lists lie in LDS: see mcq_iteration_ext_fast */, class Acc = McqLaneAcc>
 MCQ_HD bool mcq_iteration_ext(const McqExtCtx &qc, const McqExtWaveCtx &wc, Draws &dr, const McqCard *cards,
                               const uint32_t *sel8, uint16_t *ids, uint32_t ids_stride,
-                              const uint32_t *tf, const uint32_t *tops, const uint32_t *sd, McqLaneAcc &acc) {
+                              const uint32_t *tf, const uint32_t *tops, const uint32_t *sd, Acc &acc) {
+    static_assert(MCQ_STREAM_ITERS < 64u && MCQ_EXT_SHORT_STREAM < 64u, "6-bit fields of the lane accumulator");
     uint32_t dlo = qc.deck_lo, dhi = qc.deck_hi;
     bool dealt = true;
     uint32_t li = 0; /* candidate list of the next known hand given as a range; the opponents' comes after them */
@@ -1246,22 +1255,29 @@ MCQ_HD bool mcq_iteration_ext(const McqExtCtx &qc, const McqExtWaveCtx &wc, Draw
     for (uint32_t k = 0; k < qc.n_deal; k++) {
         const uint32_t L = mcq_popc(dlo) + mcq_popc(dhi);
         const uint32_t c = mcq_select_pop(dlo, dhi, dr.table(k, L - 1u), sel8);
+        MCQ_EXT_DEALT(0x100u + k, c, 0u);
         b.add(cards[c < 52u ? c : 0u]);
     }
     McqFlushSel fs;
     fs.from_board(b);
     uint32_t hk = 0, best = 0;
+    uint32_t n_equal = 0; /* (split-pot form only) other hands whose key equals hero's */
     for (uint32_t h = 0; h < qc.n_players; h++) {
         const uint32_t v = ids[h * ids_stride];
+        MCQ_EXT_DEALT(h, v & 0xFFu, (v >> 8) & 0xFFu);
         McqHole hh;
         hh.set(cards[v & 0xFFu], cards[(v >> 8) & 0xFFu]);
         const uint32_t k = mcq_eval_key(b, fs, hh, tf, tops, sd);
         if (h == 0) hk = k;
-        else best = k > best ? k : best;
+        else {
+            best = k > best ? k : best;
+            if (Acc::kWays) n_equal += k == hk ? 1u : 0u; /* (hero comes first: hk is known) */
+        }
     }
     uint64_t won = hk >= best ? 1u : 0u;
     acc.types += won << (6u * (hk >> MCQ_KEY_SHIFT));
-    acc.tie += hk == best ? 1u : 0u;
+    if constexpr (Acc::kWays) acc.ways += won << (6u * n_equal); /* pot shared by 1 + n_equal hands */
+    else acc.tie += hk == best ? 1u : 0u;
     return dealt;
 }
 
@@ -1277,10 +1293,11 @@ MCQ_HD bool mcq_iteration_ext(const McqExtCtx &qc, const McqExtWaveCtx &wc, Draw
 // (LDS_LIST: the caller knows the candidate list lies in LDS -- staged by the block -- so a trial reads it with a
 // 32-bit LDS address instead of through a generic pointer: a flat load waits for both memory counters and takes
 // several times as long, in a loop where every trial is one dependent chain word -> index -> entry -> test.)
-template <class Draws, bool PIN = true, bool LDS_LIST = false>
+// (Acc: as mcq_iteration_ext -- the split-pot form counts the equal keys where the maximum is taken.)
+template <class Draws, bool PIN = true, bool LDS_LIST = false, class Acc = McqLaneAcc>
 MCQ_HD bool mcq_iteration_ext_fast(const McqExtCtx &qc, const McqExtWaveCtx &wc, Draws &dr, const McqCard *cards,
                                    const uint32_t *sel8, const uint32_t *tf, const uint32_t *tops, const uint32_t *sd,
-                                   McqLaneAcc &acc) {
+                                   Acc &acc) {
     uint64_t deck = ((uint64_t)qc.fdeck_hi << 32) | qc.fdeck_lo;
     const uint32_t n = wc.cnt[0];
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1312,6 +1329,7 @@ MCQ_HD bool mcq_iteration_ext_fast(const McqExtCtx &qc, const McqExtWaveCtx &wc,
         if (ok && c2 > c1) c2 = mcq_deck_next(dlo, dhi, c2); /* deck.pop(r2) after deck.pop(r1), l.178-179 */       \
         /* (c1, c2 are entries of the list -- card ids below 52 -- or, with an empty trial budget, zero: no clamp) */ \
         deck &= ~(((uint64_t)1 << c1) | ((uint64_t)1 << c2));                                                       \
+        MCQ_EXT_DEALT(P + 1u, c1, c2);                                                                              \
         opp[P].set(cards[c1], cards[c2]);                                                                           \
     }
     MCQ_XOPP(0) MCQ_XOPP(1) MCQ_XOPP(2) MCQ_XOPP(3) MCQ_XOPP(4) MCQ_XOPP(5) MCQ_XOPP(6) MCQ_XOPP(7) MCQ_XOPP(8)
@@ -1322,22 +1340,26 @@ MCQ_HD bool mcq_iteration_ext_fast(const McqExtCtx &qc, const McqExtWaveCtx &wc,
     McqBoard b = qc.board;
     for (uint32_t k = 0; k < qc.n_deal; k++, L--) {
         const uint32_t c = mcq_select_pop(dlo, dhi, dr.table(k, L - 1u), sel8);
+        MCQ_EXT_DEALT(0x100u + k, c, 0u);
         b.add(cards[c < 52u ? c : 0u]);
     }
     McqFlushSel fs;
     fs.from_board(b);
     const uint32_t hk = mcq_eval_key(b, fs, qc.hero, tf, tops, sd);
     uint32_t best = 0;
+    uint32_t n_equal = 0; /* (split-pot form only) opponents whose key equals hero's */
     const uint32_t n_opp_e = PIN ? mcq_opaque_uniform(qc.n_players - 1u) : qc.n_players - 1u;
 #define MCQ_XEVAL(P)                                                  \
     if (P < n_opp_e) {                                                \
         const uint32_t k = mcq_eval_key(b, fs, opp[P], tf, tops, sd); \
+        if (Acc::kWays) n_equal += k == hk ? 1u : 0u;                 \
         best = k > best ? k : best;                                   \
     }
     MCQ_XEVAL(0) MCQ_XEVAL(1) MCQ_XEVAL(2) MCQ_XEVAL(3) MCQ_XEVAL(4) MCQ_XEVAL(5) MCQ_XEVAL(6) MCQ_XEVAL(7) MCQ_XEVAL(8)
 #undef MCQ_XEVAL
     uint64_t won = hk >= best ? 1u : 0u;
     acc.types += won << (6u * (hk >> MCQ_KEY_SHIFT));
-    acc.tie += hk == best ? 1u : 0u;
+    if constexpr (Acc::kWays) acc.ways += won << (6u * n_equal); /* pot shared by 1 + n_equal hands */
+    else acc.tie += hk == best ? 1u : 0u;
     return dealt;
 }

@@ -149,6 +149,7 @@ MCQ_HD uint32_t mcq_exact_w2(bool ref_law, uint32_t r1, uint32_t r2) {
 }
 
 struct McqExactAcc { /* one table completion, one lane: weights of strict wins, ties, everything */
+    static constexpr bool kWays = false;
     uint32_t win, tie, tot;
 };
 

@@ -125,6 +125,30 @@ MCQ_HD uint32_t mcq_exact_ext_known_best(const McqExactExtQuery &e, const McqExa
     return best;
 }
 
+// Split-pot form (kinds 0 and 1: at most one random opponent).  The tie weights are split by k = the hands that share
+// the pot, hero included: the known hands whose key equals hero's come from the same keys as the best of them, and the
+// one candidate hand adds itself when its own key equals hero's.  Per completion the known hands' count n_eq is
+// wave-uniform, so a lane keeps ONE further sum -- tie_c, the ties in which the candidate's key equals hero's: those are
+// shared by 2 + n_eq hands, the other ties (tie - tie_c: the candidate below hero, a known hand level) by 1 + n_eq.
+MCQ_HD uint32_t mcq_exact_ext_known_best_eq(const McqExactExtQuery &e, const McqExactBoard &bd, const uint32_t *tf,
+                                            const uint32_t *tops, const uint32_t *sd, uint32_t &n_eq) {
+    uint32_t best = 0;
+    n_eq = 0;
+    for (uint32_t h = 0; h < e.n_known; h++) {
+        McqHole kh;
+        kh.set(mcq_card(e.known[h] & 0xFFu), mcq_card(e.known[h] >> 8));
+        const uint32_t k = mcq_eval_key(bd.b, bd.fs, kh, tf, tops, sd);
+        best = k > best ? k : best;
+        n_eq += k == bd.hero_key ? 1u : 0u;
+    }
+    return best;
+}
+struct McqExactAccWays {
+    static constexpr bool kWays = true;
+    uint32_t win, tie, tot;
+    uint32_t tie_c; /* part of `tie` in which the candidate hand's own key equals hero's */
+};
+
 struct McqExactExtSums { /* 64-bit: a first hand's sums over all completions */
     unsigned long long win, tie, tot, type[9];
 };
@@ -138,6 +162,20 @@ MCQ_HD uint32_t mcq_exact_ext_lone(const McqExactExtQuery &e, uint32_t idx, cons
     McqExactBoard bd;
     mcq_exact_board(e.b, pos, sel8, tf, tops, sd, bd);
     const uint32_t kb = mcq_exact_ext_known_best(e, bd, tf, tops, sd);
+    const uint32_t w = !e.b.ref_law || bd.u > 0u ? 1u : 0u;
+    acc.win += kb < bd.hero_key ? w : 0u;
+    acc.tie += kb == bd.hero_key ? w : 0u;
+    acc.tot += w;
+    return mcq_key_type(bd.hero_key);
+}
+// The same, split: n_eq = the known hands level with hero (the pot of a tie is shared by 1 + n_eq hands).
+MCQ_HD uint32_t mcq_exact_ext_lone_ways(const McqExactExtQuery &e, uint32_t idx, const uint32_t *sel8, const uint32_t *tf,
+                                        const uint32_t *tops, const uint32_t *sd, McqExactAcc &acc, uint32_t &n_eq) {
+    uint32_t pos[5];
+    mcq_exact_unrank(idx, e.b.L, e.b.k, pos);
+    McqExactBoard bd;
+    mcq_exact_board(e.b, pos, sel8, tf, tops, sd, bd);
+    const uint32_t kb = mcq_exact_ext_known_best_eq(e, bd, tf, tops, sd, n_eq);
     const uint32_t w = !e.b.ref_law || bd.u > 0u ? 1u : 0u;
     acc.win += kb < bd.hero_key ? w : 0u;
     acc.tie += kb == bd.hero_key ? w : 0u;
@@ -158,15 +196,18 @@ MCQ_HD void mcq_exact_ext_cb_table(const McqExactExtQuery &e, const uint8_t *r_i
 // rem_pos: the m cards left, pair_xy as in mcq_exact.hpp), each raised to the known hands' best kb; cb_tab from
 // mcq_exact_ext_cb_table.  One opponent (keys == nullptr): the outcome is tallied.  Two opponents: key and packed record
 // are stored for pass B.
+// Acc = McqExactAccWays (one opponent only): tie_c is kept beside the tallies.
+template <class Acc>
 MCQ_HD void mcq_exact_ext_pass_a(const McqExactExtQuery &e, const McqExactBoard &bd, uint32_t kb, uint32_t lane,
                                  uint32_t n_lanes, const uint16_t *pair_xy, const McqCard *rem_card, const uint32_t *rem_pos,
                                  const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops, const uint32_t *sd,
-                                 uint32_t *keys, uint32_t *rec, McqExactAcc &acc) {
+                                 uint32_t *keys, uint32_t *rec, Acc &acc) {
     for (uint32_t i = lane; i < e.n_pairs; i += n_lanes) {
         const uint32_t xy = pair_xy[i], x = xy & 0xFFu, y = xy >> 8;
         McqHole h;
         h.set(rem_card[x], rem_card[y]);
         uint32_t key = mcq_eval_key(bd.b, bd.fs, h, tf, tops, sd);
+        const bool level = key == bd.hero_key; /* (split-pot form only) */
         key = key > kb ? key : kb;
         const uint32_t pa = rem_pos[x], pb = rem_pos[y];
         const uint32_t r = mcq_exact_ext_pack(pa, pb, bd.top, e.b.k != 0u, cb_tab[pb * (pb - 1u) / 2u + pa]);
@@ -179,6 +220,7 @@ MCQ_HD void mcq_exact_ext_pass_a(const McqExactExtQuery &e, const McqExactBoard 
             acc.win += key < bd.hero_key ? w : 0u;
             acc.tie += key == bd.hero_key ? w : 0u;
             acc.tot += w;
+            if constexpr (Acc::kWays) acc.tie_c += level && key == bd.hero_key ? w : 0u;
         }
     }
 }

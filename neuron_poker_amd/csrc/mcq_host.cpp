@@ -961,9 +961,13 @@ int mcq_eval_one(mcq_ctx *c, const mcq_query *q, uint64_t seed, int mode, mcq_re
     return mcq_eval_batch(c, q, 1, seed, 0, mode, out);
 }
 
-int mcq_eval_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
-                       uint64_t first_query_id, int mode, mcq_result *out) {
-    ABI_GUARD_BEGIN
+}  // extern "C"
+
+/* mcq_eval_batch_ext and mcq_eval_batch_ext_ways: rw = 64-bit words of a result row (out -> rows of that length) */
+static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
+                               uint64_t first_query_id, int mode, void *out, uint32_t rw) {
+    const bool ways = rw == kWaysWords;
+    const size_t row_bytes = (size_t)rw * 8u;
     if (mode != MCQ_MODE_PHILOX && mode != MCQ_MODE_REPLAY_MT19937) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: bad mode");
     if (n == 0) return MCQ_OK;
     if (!c) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: null context");
@@ -995,7 +999,7 @@ int mcq_eval_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext,
     MCQ_ENTER(c, "mcq_eval_batch_ext");
     McqDeviceScope dev_(c->device);
     HIP_TRY(dev_.err);
-    HIP_TRY(c->h_res.reserve(n * sizeof(mcq_result)));
+    HIP_TRY(c->h_res.reserve(n * row_bytes));
     if (mode == MCQ_MODE_PHILOX && c->ext_small && n <= MCQ_EXT_SMALL_Q && lists_stride <= MCQ_EXT_SMALL_LISTS &&
         most_tasks <= MCQ_EXT_SMALL_TASKS && !stream_capturing(c->stream)) {
         /* what a decision of the reference's agents asks for -- one ranged query of a thousand iterations -- in ONE
@@ -1023,7 +1027,7 @@ int mcq_eval_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext,
             for (uint32_t p = 0; p < parts; p++) karg.blk[n_blocks++] = (uint32_t)i | (p << 8) | (parts << 16) | (wpb << 24);
         }
         first_block[n] = n_blocks;
-        HIP_TRY(c->h_res.reserve(MCQ_EXT_SMALL_BLOCKS * sizeof(mcq_result)));
+        HIP_TRY(c->h_res.reserve(MCQ_EXT_SMALL_BLOCKS * row_bytes));
         int rc = flag_ready(c);
         if (rc) return rc;
         const uint32_t ticket = next_ticket(c);
@@ -1032,28 +1036,29 @@ int mcq_eval_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext,
         c->last_ms = 0.f;
         HIP_TRY(mcq_launch_eval_ext_small(&karg, n_blocks, (mcq_result *)c->h_res.dev, seed, first_query_id, c->d_luts,
                                           (uint32_t *)c->d_done.p, (uint32_t *)c->h_flag.dev, ticket, c->stream,
-                                          timed ? c->ev0[slot] : nullptr, timed ? c->ev1[slot] : nullptr));
+                                          timed ? c->ev0[slot] : nullptr, timed ? c->ev1[slot] : nullptr, ways));
         if (timed) c->n_timed++;
         rc = wait_ticket(c, ticket, nullptr);
         if (rc) return rc;
         if (timed && kernel_times_impl(c, &c->last_ms, 1) != 1) c->last_ms = 0.f;
-        const uint64_t *hr = (const uint64_t *)c->h_res.p; /* one 13-word row per block */
+        const uint64_t *hr = (const uint64_t *)c->h_res.p; /* one row (13 or 22 words) per block */
         static_assert(sizeof(mcq_result) == 13 * sizeof(uint64_t), "result row");
-        for (size_t i = 0; i < n; i++) {
-            uint64_t row[13] = {q[i].runs};
-            for (uint32_t b = first_block[i]; b < first_block[i + 1]; b++) {
-                if (hr[13u * b] != q[i].runs)
+        for (size_t i = 0; i < n; i++) /* all rows first: an undealable range leaves `out` untouched */
+            for (uint32_t b = first_block[i]; b < first_block[i + 1]; b++)
+                if (hr[(size_t)rw * b] != q[i].runs)
                     return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: a range cannot be dealt from the remaining cards");
-                for (int k = 1; k < 13; k++) row[k] += hr[13u * b + k];
-            }
-            memcpy(&out[i], row, sizeof row);
+        for (size_t i = 0; i < n; i++) {
+            uint64_t row[kWaysWords] = {q[i].runs};
+            for (uint32_t b = first_block[i]; b < first_block[i + 1]; b++)
+                for (uint32_t k = 1; k < rw; k++) row[k] += hr[(size_t)rw * b + k];
+            memcpy(static_cast<uint8_t *>(out) + i * row_bytes, row, row_bytes);
         }
         return MCQ_OK;
     }
     HIP_TRY(c->h_q.reserve(n * (sizeof(mcq_query) + sizeof(mcq_query_ext))));
     HIP_TRY(c->d_q.reserve(n * sizeof(mcq_query)));
     HIP_TRY(c->d_ext.reserve(n * sizeof(mcq_query_ext)));
-    HIP_TRY(c->d_res.reserve(n * sizeof(mcq_result)));
+    HIP_TRY(c->d_res.reserve(n * row_bytes));
     c->res_clean = 0;
     HIP_TRY(c->scratch[0].prefix.reserve((n + 3) * sizeof(uint64_t)));
     uint8_t *hq = (uint8_t *)c->h_q.p;
@@ -1080,7 +1085,7 @@ int mcq_eval_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext,
         HIP_TRY(hipMemcpyAsync(c->d_off.p, off, n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     }
     HIP_TRY(mcq_launch_prep_ext((const mcq_query *)c->d_q.p, (const mcq_query_ext *)c->d_ext.p, (uint32_t)n, mode,
-                                (mcq_result *)c->d_res.p, (uint64_t *)c->scratch[0].prefix.p, c->stream));
+                                (mcq_result *)c->d_res.p, (uint64_t *)c->scratch[0].prefix.p, c->stream, rw));
     const int slot = (int)(c->n_timed % mcq_ctx::kRing);
     hipEvent_t t0 = c->timing ? c->ev0[slot] : nullptr; /* parity mode: the timed region starts in front of the stream walk */
     if (mode == MCQ_MODE_REPLAY_MT19937) {
@@ -1090,7 +1095,7 @@ int mcq_eval_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext,
                                         (uint32_t)(seed + first_query_id), (uint8_t *)c->d_draws.p, (const uint64_t *)c->d_off.p,
                                         (mcq_result *)c->d_res.p,
                                         reinterpret_cast<uint32_t *>((uint64_t *)c->scratch[0].prefix.p + n + 2), (uint32_t)c->n_cu,
-                                        c->stream));
+                                        c->stream, rw));
     }
     if (mode == MCQ_MODE_PHILOX) { /* the candidate lists of the ranges, once per query */
         HIP_TRY(c->d_lists.reserve(n * (size_t)lists_stride * MCQ_EXT_LIST_STRIDE * sizeof(uint16_t)));
@@ -1102,18 +1107,33 @@ int mcq_eval_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext,
                                 (const uint64_t *)c->scratch[0].prefix.p, (mcq_result *)c->d_res.p, seed, first_query_id, c->d_luts,
                                 (const uint8_t *)c->d_draws.p, (const uint64_t *)c->d_off.p, (const uint16_t *)c->d_lists.p,
                                 (const uint32_t *)c->d_cnts.p, lists_stride, grid, block, c->stream,
-                                t0, c->timing ? c->ev1[slot] : nullptr));
+                                t0, c->timing ? c->ev1[slot] : nullptr, ways));
     if (c->timing) c->n_timed++;
-    HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * sizeof(mcq_result), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * row_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (!c->timing || kernel_times_impl(c, &c->last_ms, 1) != 1) c->last_ms = 0.f;
-    const mcq_result *hr = (const mcq_result *)c->h_res.p;
-    for (size_t i = 0; i < n; i++)
-        if (hr[i].runs != q[i].runs || hr[i].passes == ~0ull) /* (parity mode: the stream walk marks such a query) */
+    const uint64_t *hr = (const uint64_t *)c->h_res.p;
+    for (size_t i = 0; i < n; i++) /* word 0 runs, word 1 passes (parity mode: the stream walk marks such a query) */
+        if (hr[(size_t)rw * i] != q[i].runs || hr[(size_t)rw * i + 1u] == ~0ull)
             return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: a range cannot be dealt from the remaining cards");
-    memcpy(out, hr, n * sizeof(mcq_result));
+    memcpy(out, hr, n * row_bytes);
     return MCQ_OK;
+}
+
+extern "C" {
+
+int mcq_eval_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
+                       uint64_t first_query_id, int mode, mcq_result *out) {
+    ABI_GUARD_BEGIN
+    return eval_batch_ext_impl(c, q, ext, n, seed, first_query_id, mode, out, kPlainWords);
     ABI_GUARD_END("mcq_eval_batch_ext")
+}
+
+int mcq_eval_batch_ext_ways(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
+                            uint64_t first_query_id, int mode, mcq_result_ways *out) {
+    ABI_GUARD_BEGIN
+    return eval_batch_ext_impl(c, q, ext, n, seed, first_query_id, mode, out, kWaysWords);
+    ABI_GUARD_END("mcq_eval_batch_ext_ways")
 }
 
 int mcq_eval_batch_numpy_stream(mcq_ctx *c, const mcq_query *q, size_t n, uint32_t *mt_key, uint32_t *mt_pos,
@@ -1229,10 +1249,14 @@ int mcq_exact_batch(mcq_ctx *c, const mcq_query *q, size_t n, int law, mcq_resul
     ABI_GUARD_END("mcq_exact_batch")
 }
 
-int mcq_exact_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, mcq_exact_prob *prob,
-                        mcq_result *weights) {
-    ABI_GUARD_BEGIN
-    static const char *who = "mcq_exact_batch_ext";
+}  // extern "C"
+
+/* mcq_exact_batch_ext and mcq_exact_batch_ext_ways: rw = 64-bit words of a weight row; prob -> mcq_exact_prob or
+ * mcq_exact_prob_ways, weights -> rows of rw words */
+static int exact_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, void *prob,
+                                void *weights, uint32_t rw, const char *who) {
+    const bool ways = rw == kWaysWords;
+    const size_t row_bytes = (size_t)rw * 8u;
     if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
     if (n == 0) return MCQ_OK;
     if (!q || !ext || !prob) return mcq_fail(MCQ_EINVAL, who, "null buffer");
@@ -1259,15 +1283,21 @@ int mcq_exact_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext
             snprintf(buf, sizeof buf, "query %zu: the opponents' range cannot be dealt from the remaining cards", i);
             return mcq_fail(MCQ_EINVAL, who, buf);
         }
-        if (xq[i].b.n_opp == 2u) h1_words += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
+        if (xq[i].b.n_opp == 2u) {
+            if (ways) {
+                snprintf(buf, sizeof buf, "query %zu: two random opponents have no split-pot enumeration", i);
+                return mcq_fail(MCQ_EINVAL, who, buf);
+            }
+            h1_words += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
+        }
     }
     MCQ_ENTER(c, who);
     McqDeviceScope dev_(c->device);
     HIP_TRY(dev_.err);
-    HIP_TRY(c->d_res.reserve(n * sizeof(mcq_result)));
+    HIP_TRY(c->d_res.reserve(n * row_bytes));
     c->res_clean = 0;
-    HIP_TRY(c->h_res.reserve(n * sizeof(mcq_result) + h1_words * 8u));
-    HIP_TRY(hipMemsetAsync(c->d_res.p, 0, n * sizeof(mcq_result), c->stream));
+    HIP_TRY(c->h_res.reserve(n * row_bytes + h1_words * 8u));
+    HIP_TRY(hipMemsetAsync(c->d_res.p, 0, n * row_bytes, c->stream));
     /* the per-first-hand sums of the two-opponent queries: the parity mode's draw buffer is free during this call */
     if (h1_words) {
         HIP_TRY(c->d_draws.reserve(h1_words * 8u));
@@ -1295,22 +1325,43 @@ int mcq_exact_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext
             if (kind == 2u) off += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
         }
         HIP_TRY(mcq_launch_exact_ext(d_jobs + first, (uint32_t)(at - first), max_grid, kind, d_ext, law, (mcq_result *)c->d_res.p,
-                                     (unsigned long long *)c->d_draws.p, c->d_luts, c->stream));
+                                     (unsigned long long *)c->d_draws.p, c->d_luts, c->stream, ways));
     }
     uint8_t *hr = static_cast<uint8_t *>(c->h_res.p);
-    HIP_TRY(hipMemcpyAsync(hr, c->d_res.p, n * sizeof(mcq_result), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hr, c->d_res.p, n * row_bytes, hipMemcpyDeviceToHost, c->stream));
     if (h1_words)
-        HIP_TRY(hipMemcpyAsync(hr + n * sizeof(mcq_result), c->d_draws.p, h1_words * 8u, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hr + n * row_bytes, c->d_draws.p, h1_words * 8u, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const unsigned long long *h1 = reinterpret_cast<const unsigned long long *>(hr + n * sizeof(mcq_result));
+    const unsigned long long *h1 = reinterpret_cast<const unsigned long long *>(hr + n * row_bytes);
     for (size_t i = 0; i < n; i++) {
-        mcq_result w;
-        memcpy(&w, hr + i * sizeof(mcq_result), sizeof w);
-        mcq_exact_ext_finish(xq[i], &rid[64u * i], h1 + h1_off[i], w, prob[i]);
-        if (weights) weights[i] = w;
+        mcq_result_ways w = {};
+        memcpy(&w, hr + i * row_bytes, row_bytes);
+        if (!ways) {
+            mcq_exact_ext_finish(xq[i], &rid[64u * i], h1 + h1_off[i], w.r, static_cast<mcq_exact_prob *>(prob)[i]);
+        } else { /* (at most one random opponent: one common total, the weights are always defined) */
+            mcq_exact_prob_ways &pw = static_cast<mcq_exact_prob_ways *>(prob)[i];
+            mcq_exact_ext_finish(xq[i], &rid[64u * i], h1, w.r, pw.p);
+            for (uint32_t k = 0; k < 9u; k++) pw.tie_ways[k] = (double)w.tie_ways[k] / (double)w.r.runs;
+        }
+        if (weights) memcpy(static_cast<uint8_t *>(weights) + i * row_bytes, &w, row_bytes);
     }
     return MCQ_OK;
+}
+
+extern "C" {
+
+int mcq_exact_batch_ext(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, mcq_exact_prob *prob,
+                        mcq_result *weights) {
+    ABI_GUARD_BEGIN
+    return exact_batch_ext_impl(c, q, ext, n, law, prob, weights, kPlainWords, "mcq_exact_batch_ext");
     ABI_GUARD_END("mcq_exact_batch_ext")
+}
+
+int mcq_exact_batch_ext_ways(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                             mcq_exact_prob_ways *prob, mcq_result_ways *weights) {
+    ABI_GUARD_BEGIN
+    return exact_batch_ext_impl(c, q, ext, n, law, prob, weights, kWaysWords, "mcq_exact_batch_ext_ways");
+    ABI_GUARD_END("mcq_exact_batch_ext_ways")
 }
 
 }  // extern "C"

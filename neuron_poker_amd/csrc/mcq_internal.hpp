@@ -37,7 +37,8 @@ uint32_t mcq_exact_ext_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint
                             uint32_t n_cu, McqExactExtJob *job);
 hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, uint32_t kind,
                                 const uint32_t *d_ext, int law, mcq_result *d_rows, unsigned long long *d_h1,
-                                const McqTables *d_luts, hipStream_t s);
+                                const McqTables *d_luts, hipStream_t s,
+                                bool ways = false /* kinds 0 and 1: d_rows holds zeroed mcq_result_ways rows */);
 hipError_t mcq_launch_exact(const McqExactJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, bool two_opp, int law,
                             mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
 /* hands / winner / wtype / keys: device-visible memory (pinned host memory or HBM), 16-byte aligned and padded to whole
@@ -59,9 +60,10 @@ struct McqExtSmallKarg {
 };
 hipError_t mcq_launch_eval_ext_small(const McqExtSmallKarg *karg, uint32_t n_blocks, mcq_result *h_res_dev, uint64_t seed,
                                      uint64_t first_qid, const McqTables *d_luts, uint32_t *d_done, uint32_t *done_flag,
-                                     uint32_t ticket, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
+                                     uint32_t ticket, hipStream_t s, hipEvent_t t0, hipEvent_t t1,
+                                     bool ways = false /* one mcq_result_ways row per block */);
 hipError_t mcq_launch_prep_ext(const mcq_query *d_q, const mcq_query_ext *d_ext, uint32_t n, int mode, mcq_result *d_res,
-                               uint64_t *d_prefix, hipStream_t s);
+                               uint64_t *d_prefix, hipStream_t s, uint32_t row_words = 13);
 /* production mode of the extended queries: lays out the candidate lists (lists_stride per query, MCQ_EXT_LIST_STRIDE
  * uint16 entries each) and their lengths */
 hipError_t mcq_launch_ext_lists(const mcq_query *d_q, const mcq_query_ext *d_ext, uint32_t n, uint32_t lists_stride,
@@ -70,7 +72,8 @@ hipError_t mcq_launch_eval_ext(int mode, const mcq_query *d_q, const mcq_query_e
                                const uint64_t *d_prefix, mcq_result *d_res, uint64_t seed, uint64_t first_qid,
                                const McqTables *d_luts, const uint8_t *d_draws, const uint64_t *d_draw_off,
                                const uint16_t *d_lists, const uint32_t *d_cnts, uint32_t lists_stride, uint32_t grid,
-                               uint32_t block, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+                               uint32_t block, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
+                               bool ways = false /* d_res holds mcq_result_ways rows (prepared with row_words = 22) */);
 /* host-buffer calls with few rows: d_rows[0..n_rows) -> pinned host memory (device address h_rows_dev), d_rows zeroed,
  * then *done_flag = ticket; n_rows even (buffers hold the odd row's neighbour), d_done a zeroed device word */
 hipError_t mcq_launch_publish(mcq_result *d_rows, mcq_result *h_rows_dev, uint64_t n_rows, uint32_t *d_done,
@@ -97,7 +100,8 @@ uint64_t mcq_mtb_part_words(void); /* per query */
 /* ... and for extended queries (mcq_mt_ext.hpp); d_counter zero (mcq_prep_ext_kernel leaves one behind its prefix); a
  * query whose range cannot be dealt gets passes = UINT64_MAX */
 hipError_t mcq_launch_mt_parse_ext(const mcq_query *d_q, const mcq_query_ext *d_ext, uint32_t n, uint32_t seed32, uint8_t *d_draws,
-                                   const uint64_t *d_draw_off, mcq_result *d_res, uint32_t *d_counter, uint32_t n_cu, hipStream_t s);
+                                   const uint64_t *d_draw_off, mcq_result *d_res, uint32_t *d_counter, uint32_t n_cu, hipStream_t s,
+                                   uint32_t row_words = 13);
 /* small queries, one launch and nothing else: work_rec / work_qi (the work laid out wave by wave, see the kernel), res
  * and done_flag may be pinned host memory (device-visible); d_done: a zeroed device word */
 #define MCQ_DIRECT_IDLE 0xFFFFFFFFu

@@ -257,7 +257,9 @@ __global__ __launch_bounds__(kMtBlock) void mcq_mt_parse_kernel(const mcq_query 
 
 // The same for extended queries (mcq_mt_ext.hpp: the reference's loops over ranges, ghost cards and known hands walked
 // stage by stage).  6.5 KB of LDS per wave.  A query whose range cannot be dealt gets passes = UINT64_MAX.
+// ROW_WORDS: as mcq_prep_kernel (the walk itself, and what it stores, are the same for either row).
 constexpr int kMtExtBlock = 256;
+template <uint32_t ROW_WORDS>
 __global__ __launch_bounds__(kMtExtBlock) void mcq_mt_parse_ext_kernel(const mcq_query *__restrict__ queries,
                                                                     const mcq_query_ext *__restrict__ ext, uint32_t n, uint32_t seed32,
                                                                     uint8_t *__restrict__ draws, const uint64_t *__restrict__ draw_off,
@@ -282,7 +284,7 @@ __global__ __launch_bounds__(kMtExtBlock) void mcq_mt_parse_ext_kernel(const mcq
             McqMtExtState st = {MCQ_MT_N, 0u, 0u, 0u, 0u, 0u, 0ull, false};
             const bool ok = mcq_mt_parse_query_ext(w, st, q, ew, draws + draw_off[qi], ((uint64_t)q.runs() + 63u) & ~63ull);
             /* (every lane stores the same word: no divergent branch in front of the loop's back edge) */
-            reinterpret_cast<unsigned long long *>(res + qi)[1] = ok ? st.passes : ~0ull;
+            (reinterpret_cast<unsigned long long *>(res) + (size_t)qi * ROW_WORDS)[1] = ok ? st.passes : ~0ull;
         }
     }
 }
@@ -1331,7 +1333,9 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
 // SURVEY 8f-2 (ranges, ghost cards, any number of known hands, each two cards or a range): same slicing and tallying
 // as above, the mask-based iteration of mcq_iteration_ext.  Production mode draws from candidate lists that
 // mcq_ext_lists_kernel lays out once per query (mcq_device.hpp).  A range that could not be dealt zeroes the row's
-// `runs`.
+// `runs`.  ROW_WORDS / WAYS: 22-word rows (mcq_result_ways) with the ties split as in the plain kernels; the failed-range
+// marker (runs := 0) and the invalid marker (passes = UINT64_MAX) leave zeros in the nine further words.
+template <uint32_t ROW_WORDS>
 __global__ __launch_bounds__(1024) void mcq_prep_ext_kernel(const mcq_query *__restrict__ q,
                                                             const mcq_query_ext *__restrict__ ext, uint32_t n, int mode,
                                                             mcq_result *__restrict__ res, uint64_t *__restrict__ prefix) {
@@ -1348,11 +1352,11 @@ __global__ __launch_bounds__(1024) void mcq_prep_ext_kernel(const mcq_query *__r
             bool ok = mcq_query_ext_valid(qq, er);
             const uint32_t s_iters = ok && mode == MCQ_MODE_PHILOX ? mcq_ext_stream_iters(qq, er) : MCQ_STREAM_ITERS;
             cost = ok ? (uint64_t)mcq_ext_task_count(qq, s_iters) * mcq_ext_task_weight(qq, s_iters) : 0ull;
-            uint64_t *r = reinterpret_cast<uint64_t *>(res + i);
+            uint64_t *r = reinterpret_cast<uint64_t *>(res) + (size_t)i * ROW_WORDS;
             r[0] = ok ? qq.runs() : 0ull;
             r[1] = ok ? 0ull : ~0ull;
 #pragma unroll
-            for (int k = 2; k < 13; k++) r[k] = 0;
+            for (int k = 2; k < (int)ROW_WORDS; k++) r[k] = 0;
         }
         uint64_t chunk_total;
         const uint64_t before = block_exclusive_scan_1024(cost, wave_tot, &chunk_total);
@@ -1418,7 +1422,7 @@ __global__ __launch_bounds__(kListBlock) void mcq_ext_lists_kernel(const mcq_que
     }
 }
 
-template <int MODE>
+template <int MODE, bool WAYS>
 __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query *__restrict__ queries,
                                                                  const mcq_query_ext *__restrict__ ext, uint32_t n,
                                                                  const uint64_t *__restrict__ prefix,
@@ -1428,6 +1432,8 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
                                                                  const uint64_t *__restrict__ draw_off,
                                                                  const uint16_t *__restrict__ lists,
                                                                  const uint32_t *__restrict__ cnts, uint32_t lists_stride) {
+    typedef McqRowKind<WAYS> Row; /* WAYS: 22-word rows with the ties split by the hands that share the pot */
+    typedef typename Row::Acc Acc;
     __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
     __shared__ McqCard cards[64];
     __shared__ McqExtWaveCtx wave_ctx[kExtBlock / 64];
@@ -1509,7 +1515,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
     uint32_t task = 0, n_tasks = 0, weight = 1, s_iters = MCQ_STREAM_ITERS;
     uint64_t pfx = 0;
     McqExtCtx qc;
-    WaveTally tally;
+    typename Row::Tally tally;
     tally.clear();
     bool failed = false, fresh = true, list_in_lds = false;
     for (;;) {
@@ -1553,17 +1559,17 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
         }
         if (task >= n_tasks) {
             if (__any(failed)) {
-                if (lane == 0) atomicExch(reinterpret_cast<unsigned long long *>(res + qi), 0ull); /* runs := 0 */
+                if (lane == 0) atomicExch(reinterpret_cast<unsigned long long *>(Row::row(res, qi)), 0ull); /* runs := 0 */
                 failed = false;
             }
-            tally.flush(res + qi, lane);
+            tally.flush(Row::row(res, qi), lane);
             qi++;
             fresh = true;
             continue;
         }
         if (pfx + (uint64_t)task * weight >= hi) break;
 
-        McqLaneAcc acc = {0, 0, 0};
+        Acc acc = {};
         if (MODE == MCQ_MODE_PHILOX) {
             const uint32_t stream = task * MCQ_WAVE + lane;
             const uint64_t it0 = (uint64_t)stream * s_iters;
@@ -1573,16 +1579,16 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
                 const uint32_t cnt = (uint32_t)min((uint64_t)s_iters, (uint64_t)qc.runs - it0);
                 if (qc.fast && list_in_lds) /* (wave-uniform) */
                     for (uint32_t j = 0; j < cnt && !failed; j++)
-                        failed = !mcq_iteration_ext_fast<McqExtCtrDraws, true, true>(qc, wc, dr, cards, tab.sel8, g_tab->tf, tab.tops, tab.sd, acc);
+                        failed = !mcq_iteration_ext_fast<McqExtCtrDraws, true, true, Acc>(qc, wc, dr, cards, tab.sel8, g_tab->tf, tab.tops, tab.sd, acc);
                 else if (qc.fast)
                     for (uint32_t j = 0; j < cnt && !failed; j++)
-                        failed = !mcq_iteration_ext_fast(qc, wc, dr, cards, tab.sel8, g_tab->tf, tab.tops, tab.sd, acc);
+                        failed = !mcq_iteration_ext_fast<McqExtCtrDraws, true, false, Acc>(qc, wc, dr, cards, tab.sel8, g_tab->tf, tab.tops, tab.sd, acc);
                 else if (list_in_lds)
                     for (uint32_t j = 0; j < cnt && !failed; j++)
-                        failed = !mcq_iteration_ext<McqExtCtrDraws, true>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
+                        failed = !mcq_iteration_ext<McqExtCtrDraws, true, Acc>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
                 else
                     for (uint32_t j = 0; j < cnt && !failed; j++)
-                        failed = !mcq_iteration_ext(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
+                        failed = !mcq_iteration_ext<McqExtCtrDraws, false, Acc>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
             }
         } else {
             const uint64_t stride = (qc.runs + 63u) & ~63ull;
@@ -1591,17 +1597,20 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
                 const uint64_t it = (uint64_t)task * MCQ_TASK_ITERS + j * MCQ_WAVE + lane;
                 if (it < qc.runs) {
                     McqExtReplayDraws dr = {dbase + it, stride};
-                    mcq_iteration_ext(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
+                    mcq_iteration_ext<McqExtReplayDraws, false, Acc>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
                 }
             }
             acc.passes = 0;
         }
         tally.add(acc);
+        if constexpr (WAYS) {
+            if (tally.full()) tally.flush(Row::row(res, qi), lane); /* its packed counters are about to overflow */
+        }
         task++;
     }
     if (qi < n) {
-        if (__any(failed) && lane == 0) atomicExch(reinterpret_cast<unsigned long long *>(res + qi), 0ull);
-        tally.flush(res + qi, lane);
+        if (__any(failed) && lane == 0) atomicExch(reinterpret_cast<unsigned long long *>(Row::row(res, qi)), 0ull);
+        tally.flush(Row::row(res, qi), lane);
     }
 }
 
@@ -1615,11 +1624,14 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
 // stores the row into the host's pinned result buffer, one row per BLOCK (the host adds the parts of a query); the last
 // block to finish raises the completion flag (as mcq_eval_direct_kernel does).  The host sends queries here whose lists fit (at most MCQ_EXT_SMALL_LISTS) and
 // that have at most MCQ_EXT_SMALL_TASKS wave tasks.  Same streams, same draws, same tallies as the general path.
+template <bool WAYS>
 __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_small_kernel(McqExtSmallKarg karg, mcq_result *__restrict__ res,
                                                                        uint64_t seed, uint64_t first_qid,
                                                                        const McqTables *__restrict__ g_tab,
                                                                        uint32_t *__restrict__ done, volatile uint32_t *done_flag,
                                                                        uint32_t ticket) {
+    typedef McqRowKind<WAYS> Row; /* WAYS: one 22-word row per block */
+    typedef typename Row::Acc Acc;
     constexpr uint32_t kWaves = kExtBlock / 64;
     constexpr uint32_t kStageEntries = MCQ_EXT_SMALL_LISTS * MCQ_EXT_LIST_STRIDE;
     __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
@@ -1629,7 +1641,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_small_kernel(McqExtSma
     __shared__ __attribute__((aligned(16))) uint16_t s_lists[kStageEntries];
     __shared__ uint32_t s_rec[4 + MCQ_EXT_WORDS];
     __shared__ uint32_t wave_tot[kWaves];
-    __shared__ unsigned long long partial[kWaves][12];
+    __shared__ unsigned long long partial[kWaves][Row::kLanes];
     __shared__ uint32_t s_failed;
     const uint32_t blk = karg.blk[blockIdx.x], qi = blk & 0xFFu, part = (blk >> 8) & 0xFFu, parts = (blk >> 16) & 0xFFu, wpb = blk >> 24;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
@@ -1701,11 +1713,11 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_small_kernel(McqExtSma
     __syncthreads();
     const uint32_t s_iters = __builtin_amdgcn_readfirstlane(valid ? mcq_ext_stream_iters(q, er) : MCQ_STREAM_ITERS);
     const uint32_t n_tasks = __builtin_amdgcn_readfirstlane(ok ? mcq_ext_task_count(q, s_iters) : 0u);
-    WaveTally tally;
+    typename Row::Tally tally;
     tally.clear();
     bool failed = false;
     for (uint32_t task = part * wpb + __builtin_amdgcn_readfirstlane(wv); wv < wpb && task < n_tasks; task += parts * wpb) {
-        McqLaneAcc acc = {0, 0, 0};
+        Acc acc = {};
         const uint32_t stream = task * MCQ_WAVE + lane;
         const uint64_t it0 = (uint64_t)stream * s_iters;
         if (it0 < qc.runs) {
@@ -1714,25 +1726,25 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_small_kernel(McqExtSma
             const uint32_t cnt = (uint32_t)min((uint64_t)s_iters, (uint64_t)qc.runs - it0);
             if (qc.fast) /* (block-uniform) */
                 for (uint32_t j = 0; j < cnt && !failed; j++)
-                    failed = !mcq_iteration_ext_fast<McqExtCtrDraws, false, true>(qc, wave_ctx, dr, cards, tab.sel8, g_tab->tf, tab.tops, tab.sd, acc);
+                    failed = !mcq_iteration_ext_fast<McqExtCtrDraws, false, true, Acc>(qc, wave_ctx, dr, cards, tab.sel8, g_tab->tf, tab.tops, tab.sd, acc);
             else
                 for (uint32_t j = 0; j < cnt && !failed; j++)
-                    failed = !mcq_iteration_ext<McqExtCtrDraws, true>(qc, wave_ctx, dr, cards, tab.sel8, ids + tid, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
+                    failed = !mcq_iteration_ext<McqExtCtrDraws, true, Acc>(qc, wave_ctx, dr, cards, tab.sel8, ids + tid, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
         }
         tally.add(acc);
     }
     if (__any(failed) && lane == 0) atomicOr(&s_failed, 1u);
     const unsigned long long mine = tally.row_words(lane);
-    if (lane < 12u) partial[wv][lane] = mine;
+    if (lane < Row::kLanes) partial[wv][lane] = mine;
     __syncthreads();
-    if (tid < 13u) { /* word tid of the row */
+    if (tid < Row::kWords) { /* word tid of the row */
         unsigned long long v = 0;
         if (tid > 0u)
             for (uint32_t k = 0; k < kWaves; k++) v += partial[k][tid - 1u];
         const bool bad = !ok || s_failed != 0u;
         if (tid == 0u) v = bad ? 0ull : (unsigned long long)qc.runs;
         else if (bad) v = tid == 1u && !valid ? ~0ull : 0ull; /* invalid: passes = UINT64_MAX, as mcq_prep_ext_kernel marks it */
-        reinterpret_cast<unsigned long long *>(res + blockIdx.x)[tid] = v;
+        reinterpret_cast<unsigned long long *>(Row::row(res, blockIdx.x))[tid] = v;
     }
     __syncthreads();
     if (tid == 0) {
@@ -1912,7 +1924,8 @@ __global__ __launch_bounds__(TWO_OPP ? 384 : 1024) void mcq_exact_kernel(const M
 //      until the block's last completion and go to h1_sums[job.h1_off + 12 * hand] (integer atomics: deterministic).
 //      LDS: 97 KB of tables + 10 KB of keys and records, one block of 16 waves per CU.
 // Kinds 0 and 1 add into the zeroed row rows[job.row] by lane roles as mcq_exact_kernel does.
-template <uint32_t KIND>
+// WAYS (kinds 0 and 1): 22-word rows; lane 13 + (k - 2) adds the weight of the ties shared by k hands (mcq_exact_ext.hpp).
+template <uint32_t KIND, bool WAYS>
 __global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
                                                              int law, mcq_result *__restrict__ rows,
                                                              unsigned long long *__restrict__ h1_sums,
@@ -1950,8 +1963,74 @@ __global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJo
         __syncthreads();
     }
     const uint32_t n_boards = job.n_boards;
+    static_assert(!WAYS || KIND != 2u, "two random opponents have no split-pot form");
 
-    if (KIND == 0u) {
+    if constexpr (KIND == 0u && WAYS) {
+        McqExactAcc acc = {0, 0, 0};
+        uint32_t by_type[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ways[MCQ_N_WAYS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t idx = blockIdx.x * blockDim.x + tid; idx < n_boards; idx += job.grid * blockDim.x) {
+            McqExactAcc a = {0, 0, 0};
+            uint32_t n_eq;
+            const uint32_t t = mcq_exact_ext_lone_ways(e, idx, tab.sel8, g_tab->tf, tab.tops, tab.sd, a, n_eq);
+            acc.win += a.win;
+            acc.tie += a.tie;
+            acc.tot += a.tot;
+#pragma unroll
+            for (uint32_t j = 0; j < 9; j++) by_type[j] += j == t ? a.win + a.tie : 0u;
+#pragma unroll
+            for (uint32_t j = 0; j < MCQ_N_WAYS; j++) ways[j] += j + 1u == n_eq ? a.tie : 0u; /* a tie: n_eq >= 1 */
+        }
+        uint32_t mine = 0;
+        const uint32_t tot = wave_sum(acc.tot), win = wave_sum(acc.win), tie = wave_sum(acc.tie);
+        mine = lane == 0u ? tot : lane == 2u ? win : lane == 3u ? tie : 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 9; j++) {
+            const uint32_t v = wave_sum(by_type[j]);
+            mine = lane == 4u + j ? v : mine;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < MCQ_N_WAYS; j++) {
+            const uint32_t v = wave_sum(ways[j]);
+            mine = lane == 13u + j ? v : mine;
+        }
+        if (lane < 13u + MCQ_N_WAYS && mine != 0u)
+            atomicAdd(McqRowKind<true>::row(rows, job.row) + lane, (unsigned long long)mine);
+    } else if constexpr (KIND == 1u && WAYS) {
+        McqCard *rem_card = rem_card_all[wib];
+        uint32_t *rem_pos = rem_pos_all[wib];
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wib), n_waves = job.grid * kWaves;
+        unsigned long long sum = 0;
+        for (uint32_t board = wave; board < n_boards; board += n_waves) {
+            uint32_t pos[5];
+            mcq_exact_unrank(board, e.b.L, e.b.k, pos);
+            McqExactBoard bd;
+            mcq_exact_board(e.b, pos, tab.sel8, g_tab->tf, tab.tops, tab.sd, bd);
+            uint32_t n_eq;
+            const uint32_t kb = mcq_exact_ext_known_best_eq(e, bd, g_tab->tf, tab.tops, tab.sd, n_eq);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* the previous completion's reads are done (same wave) */
+            if (lane < e.m) {
+                const uint32_t rp = mcq_exact_rem_pos(pos, lane);
+                rem_pos[lane] = rp;
+                rem_card[lane] = mcq_card(r_id[rp]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            McqExactAccWays acc = {0, 0, 0, 0};
+            mcq_exact_ext_pass_a(e, bd, kb, lane, 64u, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, nullptr,
+                                 nullptr, acc);
+            const uint32_t win = wave_sum(acc.win), tie = wave_sum(acc.tie), tot = wave_sum(acc.tot), tie_c = wave_sum(acc.tie_c);
+            const uint32_t type = mcq_key_type(bd.hero_key);
+            if (lane == 0u) sum += tot;
+            if (lane == 2u) sum += win;
+            if (lane == 3u) sum += tie;
+            if (lane == 4u + type) sum += win + tie;
+            /* the candidate level with hero: 2 + n_eq hands share; else a known hand is (n_eq >= 1): 1 + n_eq hands.
+             * One random opponent leaves at most eight known hands: lane 13 + n_eq <= 21 */
+            if (lane == 13u + n_eq) sum += tie_c;
+            if (lane + 1u == 13u + n_eq) sum += tie - tie_c; /* (n_eq == 0: lane 12, and the difference is zero) */
+        }
+        if (lane < 13u + MCQ_N_WAYS && sum != 0ull) atomicAdd(McqRowKind<true>::row(rows, job.row) + lane, sum);
+    } else if (KIND == 0u) {
         McqExactAcc acc = {0, 0, 0};
         uint32_t by_type[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (uint32_t idx = blockIdx.x * blockDim.x + tid; idx < n_boards; idx += job.grid * blockDim.x) {
@@ -2167,12 +2246,18 @@ hipError_t mcq_launch_mt_blocks(const mcq_query *d_q, uint32_t n, uint32_t seed3
 }
 
 hipError_t mcq_launch_mt_parse_ext(const mcq_query *d_q, const mcq_query_ext *d_ext, uint32_t n, uint32_t seed32, uint8_t *d_draws,
-                                   const uint64_t *d_draw_off, mcq_result *d_res, uint32_t *d_counter, uint32_t n_cu, hipStream_t s) {
+                                   const uint64_t *d_draw_off, mcq_result *d_res, uint32_t *d_counter, uint32_t n_cu, hipStream_t s,
+                                   uint32_t row_words) {
     if (n == 0) return hipSuccess;
+    if (row_words != 13u && row_words != 22u) return hipErrorInvalidValue;
     uint32_t blocks = (n + kMtExtBlock / 64 - 1) / (kMtExtBlock / 64);
     if (blocks > 5u * n_cu) blocks = 5u * n_cu; /* what fits a CU at once: 27 KB of LDS per block */
-    hipLaunchKernelGGL(mcq_mt_parse_ext_kernel, dim3(blocks), dim3(kMtExtBlock), 0, s, d_q, d_ext, n, seed32, d_draws, d_draw_off,
-                       d_res, d_counter);
+    if (row_words == 13u)
+        hipLaunchKernelGGL(mcq_mt_parse_ext_kernel<13u>, dim3(blocks), dim3(kMtExtBlock), 0, s, d_q, d_ext, n, seed32, d_draws,
+                           d_draw_off, d_res, d_counter);
+    else
+        hipLaunchKernelGGL(mcq_mt_parse_ext_kernel<22u>, dim3(blocks), dim3(kMtExtBlock), 0, s, d_q, d_ext, n, seed32, d_draws,
+                           d_draw_off, d_res, d_counter);
     return hipGetLastError();
 }
 
@@ -2198,8 +2283,12 @@ hipError_t mcq_launch_add_u64(uint64_t *d_dst, const uint64_t *d_src, uint64_t n
 }
 
 hipError_t mcq_launch_prep_ext(const mcq_query *d_q, const mcq_query_ext *d_ext, uint32_t n, int mode, mcq_result *d_res,
-                               uint64_t *d_prefix, hipStream_t s) {
-    hipLaunchKernelGGL(mcq_prep_ext_kernel, dim3(1), dim3(1024), 0, s, d_q, d_ext, n, mode, d_res, d_prefix);
+                               uint64_t *d_prefix, hipStream_t s, uint32_t row_words) {
+    if (row_words != 13u && row_words != 22u) return hipErrorInvalidValue;
+    if (row_words == 13u)
+        hipLaunchKernelGGL(mcq_prep_ext_kernel<13u>, dim3(1), dim3(1024), 0, s, d_q, d_ext, n, mode, d_res, d_prefix);
+    else
+        hipLaunchKernelGGL(mcq_prep_ext_kernel<22u>, dim3(1), dim3(1024), 0, s, d_q, d_ext, n, mode, d_res, d_prefix);
     return hipGetLastError();
 }
 
@@ -2214,21 +2303,29 @@ hipError_t mcq_launch_eval_ext(int mode, const mcq_query *d_q, const mcq_query_e
                                const uint64_t *d_prefix, mcq_result *d_res, uint64_t seed, uint64_t first_qid,
                                const McqTables *d_luts, const uint8_t *d_draws, const uint64_t *d_draw_off,
                                const uint16_t *d_lists, const uint32_t *d_cnts, uint32_t lists_stride, uint32_t grid,
-                               uint32_t block, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
-    if (mode == MCQ_MODE_PHILOX)
-        MCQ_LAUNCH_TIMED(mcq_eval_ext_kernel<MCQ_MODE_PHILOX>, grid, block, d_q, d_ext, n,
-                              d_prefix, d_res, seed, first_qid, d_luts, d_draws, d_draw_off, d_lists, d_cnts, lists_stride);
-    else
-        MCQ_LAUNCH_TIMED(mcq_eval_ext_kernel<MCQ_MODE_REPLAY_MT19937>, grid, block, d_q, d_ext,
-                              n, d_prefix, d_res, seed, first_qid, d_luts, d_draws, d_draw_off, d_lists, d_cnts, lists_stride);
+                               uint32_t block, hipStream_t s, hipEvent_t t0, hipEvent_t t1, bool ways) {
+#define MCQ_LAUNCH_EXT(M, W)                                                                                        \
+    MCQ_LAUNCH_TIMED((mcq_eval_ext_kernel<M, W>), grid, block, d_q, d_ext, n, d_prefix, d_res, seed, first_qid, d_luts, d_draws, \
+                     d_draw_off, d_lists, d_cnts, lists_stride)
+    if (mode == MCQ_MODE_PHILOX) {
+        if (ways) MCQ_LAUNCH_EXT(MCQ_MODE_PHILOX, true);
+        else MCQ_LAUNCH_EXT(MCQ_MODE_PHILOX, false);
+    } else {
+        if (ways) MCQ_LAUNCH_EXT(MCQ_MODE_REPLAY_MT19937, true);
+        else MCQ_LAUNCH_EXT(MCQ_MODE_REPLAY_MT19937, false);
+    }
+#undef MCQ_LAUNCH_EXT
     return hipGetLastError();
 }
 
 hipError_t mcq_launch_eval_ext_small(const McqExtSmallKarg *karg, uint32_t n, /* blocks */ mcq_result *h_res_dev, uint64_t seed,
                                      uint64_t first_qid, const McqTables *d_luts, uint32_t *d_done, uint32_t *done_flag,
-                                     uint32_t ticket, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
+                                     uint32_t ticket, hipStream_t s, hipEvent_t t0, hipEvent_t t1, bool ways) {
     if (n == 0 || n > MCQ_EXT_SMALL_BLOCKS) return hipErrorInvalidValue;
-    MCQ_LAUNCH_TIMED(mcq_eval_ext_small_kernel, n, kExtBlock, *karg, h_res_dev, seed, first_qid, d_luts, d_done, done_flag, ticket);
+    if (ways)
+        MCQ_LAUNCH_TIMED(mcq_eval_ext_small_kernel<true>, n, kExtBlock, *karg, h_res_dev, seed, first_qid, d_luts, d_done, done_flag, ticket);
+    else
+        MCQ_LAUNCH_TIMED(mcq_eval_ext_small_kernel<false>, n, kExtBlock, *karg, h_res_dev, seed, first_qid, d_luts, d_done, done_flag, ticket);
     return hipGetLastError();
 }
 
@@ -2299,15 +2396,21 @@ uint32_t mcq_exact_ext_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint
 
 hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, uint32_t kind,
                                 const uint32_t *d_ext, int law, mcq_result *d_rows, unsigned long long *d_h1,
-                                const McqTables *d_luts, hipStream_t s) {
+                                const McqTables *d_luts, hipStream_t s, bool ways) {
     if (n_jobs == 0) return hipSuccess;
-    if (n_jobs > 65535u || max_grid == 0 || kind > 2u) return hipErrorInvalidValue;
-    if (kind == 0u)
-        hipLaunchKernelGGL(mcq_exact_ext_kernel<0u>, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, d_rows, d_h1, d_luts);
-    else if (kind == 1u)
-        hipLaunchKernelGGL(mcq_exact_ext_kernel<1u>, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, d_rows, d_h1, d_luts);
-    else
-        hipLaunchKernelGGL(mcq_exact_ext_kernel<2u>, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, d_rows, d_h1, d_luts);
+    if (n_jobs > 65535u || max_grid == 0 || kind > 2u || (ways && kind == 2u)) return hipErrorInvalidValue;
+#define MCQ_LAUNCH_XX(K, W) \
+    hipLaunchKernelGGL((mcq_exact_ext_kernel<K, W>), dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, d_rows, d_h1, d_luts)
+    if (kind == 0u) {
+        if (ways) MCQ_LAUNCH_XX(0u, true);
+        else MCQ_LAUNCH_XX(0u, false);
+    } else if (kind == 1u) {
+        if (ways) MCQ_LAUNCH_XX(1u, true);
+        else MCQ_LAUNCH_XX(1u, false);
+    } else {
+        MCQ_LAUNCH_XX(2u, false);
+    }
+#undef MCQ_LAUNCH_XX
     return hipGetLastError();
 }
 

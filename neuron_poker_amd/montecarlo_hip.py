@@ -179,13 +179,19 @@ class MonteCarlo(object):
         self.result = None
 
     def run_montecarlo(self, original_player_card_list, original_table_card_list, player_amount, ui, maxRuns,
-                       timeout, ghost_cards, opponent_range=1, *, mode=None, seed=None):
+                       timeout, ghost_cards, opponent_range=1, *, mode=None, seed=None, ties="credited"):
         """mode: None (the configured one), 'philox', 'replay', or 'exact' (the exact probabilities the Monte-Carlo modes
-        converge to: see _run_exact)."""
+        converge to: see _run_exact).
+        ties="credited" (default): a tied pot counts for hero in full, as the reference does.  ties="split": `equity`
+        is hero's expected SHARE of the pot (a tie among k hands counts 1/k) and `result` the 22-word row
+        (RESULT_WAYS_DTYPE); winnerCardTypeList stays on the credited counts.  Same streams, same query ids."""
+        if ties not in ("credited", "split"):
+            raise ValueError("ties must be 'credited' or 'split'")
+        split = ties == "split"
         eng = self._engine or _lib.default_engine()
         if mode == "exact":
             return self._run_exact(eng, original_player_card_list, original_table_card_list, player_amount, ghost_cards,
-                                   opponent_range)
+                                   opponent_range, split)
         m = _state["mode"] if mode is None else _MODES[mode]
         players = list(original_player_card_list)
         if not 1 <= len(players) <= 1 + _lib.MAX_KNOWN:
@@ -197,19 +203,22 @@ class MonteCarlo(object):
         q = _query(["2C", "2D"] if hero_is_range else list(hero), list(original_table_card_list), player_amount, maxRuns)
         if plain:
             if m == _lib.MODE_REPLAY_MT19937 and _state["couple_numpy"] and seed is None:
+                if split:
+                    raise ValueError("ties='split': configure(couple_numpy=True) has no split-pot form")
                 res = eng.eval_batch_numpy_stream(q)[0]
             else:
                 s, first = _take_ids(1) if seed is None else (int(seed), 0)
-                res = eng.eval_batch(q, s, first_query_id=first, mode=m)[0]
+                res = (eng.eval_batch_ways if split else eng.eval_batch)(q, s, first_query_id=first, mode=m)[0]
         else:
             if hero_is_range:
                 q["hole"] = 0
             ext = _ext_record(hero, hero_is_range, players[1:], ghost_cards, opponent_range, opp_bits)
             s, first = _take_ids(1) if seed is None else (int(seed), 0)
             # (straight to the C ABI: Engine.eval_batch_ext's conversions of arrays that are already right cost 8 us)
-            out = np.zeros(1, _lib.RESULT_DTYPE)
-            rc = eng._lib.mcq_eval_batch_ext(eng._ctx, q.ctypes.data, ext.ctypes.data, 1, s & 0xFFFFFFFFFFFFFFFF,
-                                             first & 0xFFFFFFFFFFFFFFFF, m, out.ctypes.data)
+            out = np.zeros(1, _lib.RESULT_WAYS_DTYPE if split else _lib.RESULT_DTYPE)
+            entry = eng._lib.mcq_eval_batch_ext_ways if split else eng._lib.mcq_eval_batch_ext
+            rc = entry(eng._ctx, q.ctypes.data, ext.ctypes.data, 1, s & 0xFFFFFFFFFFFFFFFF,
+                       first & 0xFFFFFFFFFFFFFFFF, m, out.ctypes.data)
             if rc:
                 _lib._raise(rc)
             res = out[0]
@@ -217,6 +226,8 @@ class MonteCarlo(object):
         wins = int(res["win"]) + int(res["tie"])
         self.result = res
         self.equity = wins / runs                                   # montecarlo_python.py:243
+        if split:
+            self.equity = float(_lib.pot_share(np.array([res], _lib.RESULT_WAYS_DTYPE))[0])
         self.winnerCardTypeList = Counter({TYPES[t]: int(c) / runs   # :244-246
                                            for t, c in enumerate(res["by_type"]) if c})
         self.winTypesDict = self.winnerCardTypeList.items()          # :248
@@ -225,11 +236,12 @@ class MonteCarlo(object):
         return self.equity, self.winTypesDict
 
     def _run_exact(self, eng, original_player_card_list, original_table_card_list, player_amount, ghost_cards,
-                   opponent_range):
+                   opponent_range, split=False):
         """mode='exact': what run_montecarlo converges to, by enumeration (mcq_exact_batch_ext under the reference's law):
         equity and winTypesDict are the exact probabilities, result the row of integer weights (zero when there is
         none: a range with two random opponents), runs and passes 0.  Known hands are two cards each; a hero range,
-        ranged known hands and more than two random opponents raise ValueError."""
+        ranged known hands and more than two random opponents raise ValueError.  split: the exact pot share and the
+        22-word row of weights (mcq_exact_batch_ext_ways: at most ONE random opponent)."""
         players = list(original_player_card_list)
         if not 1 <= len(players) <= 1 + _lib.MAX_KNOWN:
             raise ValueError("between one and ten known hands")
@@ -241,10 +253,14 @@ class MonteCarlo(object):
         opp_bits = _opponent_range_bits(opponent_range)
         q = _query(list(players[0]), list(original_table_card_list), player_amount, 1)
         ext = _ext_record(list(players[0]), False, players[1:], ghost_cards, opponent_range, opp_bits)
-        prob, weights = eng.exact_ext(q, ext, "reference")
-        p = prob[0]
+        if split:
+            prob, weights = eng.exact_ext_ways(q, ext, "reference")
+            p = prob[0]["p"]
+        else:
+            prob, weights = eng.exact_ext(q, ext, "reference")
+            p = prob[0]
         self.result = weights[0]
-        self.equity = float(p["win"] + p["tie"])
+        self.equity = float(_lib.pot_share(weights)[0]) if split else float(p["win"] + p["tie"])
         self.winnerCardTypeList = Counter({TYPES[t]: float(v) for t, v in enumerate(p["by_type"]) if v})
         self.winTypesDict = self.winnerCardTypeList.items()
         self.runs = 0
@@ -294,13 +310,21 @@ def get_equity(player_cards, table_cards, players, runs):
     return (out[2] + out[3]) / out[0]
 
 
-def get_pot_equity(player_cards, table_cards, players, runs):
+def get_pot_equity(player_cards, table_cards, players, runs, *, known_hands=(), ghost_cards=None, opponent_range=None):
     """get_equity's sibling: hero's expected SHARE of the pot, a tie among k hands counting 1/k (mcq_eval_batch_ways),
     where get_equity -- as the reference, tools/hand_evaluator.py:23 -- credits a tied pot to hero in full.  Same
     arguments, same seed()/stream state (a call takes one query id, as a get_equity call does) and the same configure()
-    switches: mode and dealing law; couple_numpy has no split-pot form and raises ValueError."""
+    switches: mode and dealing law; couple_numpy has no split-pot form and raises ValueError.
+    known_hands / ghost_cards / opponent_range (run_montecarlo's conventions; `players` counts the known hands): the
+    extended split-pot entry (mcq_eval_batch_ext_ways) -- hand against hand, hand against range."""
     if _state["couple_numpy"] and _state["mode"] == _lib.MODE_REPLAY_MT19937:
         raise ValueError("get_pot_equity: configure(couple_numpy=True) has no split-pot form")
+    if known_hands or ghost_cards or opponent_range is not None:
+        sim = MonteCarlo()
+        sim.run_montecarlo([list(player_cards)] + [h if isinstance(h, (set, frozenset)) else list(h) for h in known_hands],
+                           list(table_cards), players, 1, maxRuns=runs, timeout=0, ghost_cards=ghost_cards or '',
+                           opponent_range=1 if opponent_range is None else opponent_range, ties="split")
+        return sim.equity
     q = _query(list(player_cards), list(table_cards), players, runs)
     s, first = _take_ids(1)
     rows = _lib.default_engine().eval_batch_ways(q, s, first_query_id=first, mode=_state["mode"])
@@ -371,7 +395,7 @@ def get_equity_batch(hole, board, n_players, runs, seed=None, first_query_id=0, 
 
 
 def get_equity_exact(player_cards, table_cards, players, dealing="reference", engine=None, *, known_hands=(),
-                     ghost_cards='', opponent_range=1):
+                     ghost_cards='', opponent_range=1, ties="credited"):
     """The number get_equity() converges to, by exhaustive enumeration on the GPU (1 to 3 players).
 
     dealing='reference': the exact expectation of tools/montecarlo_python.py's dealing (index bias included);
@@ -381,11 +405,22 @@ def get_equity_exact(player_cards, table_cards, players, dealing="reference", en
     known_hands (further hands of two cards, in the order of original_player_card_list after the hero), ghost_cards and
     opponent_range follow run_montecarlo's conventions; `players` counts them all, and at most two of them may be random
     opponents (mcq_exact_batch_ext).  The row of weights is zero for a range with two random opponents: those outcomes
-    have no common integer total, the equity is exact all the same."""
+    have no common integer total, the equity is exact all the same.
+    ties="split": the equity is hero's exact pot share and the row a RESULT_WAYS_DTYPE row of weights
+    (mcq_exact_batch_ext_ways: at most ONE random opponent)."""
+    if ties not in ("credited", "split"):
+        raise ValueError("ties must be 'credited' or 'split'")
     opp_bits = _opponent_range_bits(opponent_range)
     known_hands = [list(h) for h in known_hands]
     q = _query(list(player_cards), list(table_cards), players, 1)
     eng = engine or _lib.default_engine()
+    if ties == "split":
+        for h in known_hands:
+            if len(h) != 2:
+                raise ValueError("a known hand is two cards here (ranged known hands are not enumerated)")
+        ext = _ext_record(list(player_cards), False, known_hands, ghost_cards, opponent_range, opp_bits)
+        _, weights = eng.exact_ext_ways(q, ext, dealing)
+        return float(_lib.pot_share(weights)[0]), weights[0]
     if not known_hands and opp_bits is None and (ghost_cards == '' or ghost_cards is None):
         res = eng.exact(q, dealing)[0]
         return (int(res["win"]) + int(res["tie"])) / int(res["runs"]), res

@@ -1,0 +1,202 @@
+// hs_ext_ways.cpp -- TEST HARNESS ONLY (built and loaded by tests/, never by the product).
+//
+// Compiles the product's EXTENDED lane code with the split-pot switch ON (McqLaneAccWays: mcq_iteration_ext and
+// mcq_iteration_ext_fast, neuron_poker_amd/csrc/mcq_device.hpp) for the HOST compiler and walks the kernels' stream / lane
+// decomposition sequentially, as tests/hostsim does for the credited form.  The oracle has no per-iteration trace for
+// extended queries, so this build also hands back every iteration's dealt hands -- through MCQ_EXT_DEAL_HOOK, which
+// exists in host builds only -- and the tests recount the ways from them with the oracle's own comparison.
+// The exact enumeration's split-pot lane code (mcq_exact_ext.hpp, kinds 0 and 1) is walked here too.
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+namespace {
+thread_local uint8_t *g_hands = nullptr; /* the current iteration's record: n_players x 2 ids, then five table ids */
+thread_local uint32_t g_players = 0, g_board = 0;
+inline void hs_dealt(uint32_t h, uint32_t c1, uint32_t c2) {
+    if (!g_hands) return;
+    if (h >= 0x100u) g_hands[2u * g_players + g_board + (h - 0x100u)] = (uint8_t)c1; /* table card number h - 0x100 to come */
+    else { g_hands[2u * h] = (uint8_t)c1; g_hands[2u * h + 1u] = (uint8_t)c2; }
+}
+}  // namespace
+#define MCQ_EXT_DEAL_HOOK(h, c1, c2) hs_dealt(h, c1, c2)
+
+#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_replay.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_exact_ext.hpp"
+
+namespace {
+McqTables g_tab;
+bool g_init = false;
+const McqTables &luts() {
+    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
+    return g_tab;
+}
+void fold(const McqLaneAccWays &a, mcq_result_ways *o) { /* as WaveTallyWays: `tie` is the sum of the ways */
+    uint64_t wins = 0, ties = 0;
+    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
+        if (c == 5) continue;
+        const uint64_t v = (a.types >> (6 * c)) & 63;
+        o->r.by_type[mcq_code_to_type(c)] += v;
+        wins += v;
+    }
+    for (uint32_t k = 0; k < MCQ_N_WAYS; k++) {
+        const uint64_t v = (a.ways >> (6u * (k + 1u))) & 63;
+        o->tie_ways[k] += v;
+        ties += v;
+    }
+    o->r.tie += ties;
+    o->r.win += wins - ties;
+    o->r.passes += a.passes;
+}
+}  // namespace
+
+extern "C" {
+
+// replay != 0: MT19937 replay with seed32 = seed (the caller adds the query id); else MCQ-CTR v5x.  general != 0: every
+// iteration through mcq_iteration_ext (else the form the kernels pick: the fast one where it applies).  out: 22 words.
+// hands (may be null): runs x (2 n_players + 5) card ids.
+int hs_ext_ways_run(int replay, const mcq_query *q, const mcq_query_ext *e, uint64_t seed, uint64_t qid, int general,
+                    mcq_result_ways *out, uint8_t *hands) {
+    const McqExtRec er = {reinterpret_cast<const uint32_t *>(e)};
+    const McqQueryWords qw = mcq_query_words(*q);
+    if (!mcq_query_ext_valid(qw, er)) return MCQ_EINVAL;
+    const McqTables &t = luts();
+    McqExtCtx qc;
+    mcq_ext_ctx(qw, er, qc);
+    McqExtWaveCtx wc;
+    memset(&wc, 0, sizeof wc);
+    for (uint32_t h = 0; h < qc.n_hands; h++) wc.hand[h] = mcq_ext_hand(qw, er, h);
+    const uint32_t n_lists = mcq_ext_n_lists(qw, er);
+    std::vector<uint16_t> lists((size_t)(n_lists ? n_lists : 1) * MCQ_EXT_LIST_STRIDE);
+    for (uint32_t li = 0; li < n_lists; li++) { /* as mcq_ext_lists_kernel lays them out */
+        uint64_t U;
+        uint32_t set_off, cnt = 0;
+        mcq_ext_list_plan(qw, er, li, U, set_off);
+        for (uint32_t c = 0; c < 2704u; c++)
+            if (mcq_ext_candidate(U, er.w + set_off, c)) lists[(size_t)li * MCQ_EXT_LIST_STRIDE + cnt++] = (uint16_t)((c / 52u) | ((c % 52u) << 8));
+        wc.cnt[li] = cnt;
+        wc.list[li] = lists.data() + (size_t)li * MCQ_EXT_LIST_STRIDE;
+        if (cnt == 0 && !replay) return MCQ_EINVAL;
+    }
+    McqCard cards[64];
+    for (uint32_t c = 0; c < 64; c++) cards[c] = mcq_card(c < 52 ? c : 0);
+    memset(out, 0, sizeof(*out));
+    out->r.runs = q->runs;
+    uint16_t ids[MCQ_MAX_OPP + 1];
+    const uint32_t rec = 2u * q->n_players + 5u;
+    g_players = q->n_players;
+    g_board = q->n_board;
+    struct Unhook { ~Unhook() { g_hands = nullptr; } } unhook;
+    auto begin = [&](uint64_t it) {
+        if (!hands) return;
+        g_hands = hands + it * rec;
+        g_hands[0] = q->hole[0]; /* (the fast form never deals hero: its hand is part of the query) */
+        g_hands[1] = q->hole[1];
+        for (uint32_t k = 0; k < q->n_board; k++) g_hands[2u * q->n_players + k] = q->board[k];
+    };
+    if (replay) {
+        size_t stride = q->runs ? q->runs : 1;
+        std::vector<uint8_t> draws((size_t)mcq_ext_draws_per_iteration(*q, *e) * stride + 1);
+        McqMt19937 g;
+        g.seed((uint32_t)seed);
+        uint64_t passes = mcq_replay_parse_ext(*q, *e, g, draws.data(), stride, 1000000u);
+        if (passes == ~0ull) return MCQ_EINVAL;
+        out->r.passes = passes;
+        for (uint32_t it = 0; it < q->runs; it++) {
+            McqExtReplayDraws dr = {draws.data() + it, stride};
+            McqLaneAccWays acc = {};
+            begin(it);
+            mcq_iteration_ext<McqExtReplayDraws, false, McqLaneAccWays>(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc);
+            acc.passes = 0;
+            fold(acc, out);
+        }
+        return MCQ_OK;
+    }
+    const uint32_t s_iters = mcq_ext_stream_iters(qw, er);
+    const uint32_t n_streams = (q->runs + s_iters - 1) / s_iters;
+    for (uint32_t s = 0; s < n_streams; s++) {
+        McqExtCtrDraws dr;
+        dr.start(seed, qid, s);
+        McqLaneAccWays acc = {};
+        for (uint32_t j = 0; j < s_iters; j++) {
+            const uint64_t it = (uint64_t)s * s_iters + j;
+            if (it >= q->runs) break;
+            begin(it);
+            const bool ok = qc.fast && !general
+                ? mcq_iteration_ext_fast<McqExtCtrDraws, true, false, McqLaneAccWays>(qc, wc, dr, cards, t.sel8, t.tf, t.tops, t.sd, acc)
+                : mcq_iteration_ext<McqExtCtrDraws, false, McqLaneAccWays>(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc);
+            if (!ok) return MCQ_EINVAL;
+        }
+        fold(acc, out);
+    }
+    return MCQ_OK;
+}
+
+// 1 if the kernels take the fast form for this query
+int hs_ext_ways_is_fast(const mcq_query *q, const mcq_query_ext *e) {
+    const McqExtRec er = {reinterpret_cast<const uint32_t *>(e)};
+    McqExtCtx qc;
+    mcq_ext_ctx(mcq_query_words(*q), er, qc);
+    return qc.fast ? 1 : 0;
+}
+
+// The exact enumeration's split-pot lane code, kinds 0 and 1, walked as mcq_exact_ext_kernel<KIND, true> walks it.
+// -> 0, MCQ_XX_* (1..4), 5 = cannot be dealt, 6 = two random opponents.  weights: 22 words.
+int hs_exact_ext_ways(const mcq_query *q, const mcq_query_ext *x, int law, uint64_t *weights) {
+    const McqTables &t = luts();
+    McqExactExtQuery e;
+    const McqExtRec er = {reinterpret_cast<const uint32_t *>(x)};
+    const int why = mcq_exact_ext_query(mcq_query_words(*q), er, law, e);
+    if (why) return why;
+    uint8_t r_id[64];
+    mcq_exact_ext_r_ids(e, r_id);
+    if (!mcq_exact_ext_dealable(e, r_id)) return 5;
+    if (e.b.n_opp == 2u) return 6;
+    std::vector<uint8_t> cb_tab(MCQ_XX_MAX_RP);
+    mcq_exact_ext_cb_table(e, r_id, 0u, 1u, cb_tab.data());
+    std::vector<uint16_t> pair_xy(MCQ_EXACT_PAIRS);
+    for (uint32_t i = 0; i < MCQ_EXACT_PAIRS; i++) {
+        uint32_t a, b;
+        mcq_exact_pair_xy(i, a, b);
+        pair_xy[i] = (uint16_t)(a | (b << 8));
+    }
+    mcq_result_ways w;
+    memset(&w, 0, sizeof w);
+    const uint32_t n_boards = mcq_exact_binom(e.b.L, e.b.k);
+    for (uint32_t board = 0; board < n_boards; board++) {
+        uint32_t type, n_eq;
+        if (e.b.n_opp == 0u) {
+            McqExactAcc acc = {0, 0, 0};
+            type = mcq_exact_ext_lone_ways(e, board, t.sel8, t.tf, t.tops, t.sd, acc, n_eq);
+            w.r.runs += acc.tot; w.r.win += acc.win; w.r.tie += acc.tie;
+            w.r.by_type[type] += acc.win + acc.tie;
+            if (acc.tie) w.tie_ways[n_eq - 1u] += acc.tie;
+            continue;
+        }
+        uint32_t pos[5];
+        mcq_exact_unrank(board, e.b.L, e.b.k, pos);
+        McqExactBoard bd;
+        mcq_exact_board(e.b, pos, t.sel8, t.tf, t.tops, t.sd, bd);
+        type = mcq_key_type(bd.hero_key);
+        const uint32_t kb = mcq_exact_ext_known_best_eq(e, bd, t.tf, t.tops, t.sd, n_eq);
+        McqCard rem_card[64];
+        uint32_t rem_pos[64];
+        for (uint32_t l = 0; l < e.m; l++) {
+            rem_pos[l] = mcq_exact_rem_pos(pos, l);
+            rem_card[l] = mcq_card(r_id[rem_pos[l]]);
+        }
+        McqExactAccWays acc = {0, 0, 0, 0};
+        for (uint32_t lane = 0; lane < 64; lane++)
+            mcq_exact_ext_pass_a(e, bd, kb, lane, 64u, pair_xy.data(), rem_card, rem_pos, cb_tab.data(), t.tf, t.tops, t.sd,
+                                 (uint32_t *)nullptr, (uint32_t *)nullptr, acc);
+        w.r.runs += acc.tot; w.r.win += acc.win; w.r.tie += acc.tie;
+        w.r.by_type[type] += acc.win + acc.tie;
+        w.tie_ways[n_eq] += acc.tie_c;
+        if (acc.tie != acc.tie_c) w.tie_ways[n_eq - 1u] += acc.tie - acc.tie_c;
+    }
+    memcpy(weights, &w, sizeof w);
+    return 0;
+}
+}
