@@ -20,6 +20,9 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "../../include/mcq.h"
 
 #if defined(__HIPCC__)
@@ -186,6 +189,40 @@ MCQ_HD uint32_t mcq_straight_runs(uint32_t m) {
     return r2 & (m2 >> 4);
 }
 
+// ------------------------------------------------------------------------------------------ rank-sum hash
+// The key of a hand without a flush depends on the MULTISET of its seven ranks only, and a multiset is additive over
+// cards: every rank has an integer weight such that all 49 205 multisets (seven cards, at most four of a rank) have
+// distinct sums (tools/sum_hash.py chooses and checks them).  The table cards are then one running sum, a hand is
+// board sum + hole sum, and the hand's rank comes out of a two-level row-displacement perfect hash,
+//     id = hrank[hoff[s & MCQ_SUM_MASK] + (s >> MCQ_SUM_SHIFT)]
+// (rows packed first-fit-decreasing by mcq_fill_tables).  The LOW bits of the sum choose the row: the weights grow
+// about fourfold from rank to rank, so the high parts of all rows are translates of one self-similar pattern, and
+// such rows do not interlock (rows by high bits: the packing stops at load factor 0.26); rows by the low 13 bits hold
+// about six entries each, spread over 956 columns, and pack to 0.987.  An id is 16 bits, code << 12 | index: the index numbers the
+// keys of one hand type in rising order from 1 (at most 2860 of a type: a pair with three kickers), so ids compare
+// exactly as the 32-bit keys of mcq_eval_key do, an id is never 0, and a hand's type code is id >> 12.
+#ifndef MCQ_SUM_SHIFT
+#define MCQ_SUM_SHIFT 13u
+#define MCQ_SUM_ROWS 8192u       /* 1 << MCQ_SUM_SHIFT */
+#define MCQ_SUM_SLOTS 50176u     /* the packing ends at slot 49 857: load factor 0.987; hoff + hrank = 114 KB of LDS */
+#endif
+#define MCQ_SUM_MASK ((1u << MCQ_SUM_SHIFT) - 1u)
+#define MCQ_SUM_ROW(s) ((s) & MCQ_SUM_MASK)
+#define MCQ_SUM_COL(s) ((s) >> MCQ_SUM_SHIFT)
+#define MCQ_SUM_MULTISETS 49205u
+#define MCQ_ID_SHIFT 12
+MCQ_HD uint32_t mcq_rank_weight(uint32_t rank) { /* rank < 13 */
+    constexpr uint32_t kWeight[13] = {0u, 1u, 5u, 22u, 98u, 453u, 2031u, 8698u, 22854u, 83661u, 262349u, 636345u, 1479181u};
+    return kWeight[rank];
+}
+
+struct McqSumImage { /* one piece, so that it travels global -> LDS as it lies */
+    uint16_t hoff[MCQ_SUM_ROWS];   /* row displacement of the rank-sum hash */
+    uint16_t hrank[MCQ_SUM_SLOTS]; /* id of the rank multiset whose sum hashes here, 0 in an empty slot */
+    uint32_t sel8[256];            /* a copy of McqTables::sel8 */
+};
+static_assert(sizeof(McqSumImage) % 1024u == 0, "the one-launch kernel sends the image in 1 KB pieces");
+
 // ------------------------------------------------------------------------------------------ lookup tables (LDS)
 // sel8: only for laying out the per-query base deck (once per wave task).
 // All mask-indexed tables are addressed with x4-domain masks (m4 = m << 2):
@@ -208,8 +245,8 @@ MCQ_HD uint32_t mcq_straight_runs(uint32_t m) {
 //           when popcount(m) < 5
 struct McqTables { /* order matters on the device: the first 64 KB are reachable through the 16-bit offset field of
                      the LDS read, i.e. the lookups whose index comes straight out of a logic instruction (tops,
-                     sd); the index of kc is formed by an xor that takes the table base along.  The evaluation
-                     kernels keep tops, sd | kc (the first 96 KB) and sel8 in LDS and read tf from GLOBAL memory
+                     sd); the index of kc is formed by an xor that takes the table base along.  The kernels of
+                     the mask form (extended, exact, showdown) keep tops, sd | kc (the first 96 KB) and sel8 in LDS and read tf from GLOBAL memory
                      through the vector L1: the LDS pipe is their co-limiter and the flush lookup, whose index is
                      the sparsest, is the one that costs least there (measured) */
     uint32_t tops[8192];
@@ -218,12 +255,16 @@ struct McqTables { /* order matters on the device: the first 64 KB are reachable
                            m of the ranks held at least three times the upper half of a finished FullHouse key, top
                            set bit of m << 15 | MCQ_C_FULL << 28, and 0 for m = 0 (see mcq_eval_key) */
     uint32_t sel8[256];
+    /* the sum form (see "rank-sum hash" below): what the plain evaluation kernels read instead of tops / sd / tf */
+    uint32_t tfid[8192]; /* tf[] as ids: the id of the suit mask's key, 0 when popcount(m) < 5; read from global memory */
+    McqSumImage sum;     /* what those kernels keep in LDS */
 };
 #define MCQ_KC_BYTE_OFFSET 32768u /* kc relative to sd */
 #define MCQ_TF_BYTE_OFFSET 98304u /* tf relative to tops = size of the part the evaluation kernels keep in LDS */
 static_assert(__builtin_offsetof(McqTables, tops) == 0 && __builtin_offsetof(McqTables, tf) == MCQ_TF_BYTE_OFFSET,
               "McqTables layout");
 
+static inline void mcq_fill_sum_tables(McqTables *t); /* tfid, hoff, hrank: behind the evaluator it restates */
 static inline void mcq_fill_tables(McqTables *t) {
     for (uint32_t v = 0; v < 256; v++) {
         uint32_t e = 0, j = 0;
@@ -255,6 +296,7 @@ static inline void mcq_fill_tables(McqTables *t) {
         }
         t->tf[m] = key;
     }
+    mcq_fill_sum_tables(t);
 }
 
 // ------------------------------------------------------------------------------------------ RNG: MCQ-CTR v5
@@ -509,7 +551,8 @@ struct McqHole { /* two hole cards: B = r1 | r2, P = r1 & r2 (pocket pair) */
 // and tf[] = 0.
 struct McqFlushSel {
     uint32_t psel, bfl4;
-    MCQ_HDM void from_board(const McqBoard &b) {
+    template <class Board>
+    MCQ_HDM void from_board(const Board &b) {
         const uint32_t f = (b.cnt + 0x5555u) & 0x8888u; /* bit 4s+3 <=> suit s has >= 3 table cards */
         psel = 0x0C0C0100u + ((f & 0x8800u) != 0 ? 0x0404u : 0u) /* hearts or spades: his */
                + ((f & 0x8080u) != 0 ? 0x0202u : 0u);            /* diamonds or spades: upper half-word */
@@ -586,6 +629,189 @@ MCQ_HD uint32_t mcq_eval_key(const McqBoard &b, const McqFlushSel &fs, const Mcq
     return k > c[3] ? k : c[3];
 }
 
+// ------------------------------------------------------------------------------------------ evaluator, sum form
+// What the plain path (mcq_iteration) runs.  A card is the same 16 bytes with the rank's WEIGHT in place of its bit
+// (McqCard::rb), so the table is one add per card and a hand one add and two dependent 16-bit LDS reads.
+MCQ_HD McqCard mcq_card_sum(uint32_t c) { /* c < 52 */
+    McqCard e = mcq_card(c);
+    e.rb = mcq_rank_weight(c >> 2);
+    return e;
+}
+struct McqSumBoard {
+    uint32_t sum, cnt, los, his;
+    MCQ_HDM void clear() { sum = cnt = los = his = 0; }
+    MCQ_HDM void add(const McqCard &c) {
+        sum += c.rb;
+        cnt += c.cnt;
+        los |= c.los;
+        his |= c.his;
+    }
+};
+struct McqSumHole {
+    uint32_t ksum, los, his;
+    MCQ_HDM void set(const McqCard &a, const McqCard &b) {
+        ksum = a.rb + b.rb;
+        los = a.los | b.los;
+        his = a.his | b.his;
+    }
+};
+struct McqSumTabs {
+    const uint16_t *hoff, *hrank; /* LDS in the kernels */
+    const uint32_t *tfid;         /* global memory, as tf is for the mask form */
+};
+/* the sum-form tables of the McqTables object whose tf member `tf` points at (host builds of the lane code) */
+MCQ_HD McqSumTabs mcq_sum_tabs_of(const uint32_t *tf) {
+    const McqTables *t = reinterpret_cast<const McqTables *>(reinterpret_cast<const char *>(tf) - MCQ_TF_BYTE_OFFSET);
+    const McqSumTabs s = {t->sum.hoff, t->sum.hrank, t->tfid};
+    return s;
+}
+MCQ_HD uint32_t mcq_ld_u16(const uint16_t *t, uint32_t byte_off) {
+    return *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(t) + byte_off);
+}
+// The two ids of table + hole: of the rank multiset (never 0) and of the flush suit (0 without a flush); the hand's
+// id is the greater one.
+MCQ_HD void mcq_sum_ids(const McqSumBoard &b, const McqFlushSel &fs, const McqSumHole &h, const McqSumTabs &t,
+                        uint32_t &rank_id, uint32_t &flush_id) {
+#ifdef MCQ_ABLATE_EVAL /* diagnostic timing build: wrong results */
+    rank_id = ((b.sum ^ h.ksum ^ (h.los >> 3)) & 0xFFFu) | (1u << MCQ_ID_SHIFT);
+    flush_id = 0u;
+    return;
+#endif
+    const uint32_t s = b.sum + h.ksum;
+    flush_id = mcq_ld_u32(t.tfid, fs.bfl4 | mcq_perm(h.his, h.los, fs.psel));
+    const uint32_t d = mcq_ld_u16(t.hoff, (s & MCQ_SUM_MASK) << 1);
+    rank_id = mcq_ld_u16(t.hrank, (d + (s >> MCQ_SUM_SHIFT)) << 1);
+}
+MCQ_HD uint32_t mcq_sum_key(const McqSumBoard &b, const McqFlushSel &fs, const McqSumHole &h, const McqSumTabs &t) {
+    uint32_t r, f;
+    mcq_sum_ids(b, fs, h, t, r, f);
+    return r > f ? r : f;
+}
+MCQ_HD uint32_t mcq_id_type(uint32_t id) { return mcq_code_to_type(id >> MCQ_ID_SHIFT); }
+
+// ------------------------------------------------------------------------------------------ sum-form tables
+// Host only, deterministic: mcq_eval_key (without a flush) over every rank multiset and every non-zero tf[] entry give
+// the set of keys; sorted and numbered per type code they are the ids.  The rows of the hash are packed
+// first-fit-decreasing (most entries first, ties by row number; every row at the lowest displacement that fits).
+// Returns false if the tables do not fit their sizes (never, for the constants above: tests/test_sum_hash_host.py).
+static inline bool mcq_fill_sum_tables_checked(McqTables *t, uint32_t *n_ids_by_code /* MCQ_N_CODES, or null */) {
+    struct Entry { uint32_t sum, key; };
+    std::vector<Entry> ms;
+    ms.reserve(MCQ_SUM_MULTISETS);
+    /* all multisets: a count per rank, at most four, seven in all (ranks in rising order, depth first) */
+    uint32_t cnt[13] = {0}, left = 7u;
+    for (int r = 0;;) {
+        if (r == 13 || left == 0u) {
+            if (left == 0u) {
+                McqCard c[7];
+                uint32_t k = 0, sum = 0;
+                for (uint32_t q = 0; q < 13; q++)
+                    for (uint32_t j = 0; j < cnt[q]; j++) {
+                        c[k].rb = 4u << q;
+                        c[k].cnt = c[k].los = c[k].his = 0u; /* no suits: tf[0] = 0, the flush candidate stays out */
+                        k++;
+                        sum += mcq_rank_weight(q);
+                    }
+                McqBoard b;
+                b.clear();
+                for (int i = 0; i < 5; i++) b.add(c[i]);
+                McqFlushSel fs;
+                fs.from_board(b);
+                McqHole h;
+                h.set(c[5], c[6]);
+                const Entry e = {sum, mcq_eval_key(b, fs, h, t->tf, t->tops, t->sd)};
+                ms.push_back(e);
+            }
+            /* back to the last rank whose count can still grow */
+            for (r--; r >= 0 && (cnt[r] == 4u || left == 0u); r--) {
+                left += cnt[r];
+                cnt[r] = 0u;
+            }
+            if (r < 0) break;
+            cnt[r]++;
+            left--;
+            r++;
+        } else {
+            r++; /* count 0 of this rank first */
+        }
+    }
+    bool ok = ms.size() == MCQ_SUM_MULTISETS;
+
+    std::vector<uint32_t> keys;
+    keys.reserve(ms.size() + 8192u);
+    for (const Entry &e : ms) keys.push_back(e.key);
+    for (uint32_t m = 0; m < 8192u; m++)
+        if (t->tf[m]) keys.push_back(t->tf[m]);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    uint32_t first[MCQ_N_CODES + 1]; /* position of a code's first key */
+    for (uint32_t c = 0; c <= MCQ_N_CODES; c++)
+        first[c] = (uint32_t)(std::lower_bound(keys.begin(), keys.end(), c << MCQ_KEY_SHIFT) - keys.begin());
+    first[MCQ_N_CODES] = (uint32_t)keys.size();
+    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
+        const uint32_t n = first[c + 1] - first[c];
+        if (n_ids_by_code) n_ids_by_code[c] = n;
+        ok = ok && n < (1u << MCQ_ID_SHIFT); /* index 1..n */
+    }
+    auto id_of = [&](uint32_t key) -> uint32_t {
+        const uint32_t pos = (uint32_t)(std::lower_bound(keys.begin(), keys.end(), key) - keys.begin());
+        const uint32_t code = key >> MCQ_KEY_SHIFT;
+        return (code << MCQ_ID_SHIFT) | (pos - first[code] + 1u);
+    };
+    for (uint32_t m = 0; m < 8192u; m++) t->tfid[m] = t->tf[m] ? id_of(t->tf[m]) : 0u;
+
+    /* rows of the hash, by number of entries */
+    std::sort(ms.begin(), ms.end(), [](const Entry &a, const Entry &b) {
+        return MCQ_SUM_ROW(a.sum) != MCQ_SUM_ROW(b.sum) ? MCQ_SUM_ROW(a.sum) < MCQ_SUM_ROW(b.sum) : a.sum < b.sum;
+    });
+    for (size_t i = 1; i < ms.size(); i++) ok = ok && ms[i].sum != ms[i - 1].sum;
+    std::vector<uint32_t> row_lo(MCQ_SUM_ROWS + 1u, 0u); /* entries of row r: ms[row_lo[r] .. row_lo[r + 1]), columns rising */
+    for (const Entry &e : ms) row_lo[MCQ_SUM_ROW(e.sum) + 1u]++;
+    for (uint32_t r = 0; r < MCQ_SUM_ROWS; r++) row_lo[r + 1u] += row_lo[r];
+    std::vector<uint32_t> order(MCQ_SUM_ROWS);
+    for (uint32_t r = 0; r < MCQ_SUM_ROWS; r++) order[r] = r;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return row_lo[a + 1u] - row_lo[a] > row_lo[b + 1u] - row_lo[b];
+    });
+    /* nxt[i]: a slot >= i below which, from i on, nothing is free (followed and shortened as in a union-find): the
+     * search for a row's place only visits displacements that put the row's first entry on a free slot */
+    std::vector<uint32_t> nxt(MCQ_SUM_SLOTS + 1u);
+    for (uint32_t i = 0; i <= MCQ_SUM_SLOTS; i++) nxt[i] = i;
+    auto next_free = [&](uint32_t i) -> uint32_t {
+        while (nxt[i] != i) {
+            nxt[i] = nxt[nxt[i]];
+            i = nxt[i];
+        }
+        return i;
+    };
+    for (uint32_t i = 0; i < 256u; i++) t->sum.sel8[i] = t->sel8[i];
+    for (uint32_t i = 0; i < MCQ_SUM_ROWS; i++) t->sum.hoff[i] = 0;
+    for (uint32_t i = 0; i < MCQ_SUM_SLOTS; i++) t->sum.hrank[i] = 0;
+    for (uint32_t oi = 0; oi < MCQ_SUM_ROWS && ok; oi++) {
+        const uint32_t r = order[oi], lo = row_lo[r], hi = row_lo[r + 1u];
+        if (lo == hi) break; /* empty rows: displacement 0, never read */
+        const uint32_t col0 = MCQ_SUM_COL(ms[lo].sum), col1 = MCQ_SUM_COL(ms[hi - 1u].sum);
+        uint32_t d = 0;
+        for (;; d++) {
+            const uint32_t at = next_free(d + col0 < MCQ_SUM_SLOTS ? d + col0 : MCQ_SUM_SLOTS);
+            d = at - col0;
+            if (d + col1 >= MCQ_SUM_SLOTS || d > 0xFFFFu) { ok = false; break; }
+            bool fits = true;
+            for (uint32_t k = lo + 1u; k < hi && fits; k++) fits = t->sum.hrank[d + MCQ_SUM_COL(ms[k].sum)] == 0u;
+            if (fits) break;
+        }
+        if (!ok) break;
+        t->sum.hoff[r] = (uint16_t)d;
+        for (uint32_t k = lo; k < hi; k++) {
+            const uint32_t slot = d + MCQ_SUM_COL(ms[k].sum);
+            nxt[slot] = slot + 1u;
+            t->sum.hrank[slot] = (uint16_t)id_of(ms[k].key); /* never 0 */
+        }
+    }
+    return ok;
+}
+static inline void mcq_fill_sum_tables(McqTables *t) { (void)mcq_fill_sum_tables_checked(t, nullptr); }
+
 // ------------------------------------------------------------------------------------------ one query, one lane
 struct McqQueryCtx { /* wave-uniform */
     uint32_t deck_lo, deck_hi; /* remaining deck after removing the known table cards and hero (l.126-161) */
@@ -595,6 +821,8 @@ struct McqQueryCtx { /* wave-uniform */
     uint32_t runs;
     McqHole hero;
     McqBoard board; /* the known table cards */
+    McqSumHole hero_s; /* the same two in the sum form (what mcq_iteration reads) */
+    McqSumBoard board_s;
 };
 
 // The 16-byte query record as four little-endian words (kept in SGPRs by the kernels): bytes 0-1 hole,
@@ -627,15 +855,18 @@ MCQ_HD bool mcq_query_valid(const McqQueryWords &q) {
 MCQ_HD void mcq_query_ctx(const McqQueryWords &q, McqQueryCtx &c) {
     uint64_t deck = (1ull << 52) - 1;
     c.board.clear();
+    c.board_s.clear();
     for (uint32_t i = 0; i < q.n_board(); i++) {
         const uint32_t cd = q.card(2u + i);
         deck &= ~(1ull << cd);
         c.board.add(mcq_card(cd));
+        c.board_s.add(mcq_card_sum(cd));
     }
     const uint32_t h0 = q.card(0), h1 = q.card(1);
     deck &= ~(1ull << h0);
     deck &= ~(1ull << h1);
     c.hero.set(mcq_card(h0), mcq_card(h1));
+    c.hero_s.set(mcq_card_sum(h0), mcq_card_sum(h1));
     c.deck_lo = (uint32_t)deck;
     c.deck_hi = (uint32_t)(deck >> 32);
     c.L0 = 50u - q.n_board();
@@ -688,11 +919,11 @@ static inline McqQueryWords mcq_query_words(const mcq_query &q) { /* host side *
     return w;
 }
 
-// entry l of the base deck = the l-th card of the ordered remaining deck (device: lane l computes entry l)
+// entry l of the base deck = the l-th card of the ordered remaining deck (device: lane l computes entry l), sum form
 MCQ_HD McqCard mcq_base_entry(const McqQueryCtx &qc, uint32_t l, const uint32_t *sel8) {
     uint32_t dlo = qc.deck_lo, dhi = qc.deck_hi;
     uint32_t c = mcq_select_pop(dlo, dhi, l, sel8);
-    return mcq_card(c < 52u ? c : 0u); /* lanes beyond the deck length write an entry nobody reads */
+    return mcq_card_sum(c < 52u ? c : 0u); /* lanes beyond the deck length write an entry nobody reads */
 }
 
 struct McqLaneAcc {
@@ -800,7 +1031,7 @@ MCQ_HD uint32_t mcq_draw_table(uint32_t rp, const uint32_t (&H)[5], uint32_t &hb
 // the missing table cards (montecarlo_python.py:185-189) after opponents whose holes fill NREGS registers
 template <int NREGS, class Draws, int NDEAL = -1>
 MCQ_HD void mcq_deal_table(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const uint32_t (&H)[5], uint32_t L,
-                           McqBoard &b) {
+                           McqSumBoard &b) {
     uint32_t hb = MCQ_HOLE_SENTINEL;
     /* scalar compares, no lane masks kept in SGPR pairs; NDEAL >= 0: known at compile time, no branches at all */
     const uint32_t n_deal = NDEAL >= 0 ? (uint32_t)NDEAL : mcq_opaque_uniform(qc.n_deal);
@@ -826,13 +1057,15 @@ MCQ_HD void mcq_deal_table(const McqQueryCtx &qc, Draws &dr, const McqCard *base
 // qc.n_opp / qc.n_deal): the iteration is ONE basic block, which lets the compiler send lookups early and wait late
 // across hands and draws -- the wave-uniform branches of the general form are scheduling barriers.
 // Acc = McqLaneAccWays: the split-pot form (see there); McqLaneAcc: the code is what it was before that form existed.
+// The hands are in the sum form (McqSumBoard / McqSumHole, ids instead of keys); mcq_iteration / mcq_iterations keep the
+// mask form's table arguments for the host builds of this file and find the sum-form tables behind them
+// (mcq_sum_tabs_of), the kernels call the _sum forms with their LDS image.
 template <class Draws, int NOPP = -1, int NDEAL = -1, class Acc = McqLaneAcc>
 // base128 = (base deck table) - 128 entries: draw indices carry a bias of 128 (r | 0x80), folded into the pointer.
-MCQ_HD void mcq_iteration(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const uint32_t *tf,
-                          const uint32_t *tops, const uint32_t *sd, Acc &acc) {
+MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const McqSumTabs &tabs, Acc &acc) {
     uint32_t H[5] = {MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL};
     uint32_t L = qc.L0;
-    McqHole opp[MCQ_MAX_OPP];
+    McqSumHole opp[MCQ_MAX_OPP];
     const uint32_t n_opp_d = NOPP >= 0 ? (uint32_t)NOPP : mcq_opaque_uniform(qc.n_opp);
 #define MCQ_OPP(P)                                                                                             \
     if (P < n_opp_d) {                                                                                         \
@@ -846,7 +1079,7 @@ MCQ_HD void mcq_iteration(const McqQueryCtx &qc, Draws &dr, const McqCard *base1
     }
     MCQ_OPP(0) MCQ_OPP(1) MCQ_OPP(2) MCQ_OPP(3) MCQ_OPP(4) MCQ_OPP(5) MCQ_OPP(6) MCQ_OPP(7) MCQ_OPP(8)
 #undef MCQ_OPP
-    McqBoard b = qc.board;
+    McqSumBoard b = qc.board_s;
     if (NOPP >= 0) {
         mcq_deal_table<(NOPP >= 0 ? (2 * NOPP + 3) / 4 : 0), Draws, NDEAL>(qc, dr, base128, H, L, b);
     } else switch (mcq_opaque_uniform((2u * qc.n_opp + 3u) / 4u)) { /* registers holding the opponents' holes: wave-uniform */
@@ -859,29 +1092,33 @@ MCQ_HD void mcq_iteration(const McqQueryCtx &qc, Draws &dr, const McqCard *base1
     }
     McqFlushSel fs;
     fs.from_board(b);
-    const uint32_t hk = mcq_eval_key(b, fs, qc.hero, tf, tops, sd);
+    const uint32_t hk = mcq_sum_key(b, fs, qc.hero_s, tabs);
     uint32_t best = 0;
-    uint32_t n_equal = 0; /* (split-pot form only) opponents whose key equals hero's */
+    uint32_t n_equal = 0; /* (split-pot form only) opponents whose id equals hero's */
     const uint32_t n_opp_e = NOPP >= 0 ? (uint32_t)NOPP : mcq_opaque_uniform(qc.n_opp); /* a fresh scalar compare per block, see mcq_opaque_uniform */
-#define MCQ_EVAL(P) /* the opponents' best key straight from the candidates: two v_max3_u32 per hand */ \
+#define MCQ_EVAL(P) /* the opponents' best id straight from the two lookups: one v_max3_u32 per hand */ \
     if (P < n_opp_e) {                                                     \
-        uint32_t c[4];                                                     \
-        mcq_eval_cands(b, fs, opp[P], tf, tops, sd, c);                    \
-        if (Acc::kWays) { /* the hand's own key: max3, max, compare, add with carry, max */ \
-            const uint32_t k3 = mcq_max3(c[0], c[1], c[2]);                \
-            const uint32_t k = k3 > c[3] ? k3 : c[3];                      \
+        uint32_t rid, fid;                                                 \
+        mcq_sum_ids(b, fs, opp[P], tabs, rid, fid);                        \
+        if (Acc::kWays) { /* the hand's own id: max, compare, add with carry, max */ \
+            const uint32_t k = rid > fid ? rid : fid;                      \
             n_equal += k == hk ? 1u : 0u;                                  \
             best = k > best ? k : best;                                    \
         } else {                                                           \
-            best = mcq_max3(mcq_max3(best, c[0], c[1]), c[2], c[3]);       \
+            best = mcq_max3(best, rid, fid);                               \
         }                                                                  \
     }
     MCQ_EVAL(0) MCQ_EVAL(1) MCQ_EVAL(2) MCQ_EVAL(3) MCQ_EVAL(4) MCQ_EVAL(5) MCQ_EVAL(6) MCQ_EVAL(7) MCQ_EVAL(8)
 #undef MCQ_EVAL
     uint64_t won = hk >= best ? 1u : 0u; /* ties go to hero (hand_evaluator.py:23) */
-    acc.types += won << (6u * (hk >> MCQ_KEY_SHIFT));
+    acc.types += won << (6u * (hk >> MCQ_ID_SHIFT));
     if constexpr (Acc::kWays) acc.ways += won << (6u * n_equal); /* pot shared by 1 + n_equal hands */
     else acc.tie += hk == best ? 1u : 0u;
+}
+template <class Draws, int NOPP = -1, int NDEAL = -1, class Acc = McqLaneAcc>
+MCQ_HD void mcq_iteration(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const uint32_t *tf,
+                          const uint32_t *, const uint32_t *, Acc &acc) {
+    mcq_iteration_sum<Draws, NOPP, NDEAL, Acc>(qc, dr, base128, mcq_sum_tabs_of(tf), acc);
 }
 
 // `cnt` iterations of one lane.  STRAIGHT: by the (wave-uniform) number of opponents, and before the flop also by the
@@ -889,33 +1126,65 @@ MCQ_HD void mcq_iteration(const McqQueryCtx &qc, Draws &dr, const McqCard *base1
 // which the compiler sends lookups early and waits late across hands and draws (6-max before the flop: 6.37 -> 6.00 ms;
 // the general form's wave-uniform branches are scheduling barriers).  Same arithmetic, same results.
 template <bool STRAIGHT, class Draws, class Acc>
-MCQ_HD void mcq_iterations(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const uint32_t *tf,
-                                               const uint32_t *tops, const uint32_t *sd, Acc &acc, uint32_t cnt) {
+MCQ_HD void mcq_iterations_sum(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const McqSumTabs &tabs, Acc &acc,
+                               uint32_t cnt) {
     if (STRAIGHT) {
 #define MCQ_STRAIGHT(N)                                                                                   \
     case N:                                                                                               \
         if (qc.n_deal == 5u)                                                                          \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, 5, Acc>(qc, dr, base128, tf, tops, sd, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, 5, Acc>(qc, dr, base128, tabs, acc); \
         else if (qc.n_deal == 2u)                                                                         \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, 2, Acc>(qc, dr, base128, tf, tops, sd, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, 2, Acc>(qc, dr, base128, tabs, acc); \
         else if (qc.n_deal == 1u)                                                                         \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, 1, Acc>(qc, dr, base128, tf, tops, sd, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, 1, Acc>(qc, dr, base128, tabs, acc); \
         else                                                                                              \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, N, -1, Acc>(qc, dr, base128, tf, tops, sd, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, -1, Acc>(qc, dr, base128, tabs, acc); \
         return;
         switch (qc.n_opp) {
             MCQ_STRAIGHT(1) MCQ_STRAIGHT(2) MCQ_STRAIGHT(3) MCQ_STRAIGHT(4) MCQ_STRAIGHT(5) MCQ_STRAIGHT(6) MCQ_STRAIGHT(7)
             case 8: /* (only the form with the table cards counted at run time: the others spill registers) */
-                for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, 8, -1, Acc>(qc, dr, base128, tf, tops, sd, acc);
+                for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, 8, -1, Acc>(qc, dr, base128, tabs, acc);
                 return;
             case 9:
-                for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, 9, -1, Acc>(qc, dr, base128, tf, tops, sd, acc);
+                for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, 9, -1, Acc>(qc, dr, base128, tabs, acc);
                 return;
             default: break; /* hero alone: the general form */
         }
 #undef MCQ_STRAIGHT
     }
-    for (uint32_t j = 0; j < cnt; j++) mcq_iteration<Draws, -1, -1, Acc>(qc, dr, base128, tf, tops, sd, acc);
+    for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, -1, -1, Acc>(qc, dr, base128, tabs, acc);
+}
+template <bool STRAIGHT, class Draws, class Acc>
+MCQ_HD void mcq_iterations(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const uint32_t *tf, const uint32_t *,
+                           const uint32_t *, Acc &acc, uint32_t cnt) {
+    mcq_iterations_sum<STRAIGHT>(qc, dr, base128, mcq_sum_tabs_of(tf), acc, cnt);
+}
+
+// Parity mode: the (up to four) iterations a lane takes from one McqReplayDraws4 load.  As in mcq_iterations_sum the loop
+// body is picked by the (wave-uniform) number of opponents, so that the opponents' deals and hands are straight code
+// without the general form's scalar compare and branch per opponent; the table cards to come stay counted at run time.
+// Same arithmetic, same results.
+template <class Acc>
+MCQ_HD void mcq_iterations_replay4(const McqQueryCtx &qc, McqReplayDraws4 &dr, const McqCard *base128, const McqSumTabs &tabs,
+                                   Acc &acc, uint32_t cnt4) {
+#define MCQ_REPLAY4(N)                                                                      \
+    case N:                                                                                 \
+        for (uint32_t k = 0; k < cnt4; k++) {                                               \
+            dr.sh = 8u * k;                                                                 \
+            mcq_iteration_sum<McqReplayDraws4, N, -1, Acc>(qc, dr, base128, tabs, acc);     \
+        }                                                                                   \
+        return;
+    /* (not the split-pot form: it sits at the register limit and the straight forms spill there, 24-40 bytes per lane) */
+    if constexpr (!Acc::kWays) switch (qc.n_opp) {
+        MCQ_REPLAY4(1) MCQ_REPLAY4(2) MCQ_REPLAY4(3) MCQ_REPLAY4(4) MCQ_REPLAY4(5)
+        default: break; /* hero alone, and seven to ten players (the straight forms of six and more opponents spill registers
+                           beside the 23 draw words of McqReplayDraws4): the general form */
+    }
+#undef MCQ_REPLAY4
+    for (uint32_t k = 0; k < cnt4; k++) {
+        dr.sh = 8u * k;
+        mcq_iteration_sum(qc, dr, base128, tabs, acc);
+    }
 }
 
 // ================================================================================================ extended queries

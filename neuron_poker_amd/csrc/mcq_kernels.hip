@@ -77,6 +77,23 @@ __device__ __forceinline__ void load_tables(LdsTablesEval &dst, const McqTables 
     __syncthreads();
 }
 
+// The plain evaluation kernels' image: the rank-sum hash and sel8 (McqSumImage, 115 KB), one contiguous copy.
+__device__ __forceinline__ void load_sum_tables(McqSumImage &dst, const McqTables *__restrict__ g) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(&g->sum);
+    uint4 *d = reinterpret_cast<uint4 *>(&dst);
+    constexpr uint32_t kVec = sizeof(McqSumImage) / 16;
+    uint32_t i = threadIdx.x;
+    for (; i + 7u * blockDim.x < kVec; i += 8u * blockDim.x) { /* eight 16-byte loads in flight per lane */
+        uint4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = src[i + k * blockDim.x];
+#pragma unroll
+        for (int k = 0; k < 8; k++) d[i + k * blockDim.x] = v[k];
+    }
+    for (; i < kVec; i += blockDim.x) d[i] = src[i];
+    __syncthreads();
+}
+
 // Exclusive prefix sum of one 64-bit value per thread over a 1024-thread block (two barriers): wave-level scan by
 // shuffles, the 16 wave totals through LDS.  Returns the sum of the values of all lower threads; *total = block sum.
 __device__ __forceinline__ uint64_t block_exclusive_scan_1024(uint64_t v, uint64_t *wave_tot /* LDS, 16 entries */,
@@ -926,7 +943,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
     /* split (0..4): small batches cut every 1024-iteration task into 2^split sub-tasks of 16 >> split iterations per
      * lane so that more waves share the work; the iterations and their random numbers stay the same (a sub-task
      * skips ahead in its lane's stream), so the tallies do not depend on it. */
-    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ __attribute__((aligned(16))) McqSumImage tab; /* first: the hash is read at constant offsets from LDS address 0 */
     __shared__ McqCard base_tab[kMaxBlock]; /* per wave: the query's ordered remaining deck, 64 entries x 16 B */
     /* SPLIT (small batches): the rows the work-group's waves END on are added up in LDS when they are one query's -- a
      * single long query is hundreds of waves, and twelve atomics per wave on ONE row serialise (a 100 000-run query: 392
@@ -943,10 +960,11 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
             s_done = 0u;
         }
     }
-    load_tables(tab, g_tab); /* (ends with a block barrier) */
+    load_sum_tables(tab, g_tab); /* (ends with a block barrier) */
+    const McqSumTabs tabs = {tab.hoff, tab.hrank, g_tab->tfid};
 
     const uint32_t lane = threadIdx.x & 63u;
-    /* small batches launch more waves than take work: the extra ones only help to bring the 97 KB table image in */
+    /* small batches launch more waves than take work: the extra ones only help to bring the 115 KB table image in */
     const uint32_t waves_per_block = work_wpb ? work_wpb : blockDim.x >> 6;
     if ((threadIdx.x >> 6) >= waves_per_block) return;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * waves_per_block + (threadIdx.x >> 6));
@@ -1009,7 +1027,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
                 /* words per iteration: one per opponent, one per two table cards */
                 for (uint32_t k = sub * chunk * (qc.n_opp + ((qc.n_deal + 1u) >> 1)); k != 0; k--) dr.rng.next();
                 const uint32_t cnt = (uint32_t)min((uint64_t)chunk, (uint64_t)qc.runs - it0);
-                mcq_iterations<true>(qc, dr, base - 128, g_tab->tf, tab.tops, tab.sd, acc, cnt); /* both dealing laws */
+                mcq_iterations_sum<true>(qc, dr, base - 128, tabs, acc, cnt); /* both dealing laws */
                 acc.passes = cnt * qc.n_opp; /* MCQ-CTR v5: one attempt per opponent, never re-drawn */
             }
         } else {
@@ -1024,10 +1042,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
                     McqReplayDraws4 dr;
                     dr.load(dbase + it4, stride, qc.n_opp, qc.n_deal);
                     const uint32_t cnt4 = (uint32_t)min((uint64_t)4u, (uint64_t)qc.runs - it4);
-                    for (uint32_t k = 0; k < cnt4; k++) {
-                        dr.sh = 8u * k;
-                        mcq_iteration(qc, dr, base - 128, g_tab->tf, tab.tops, tab.sd, acc);
-                    }
+                    mcq_iterations_replay4(qc, dr, base - 128, tabs, acc, cnt4);
                 }
             }
             acc.passes = 0; /* `passes` comes from the stream walk: mcq_mt_parse_kernel writes it into the row (the host walk
@@ -1137,7 +1152,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
                                                                     uint32_t *__restrict__ done, volatile uint32_t *done_flag,
                                                                     uint32_t ticket, uint32_t use_karg, McqDirectKarg karg) {
     constexpr uint32_t kWaves = kMaxBlock / 64, kStage = MCQ_DIRECT_STAGE_ROUNDS * kWaves;
-    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ __attribute__((aligned(16))) McqSumImage tab; /* first: the hash is read at constant offsets from LDS address 0 */
     __shared__ McqCard base_tab[kMaxBlock];
     typedef McqRowKind<WAYS> Row; /* WAYS: 22-word rows, tie_ways[9] behind by_type[9] */
     constexpr uint32_t kLanes = Row::kLanes;
@@ -1147,6 +1162,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
 
     const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
     McqCard *base = base_tab + (threadIdx.x & ~63u);
+    const McqSumTabs tabs = {tab.hoff, tab.hrank, g_tab->tfid};
     typedef McqCtrDrawsT<MODE == MCQ_INTERNAL_MODE_UNIFORM> Draws;
     /* The start of a one-launch query is a chain of latencies, so they overlap: the first rounds' work is asked for,
      * the table image is sent on its way global -> LDS without passing through registers (global_load_lds_dwordx4:
@@ -1181,21 +1197,18 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
     {
         typedef const __attribute__((address_space(1))) void *GlobalPtr;
         typedef __attribute__((address_space(3))) void *LdsPtr;
-        constexpr uint32_t kChunks = (MCQ_TF_BYTE_OFFSET + 1024u) / 1024u; /* tops, sd | kc, sel8: 1 KB per wave instruction */
-        static_assert(sizeof(LdsTablesEval) == kChunks * 1024u, "table image in LDS: whole 1 KB pieces");
-        const char *src = reinterpret_cast<const char *>(g_tab);
+        constexpr uint32_t kChunks = sizeof(McqSumImage) / 1024u; /* hoff, hrank, sel8: 1 KB per wave instruction */
+        const char *src = reinterpret_cast<const char *>(&g_tab->sum);
         char *dst = reinterpret_cast<char *>(&tab);
-        const char *sel = reinterpret_cast<const char *>(g_tab->sel8); /* the last piece: not behind sd in the global image */
-        /* the same number of pieces for every wave (the last one, sel8, is sent by all of them: same bytes, same
-         * place), so that the count of loads in flight is a constant the compiler can wait against */
+        /* the same number of pieces for every wave (a wave whose last piece would lie behind the image sends the
+         * image's last one again: same bytes, same place), so that the count of loads in flight is a constant the
+         * compiler can wait against */
         constexpr uint32_t kPer = (kChunks + kWaves - 1u) / kWaves;
-        static_assert((kPer - 1u) * kWaves == kChunks - 1u, "pieces per wave");
         const uint32_t wu = __builtin_amdgcn_readfirstlane(wib);
 #pragma unroll
         for (uint32_t k = 0; k < kPer; k++) {
-            const uint32_t c = k + 1u < kPer ? wu + k * kWaves : kChunks - 1u;
-            __builtin_amdgcn_global_load_lds((GlobalPtr)((k + 1u < kPer ? src + c * 1024u : sel) + lane * 16u),
-                                             (LdsPtr)(dst + c * 1024u), 16, 0, 0);
+            const uint32_t at = wu + k * kWaves, c = at < kChunks ? at : kChunks - 1u;
+            __builtin_amdgcn_global_load_lds((GlobalPtr)(src + c * 1024u + lane * 16u), (LdsPtr)(dst + c * 1024u), 16, 0, 0);
         }
     }
     /* round 0, task 0 of this wave: the lanes that have iterations to run there */
@@ -1278,7 +1291,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
                         }
                         MCQ_STAMP(5);
                         const uint32_t cnt = (uint32_t)min((uint64_t)chunk, (uint64_t)qc.runs - it0);
-                        for (uint32_t j = 0; j < cnt; j++) mcq_iteration(qc, dr, base - 128, g_tab->tf, tab.tops, tab.sd, acc);
+                        for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum(qc, dr, base - 128, tabs, acc);
                         acc.passes = cnt * qc.n_opp;
                         MCQ_STAMP(6);
                     }
