@@ -15,6 +15,7 @@
 typedef char query_is_16_bytes[sizeof(mcq_query) == 16 ? 1 : -1];
 typedef char result_is_104_bytes[sizeof(mcq_result) == 104 ? 1 : -1];
 typedef char result_ways_is_176_bytes[sizeof(mcq_result_ways) == 176 && offsetof(mcq_result_ways, tie_ways) == 104 ? 1 : -1];
+typedef char result_seats_is_256_bytes[sizeof(mcq_result_seats) == 256 && sizeof(mcq_seat) == 24 && offsetof(mcq_result_seats, seat) == 16 ? 1 : -1];
 typedef char ext_is_304_bytes[sizeof(mcq_query_ext) == 304 && sizeof(mcq_known_hand) == 28 ? 1 : -1];
 typedef char config_is_224_bytes[sizeof(mcq_tables_config) == 224 ? 1 : -1];
 typedef char runs_at_12[offsetof(mcq_query, runs) == 12 ? 1 : -1];
@@ -39,6 +40,10 @@ int main(int argc, char **argv) {
     }
     if (argc > 1 && strcmp(argv[1], "--layout-ways") == 0) { /* likewise, for the split-pot rows */
         printf("%d\n", (int)sizeof(mcq_result_ways));
+        return 0;
+    }
+    if (argc > 1 && strcmp(argv[1], "--layout-seats") == 0) { /* likewise, for the per-seat rows */
+        printf("%d\n", (int)sizeof(mcq_result_seats));
         return 0;
     }
     ctx = mcq_create(0, 0);

@@ -89,6 +89,26 @@ typedef struct mcq_result_ways {
     uint64_t tie_ways[9];
 } mcq_result_ways;
 
+/* Per-SEAT tallies of an extended query (256 bytes): what every hand of the query is worth, from ONE run of the
+ * iterations -- one random stream, so the shares add up to one pot.  Seat 0 is the hero, seats 1..n_known are
+ * mcq_query_ext.known[0..] in the order of original_player_card_list, the seats after them are the random or ranged
+ * opponents in dealing order; seats at or above n_players are all zero.  Per iteration, with best = the greatest ranking
+ * key among the n_players hands and k = the number of hands holding it, each of those k seats gets
+ *     win += (k == 1),  tie += (k > 1),  share += MCQ_SHARE_UNIT / k
+ * so the pot share of seat s is seat[s].share / (MCQ_SHARE_UNIT * runs) and sum_s seat[s].share == MCQ_SHARE_UNIT * runs
+ * exactly.  "Equal" means equal ranking key, as for mcq_result_ways.  All counters are integers and add across shards and
+ * calls.  runs and passes are what mcq_eval_batch_ext writes. */
+#define MCQ_SHARE_UNIT 2520u /* lcm(1..10): a pot split k ways gives each hand 2520 / k units, exactly */
+typedef struct mcq_seat {
+    uint64_t win;   /* this hand strictly best */
+    uint64_t tie;   /* this hand best together with at least one other */
+    uint64_t share; /* sum of MCQ_SHARE_UNIT / k over the iterations in which it is best */
+} mcq_seat;
+typedef struct mcq_result_seats {
+    uint64_t runs, passes;
+    mcq_seat seat[10];
+} mcq_result_seats;
+
 /* Optional extension of a query (304 bytes) for the rest of run_montecarlo's arguments:
  * ghost_cards (tools/montecarlo_python.py:206-208), any number of further known hands (collusion players, :133-163),
  * the hero or any known hand given as a SET of preflop classes instead of two cards (:136-148), and opponents
@@ -168,6 +188,20 @@ MCQ_API int mcq_eval_batch_ext(mcq_ctx *ctx, const mcq_query *q, const mcq_query
  * the one-launch path for up to eight small queries. */
 MCQ_API int mcq_eval_batch_ext_ways(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
                                     uint64_t first_query_id, int mode, mcq_result_ways *out);
+
+/* mcq_eval_batch_ext writing mcq_result_seats rows: every hand's win, tie and pot share from the same iterations.  The
+ * streams are those of mcq_eval_batch_ext (MCQ-CTR v5x keyed by (seed, first_query_id + i), same draws, same acceptance),
+ * so the hero's seat is pinned to the mcq_eval_batch_ext_ways row of the same arguments: runs, passes, seat[0].win and
+ * seat[0].tie equal that row's runs, passes, win and tie, and
+ *     seat[0].share == MCQ_SHARE_UNIT * win + sum_k (MCQ_SHARE_UNIT / k) * tie_ways[k - 2].
+ * A known hand that lost a card to an earlier ranged hand is evaluated with the cards it names, as there.  Every contract
+ * of mcq_eval_batch_ext holds: validation first and MCQ_EINVAL leaves out untouched, MCQ_EBUSY, the undealable range, the
+ * refusal under MCQ_LAW_UNIFORM, sharding by first_query_id.
+ * MCQ_MODE_PHILOX only: MCQ_MODE_REPLAY_MT19937 gives MCQ_EINVAL -- the reference has no per-seat number to be bit-exact
+ * against, and the parity walk for rows of this width is not built.  Every call takes the general path (prep, candidate
+ * lists, evaluation kernel); the one-launch path for small queries has no per-seat form. */
+MCQ_API int mcq_eval_batch_ext_seats(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
+                                     uint64_t first_query_id, int mode, mcq_result_seats *out);
 
 /* Parity mode coupled to numpy's GLOBAL random state, as consecutive reference calls are: the n
  * queries consume ONE MT19937 stream in order.  mt_key[624] / *mt_pos are numpy's state words and position
@@ -268,6 +302,18 @@ typedef struct mcq_exact_prob_ways {
 } mcq_exact_prob_ways; /* 160 bytes */
 MCQ_API int mcq_exact_batch_ext_ways(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
                                      mcq_exact_prob_ways *prob, mcq_result_ways *weights);
+
+/* The ALL-IN case, exact and per seat: records with NO random opponent (n_players == 1 + n_known, 2..10 hands, every hand
+ * given as two cards, optional ghost cards, 0/3/4/5 table cards, both laws).  Every table completion (at most
+ * C(48, 5) = 1 712 304, each of weight 0 or 1) is ranked for every hand: weights[i].runs = total weight, passes = 0,
+ * seat[s].win and seat[s].tie in weight units, seat[s].share in weight x MCQ_SHARE_UNIT units -- the exact pot share of
+ * seat s is seat[s].share / (MCQ_SHARE_UNIT * runs).  Seat 0's win and tie are mcq_exact_batch_ext_ways's weights, and
+ * because the deck and the completion weights do not depend on the order of the hands, seat s equals the hero columns of
+ * the record with hand s rotated to the front.
+ * Refused with MCQ_EINVAL, nothing launched: whatever mcq_exact_batch_ext refuses, and any record with a random opponent
+ * (one or two random opponents need a per-seat form of that enumeration's candidate-hand passes: not built). */
+MCQ_API int mcq_exact_batch_seats(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                                  mcq_result_seats *weights);
 
 /* Select the dealing law used by MCQ_MODE_PHILOX on this context (MCQ_LAW_*).  Extended queries
  * (mcq_eval_batch_ext) are dealt by the reference's law only: under MCQ_LAW_UNIFORM that call gives MCQ_EINVAL. */

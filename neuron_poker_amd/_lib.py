@@ -22,6 +22,12 @@ RESULT_DTYPE = np.dtype([("runs", "<u8"), ("passes", "<u8"), ("win", "<u8"), ("t
                          ("by_type", "<u8", (9,))])
 # mcq_result_ways: the same 13 counters, then tie_ways[k - 2] = iterations in which k hands share the pot, k = 2..10
 RESULT_WAYS_DTYPE = np.dtype(RESULT_DTYPE.descr + [("tie_ways", "<u8", (9,))])
+# mcq_result_seats: runs, passes, then win / tie / share of every seat (seat 0 = hero, then the known hands, then the random
+# or ranged opponents in dealing order); share counts SHARE_UNIT / k per iteration in which the seat is one of k best hands
+SHARE_UNIT = 2520
+SEAT_DTYPE = np.dtype([("win", "<u8"), ("tie", "<u8"), ("share", "<u8")])
+RESULT_SEATS_DTYPE = np.dtype([("runs", "<u8"), ("passes", "<u8"), ("seat", SEAT_DTYPE, (10,))])
+RESULT_SEATS = RESULT_SEATS_DTYPE
 KNOWN_HAND_DTYPE = np.dtype([("cards", "u1", (2,)), ("is_range", "u1"), ("reserved", "u1"), ("range", "<u4", (6,))])
 MAX_KNOWN = 9
 QUERY_EXT_DTYPE = np.dtype([("ghost", "u1", (2,)), ("hero_is_range", "u1"), ("n_known", "u1"), ("opp_range", "<u4", (6,)),
@@ -115,6 +121,10 @@ def load_library():
         L.mcq_eval_batch_ext_ways.restype = C.c_int
         L.mcq_exact_batch_ext_ways.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
         L.mcq_exact_batch_ext_ways.restype = C.c_int
+        L.mcq_eval_batch_ext_seats.argtypes = [vp, vp, vp, sz, u64, u64, C.c_int, vp]
+        L.mcq_eval_batch_ext_seats.restype = C.c_int
+        L.mcq_exact_batch_seats.argtypes = [vp, vp, vp, sz, C.c_int, vp]
+        L.mcq_exact_batch_seats.restype = C.c_int
         L.mcq_eval_batch_device_small.argtypes = [vp, vp, sz, u64, u64, vp, vp]
         L.mcq_eval_batch_device_small.restype = C.c_int
         L.mcq_showdown.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp]
@@ -218,6 +228,22 @@ def pot_share(rows, exact=False):
         t = t.view(np.uint64)
     t = t.reshape(-1, 22).astype(np.float64)
     return (t[:, 2] + (t[:, 13:22] / np.arange(2, 11, dtype=np.float64)).sum(1)) / np.maximum(t[:, 0], 1.0)
+
+
+def seat_shares(rows, n_players=None):
+    """Pot share of every seat, float64 [B, 10], from rows of RESULT_SEATS_DTYPE (or a [B, 32] integer matrix) -- Monte-Carlo
+    tallies of Engine.eval_batch_ext_seats or the integer weights of Engine.exact_seats alike: share / (SHARE_UNIT * runs).
+    The columns of the seats nobody sits in (at or above a query's n_players) are 0.0 when n_players is None, as the rows
+    hold them, and NaN when n_players (one number, or one per row) is passed."""
+    t = np.ascontiguousarray(rows)
+    if t.dtype == RESULT_SEATS_DTYPE:
+        t = t.view(np.uint64)
+    t = t.reshape(-1, 32)
+    out = t[:, 4::3].astype(np.float64) / (float(SHARE_UNIT) * np.maximum(t[:, :1].astype(np.float64), 1.0))
+    if n_players is not None:
+        n = np.broadcast_to(np.asarray(n_players, np.int64).reshape(-1, 1), (len(out), 1))
+        out[np.arange(10)[None, :] >= n] = np.nan
+    return out
 
 
 def pack_query_one(hole, board, n_players, runs):
@@ -418,6 +444,38 @@ class Engine:
         out = np.zeros(len(q), RESULT_WAYS_DTYPE)
         rc = self._lib.mcq_eval_batch_ext_ways(self._ctx, q.ctypes.data, e.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
                                                int(first_query_id) & (2 ** 64 - 1), int(mode), out.ctypes.data)
+        if rc:
+            _raise(rc)
+        return out
+
+    def eval_batch_ext_seats(self, queries, ext, seed, first_query_id=0):
+        """eval_batch_ext with one tally per SEAT (mcq_eval_batch_ext_seats; production mode): every hand's win, tie and
+        pot share from the same iterations.  -> array of RESULT_SEATS_DTYPE; runs, passes and seat 0's win and tie are
+        what eval_batch_ext_ways returns for the same arguments; seat_shares(rows) gives the pot shares."""
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        out = np.zeros(len(q), RESULT_SEATS_DTYPE)
+        rc = self._lib.mcq_eval_batch_ext_seats(self._ctx, q.ctypes.data, e.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
+                                                int(first_query_id) & (2 ** 64 - 1), MODE_PHILOX, out.ctypes.data)
+        if rc:
+            _raise(rc)
+        return out
+
+    def exact_seats(self, queries, ext, law="reference"):
+        """Exact per-seat enumeration of the all-in case (mcq_exact_batch_seats): every hand known, no random opponent.
+        -> RESULT_SEATS_DTYPE rows of integer weights: runs = total weight, seat[s].share / (SHARE_UNIT * runs) is the
+        exact pot share of seat s (seat_shares(rows))."""
+        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
+        if code is None:
+            raise ValueError("law must be 'reference' or 'uniform'")
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        out = np.zeros(len(q), RESULT_SEATS_DTYPE)
+        rc = self._lib.mcq_exact_batch_seats(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, out.ctypes.data)
         if rc:
             _raise(rc)
         return out

@@ -927,7 +927,7 @@ MCQ_HD McqCard mcq_base_entry(const McqQueryCtx &qc, uint32_t l, const uint32_t 
 }
 
 struct McqLaneAcc {
-    static constexpr bool kWays = false;
+    static constexpr bool kWays = false, kSeats = false;
     uint64_t types; /* MCQ_N_CODES fields of 6 bits: hero's winning hand codes (<= 16 per lane per task) */
     uint32_t tie;
     uint32_t passes;
@@ -939,11 +939,33 @@ struct McqLaneAcc {
 #define MCQ_N_WAYS 9u /* tie_ways[k - 2], k = 2..10 hands sharing the pot */
 // (No `tie` here: it is the sum of fields 1..9, taken when the lanes are added up -- a register the iteration keeps.)
 struct McqLaneAccWays {
-    static constexpr bool kWays = true;
+    static constexpr bool kWays = true, kSeats = false;
     uint64_t types;
     uint32_t passes;
     uint64_t ways;
 };
+// The per-seat form (mcq_result_seats; extended queries, mcq_iteration_ext only): every hand's key is compared with the
+// best of ALL hands, and each of the k seats holding it is credited.  One word per seat, three fields: share (16 bits:
+// at most 16 iterations x 2520 per lane per task), win and tie (5 bits each, <= 16).  The word an iteration adds to each
+// level seat depends on k alone: 2520 / k from a table (never a division), plus the win field's unit for k == 1, the tie
+// field's otherwise.
+#define MCQ_MAX_SEATS 10u
+#define MCQ_SEAT_WIN_SHIFT 16u
+#define MCQ_SEAT_TIE_SHIFT 21u
+struct McqLaneAccSeats {
+    static constexpr bool kWays = false, kSeats = true;
+    uint32_t passes;
+    uint32_t seat[MCQ_MAX_SEATS];
+};
+static_assert(MCQ_STREAM_ITERS * MCQ_SHARE_UNIT < (1u << MCQ_SEAT_WIN_SHIFT) && MCQ_STREAM_ITERS < 32u, "fields of McqLaneAccSeats");
+MCQ_HD uint32_t mcq_seat_increment(uint32_t k) { /* k = 1..10 hands share the pot */
+    static constexpr uint32_t kInc[MCQ_MAX_SEATS] = {
+        2520u | (1u << MCQ_SEAT_WIN_SHIFT), 1260u | (1u << MCQ_SEAT_TIE_SHIFT), 840u | (1u << MCQ_SEAT_TIE_SHIFT),
+        630u | (1u << MCQ_SEAT_TIE_SHIFT),  504u | (1u << MCQ_SEAT_TIE_SHIFT),  420u | (1u << MCQ_SEAT_TIE_SHIFT),
+        360u | (1u << MCQ_SEAT_TIE_SHIFT),  315u | (1u << MCQ_SEAT_TIE_SHIFT),  280u | (1u << MCQ_SEAT_TIE_SHIFT),
+        252u | (1u << MCQ_SEAT_TIE_SHIFT)};
+    return kInc[k - 1u];
+}
 
 // ------------------------------------------------------------------------------------------ dealing without search
 // list.pop(r) on the ordered remaining deck, reformulated so that no k-th-set-bit search is needed:
@@ -1531,6 +1553,23 @@ MCQ_HD bool mcq_iteration_ext(const McqExtCtx &qc, const McqExtWaveCtx &wc, Draw
     fs.from_board(b);
     uint32_t hk = 0, best = 0;
     uint32_t n_equal = 0; /* (split-pot form only) other hands whose key equals hero's */
+    if constexpr (Acc::kSeats) { /* the best of ALL hands and the seats that hold it; no key is kept */
+        uint32_t level = 0;
+        for (uint32_t h = 0; h < qc.n_players; h++) {
+            const uint32_t v = ids[h * ids_stride];
+            MCQ_EXT_DEALT(h, v & 0xFFu, (v >> 8) & 0xFFu);
+            McqHole hh;
+            hh.set(cards[v & 0xFFu], cards[(v >> 8) & 0xFFu]);
+            const uint32_t k = mcq_eval_key(b, fs, hh, tf, tops, sd);
+            level = k > best ? 0u : level;
+            level |= k >= best ? 1u << h : 0u;
+            best = k > best ? k : best;
+        }
+        const uint32_t inc = mcq_seat_increment(mcq_popc(level)); /* (hero is always dealt: at least one seat) */
+#pragma unroll
+        for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) acc.seat[s] += ((level >> s) & 1u) ? inc : 0u;
+        return dealt;
+    }
     for (uint32_t h = 0; h < qc.n_players; h++) {
         const uint32_t v = ids[h * ids_stride];
         MCQ_EXT_DEALT(h, v & 0xFFu, (v >> 8) & 0xFFu);
@@ -1543,10 +1582,12 @@ MCQ_HD bool mcq_iteration_ext(const McqExtCtx &qc, const McqExtWaveCtx &wc, Draw
             if (Acc::kWays) n_equal += k == hk ? 1u : 0u; /* (hero comes first: hk is known) */
         }
     }
-    uint64_t won = hk >= best ? 1u : 0u;
-    acc.types += won << (6u * (hk >> MCQ_KEY_SHIFT));
-    if constexpr (Acc::kWays) acc.ways += won << (6u * n_equal); /* pot shared by 1 + n_equal hands */
-    else acc.tie += hk == best ? 1u : 0u;
+    if constexpr (!Acc::kSeats) {
+        uint64_t won = hk >= best ? 1u : 0u;
+        acc.types += won << (6u * (hk >> MCQ_KEY_SHIFT));
+        if constexpr (Acc::kWays) acc.ways += won << (6u * n_equal); /* pot shared by 1 + n_equal hands */
+        else acc.tie += hk == best ? 1u : 0u;
+    }
     return dealt;
 }
 

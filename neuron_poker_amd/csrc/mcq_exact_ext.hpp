@@ -183,6 +183,29 @@ MCQ_HD uint32_t mcq_exact_ext_lone_ways(const McqExactExtQuery &e, uint32_t idx,
     return mcq_key_type(bd.hero_key);
 }
 
+// The same per SEAT (mcq_result_seats: no random opponent): the greatest key among hero (seat 0) and the known hands
+// (seats 1..n_known) of completion `idx`, level = the mask of the seats that hold it, k = how many they are.  Returns the
+// completion's weight (0 or 1).
+MCQ_HD uint32_t mcq_exact_ext_lone_seats(const McqExactExtQuery &e, uint32_t idx, const uint32_t *sel8, const uint32_t *tf,
+                                         const uint32_t *tops, const uint32_t *sd, uint32_t &level, uint32_t &k) {
+    uint32_t pos[5];
+    mcq_exact_unrank(idx, e.b.L, e.b.k, pos);
+    McqExactBoard bd;
+    mcq_exact_board(e.b, pos, sel8, tf, tops, sd, bd);
+    uint32_t best = bd.hero_key;
+    level = 1u;
+    for (uint32_t h = 0; h < e.n_known; h++) {
+        McqHole kh;
+        kh.set(mcq_card(e.known[h] & 0xFFu), mcq_card(e.known[h] >> 8));
+        const uint32_t key = mcq_eval_key(bd.b, bd.fs, kh, tf, tops, sd);
+        level = key > best ? 0u : level;
+        level |= key >= best ? 2u << h : 0u;
+        best = key > best ? key : best;
+    }
+    k = mcq_popc(level);
+    return !e.b.ref_law || bd.u > 0u ? 1u : 0u;
+}
+
 // the range bits of every R-pair (index pb (pb - 1) / 2 + pa): they do not depend on the completion; entries rp, rp + step, ...
 MCQ_HD void mcq_exact_ext_cb_table(const McqExactExtQuery &e, const uint8_t *r_id, uint32_t rp0, uint32_t step, uint8_t *cb_tab) {
     for (uint32_t rp = rp0; rp < e.n_rp; rp += step) {

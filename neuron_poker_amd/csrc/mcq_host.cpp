@@ -35,6 +35,8 @@ constexpr uint32_t kBlock = 1024;                /* threads per block of the eva
  * as `rw` words; row i of a buffer starts rw * 8 * i bytes in. */
 constexpr uint32_t kPlainWords = sizeof(mcq_result) / 8u, kWaysWords = sizeof(mcq_result_ways) / 8u;
 static_assert(kPlainWords == 13u && kWaysWords == 22u && sizeof(mcq_result_ways) % 16u == 0u, "result rows");
+constexpr uint32_t kSeatsWords = sizeof(mcq_result_seats) / 8u; /* per-seat rows: the extended general path and the all-in enumeration */
+static_assert(kSeatsWords == 32u && sizeof(mcq_seat) == 24u, "per-seat rows");
 inline mcq_result *row_at(void *rows, size_t i, uint32_t rw) { /* (the first 13 words of either row are an mcq_result) */
     return reinterpret_cast<mcq_result *>(static_cast<char *>(rows) + i * rw * 8u);
 }
@@ -963,12 +965,15 @@ int mcq_eval_one(mcq_ctx *c, const mcq_query *q, uint64_t seed, int mode, mcq_re
 
 }  // extern "C"
 
-/* mcq_eval_batch_ext and mcq_eval_batch_ext_ways: rw = 64-bit words of a result row (out -> rows of that length) */
+/* mcq_eval_batch_ext, mcq_eval_batch_ext_ways and mcq_eval_batch_ext_seats: rw = 64-bit words of a result row (out ->
+ * rows of that length).  The per-seat rows: production mode only, always the general path. */
 static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
                                uint64_t first_query_id, int mode, void *out, uint32_t rw) {
-    const bool ways = rw == kWaysWords;
+    const bool ways = rw == kWaysWords, seats = rw == kSeatsWords;
     const size_t row_bytes = (size_t)rw * 8u;
     if (mode != MCQ_MODE_PHILOX && mode != MCQ_MODE_REPLAY_MT19937) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: bad mode");
+    if (seats && mode != MCQ_MODE_PHILOX)
+        return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext_seats: MCQ_MODE_PHILOX only (the per-seat rows have no parity form)");
     if (n == 0) return MCQ_OK;
     if (!c) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: null context");
     if (!q || !ext || !out) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: null buffer");
@@ -1000,7 +1005,7 @@ static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_e
     McqDeviceScope dev_(c->device);
     HIP_TRY(dev_.err);
     HIP_TRY(c->h_res.reserve(n * row_bytes));
-    if (mode == MCQ_MODE_PHILOX && c->ext_small && n <= MCQ_EXT_SMALL_Q && lists_stride <= MCQ_EXT_SMALL_LISTS &&
+    if (!seats && mode == MCQ_MODE_PHILOX && c->ext_small && n <= MCQ_EXT_SMALL_Q && lists_stride <= MCQ_EXT_SMALL_LISTS &&
         most_tasks <= MCQ_EXT_SMALL_TASKS && !stream_capturing(c->stream)) {
         /* what a decision of the reference's agents asks for -- one ranged query of a thousand iterations -- in ONE
          * launch: the records in the kernel arguments, a block per query (lists laid out in its LDS), the rows into
@@ -1107,7 +1112,7 @@ static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_e
                                 (const uint64_t *)c->scratch[0].prefix.p, (mcq_result *)c->d_res.p, seed, first_query_id, c->d_luts,
                                 (const uint8_t *)c->d_draws.p, (const uint64_t *)c->d_off.p, (const uint16_t *)c->d_lists.p,
                                 (const uint32_t *)c->d_cnts.p, lists_stride, grid, block, c->stream,
-                                t0, c->timing ? c->ev1[slot] : nullptr, ways));
+                                t0, c->timing ? c->ev1[slot] : nullptr, ways, seats));
     if (c->timing) c->n_timed++;
     HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * row_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1134,6 +1139,13 @@ int mcq_eval_batch_ext_ways(mcq_ctx *c, const mcq_query *q, const mcq_query_ext 
     ABI_GUARD_BEGIN
     return eval_batch_ext_impl(c, q, ext, n, seed, first_query_id, mode, out, kWaysWords);
     ABI_GUARD_END("mcq_eval_batch_ext_ways")
+}
+
+int mcq_eval_batch_ext_seats(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, uint64_t seed,
+                             uint64_t first_query_id, int mode, mcq_result_seats *out) {
+    ABI_GUARD_BEGIN
+    return eval_batch_ext_impl(c, q, ext, n, seed, first_query_id, mode, out, kSeatsWords);
+    ABI_GUARD_END("mcq_eval_batch_ext_seats")
 }
 
 int mcq_eval_batch_numpy_stream(mcq_ctx *c, const mcq_query *q, size_t n, uint32_t *mt_key, uint32_t *mt_pos,
@@ -1251,15 +1263,15 @@ int mcq_exact_batch(mcq_ctx *c, const mcq_query *q, size_t n, int law, mcq_resul
 
 }  // extern "C"
 
-/* mcq_exact_batch_ext and mcq_exact_batch_ext_ways: rw = 64-bit words of a weight row; prob -> mcq_exact_prob or
- * mcq_exact_prob_ways, weights -> rows of rw words */
+/* mcq_exact_batch_ext, mcq_exact_batch_ext_ways and mcq_exact_batch_seats: rw = 64-bit words of a weight row; prob ->
+ * mcq_exact_prob or mcq_exact_prob_ways (none for the per-seat rows), weights -> rows of rw words */
 static int exact_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, void *prob,
                                 void *weights, uint32_t rw, const char *who) {
-    const bool ways = rw == kWaysWords;
+    const bool ways = rw == kWaysWords, seats = rw == kSeatsWords;
     const size_t row_bytes = (size_t)rw * 8u;
     if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
     if (n == 0) return MCQ_OK;
-    if (!q || !ext || !prob) return mcq_fail(MCQ_EINVAL, who, "null buffer");
+    if (!q || !ext || (seats ? !weights : !prob)) return mcq_fail(MCQ_EINVAL, who, "null buffer");
     if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return mcq_fail(MCQ_EINVAL, who, "bad law");
     if (n > 65535u) return mcq_fail(MCQ_EINVAL, who, "at most 65535 queries per call");
     /* validation first: nothing is launched for a batch with one query that cannot be enumerated */
@@ -1281,6 +1293,10 @@ static int exact_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_
         mcq_exact_ext_r_ids(xq[i], &rid[64u * i]);
         if (!mcq_exact_ext_dealable(xq[i], &rid[64u * i])) {
             snprintf(buf, sizeof buf, "query %zu: the opponents' range cannot be dealt from the remaining cards", i);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+        if (seats && xq[i].b.n_opp != 0u) {
+            snprintf(buf, sizeof buf, "query %zu: the per-seat enumeration takes known hands only (n_players == 1 + n_known)", i);
             return mcq_fail(MCQ_EINVAL, who, buf);
         }
         if (xq[i].b.n_opp == 2u) {
@@ -1325,13 +1341,17 @@ static int exact_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_
             if (kind == 2u) off += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
         }
         HIP_TRY(mcq_launch_exact_ext(d_jobs + first, (uint32_t)(at - first), max_grid, kind, d_ext, law, (mcq_result *)c->d_res.p,
-                                     (unsigned long long *)c->d_draws.p, c->d_luts, c->stream, ways));
+                                     (unsigned long long *)c->d_draws.p, c->d_luts, c->stream, ways, seats));
     }
     uint8_t *hr = static_cast<uint8_t *>(c->h_res.p);
     HIP_TRY(hipMemcpyAsync(hr, c->d_res.p, n * row_bytes, hipMemcpyDeviceToHost, c->stream));
     if (h1_words)
         HIP_TRY(hipMemcpyAsync(hr + n * row_bytes, c->d_draws.p, h1_words * 8u, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (seats) { /* the rows are the result: integer weights, nothing to normalise */
+        memcpy(weights, hr, n * row_bytes);
+        return MCQ_OK;
+    }
     const unsigned long long *h1 = reinterpret_cast<const unsigned long long *>(hr + n * row_bytes);
     for (size_t i = 0; i < n; i++) {
         mcq_result_ways w = {};
@@ -1362,6 +1382,12 @@ int mcq_exact_batch_ext_ways(mcq_ctx *c, const mcq_query *q, const mcq_query_ext
     ABI_GUARD_BEGIN
     return exact_batch_ext_impl(c, q, ext, n, law, prob, weights, kWaysWords, "mcq_exact_batch_ext_ways");
     ABI_GUARD_END("mcq_exact_batch_ext_ways")
+}
+
+int mcq_exact_batch_seats(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, mcq_result_seats *weights) {
+    ABI_GUARD_BEGIN
+    return exact_batch_ext_impl(c, q, ext, n, law, nullptr, weights, kSeatsWords, "mcq_exact_batch_seats");
+    ABI_GUARD_END("mcq_exact_batch_seats")
 }
 
 }  // extern "C"

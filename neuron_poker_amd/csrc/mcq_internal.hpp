@@ -38,7 +38,8 @@ uint32_t mcq_exact_ext_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint
 hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, uint32_t kind,
                                 const uint32_t *d_ext, int law, mcq_result *d_rows, unsigned long long *d_h1,
                                 const McqTables *d_luts, hipStream_t s,
-                                bool ways = false /* kinds 0 and 1: d_rows holds zeroed mcq_result_ways rows */);
+                                bool ways = false /* kinds 0 and 1: d_rows holds zeroed mcq_result_ways rows */,
+                                bool seats = false /* kind 0: d_rows holds zeroed mcq_result_seats rows */);
 hipError_t mcq_launch_exact(const McqExactJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, bool two_opp, int law,
                             mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
 /* hands / winner / wtype / keys: device-visible memory (pinned host memory or HBM), 16-byte aligned and padded to whole
@@ -73,7 +74,8 @@ hipError_t mcq_launch_eval_ext(int mode, const mcq_query *d_q, const mcq_query_e
                                const McqTables *d_luts, const uint8_t *d_draws, const uint64_t *d_draw_off,
                                const uint16_t *d_lists, const uint32_t *d_cnts, uint32_t lists_stride, uint32_t grid,
                                uint32_t block, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
-                               bool ways = false /* d_res holds mcq_result_ways rows (prepared with row_words = 22) */);
+                               bool ways = false /* d_res holds mcq_result_ways rows (prepared with row_words = 22) */,
+                               bool seats = false /* production mode: mcq_result_seats rows (row_words = 32) */);
 /* host-buffer calls with few rows: d_rows[0..n_rows) -> pinned host memory (device address h_rows_dev), d_rows zeroed,
  * then *done_flag = ticket; n_rows even (buffers hold the odd row's neighbour), d_done a zeroed device word */
 hipError_t mcq_launch_publish(mcq_result *d_rows, mcq_result *h_rows_dev, uint64_t n_rows, uint32_t *d_done,

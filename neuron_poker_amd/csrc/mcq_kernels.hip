@@ -910,15 +910,53 @@ struct WaveTallyWays {
         clear();
     }
 };
+/* The per-seat rows (mcq_result_seats, extended queries): word 1 passes, then win, tie, share of seat 0..9 -- lane l holds
+ * word 1 + l, lanes 0..30.  Thirty running counters per lane would not fit beside the iteration's state, so nothing is
+ * kept per lane between tasks: a task's lane words (McqLaneAccSeats: one packed word per seat) are summed over the wave
+ * at once -- the share field on its own (64 lanes x 16 x 2520 < 2^22), win and tie together as 16-bit halves (<= 1024
+ * each) -- and every lane adds the sum of ITS word to one 64-bit register, which goes to the row as one atomic per lane
+ * when the wave leaves the query. */
+struct WaveTallySeats {
+    unsigned long long mine;
+    bool dirty;
+    __device__ __forceinline__ void clear() {
+        mine = 0;
+        dirty = false;
+    }
+    __device__ __forceinline__ void add(const McqLaneAccSeats &a, uint32_t lane) { /* whole wave */
+        const uint32_t pass = wave_sum_dpp(a.passes);
+        uint32_t v = lane == 0u ? pass : 0u;
+#pragma unroll
+        for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) {
+            const uint32_t w = a.seat[s];
+            const uint32_t share = wave_sum_dpp(w & 0xFFFFu);
+            const uint32_t wt = wave_sum_dpp(((w >> MCQ_SEAT_WIN_SHIFT) & 31u) | (((w >> MCQ_SEAT_TIE_SHIFT) & 31u) << 16));
+            v = lane == 1u + 3u * s ? wt & 0xFFFFu : v;
+            v = lane == 2u + 3u * s ? wt >> 16 : v;
+            v = lane == 3u + 3u * s ? share : v;
+        }
+        mine += v;
+        dirty = true;
+    }
+    __device__ __forceinline__ void flush(unsigned long long *row, uint32_t lane) {
+        if (!dirty) return;
+        if (lane < 1u + 3u * MCQ_MAX_SEATS && mine != 0ull) atomicAdd(row + 1 + lane, mine);
+        clear();
+    }
+};
 /* what a kernel instantiation works with: the lane accumulator, the wave tally, the row's length in 64-bit words and the
- * lanes that hold one word of it each (every word but `runs`) */
-template <bool WAYS> struct McqRowKind {
+ * lanes that hold one word of it each (every word but `runs`).  KIND: MCQ_ROW_PLAIN (0 = false), MCQ_ROW_WAYS (1 = true),
+ * MCQ_ROW_SEATS (the extended general path only). */
+#define MCQ_ROW_PLAIN 0
+#define MCQ_ROW_WAYS 1
+#define MCQ_ROW_SEATS 2
+template <int KIND> struct McqRowKind {
     typedef McqLaneAcc Acc;
     typedef WaveTally Tally;
     static constexpr uint32_t kWords = 13u, kLanes = 12u;
     static __device__ __forceinline__ mcq_result *row(mcq_result *res, uint32_t i) { return res + i; }
 };
-template <> struct McqRowKind<true> {
+template <> struct McqRowKind<MCQ_ROW_WAYS> {
     typedef McqLaneAccWays Acc;
     typedef WaveTallyWays Tally;
     static constexpr uint32_t kWords = 13u + MCQ_N_WAYS, kLanes = 12u + MCQ_N_WAYS;
@@ -926,7 +964,16 @@ template <> struct McqRowKind<true> {
         return reinterpret_cast<unsigned long long *>(res) + (size_t)i * kWords;
     }
 };
+template <> struct McqRowKind<MCQ_ROW_SEATS> {
+    typedef McqLaneAccSeats Acc;
+    typedef WaveTallySeats Tally;
+    static constexpr uint32_t kWords = 2u + 3u * MCQ_MAX_SEATS; /* lanes 0..30 hold words 1..31 */
+    static __device__ __forceinline__ unsigned long long *row(mcq_result *res, uint32_t i) {
+        return reinterpret_cast<unsigned long long *>(res) + (size_t)i * kWords;
+    }
+};
 static_assert(McqRowKind<true>::kWords * 8u == sizeof(mcq_result_ways), "row of mcq_result_ways");
+static_assert(McqRowKind<MCQ_ROW_SEATS>::kWords * 8u == sizeof(mcq_result_seats) && sizeof(mcq_seat) == 24u, "row of mcq_result_seats");
 
 template <int MODE, bool SPLIT, bool WAYS>
 __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__restrict__ queries, uint32_t n,
@@ -1435,7 +1482,7 @@ __global__ __launch_bounds__(kListBlock) void mcq_ext_lists_kernel(const mcq_que
     }
 }
 
-template <int MODE, bool WAYS>
+template <int MODE, int ROW>
 __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query *__restrict__ queries,
                                                                  const mcq_query_ext *__restrict__ ext, uint32_t n,
                                                                  const uint64_t *__restrict__ prefix,
@@ -1445,8 +1492,11 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
                                                                  const uint64_t *__restrict__ draw_off,
                                                                  const uint16_t *__restrict__ lists,
                                                                  const uint32_t *__restrict__ cnts, uint32_t lists_stride) {
-    typedef McqRowKind<WAYS> Row; /* WAYS: 22-word rows with the ties split by the hands that share the pot */
+    typedef McqRowKind<ROW> Row; /* MCQ_ROW_WAYS: 22-word rows with the ties split by the hands that share the pot;
+                                    MCQ_ROW_SEATS: 32-word rows, every hand's win, tie and share (production mode only) */
     typedef typename Row::Acc Acc;
+    constexpr bool SEATS = ROW == MCQ_ROW_SEATS;
+    static_assert(!SEATS || MODE == MCQ_MODE_PHILOX, "the per-seat rows have no parity form");
     __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
     __shared__ McqCard cards[64];
     __shared__ McqExtWaveCtx wave_ctx[kExtBlock / 64];
@@ -1590,7 +1640,14 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
                 McqExtCtrDraws dr;
                 dr.start(seed, first_qid + qi, stream);
                 const uint32_t cnt = (uint32_t)min((uint64_t)s_iters, (uint64_t)qc.runs - it0);
-                if (qc.fast && list_in_lds) /* (wave-uniform) */
+                if constexpr (SEATS) { /* the general form only: the same draws and hands as the other rows' two forms */
+                    if (list_in_lds)
+                        for (uint32_t j = 0; j < cnt && !failed; j++)
+                            failed = !mcq_iteration_ext<McqExtCtrDraws, true, Acc>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
+                    else
+                        for (uint32_t j = 0; j < cnt && !failed; j++)
+                            failed = !mcq_iteration_ext<McqExtCtrDraws, false, Acc>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
+                } else if (qc.fast && list_in_lds) /* (wave-uniform) */
                     for (uint32_t j = 0; j < cnt && !failed; j++)
                         failed = !mcq_iteration_ext_fast<McqExtCtrDraws, true, true, Acc>(qc, wc, dr, cards, tab.sel8, g_tab->tf, tab.tops, tab.sd, acc);
                 else if (qc.fast)
@@ -1603,7 +1660,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
                     for (uint32_t j = 0; j < cnt && !failed; j++)
                         failed = !mcq_iteration_ext<McqExtCtrDraws, false, Acc>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
             }
-        } else {
+        } else if constexpr (!SEATS) {
             const uint64_t stride = (qc.runs + 63u) & ~63ull;
             const uint8_t *dbase = draws + draw_off[qi];
             for (uint32_t j = 0; j < MCQ_STREAM_ITERS; j++) {
@@ -1615,8 +1672,9 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
             }
             acc.passes = 0;
         }
-        tally.add(acc);
-        if constexpr (WAYS) {
+        if constexpr (SEATS) tally.add(acc, lane);
+        else tally.add(acc);
+        if constexpr (ROW == MCQ_ROW_WAYS) {
             if (tally.full()) tally.flush(Row::row(res, qi), lane); /* its packed counters are about to overflow */
         }
         task++;
@@ -1937,8 +1995,10 @@ __global__ __launch_bounds__(TWO_OPP ? 384 : 1024) void mcq_exact_kernel(const M
 //      until the block's last completion and go to h1_sums[job.h1_off + 12 * hand] (integer atomics: deterministic).
 //      LDS: 97 KB of tables + 10 KB of keys and records, one block of 16 waves per CU.
 // Kinds 0 and 1 add into the zeroed row rows[job.row] by lane roles as mcq_exact_kernel does.
-// WAYS (kinds 0 and 1): 22-word rows; lane 13 + (k - 2) adds the weight of the ties shared by k hands (mcq_exact_ext.hpp).
-template <uint32_t KIND, bool WAYS>
+// ROW = MCQ_ROW_WAYS (kinds 0 and 1): 22-word rows; lane 13 + (k - 2) adds the weight of the ties shared by k hands
+// (mcq_exact_ext.hpp).  ROW = MCQ_ROW_SEATS (kind 0 only: the all-in case): 32-word rows of mcq_result_seats; a lane ranks
+// every hand of its completion, the level seats' weights are summed over the wave and lane l adds word l of the row.
+template <uint32_t KIND, int ROW>
 __global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
                                                              int law, mcq_result *__restrict__ rows,
                                                              unsigned long long *__restrict__ h1_sums,
@@ -1976,9 +2036,40 @@ __global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJo
         __syncthreads();
     }
     const uint32_t n_boards = job.n_boards;
+    constexpr bool WAYS = ROW == MCQ_ROW_WAYS;
     static_assert(!WAYS || KIND != 2u, "two random opponents have no split-pot form");
+    static_assert(ROW != MCQ_ROW_SEATS || KIND == 0u, "the per-seat form is the all-in case only");
 
-    if constexpr (KIND == 0u && WAYS) {
+    if constexpr (KIND == 0u && ROW == MCQ_ROW_SEATS) {
+        /* A lane sees at most C(48, 5) / 1024 + 1 = 1673 completions (one block), each of weight 0 or 1: a seat's share,
+         * in units of 2520 / k, stays below 2^23 per lane and 2^29 per wave; win and tie share one word as 16-bit halves. */
+        uint32_t tot = 0, share[MCQ_MAX_SEATS], wt[MCQ_MAX_SEATS];
+#pragma unroll
+        for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) share[s] = wt[s] = 0;
+        for (uint32_t idx = blockIdx.x * blockDim.x + tid; idx < n_boards; idx += job.grid * blockDim.x) {
+            uint32_t level, k;
+            const uint32_t w = mcq_exact_ext_lone_seats(e, idx, tab.sel8, g_tab->tf, tab.tops, tab.sd, level, k);
+            const uint32_t inc = w ? mcq_seat_increment(k) : 0u;
+            tot += w;
+#pragma unroll
+            for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) {
+                const bool on = ((level >> s) & 1u) != 0u;
+                share[s] += on ? inc & 0xFFFFu : 0u;
+                wt[s] += on ? ((inc >> MCQ_SEAT_WIN_SHIFT) & 1u) | (((inc >> MCQ_SEAT_TIE_SHIFT) & 1u) << 16) : 0u;
+            }
+        }
+        /* (64 lanes x 1673 does not fit a 16-bit half: win and tie are summed apart) */
+        unsigned long long mine = 0;
+        const uint32_t t = wave_sum(tot);
+        mine = lane == 0u ? t : 0ull;
+#pragma unroll
+        for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) {
+            const uint32_t win = wave_sum(wt[s] & 0xFFFFu), tie = wave_sum(wt[s] >> 16), sh = wave_sum(share[s]);
+            mine = lane == 2u + 3u * s ? win : lane == 3u + 3u * s ? tie : lane == 4u + 3u * s ? sh : mine;
+        }
+        if (lane < McqRowKind<MCQ_ROW_SEATS>::kWords && mine != 0ull)
+            atomicAdd(McqRowKind<MCQ_ROW_SEATS>::row(rows, job.row) + lane, mine);
+    } else if constexpr (KIND == 0u && WAYS) {
         McqExactAcc acc = {0, 0, 0};
         uint32_t by_type[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ways[MCQ_N_WAYS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (uint32_t idx = blockIdx.x * blockDim.x + tid; idx < n_boards; idx += job.grid * blockDim.x) {
@@ -2297,9 +2388,11 @@ hipError_t mcq_launch_add_u64(uint64_t *d_dst, const uint64_t *d_src, uint64_t n
 
 hipError_t mcq_launch_prep_ext(const mcq_query *d_q, const mcq_query_ext *d_ext, uint32_t n, int mode, mcq_result *d_res,
                                uint64_t *d_prefix, hipStream_t s, uint32_t row_words) {
-    if (row_words != 13u && row_words != 22u) return hipErrorInvalidValue;
+    if (row_words != 13u && row_words != 22u && row_words != 32u) return hipErrorInvalidValue;
     if (row_words == 13u)
         hipLaunchKernelGGL(mcq_prep_ext_kernel<13u>, dim3(1), dim3(1024), 0, s, d_q, d_ext, n, mode, d_res, d_prefix);
+    else if (row_words == 32u)
+        hipLaunchKernelGGL(mcq_prep_ext_kernel<32u>, dim3(1), dim3(1024), 0, s, d_q, d_ext, n, mode, d_res, d_prefix);
     else
         hipLaunchKernelGGL(mcq_prep_ext_kernel<22u>, dim3(1), dim3(1024), 0, s, d_q, d_ext, n, mode, d_res, d_prefix);
     return hipGetLastError();
@@ -2316,16 +2409,18 @@ hipError_t mcq_launch_eval_ext(int mode, const mcq_query *d_q, const mcq_query_e
                                const uint64_t *d_prefix, mcq_result *d_res, uint64_t seed, uint64_t first_qid,
                                const McqTables *d_luts, const uint8_t *d_draws, const uint64_t *d_draw_off,
                                const uint16_t *d_lists, const uint32_t *d_cnts, uint32_t lists_stride, uint32_t grid,
-                               uint32_t block, hipStream_t s, hipEvent_t t0, hipEvent_t t1, bool ways) {
+                               uint32_t block, hipStream_t s, hipEvent_t t0, hipEvent_t t1, bool ways, bool seats) {
+    if (seats && (ways || mode != MCQ_MODE_PHILOX)) return hipErrorInvalidValue;
 #define MCQ_LAUNCH_EXT(M, W)                                                                                        \
     MCQ_LAUNCH_TIMED((mcq_eval_ext_kernel<M, W>), grid, block, d_q, d_ext, n, d_prefix, d_res, seed, first_qid, d_luts, d_draws, \
                      d_draw_off, d_lists, d_cnts, lists_stride)
     if (mode == MCQ_MODE_PHILOX) {
-        if (ways) MCQ_LAUNCH_EXT(MCQ_MODE_PHILOX, true);
-        else MCQ_LAUNCH_EXT(MCQ_MODE_PHILOX, false);
+        if (seats) MCQ_LAUNCH_EXT(MCQ_MODE_PHILOX, MCQ_ROW_SEATS);
+        else if (ways) MCQ_LAUNCH_EXT(MCQ_MODE_PHILOX, MCQ_ROW_WAYS);
+        else MCQ_LAUNCH_EXT(MCQ_MODE_PHILOX, MCQ_ROW_PLAIN);
     } else {
-        if (ways) MCQ_LAUNCH_EXT(MCQ_MODE_REPLAY_MT19937, true);
-        else MCQ_LAUNCH_EXT(MCQ_MODE_REPLAY_MT19937, false);
+        if (ways) MCQ_LAUNCH_EXT(MCQ_MODE_REPLAY_MT19937, MCQ_ROW_WAYS);
+        else MCQ_LAUNCH_EXT(MCQ_MODE_REPLAY_MT19937, MCQ_ROW_PLAIN);
     }
 #undef MCQ_LAUNCH_EXT
     return hipGetLastError();
@@ -2409,19 +2504,21 @@ uint32_t mcq_exact_ext_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint
 
 hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, uint32_t kind,
                                 const uint32_t *d_ext, int law, mcq_result *d_rows, unsigned long long *d_h1,
-                                const McqTables *d_luts, hipStream_t s, bool ways) {
+                                const McqTables *d_luts, hipStream_t s, bool ways, bool seats) {
     if (n_jobs == 0) return hipSuccess;
-    if (n_jobs > 65535u || max_grid == 0 || kind > 2u || (ways && kind == 2u)) return hipErrorInvalidValue;
+    if (n_jobs > 65535u || max_grid == 0 || kind > 2u || (ways && kind == 2u) || (seats && (ways || kind != 0u)))
+        return hipErrorInvalidValue;
 #define MCQ_LAUNCH_XX(K, W) \
     hipLaunchKernelGGL((mcq_exact_ext_kernel<K, W>), dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, d_rows, d_h1, d_luts)
     if (kind == 0u) {
-        if (ways) MCQ_LAUNCH_XX(0u, true);
-        else MCQ_LAUNCH_XX(0u, false);
+        if (seats) MCQ_LAUNCH_XX(0u, MCQ_ROW_SEATS);
+        else if (ways) MCQ_LAUNCH_XX(0u, MCQ_ROW_WAYS);
+        else MCQ_LAUNCH_XX(0u, MCQ_ROW_PLAIN);
     } else if (kind == 1u) {
-        if (ways) MCQ_LAUNCH_XX(1u, true);
-        else MCQ_LAUNCH_XX(1u, false);
+        if (ways) MCQ_LAUNCH_XX(1u, MCQ_ROW_WAYS);
+        else MCQ_LAUNCH_XX(1u, MCQ_ROW_PLAIN);
     } else {
-        MCQ_LAUNCH_XX(2u, false);
+        MCQ_LAUNCH_XX(2u, MCQ_ROW_PLAIN);
     }
 #undef MCQ_LAUNCH_XX
     return hipGetLastError();

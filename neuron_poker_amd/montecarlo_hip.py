@@ -34,7 +34,8 @@ import numpy as np
 from . import _lib
 from .cards import TYPES, card_id
 
-__all__ = ["get_equity", "get_pot_equity", "get_equity_batch", "get_equity_exact", "MonteCarlo", "seed", "configure"]
+__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_equity_batch", "get_equity_exact", "MonteCarlo", "seed",
+           "configure"]
 
 _state = {"couple_numpy": False,
           "mode": _lib.MODE_REPLAY_MT19937 if os.environ.get("MCQ_MODE", "philox").lower() == "replay"
@@ -329,6 +330,43 @@ def get_pot_equity(player_cards, table_cards, players, runs, *, known_hands=(), 
     s, first = _take_ids(1)
     rows = _lib.default_engine().eval_batch_ways(q, s, first_query_id=first, mode=_state["mode"])
     return float(_lib.pot_share(rows)[0])
+
+
+def get_seat_equities(hands, table_cards, players=None, runs=10000, *, ghost_cards=None, opponent_range=None, exact=False,
+                      dealing="reference"):
+    """What EVERY hand is worth: the pot shares of all `players` seats from one run (mcq_eval_batch_ext_seats), a tie
+    among k hands counting 1/k for each of them -- a list of `players` floats that sum to 1.
+    hands[0] is the hero, the rest are the known hands in the order of original_player_card_list (each two cards, or for
+    the Monte-Carlo form a set of class strings, as run_montecarlo takes them); the seats after them are the random
+    opponents, drawn from opponent_range (run_montecarlo's conventions; None = every class), in dealing order.  `players`
+    counts them all and defaults to len(hands).  One call takes one query id from the same seed() state as get_equity;
+    production mode and the reference's dealing law, whatever configure() has set for the other calls.
+    exact=True: the all-in case by enumeration (mcq_exact_batch_seats) under `dealing` ('reference' or 'uniform'): every
+    hand two cards and no random opponent -- players != len(hands) raises ValueError; `runs` is ignored."""
+    hands = [h if isinstance(h, (set, frozenset)) else list(h) for h in hands]
+    if not 1 <= len(hands) <= 1 + _lib.MAX_KNOWN:
+        raise ValueError("between one and ten hands")
+    players = len(hands) if players is None else int(players)
+    if exact and players != len(hands):
+        raise ValueError("exact=True enumerates known hands only: players must equal len(hands)")
+    if not exact and dealing != "reference":
+        raise ValueError("the Monte-Carlo form deals the reference's law only (exact=True has dealing='uniform')")
+    hero = hands[0]
+    hero_is_range = isinstance(hero, (set, frozenset))
+    if exact and any(isinstance(h, (set, frozenset)) or len(h) != 2 for h in hands):
+        raise ValueError("exact=True needs every hand as two cards")
+    opp_range = 1 if opponent_range is None else opponent_range
+    q = _query(["2C", "2D"] if hero_is_range else hero, list(table_cards), players, 1 if exact else runs)
+    if hero_is_range:
+        q["hole"] = 0
+    ext = _ext_record(hero, hero_is_range, hands[1:], ghost_cards or '', opp_range, _opponent_range_bits(opp_range))
+    eng = _lib.default_engine()
+    if exact:
+        rows = eng.exact_seats(q, ext, dealing)
+    else:
+        s, first = _take_ids(1)
+        rows = eng.eval_batch_ext_seats(q, ext, s, first_query_id=first)
+    return [float(x) for x in _lib.seat_shares(rows)[0, :players]]
 
 
 _MULTI = {}   # tuple of device ordinals -> MultiEngine (made at first use, kept; its callers take turns on its lock)
