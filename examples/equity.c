@@ -112,6 +112,31 @@ int main(int argc, char **argv) {
     for (k = 2; k <= 10; k++) share += (double)w.tie_ways[k - 2] / (double)k;
     printf("AhKh six-handed: equity %.4f (ties credited to hero), pot share %.4f\n",
            (double)(w.r.win + w.r.tie) / (double)w.r.runs, share / (double)w.r.runs);
+    /* what EVERY hand is worth, exactly: AhKh and a known QsQc against one caller holding any two cards, on a flop */
+    {
+        mcq_query_ext x;
+        mcq_result_seats seats;
+        int s;
+        memset(&x, 0, sizeof x);
+        x.ghost[0] = x.ghost[1] = 0xFF;
+        memset(x.opp_range, 0xFF, sizeof x.opp_range); /* every class */
+        x.n_known = 1;
+        x.known[0].cards[0] = (uint8_t)card("QS");
+        x.known[0].cards[1] = (uint8_t)card("QC");
+        q.board[0] = (uint8_t)card("2C");
+        q.board[1] = (uint8_t)card("7D");
+        q.board[2] = (uint8_t)card("9H");
+        q.n_board = 3;
+        q.n_players = 3; /* hero, the known hand, one random opponent: seat 2 */
+        rc = mcq_exact_batch_ext_seats(ctx, &q, &x, 1, MCQ_LAW_REFERENCE, &seats);
+        if (rc) {
+            fprintf(stderr, "mcq_exact_batch_ext_seats: %d %s\n", rc, mcq_last_error());
+            return 1;
+        }
+        printf("AhKh, QsQc and a random hand on 2c7d9h, exact pot shares:");
+        for (s = 0; s < 3; s++) printf(" %.6f", (double)seats.seat[s].share / ((double)MCQ_SHARE_UNIT * (double)seats.runs));
+        printf("\n");
+    }
     mcq_destroy(ctx);
     return 0;
 }

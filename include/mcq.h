@@ -311,9 +311,25 @@ MCQ_API int mcq_exact_batch_ext_ways(mcq_ctx *ctx, const mcq_query *q, const mcq
  * because the deck and the completion weights do not depend on the order of the hands, seat s equals the hero columns of
  * the record with hand s rotated to the front.
  * Refused with MCQ_EINVAL, nothing launched: whatever mcq_exact_batch_ext refuses, and any record with a random opponent
- * (one or two random opponents need a per-seat form of that enumeration's candidate-hand passes: not built). */
+ * (one random opponent is enumerated per seat by mcq_exact_batch_ext_seats below; two are by neither entry). */
 MCQ_API int mcq_exact_batch_seats(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
                                   mcq_result_seats *weights);
+
+/* The same rows for records with AT MOST ONE random opponent (n_players - 1 - n_known is 0 or 1), drawn from opp_range,
+ * restricted or not: whatever mcq_exact_batch_ext_ways accepts.  Seat order as mcq_eval_batch_ext_seats: seat 0 the hero,
+ * seats 1..n_known the known hands, seat 1 + n_known the random opponent; seats at or above n_players are zero.
+ * weights[i] as mcq_exact_batch_seats writes it: runs = the total weight (one random opponent at most means one common
+ * total), passes = 0, seat[s].win and seat[s].tie in weight units, seat[s].share in weight x MCQ_SHARE_UNIT units, and
+ * sum_s seat[s].share == MCQ_SHARE_UNIT * runs exactly.  Seat 0's win and tie are mcq_exact_batch_ext_ways's weights.  The
+ * cards the opponent is dealt from do not depend on the order of the known hands, so known seat s still equals the hero
+ * columns of the record with hand s rotated to the front.  A record without a random opponent gives
+ * mcq_exact_batch_seats's row bit for bit; a batch may mix the two shapes.
+ * Refused with MCQ_EINVAL, nothing launched, weights untouched: whatever mcq_exact_batch_ext refuses (a hero range, a
+ * ranged known hand, a range that cannot be dealt, a bad law among them), and TWO random opponents: with a range they
+ * have no common total, and without one their weights are kept per first hand, so each first hand would need the sums
+ * of every seat. */
+MCQ_API int mcq_exact_batch_ext_seats(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                                      mcq_result_seats *weights);
 
 /* Select the dealing law used by MCQ_MODE_PHILOX on this context (MCQ_LAW_*).  Extended queries
  * (mcq_eval_batch_ext) are dealt by the reference's law only: under MCQ_LAW_UNIFORM that call gives MCQ_EINVAL. */

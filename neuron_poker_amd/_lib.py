@@ -125,6 +125,8 @@ def load_library():
         L.mcq_eval_batch_ext_seats.restype = C.c_int
         L.mcq_exact_batch_seats.argtypes = [vp, vp, vp, sz, C.c_int, vp]
         L.mcq_exact_batch_seats.restype = C.c_int
+        L.mcq_exact_batch_ext_seats.argtypes = [vp, vp, vp, sz, C.c_int, vp]
+        L.mcq_exact_batch_ext_seats.restype = C.c_int
         L.mcq_eval_batch_device_small.argtypes = [vp, vp, sz, u64, u64, vp, vp]
         L.mcq_eval_batch_device_small.restype = C.c_int
         L.mcq_showdown.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp]
@@ -476,6 +478,24 @@ class Engine:
             raise ValueError("one mcq_query_ext per query")
         out = np.zeros(len(q), RESULT_SEATS_DTYPE)
         rc = self._lib.mcq_exact_batch_seats(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, out.ctypes.data)
+        if rc:
+            _raise(rc)
+        return out
+
+    def exact_ext_seats(self, queries, ext, law="reference"):
+        """exact_seats for records with at most ONE random opponent, ranged or not (mcq_exact_batch_ext_seats): seat
+        1 + n_known is that opponent.  -> RESULT_SEATS_DTYPE rows of integer weights as exact_seats returns them (and the
+        same rows bit for bit for a record without a random opponent); seat_shares(rows) gives the exact pot shares.  Two
+        random opponents raise ValueError."""
+        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
+        if code is None:
+            raise ValueError("law must be 'reference' or 'uniform'")
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        out = np.zeros(len(q), RESULT_SEATS_DTYPE)
+        rc = self._lib.mcq_exact_batch_ext_seats(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, out.ctypes.data)
         if rc:
             _raise(rc)
         return out

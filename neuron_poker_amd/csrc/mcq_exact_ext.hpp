@@ -205,6 +205,23 @@ MCQ_HD uint32_t mcq_exact_ext_lone_seats(const McqExactExtQuery &e, uint32_t idx
     k = mcq_popc(level);
     return !e.b.ref_law || bd.u > 0u ? 1u : 0u;
 }
+// ... and for a completion whose board a whole wave shares (one random opponent: mcq_exact_ext_pass_seats below): that
+// greatest key itself, wave-uniform as `level` is.  (The loop is mcq_exact_ext_lone_seats's, kept apart so that the
+// all-in kernel's code stays what it was.)
+MCQ_HD uint32_t mcq_exact_ext_level_seats(const McqExactExtQuery &e, const McqExactBoard &bd, const uint32_t *tf,
+                                          const uint32_t *tops, const uint32_t *sd, uint32_t &level) {
+    uint32_t best = bd.hero_key;
+    level = 1u;
+    for (uint32_t h = 0; h < e.n_known; h++) {
+        McqHole kh;
+        kh.set(mcq_card(e.known[h] & 0xFFu), mcq_card(e.known[h] >> 8));
+        const uint32_t key = mcq_eval_key(bd.b, bd.fs, kh, tf, tops, sd);
+        level = key > best ? 0u : level;
+        level |= key >= best ? 2u << h : 0u;
+        best = key > best ? key : best;
+    }
+    return best;
+}
 
 // the range bits of every R-pair (index pb (pb - 1) / 2 + pa): they do not depend on the completion; entries rp, rp + step, ...
 MCQ_HD void mcq_exact_ext_cb_table(const McqExactExtQuery &e, const uint8_t *r_id, uint32_t rp0, uint32_t step, uint8_t *cb_tab) {
@@ -246,6 +263,50 @@ MCQ_HD void mcq_exact_ext_pass_a(const McqExactExtQuery &e, const McqExactBoard 
             if constexpr (Acc::kWays) acc.tie_c += level && key == bd.hero_key ? w : 0u;
         }
     }
+}
+
+// Per SEAT with ONE random opponent (mcq_exact_ext_kernel<1, MCQ_ROW_SEATS>).  Per completion the best key among hero and
+// the known hands, the mask `level` of the seats holding it and their number n are wave-uniform
+// (mcq_exact_ext_level_seats), and a candidate hand is above, level with or below that key: a lane keeps THREE sums, the
+// weight above (gt), level (eq) and in all (tot); the weight below is tot - gt - eq.  Candidates, weights and the
+// reference law's completion condition are those of mcq_exact_ext_pass_a's tallying form.
+struct McqExactAccSeats {
+    uint32_t gt, eq, tot;
+};
+MCQ_HD void mcq_exact_ext_pass_seats(const McqExactExtQuery &e, const McqExactBoard &bd, uint32_t best, uint32_t lane,
+                                     uint32_t n_lanes, const uint16_t *pair_xy, const McqCard *rem_card,
+                                     const uint32_t *rem_pos, const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops,
+                                     const uint32_t *sd, McqExactAccSeats &acc) {
+    for (uint32_t i = lane; i < e.n_pairs; i += n_lanes) {
+        const uint32_t xy = pair_xy[i], x = xy & 0xFFu, y = xy >> 8;
+        McqHole h;
+        h.set(rem_card[x], rem_card[y]);
+        const uint32_t key = mcq_eval_key(bd.b, bd.fs, h, tf, tops, sd);
+        const uint32_t pa = rem_pos[x], pb = rem_pos[y];
+        const uint32_t r = mcq_exact_ext_pack(pa, pb, bd.top, e.b.k != 0u, cb_tab[pb * (pb - 1u) / 2u + pa]);
+        const bool ok = !e.b.ref_law || mcq_exact_ext_above(r) < bd.u;
+        const uint32_t w = ok ? mcq_exact_ext_w1(e.b.ref_law, mcq_exact_ext_cb(r), pa, pb) : 0u;
+        acc.gt += key > best ? w : 0u;
+        acc.eq += key == best ? w : 0u;
+        acc.tot += w;
+    }
+}
+// What one completion adds to word `word` of the mcq_result_seats row, from its three sums over all candidates: word 0 is
+// runs, word 2 + 3 s + f is win / tie / share (f = 0, 1, 2) of seat s; the random opponent sits at seat 1 + n_known.
+//   random opponent: wins gt, ties eq, share 2520 gt + 2520 / (n + 1) eq
+//   a level seat:    wins lt if it is alone (n == 1), else ties lt; ties eq; share 2520 / n lt + 2520 / (n + 1) eq
+// One random opponent leaves at most eight known hands: n + 1 <= 10, the shares come from mcq_seat_increment's table.
+// tot <= 2 x 990 per completion: the products fit 32 bits; the caller's running sums are 64-bit.
+MCQ_HD uint32_t mcq_exact_ext_seats_word(uint32_t word, uint32_t level, uint32_t n_known, uint32_t gt, uint32_t eq,
+                                         uint32_t tot) {
+    if (word < 2u) return word == 0u ? tot : 0u;
+    const uint32_t s = (word - 2u) / 3u, f = (word - 2u) - 3u * s;
+    const uint32_t n = mcq_popc(level), lt = tot - gt - eq;
+    const uint32_t with_opp = mcq_seat_increment(n + 1u) & 0xFFFFu;
+    if (s == 1u + n_known) return f == 0u ? gt : f == 1u ? eq : MCQ_SHARE_UNIT * gt + with_opp * eq;
+    if (((level >> s) & 1u) == 0u) return 0u;
+    const uint32_t alone = mcq_seat_increment(n) & 0xFFFFu;
+    return f == 0u ? (n == 1u ? lt : 0u) : f == 1u ? eq + (n > 1u ? lt : 0u) : alone * lt + with_opp * eq;
 }
 
 // Pass B for ONE first hand h1 = R-positions qa < qb: its M-index in this completion, or n_pairs when a new table card

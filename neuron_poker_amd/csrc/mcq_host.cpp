@@ -1263,10 +1263,11 @@ int mcq_exact_batch(mcq_ctx *c, const mcq_query *q, size_t n, int law, mcq_resul
 
 }  // extern "C"
 
-/* mcq_exact_batch_ext, mcq_exact_batch_ext_ways and mcq_exact_batch_seats: rw = 64-bit words of a weight row; prob ->
- * mcq_exact_prob or mcq_exact_prob_ways (none for the per-seat rows), weights -> rows of rw words */
+/* mcq_exact_batch_ext, mcq_exact_batch_ext_ways, mcq_exact_batch_seats and mcq_exact_batch_ext_seats: rw = 64-bit words of
+ * a weight row; prob -> mcq_exact_prob or mcq_exact_prob_ways (none for the per-seat rows), weights -> rows of rw words;
+ * seat_opp = the random opponents a per-seat record may have (0: the all-in entry, 1: the extended one) */
 static int exact_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, void *prob,
-                                void *weights, uint32_t rw, const char *who) {
+                                void *weights, uint32_t rw, const char *who, uint32_t seat_opp = 0u) {
     const bool ways = rw == kWaysWords, seats = rw == kSeatsWords;
     const size_t row_bytes = (size_t)rw * 8u;
     if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
@@ -1295,8 +1296,11 @@ static int exact_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_
             snprintf(buf, sizeof buf, "query %zu: the opponents' range cannot be dealt from the remaining cards", i);
             return mcq_fail(MCQ_EINVAL, who, buf);
         }
-        if (seats && xq[i].b.n_opp != 0u) {
-            snprintf(buf, sizeof buf, "query %zu: the per-seat enumeration takes known hands only (n_players == 1 + n_known)", i);
+        if (seats && xq[i].b.n_opp > seat_opp) {
+            if (seat_opp == 0u)
+                snprintf(buf, sizeof buf, "query %zu: the per-seat enumeration takes known hands only (n_players == 1 + n_known)", i);
+            else
+                snprintf(buf, sizeof buf, "query %zu: two random opponents have no per-seat enumeration", i);
             return mcq_fail(MCQ_EINVAL, who, buf);
         }
         if (xq[i].b.n_opp == 2u) {
@@ -1388,6 +1392,13 @@ int mcq_exact_batch_seats(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *e
     ABI_GUARD_BEGIN
     return exact_batch_ext_impl(c, q, ext, n, law, nullptr, weights, kSeatsWords, "mcq_exact_batch_seats");
     ABI_GUARD_END("mcq_exact_batch_seats")
+}
+
+int mcq_exact_batch_ext_seats(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                              mcq_result_seats *weights) {
+    ABI_GUARD_BEGIN
+    return exact_batch_ext_impl(c, q, ext, n, law, nullptr, weights, kSeatsWords, "mcq_exact_batch_ext_seats", 1u);
+    ABI_GUARD_END("mcq_exact_batch_ext_seats")
 }
 
 }  // extern "C"

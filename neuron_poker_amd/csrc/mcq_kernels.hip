@@ -1996,8 +1996,11 @@ __global__ __launch_bounds__(TWO_OPP ? 384 : 1024) void mcq_exact_kernel(const M
 //      LDS: 97 KB of tables + 10 KB of keys and records, one block of 16 waves per CU.
 // Kinds 0 and 1 add into the zeroed row rows[job.row] by lane roles as mcq_exact_kernel does.
 // ROW = MCQ_ROW_WAYS (kinds 0 and 1): 22-word rows; lane 13 + (k - 2) adds the weight of the ties shared by k hands
-// (mcq_exact_ext.hpp).  ROW = MCQ_ROW_SEATS (kind 0 only: the all-in case): 32-word rows of mcq_result_seats; a lane ranks
-// every hand of its completion, the level seats' weights are summed over the wave and lane l adds word l of the row.
+// (mcq_exact_ext.hpp).  ROW = MCQ_ROW_SEATS (kinds 0 and 1): 32-word rows of mcq_result_seats.  Kind 0 (the all-in case): a
+// lane ranks every hand of its completion, the level seats' weights are summed over the wave and lane l adds word l of
+// the row.  Kind 1, mcq_exact_ext_kernel<1, MCQ_ROW_SEATS>: the best key among hero and the known hands is wave-uniform,
+// so a lane keeps the candidates' weight above it, level with it and in all; after three wave sums lane l adds what the
+// completion gives word l (mcq_exact_ext_seats_word).  Two random opponents have no per-seat form.
 template <uint32_t KIND, int ROW>
 __global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
                                                              int law, mcq_result *__restrict__ rows,
@@ -2038,7 +2041,7 @@ __global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJo
     const uint32_t n_boards = job.n_boards;
     constexpr bool WAYS = ROW == MCQ_ROW_WAYS;
     static_assert(!WAYS || KIND != 2u, "two random opponents have no split-pot form");
-    static_assert(ROW != MCQ_ROW_SEATS || KIND == 0u, "the per-seat form is the all-in case only");
+    static_assert(ROW != MCQ_ROW_SEATS || KIND <= 1u, "two random opponents have no per-seat form");
 
     if constexpr (KIND == 0u && ROW == MCQ_ROW_SEATS) {
         /* A lane sees at most C(48, 5) / 1024 + 1 = 1673 completions (one block), each of weight 0 or 1: a seat's share,
@@ -2069,6 +2072,34 @@ __global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJo
         }
         if (lane < McqRowKind<MCQ_ROW_SEATS>::kWords && mine != 0ull)
             atomicAdd(McqRowKind<MCQ_ROW_SEATS>::row(rows, job.row) + lane, mine);
+    } else if constexpr (KIND == 1u && ROW == MCQ_ROW_SEATS) {
+        McqCard *rem_card = rem_card_all[wib];
+        uint32_t *rem_pos = rem_pos_all[wib];
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wib), n_waves = job.grid * kWaves;
+        unsigned long long sum = 0;
+        for (uint32_t board = wave; board < n_boards; board += n_waves) {
+            uint32_t pos[5];
+            mcq_exact_unrank(board, e.b.L, e.b.k, pos);
+            McqExactBoard bd;
+            mcq_exact_board(e.b, pos, tab.sel8, g_tab->tf, tab.tops, tab.sd, bd);
+            uint32_t level;
+            const uint32_t best = mcq_exact_ext_level_seats(e, bd, g_tab->tf, tab.tops, tab.sd, level);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* the previous completion's reads are done (same wave) */
+            if (lane < e.m) {
+                const uint32_t rp = mcq_exact_rem_pos(pos, lane);
+                rem_pos[lane] = rp;
+                rem_card[lane] = mcq_card(r_id[rp]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            McqExactAccSeats acc = {0, 0, 0};
+            mcq_exact_ext_pass_seats(e, bd, best, lane, 64u, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, acc);
+            const uint32_t gt = wave_sum(acc.gt), eq = wave_sum(acc.eq), tot = wave_sum(acc.tot);
+            /* lane l keeps word l of the row (lanes 32..63: seats nobody holds, nothing) */
+            sum += mcq_exact_ext_seats_word(lane, level, e.n_known, gt, eq, tot);
+        }
+        if (lane < McqRowKind<MCQ_ROW_SEATS>::kWords && sum != 0ull)
+            atomicAdd(McqRowKind<MCQ_ROW_SEATS>::row(rows, job.row) + lane, sum);
     } else if constexpr (KIND == 0u && WAYS) {
         McqExactAcc acc = {0, 0, 0};
         uint32_t by_type[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ways[MCQ_N_WAYS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -2506,7 +2537,7 @@ hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, u
                                 const uint32_t *d_ext, int law, mcq_result *d_rows, unsigned long long *d_h1,
                                 const McqTables *d_luts, hipStream_t s, bool ways, bool seats) {
     if (n_jobs == 0) return hipSuccess;
-    if (n_jobs > 65535u || max_grid == 0 || kind > 2u || (ways && kind == 2u) || (seats && (ways || kind != 0u)))
+    if (n_jobs > 65535u || max_grid == 0 || kind > 2u || (ways && kind == 2u) || (seats && (ways || kind == 2u)))
         return hipErrorInvalidValue;
 #define MCQ_LAUNCH_XX(K, W) \
     hipLaunchKernelGGL((mcq_exact_ext_kernel<K, W>), dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, d_rows, d_h1, d_luts)
@@ -2515,7 +2546,8 @@ hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, u
         else if (ways) MCQ_LAUNCH_XX(0u, MCQ_ROW_WAYS);
         else MCQ_LAUNCH_XX(0u, MCQ_ROW_PLAIN);
     } else if (kind == 1u) {
-        if (ways) MCQ_LAUNCH_XX(1u, MCQ_ROW_WAYS);
+        if (seats) MCQ_LAUNCH_XX(1u, MCQ_ROW_SEATS);
+        else if (ways) MCQ_LAUNCH_XX(1u, MCQ_ROW_WAYS);
         else MCQ_LAUNCH_XX(1u, MCQ_ROW_PLAIN);
     } else {
         MCQ_LAUNCH_XX(2u, MCQ_ROW_PLAIN);

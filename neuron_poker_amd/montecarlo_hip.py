@@ -34,7 +34,7 @@ import numpy as np
 from . import _lib
 from .cards import TYPES, card_id
 
-__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_equity_batch", "get_equity_exact", "MonteCarlo", "seed",
+__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "MonteCarlo", "seed",
            "configure"]
 
 _state = {"couple_numpy": False,
@@ -366,6 +366,30 @@ def get_seat_equities(hands, table_cards, players=None, runs=10000, *, ghost_car
     else:
         s, first = _take_ids(1)
         rows = eng.eval_batch_ext_seats(q, ext, s, first_query_id=first)
+    return [float(x) for x in _lib.seat_shares(rows)[0, :players]]
+
+
+def get_seat_equities_exact(hands, table_cards, players=None, ghost_cards=None, opponent_range=None, dealing="reference"):
+    """get_seat_equities by enumeration with at most ONE random opponent (mcq_exact_batch_ext_seats): the exact pot shares
+    of all `players` seats under `dealing` ('reference' or 'uniform') -- a list of `players` floats that sum to 1.
+    hands[0] is the hero, the rest are the known hands, each two cards; `players` defaults to len(hands) (the all-in case)
+    and may be len(hands) + 1: the last seat is then an opponent drawn from opponent_range (get_seat_equities'
+    conventions; None = every class).  More than one random opponent or a hand given as a range raises ValueError: two
+    random opponents have no per-seat enumeration, ranged hands are not enumerated at all.  No seed() state is used."""
+    hands = [h if isinstance(h, (set, frozenset)) else list(h) for h in hands]
+    if not 1 <= len(hands) <= 1 + _lib.MAX_KNOWN:
+        raise ValueError("between one and ten hands")
+    players = len(hands) if players is None else int(players)
+    if not len(hands) <= players <= len(hands) + 1:
+        raise ValueError("the per-seat enumeration takes at most one random opponent: players is len(hands) or len(hands) + 1")
+    if any(isinstance(h, (set, frozenset)) or len(h) != 2 for h in hands):
+        raise ValueError("every hand is two cards here (ranged hands are not enumerated)")
+    if dealing not in ("reference", "uniform"):
+        raise ValueError("dealing must be 'reference' or 'uniform'")
+    opp_range = 1 if opponent_range is None else opponent_range
+    q = _query(hands[0], list(table_cards), players, 1)
+    ext = _ext_record(hands[0], False, hands[1:], ghost_cards or '', opp_range, _opponent_range_bits(opp_range))
+    rows = _lib.default_engine().exact_ext_seats(q, ext, dealing)
     return [float(x) for x in _lib.seat_shares(rows)[0, :players]]
 
 
