@@ -116,17 +116,6 @@ MCQ_HD uint32_t mcq_opaque_uniform(uint32_t x) {
 #endif
     return x;
 }
-// Keeps a value alive without an instruction.  Used on the one field of a 16-byte card that an opponent's hole does not
-// need: with all four fields live the card is ONE ds_read_b128 (64 banks, 16 lanes per LDS cycle); without it the
-// compiler reads ds_read_b32 + ds_read_b64, and the lone first dwords of the 16-byte entries share 8 of the 32 banks
-// that instruction has.
-MCQ_HD void mcq_keep(uint32_t x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : : "v"(x));
-#else
-    (void)x;
-#endif
-}
 MCQ_HD uint32_t mcq_bfe(uint32_t x, uint32_t off, uint32_t width) { /* (x >> off) & ((1 << width) - 1), off + width <= 32 */
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_ubfe(x, off, width);
@@ -926,6 +915,49 @@ MCQ_HD McqCard mcq_base_entry(const McqQueryCtx &qc, uint32_t l, const uint32_t 
     return mcq_card_sum(c < 52u ? c : 0u); /* lanes beyond the deck length write an entry nobody reads */
 }
 
+// How an iteration reads the base deck.  `at` = base position + 128, as mcq_draw_opp / mcq_draw_table return it (the bias
+// is folded into the pointer).  card(): a table card, all four fields; hole_card(): an opponent's card, whose suit counter
+// nobody reads.
+struct McqDeckAoS { /* 64 entries of 16 bytes (host builds of the lane code) */
+    const McqCard *base128;
+    MCQ_HDM McqCard card(uint32_t at) const { return base128[at]; }
+    MCQ_HDM McqCard hole_card(uint32_t at) const { return base128[at]; }
+};
+// The kernels' form: two arrays of 8-byte entries, X[e] = (rb, cnt) and Y[e] = (los, his) YOFF entries behind it.  A card
+// is two 8-byte reads from ONE address register (Y at an immediate offset).  8-byte reads bank by (address / 4) mod 64 in
+// groups of 32 lanes, so 8-byte entries spread over 32 slots and a deck of at most 50 cards puts at most two entries
+// (e, e + 32) on a slot: a lane group is never worse than 2-way.  (16-byte entries read whole have 16 slots for 16 lanes
+// and about three distinct entries on the fullest.)
+// YOFF is the caller's layout.  Where 8 * YOFF is below 2048 or a multiple of 512, the compiler pairs the two reads of a
+// table card into ONE two-address instruction (ds_read2_b64 / ds_read2st64_b64), which banks by (address / 4) mod 32 in
+// groups of 16 lanes at twice the cycles: the kernels keep YOFF out of that set.
+struct __attribute__((aligned(8))) McqPair {
+    uint32_t a, b;
+};
+template <uint32_t YOFF>
+struct McqDeckSplit {
+    const McqPair *x128; /* X - 128 entries */
+    MCQ_HDM McqCard card(uint32_t at) const {
+        const McqPair x = x128[at], y = x128[at + YOFF];
+        const McqCard c = {x.a, x.b, y.a, y.b};
+        return c;
+    }
+    /* rb alone, a 4-byte read at the same address: with cnt loaded and dropped (an 8-byte read for both cards of a pair)
+     * the 6-max iteration spills registers */
+    MCQ_HDM McqCard hole_card(uint32_t at) const {
+        const uint32_t rb = x128[at].a;
+        const McqPair y = x128[at + YOFF];
+        const McqCard c = {rb, 0u, y.a, y.b};
+        return c;
+    }
+    /* entry e of both arrays (device: lane e writes it) */
+    static MCQ_HDM void put(McqPair *x, uint32_t e, const McqCard &c) {
+        const McqPair px = {c.rb, c.cnt}, py = {c.los, c.his};
+        x[e] = px;
+        x[e + YOFF] = py;
+    }
+};
+
 struct McqLaneAcc {
     static constexpr bool kWays = false, kSeats = false;
     uint64_t types; /* MCQ_N_CODES fields of 6 bits: hero's winning hand codes (<= 16 per lane per task) */
@@ -1051,8 +1083,8 @@ MCQ_HD uint32_t mcq_draw_table(uint32_t rp, const uint32_t (&H)[5], uint32_t &hb
 }
 
 // the missing table cards (montecarlo_python.py:185-189) after opponents whose holes fill NREGS registers
-template <int NREGS, class Draws, int NDEAL = -1>
-MCQ_HD void mcq_deal_table(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const uint32_t (&H)[5], uint32_t L,
+template <int NREGS, class Draws, int NDEAL = -1, class Deck = McqDeckAoS>
+MCQ_HD void mcq_deal_table(const McqQueryCtx &qc, Draws &dr, const Deck &deck, const uint32_t (&H)[5], uint32_t L,
                            McqSumBoard &b) {
     uint32_t hb = MCQ_HOLE_SENTINEL;
     /* scalar compares, no lane masks kept in SGPR pairs; NDEAL >= 0: known at compile time, no branches at all */
@@ -1064,7 +1096,7 @@ MCQ_HD void mcq_deal_table(const McqQueryCtx &qc, Draws &dr, const McqCard *base
     if (K < n_deal) {                                                                                           \
         const uint32_t at = mcq_draw_table<K, NREGS>(dr.template table<K>(L - Draws::kTableShort), H, hb); /* l.188 */ \
         if (K > 0) b.add(pend);                                                                                 \
-        pend = base128[at];                                                                                     \
+        pend = deck.card(at);                                                                                   \
         L -= 1;                                                                                                 \
     }
     MCQ_TABLE(0) MCQ_TABLE(1) MCQ_TABLE(2) MCQ_TABLE(3) MCQ_TABLE(4)
@@ -1082,9 +1114,10 @@ MCQ_HD void mcq_deal_table(const McqQueryCtx &qc, Draws &dr, const McqCard *base
 // The hands are in the sum form (McqSumBoard / McqSumHole, ids instead of keys); mcq_iteration / mcq_iterations keep the
 // mask form's table arguments for the host builds of this file and find the sum-form tables behind them
 // (mcq_sum_tabs_of), the kernels call the _sum forms with their LDS image.
-template <class Draws, int NOPP = -1, int NDEAL = -1, class Acc = McqLaneAcc>
-// base128 = (base deck table) - 128 entries: draw indices carry a bias of 128 (r | 0x80), folded into the pointer.
-MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const McqSumTabs &tabs, Acc &acc) {
+template <class Draws, int NOPP = -1, int NDEAL = -1, class Acc = McqLaneAcc, class Deck = McqDeckAoS>
+// deck = the base deck table behind its accessor (McqDeckAoS / McqDeckSplit), its pointer biased by -128 entries: draw
+// indices carry a bias of 128 (r | 0x80).
+MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck, const McqSumTabs &tabs, Acc &acc) {
     uint32_t H[5] = {MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL};
     uint32_t L = qc.L0;
     McqSumHole opp[MCQ_MAX_OPP];
@@ -1093,9 +1126,8 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const McqCard *b
     if (P < n_opp_d) {                                                                                         \
         uint32_t r1, r2;                                                                                       \
         dr.template pair<P>(L, r1, r2); /* r1 in [0,L-1], r2 in [0,L-2], r1 != r2 (l.167-176), both | 0x80 */  \
-        const McqCard c1 = base128[mcq_draw_opp<2 * P>(r1, H)];     /* deck.pop(r1) (l.178) */                 \
-        const McqCard c2 = base128[mcq_draw_opp<2 * P + 1>(r2, H)]; /* deck.pop(r2), shrunk list (l.179) */    \
-        mcq_keep(c1.cnt); /* (the first card of the pair only: with both, the 6-max iteration spills registers) */ \
+        const McqCard c1 = deck.hole_card(mcq_draw_opp<2 * P>(r1, H));     /* deck.pop(r1) (l.178) */          \
+        const McqCard c2 = deck.hole_card(mcq_draw_opp<2 * P + 1>(r2, H)); /* deck.pop(r2), shrunk list (l.179) */ \
         opp[P].set(c1, c2);                                                                                    \
         L -= 2;                                                                                                \
     }
@@ -1103,14 +1135,14 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const McqCard *b
 #undef MCQ_OPP
     McqSumBoard b = qc.board_s;
     if (NOPP >= 0) {
-        mcq_deal_table<(NOPP >= 0 ? (2 * NOPP + 3) / 4 : 0), Draws, NDEAL>(qc, dr, base128, H, L, b);
+        mcq_deal_table<(NOPP >= 0 ? (2 * NOPP + 3) / 4 : 0), Draws, NDEAL>(qc, dr, deck, H, L, b);
     } else switch (mcq_opaque_uniform((2u * qc.n_opp + 3u) / 4u)) { /* registers holding the opponents' holes: wave-uniform */
-        case 0: mcq_deal_table<0>(qc, dr, base128, H, L, b); break;
-        case 1: mcq_deal_table<1>(qc, dr, base128, H, L, b); break;
-        case 2: mcq_deal_table<2>(qc, dr, base128, H, L, b); break;
-        case 3: mcq_deal_table<3>(qc, dr, base128, H, L, b); break;
-        case 4: mcq_deal_table<4>(qc, dr, base128, H, L, b); break;
-        default: mcq_deal_table<5>(qc, dr, base128, H, L, b); break;
+        case 0: mcq_deal_table<0, Draws>(qc, dr, deck, H, L, b); break;
+        case 1: mcq_deal_table<1, Draws>(qc, dr, deck, H, L, b); break;
+        case 2: mcq_deal_table<2, Draws>(qc, dr, deck, H, L, b); break;
+        case 3: mcq_deal_table<3, Draws>(qc, dr, deck, H, L, b); break;
+        case 4: mcq_deal_table<4, Draws>(qc, dr, deck, H, L, b); break;
+        default: mcq_deal_table<5, Draws>(qc, dr, deck, H, L, b); break;
     }
     McqFlushSel fs;
     fs.from_board(b);
@@ -1140,60 +1172,62 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const McqCard *b
 template <class Draws, int NOPP = -1, int NDEAL = -1, class Acc = McqLaneAcc>
 MCQ_HD void mcq_iteration(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const uint32_t *tf,
                           const uint32_t *, const uint32_t *, Acc &acc) {
-    mcq_iteration_sum<Draws, NOPP, NDEAL, Acc>(qc, dr, base128, mcq_sum_tabs_of(tf), acc);
+    const McqDeckAoS deck = {base128};
+    mcq_iteration_sum<Draws, NOPP, NDEAL, Acc>(qc, dr, deck, mcq_sum_tabs_of(tf), acc);
 }
 
 // `cnt` iterations of one lane.  STRAIGHT: by the (wave-uniform) number of opponents, and before the flop also by the
 // number of table cards, the loop body is a specialisation of mcq_iteration without branches -- one basic block, in
 // which the compiler sends lookups early and waits late across hands and draws (6-max before the flop: 6.37 -> 6.00 ms;
 // the general form's wave-uniform branches are scheduling barriers).  Same arithmetic, same results.
-template <bool STRAIGHT, class Draws, class Acc>
-MCQ_HD void mcq_iterations_sum(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const McqSumTabs &tabs, Acc &acc,
+template <bool STRAIGHT, class Draws, class Acc, class Deck>
+MCQ_HD void mcq_iterations_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck, const McqSumTabs &tabs, Acc &acc,
                                uint32_t cnt) {
     if (STRAIGHT) {
 #define MCQ_STRAIGHT(N)                                                                                   \
     case N:                                                                                               \
         if (qc.n_deal == 5u)                                                                          \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, 5, Acc>(qc, dr, base128, tabs, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, 5, Acc>(qc, dr, deck, tabs, acc); \
         else if (qc.n_deal == 2u)                                                                         \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, 2, Acc>(qc, dr, base128, tabs, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, 2, Acc>(qc, dr, deck, tabs, acc); \
         else if (qc.n_deal == 1u)                                                                         \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, 1, Acc>(qc, dr, base128, tabs, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, 1, Acc>(qc, dr, deck, tabs, acc); \
         else                                                                                              \
-            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, -1, Acc>(qc, dr, base128, tabs, acc); \
+            for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, N, -1, Acc>(qc, dr, deck, tabs, acc); \
         return;
         switch (qc.n_opp) {
             MCQ_STRAIGHT(1) MCQ_STRAIGHT(2) MCQ_STRAIGHT(3) MCQ_STRAIGHT(4) MCQ_STRAIGHT(5) MCQ_STRAIGHT(6) MCQ_STRAIGHT(7)
             case 8: /* (only the form with the table cards counted at run time: the others spill registers) */
-                for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, 8, -1, Acc>(qc, dr, base128, tabs, acc);
+                for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, 8, -1, Acc>(qc, dr, deck, tabs, acc);
                 return;
             case 9:
-                for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, 9, -1, Acc>(qc, dr, base128, tabs, acc);
+                for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, 9, -1, Acc>(qc, dr, deck, tabs, acc);
                 return;
             default: break; /* hero alone: the general form */
         }
 #undef MCQ_STRAIGHT
     }
-    for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, -1, -1, Acc>(qc, dr, base128, tabs, acc);
+    for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, -1, -1, Acc>(qc, dr, deck, tabs, acc);
 }
 template <bool STRAIGHT, class Draws, class Acc>
 MCQ_HD void mcq_iterations(const McqQueryCtx &qc, Draws &dr, const McqCard *base128, const uint32_t *tf, const uint32_t *,
                            const uint32_t *, Acc &acc, uint32_t cnt) {
-    mcq_iterations_sum<STRAIGHT>(qc, dr, base128, mcq_sum_tabs_of(tf), acc, cnt);
+    const McqDeckAoS deck = {base128};
+    mcq_iterations_sum<STRAIGHT>(qc, dr, deck, mcq_sum_tabs_of(tf), acc, cnt);
 }
 
 // Parity mode: the (up to four) iterations a lane takes from one McqReplayDraws4 load.  As in mcq_iterations_sum the loop
 // body is picked by the (wave-uniform) number of opponents, so that the opponents' deals and hands are straight code
 // without the general form's scalar compare and branch per opponent; the table cards to come stay counted at run time.
 // Same arithmetic, same results.
-template <class Acc>
-MCQ_HD void mcq_iterations_replay4(const McqQueryCtx &qc, McqReplayDraws4 &dr, const McqCard *base128, const McqSumTabs &tabs,
+template <class Acc, class Deck>
+MCQ_HD void mcq_iterations_replay4(const McqQueryCtx &qc, McqReplayDraws4 &dr, const Deck &deck, const McqSumTabs &tabs,
                                    Acc &acc, uint32_t cnt4) {
 #define MCQ_REPLAY4(N)                                                                      \
     case N:                                                                                 \
         for (uint32_t k = 0; k < cnt4; k++) {                                               \
             dr.sh = 8u * k;                                                                 \
-            mcq_iteration_sum<McqReplayDraws4, N, -1, Acc>(qc, dr, base128, tabs, acc);     \
+            mcq_iteration_sum<McqReplayDraws4, N, -1, Acc>(qc, dr, deck, tabs, acc);        \
         }                                                                                   \
         return;
     /* (not the split-pot form: it sits at the register limit and the straight forms spill there, 24-40 bytes per lane) */
@@ -1205,7 +1239,7 @@ MCQ_HD void mcq_iterations_replay4(const McqQueryCtx &qc, McqReplayDraws4 &dr, c
 #undef MCQ_REPLAY4
     for (uint32_t k = 0; k < cnt4; k++) {
         dr.sh = 8u * k;
-        mcq_iteration_sum(qc, dr, base128, tabs, acc);
+        mcq_iteration_sum<McqReplayDraws4, -1, -1, Acc>(qc, dr, deck, tabs, acc);
     }
 }
 

@@ -24,7 +24,16 @@
 
 namespace {
 
+/* The base decks of a block's waves (McqDeckSplit): the X arrays of all waves, 64 entries each, then their Y arrays ONE
+ * entry further than a whole number of arrays, so that the distance between a card's two reads is no offset pair a
+ * two-address read could encode.  Entry 63 of the last wave's Y array would lie behind the table: it is never written (a
+ * deck holds 50 cards at most, the entries behind it are nobody's). */
+constexpr uint32_t kDeckY = 1024 + 1;
+typedef McqDeckSplit<kDeckY> McqDeckLds;
 constexpr int kMaxBlock = 1024; /* 16 waves = 4 per SIMD; one block per CU: tables 97 KB + 16 base decks 16 KB of the 160 KB LDS */
+static_assert(kDeckY == kMaxBlock + 1 && 8u * kDeckY >= 2048u && (8u * kDeckY) % 512u != 0u,
+              "the Y arrays start one entry behind the block's X arrays: beyond a two-address read's offsets");
+static_assert((kMaxBlock - 64) + kDeckY + 62 < 2 * kMaxBlock, "entries 0..62 of the last wave's Y array lie inside base_tab");
 constexpr int kExtBlock = 1024; /* extended queries: 40 KB of dealt card ids beside the tables */
 
 // A launch with or without the pair of timestamp events (mcq_set_kernel_timing): the timestamped form costs a
@@ -991,7 +1000,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
      * lane so that more waves share the work; the iterations and their random numbers stay the same (a sub-task
      * skips ahead in its lane's stream), so the tallies do not depend on it. */
     __shared__ __attribute__((aligned(16))) McqSumImage tab; /* first: the hash is read at constant offsets from LDS address 0 */
-    __shared__ McqCard base_tab[kMaxBlock]; /* per wave: the query's ordered remaining deck, 64 entries x 16 B */
+    __shared__ McqPair base_tab[2 * kMaxBlock]; /* per wave: the query's ordered remaining deck, 2 x 64 entries x 8 B (kDeckY) */
     /* SPLIT (small batches): the rows the work-group's waves END on are added up in LDS when they are one query's -- a
      * single long query is hundreds of waves, and twelve atomics per wave on ONE row serialise (a 100 000-run query: 392
      * waves, 18 us where the arithmetic takes 6) -- and the last wave sends the sum: s_key = that query (claimed by the
@@ -1011,6 +1020,9 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
     const McqSumTabs tabs = {tab.hoff, tab.hrank, g_tab->tfid};
 
     const uint32_t lane = threadIdx.x & 63u;
+    /* Parity mode's split-pot instance sits at the register limit: there a flush forms its row address where it is used
+     * (the lane number hidden from the optimiser); kept across the iteration loops it went to scratch. */
+    auto flush_lane = [&]() { return WAYS && MODE == MCQ_MODE_REPLAY_MT19937 ? mcq_opaque(lane) : lane; };
     /* small batches launch more waves than take work: the extra ones only help to bring the 115 KB table image in */
     const uint32_t waves_per_block = work_wpb ? work_wpb : blockDim.x >> 6;
     if ((threadIdx.x >> 6) >= waves_per_block) return;
@@ -1020,7 +1032,8 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
     const uint64_t total = prefix[n] << split; /* cost axis in sub-task units */
     /* this wave's slice of the cost axis; a task belongs to the slice its start position falls into */
     const uint64_t lo = total * wave / n_waves, hi = total * (wave + 1ull) / n_waves;
-    McqCard *base = base_tab + (threadIdx.x & ~63u);
+    McqPair *base = base_tab + (threadIdx.x & ~63u);
+    const McqDeckLds deck = {base - 128};
 
     uint32_t a = 0, b = n; /* last query with prefix <= lo: it has a positive cost because lo < total */
     while (b - a > 1) {
@@ -1051,13 +1064,13 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
             if (ok) {
                 mcq_query_ctx(q, qc);
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* earlier lookups are done (same wave) */
-                base[lane] = mcq_base_entry(qc, lane, tab.sel8);
+                if (lane < 63u) McqDeckLds::put(base, lane, mcq_base_entry(qc, lane, tab.sel8));
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 __builtin_amdgcn_wave_barrier();
             }
         }
         if (task >= n_tasks) {
-            tally.flush(Row::row(res, qi), lane);
+            tally.flush(Row::row(res, qi), flush_lane());
             qi++;
             fresh = true;
             continue;
@@ -1074,7 +1087,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
                 /* words per iteration: one per opponent, one per two table cards */
                 for (uint32_t k = sub * chunk * (qc.n_opp + ((qc.n_deal + 1u) >> 1)); k != 0; k--) dr.rng.next();
                 const uint32_t cnt = (uint32_t)min((uint64_t)chunk, (uint64_t)qc.runs - it0);
-                mcq_iterations_sum<true>(qc, dr, base - 128, tabs, acc, cnt); /* both dealing laws */
+                mcq_iterations_sum<true>(qc, dr, deck, tabs, acc, cnt); /* both dealing laws */
                 acc.passes = cnt * qc.n_opp; /* MCQ-CTR v5: one attempt per opponent, never re-drawn */
             }
         } else {
@@ -1089,7 +1102,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
                     McqReplayDraws4 dr;
                     dr.load(dbase + it4, stride, qc.n_opp, qc.n_deal);
                     const uint32_t cnt4 = (uint32_t)min((uint64_t)4u, (uint64_t)qc.runs - it4);
-                    mcq_iterations_replay4(qc, dr, base - 128, tabs, acc, cnt4);
+                    mcq_iterations_replay4(qc, dr, deck, tabs, acc, cnt4);
                 }
             }
             acc.passes = 0; /* `passes` comes from the stream walk: mcq_mt_parse_kernel writes it into the row (the host walk
@@ -1097,12 +1110,12 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
         }
         tally.add(acc);
         if constexpr (WAYS) {
-            if (tally.full()) tally.flush(Row::row(res, qi), lane); /* its packed counters are about to overflow */
+            if (tally.full()) tally.flush(Row::row(res, qi), flush_lane()); /* its packed counters are about to overflow */
         }
         task++;
     }
     if (!SPLIT) {
-        if (qi < n) tally.flush(Row::row(res, qi), lane);
+        if (qi < n) tally.flush(Row::row(res, qi), flush_lane());
         return;
     }
     const bool have = qi < n && tally.dirty; /* (wave-uniform) */
@@ -1200,7 +1213,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
                                                                     uint32_t ticket, uint32_t use_karg, McqDirectKarg karg) {
     constexpr uint32_t kWaves = kMaxBlock / 64, kStage = MCQ_DIRECT_STAGE_ROUNDS * kWaves;
     __shared__ __attribute__((aligned(16))) McqSumImage tab; /* first: the hash is read at constant offsets from LDS address 0 */
-    __shared__ McqCard base_tab[kMaxBlock];
+    __shared__ McqPair base_tab[2 * kMaxBlock]; /* as in mcq_eval_kernel */
     typedef McqRowKind<WAYS> Row; /* WAYS: 22-word rows, tie_ways[9] behind by_type[9] */
     constexpr uint32_t kLanes = Row::kLanes;
     __shared__ unsigned long long partial[2][kWaves][kLanes]; /* [round parity][wave][passes, win, tie, by_type[9](, tie_ways[9])] */
@@ -1208,7 +1221,8 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
     __shared__ uint32_t s_qi[kStage];
 
     const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
-    McqCard *base = base_tab + (threadIdx.x & ~63u);
+    McqPair *base = base_tab + (threadIdx.x & ~63u);
+    const McqDeckLds deck = {base - 128};
     const McqSumTabs tabs = {tab.hoff, tab.hrank, g_tab->tfid};
     typedef McqCtrDrawsT<MODE == MCQ_INTERNAL_MODE_UNIFORM> Draws;
     /* The start of a one-launch query is a chain of latencies, so they overlap: the first rounds' work is asked for,
@@ -1317,7 +1331,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
                 mcq_query_ctx(q, qc);
                 runs = qc.runs;
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* the previous query's lookups are done */
-                base[lane] = mcq_base_entry(qc, lane, tab.sel8);
+                if (lane < 63u) McqDeckLds::put(base, lane, mcq_base_entry(qc, lane, tab.sel8));
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 MCQ_STAMP(3);
@@ -1338,7 +1352,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
                         }
                         MCQ_STAMP(5);
                         const uint32_t cnt = (uint32_t)min((uint64_t)chunk, (uint64_t)qc.runs - it0);
-                        for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum(qc, dr, base - 128, tabs, acc);
+                        for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, -1, -1, typename Row::Acc>(qc, dr, deck, tabs, acc);
                         acc.passes = cnt * qc.n_opp;
                         MCQ_STAMP(6);
                     }

@@ -8,7 +8,8 @@ hardware (tools/ubench -> profiles/r01_ubench*.txt, profiles/r06_vcc_probe.txt, 
 What it does: unbundles the gfx950 code object (clang-offload-bundler), disassembles it (llvm-objdump -d), takes the
 kernel whose mangled name contains --kernel, finds its loops (backward branches) and picks the straight-line iteration
 of `nopp` opponents and `ndeal` table cards to come: the innermost loop WITHOUT any other branch inside whose signature
-fits -- nopp + ndeal whole card records (ds_read_b128) and 3 * nopp + ndeal + ceil(ndeal / 2) 64-bit multiply-adds
+fits -- 2 * nopp + ndeal reads of a card's second half (ds_read_b64 at McqDeckSplit's offset), 2 * (nopp + 1) 16-bit hash
+reads and 3 * nopp + ndeal + ceil(ndeal / 2) 64-bit multiply-adds
 (one per random word, one per bounded draw; mcq_device.hpp: McqCtrDrawsT, McqMwc64x).  Every instruction of that loop
 is put into an issue class:
 
@@ -252,22 +253,37 @@ def histogram(body, vcc_window, guarded=()):
             "fast_share": round(classes.get("fast", 0) / valu, 4) if valu else 0.0}
 
 
+def deck_y_offset():
+    """byte offset of a card's second half behind its first: 8 x kDeckY of mcq_kernels.hip"""
+    with open(os.path.join(ROOT, "neuron_poker_amd", "csrc", "mcq_kernels.hip")) as f:
+        m = re.search(r"constexpr uint32_t kDeckY = (\d+) \+ (\d+);", f.read())
+    if not m:
+        raise SystemExit("kDeckY not found in mcq_kernels.hip")
+    return 8 * (int(m.group(1)) + int(m.group(2)))
+
+
+def card_reads(body):
+    """the reads of the second half (los, his) of a card: ds_read_b64 at the offset of the Y arrays"""
+    tag = "offset:%d" % deck_y_offset()
+    return sum(1 for _, o, a in body if o == "ds_read_b64" and a.split()[-1] == tag)
+
+
 def signature(body):
-    return (sum(1 for _, o, _ in body if o == "ds_read_b128"), sum(1 for _, o, _ in body if o.startswith("v_mad_u64_u32")))
+    return (card_reads(body), sum(1 for _, o, _ in body if o == "ds_read_u16"),
+            sum(1 for _, o, _ in body if o.startswith("v_mad_u64_u32")))
 
 
 def pick_loop(ins, nopp, ndeal, rng_stub=False):
-    """The straight-line iteration of `nopp` opponents and `ndeal` table cards: ndeal whole card records (ds_read_b128)
-    for the table and one per opponent (the evaluator needs three of the four words of an opponent's card: the first
-    of a pair is read whole, the second as b32 + b64 -- mcq_keep in mcq_device.hpp), and one 64-bit multiply-add
-    per random word (nopp + ceil(ndeal / 2)) and per bounded draw (2 * nopp + ndeal)."""
+    """The straight-line iteration of `nopp` opponents and `ndeal` table cards: one read of a card's second half per
+    dealt card (2 * nopp + ndeal: McqDeckSplit in mcq_device.hpp), two 16-bit hash reads per hand (nopp + 1 hands), and
+    one 64-bit multiply-add per random word (nopp + ceil(ndeal / 2)) and per bounded draw (2 * nopp + ndeal)."""
     words = nopp + (ndeal + 1) // 2
     mads = (0 if rng_stub else words) + 2 * nopp + ndeal
-    want = (nopp + ndeal, mads)
+    want = (2 * nopp + ndeal, 2 * (nopp + 1), mads)
     found = [(j, i) for j, i in loops_of(ins) if signature(ins[j:i + 1]) == want]
     if not found:
-        raise SystemExit("no straight-line loop with %d card records and %d multiply-adds (nopp %d, ndeal %d)"
-                         % (want[0], want[1], nopp, ndeal))
+        raise SystemExit("no straight-line loop with %d card reads, %d hash reads and %d multiply-adds (nopp %d, ndeal %d)"
+                         % (want[0], want[1], want[2], nopp, ndeal))
     if len(found) > 1:
         print("note: %d loops fit the signature, the first is taken" % len(found), file=sys.stderr)
     return found[0]
@@ -327,7 +343,7 @@ def main():
                 best = None
                 for vj, vi in loops_of(vins):
                     vb = vins[vj:vi + 1]
-                    if a.ndeal <= sum(1 for _, o, _ in vb if o == "ds_read_b128") <= 2 * a.nopp + a.ndeal:
+                    if card_reads(vb) == 2 * a.nopp + a.ndeal:
                         vh = histogram(vb, a.vcc_window)
                         if best is None or abs(vh["valu"] - full_valu) < abs(best["valu"] - full_valu):
                             best = vh
