@@ -54,6 +54,38 @@ def is_fast(query16, ext304):
     return bool(lib().hs_ext_ways_is_fast(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p)))
 
 
+def _u32(name, query16, ext304, *more):
+    q, e = _bytes(query16, 16), _bytes(ext304, 304)
+    f = getattr(lib(), name)
+    f.restype = C.c_uint32
+    return int(f(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), *[C.c_uint32(m) for m in more]))
+
+
+def n_lists(query16, ext304):
+    """mcq_ext_n_lists: the candidate lists the query draws from."""
+    return _u32("hs_ext_n_lists", query16, ext304)
+
+
+def stream_iters(query16, ext304):
+    """mcq_ext_stream_iters: 2 or 16 iterations per stream (MCQ-CTR v5x)."""
+    return _u32("hs_ext_stream_iters", query16, ext304)
+
+
+def task_count(query16, ext304):
+    """mcq_ext_task_count under the query's stream rule: its wave tasks."""
+    return _u32("hs_ext_task_count", query16, ext304)
+
+
+def task_weight(query16, ext304):
+    """mcq_ext_task_weight under the query's stream rule: what one wave task costs on the kernels' cost axis."""
+    return _u32("hs_ext_task_weight", query16, ext304)
+
+
+def list_len(query16, ext304, li):
+    """Entries of candidate list li as mcq_ext_lists_kernel lays it out (0: the query has no such list)."""
+    return _u32("hs_ext_list_len", query16, ext304, li)
+
+
 def exact(query16, ext304, law):
     """The exact split-pot lane code (kinds 0 and 1) -> 22 words of integer weights; ValueError(code) on a refusal."""
     q, e = _bytes(query16, 16), _bytes(ext304, 304)

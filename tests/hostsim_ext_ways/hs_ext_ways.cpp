@@ -142,6 +142,38 @@ int hs_ext_ways_is_fast(const mcq_query *q, const mcq_query_ext *e) {
     return qc.fast ? 1 : 0;
 }
 
+// What the host layer and the kernels cut a batch by (tests/test_ext_kernel_grid_gpu.py mirrors their choice of path, of
+// the waves per block and of the lists' placement): candidate lists, iterations per stream, wave tasks and the cost of
+// one, and the length of list li as mcq_ext_lists_kernel lays it out (0 for a list the query does not have).
+uint32_t hs_ext_n_lists(const mcq_query *q, const mcq_query_ext *e) {
+    const McqExtRec er = {reinterpret_cast<const uint32_t *>(e)};
+    return mcq_ext_n_lists(mcq_query_words(*q), er);
+}
+uint32_t hs_ext_stream_iters(const mcq_query *q, const mcq_query_ext *e) {
+    const McqExtRec er = {reinterpret_cast<const uint32_t *>(e)};
+    return mcq_ext_stream_iters(mcq_query_words(*q), er);
+}
+uint32_t hs_ext_task_count(const mcq_query *q, const mcq_query_ext *e) {
+    const McqExtRec er = {reinterpret_cast<const uint32_t *>(e)};
+    const McqQueryWords qw = mcq_query_words(*q);
+    return mcq_ext_task_count(qw, mcq_ext_stream_iters(qw, er));
+}
+uint32_t hs_ext_task_weight(const mcq_query *q, const mcq_query_ext *e) {
+    const McqExtRec er = {reinterpret_cast<const uint32_t *>(e)};
+    const McqQueryWords qw = mcq_query_words(*q);
+    return mcq_ext_task_weight(qw, mcq_ext_stream_iters(qw, er));
+}
+uint32_t hs_ext_list_len(const mcq_query *q, const mcq_query_ext *e, uint32_t li) {
+    const McqExtRec er = {reinterpret_cast<const uint32_t *>(e)};
+    const McqQueryWords qw = mcq_query_words(*q);
+    if (li >= mcq_ext_n_lists(qw, er)) return 0;
+    uint64_t U;
+    uint32_t set_off, cnt = 0;
+    mcq_ext_list_plan(qw, er, li, U, set_off);
+    for (uint32_t c = 0; c < 2704u; c++) cnt += mcq_ext_candidate(U, er.w + set_off, c) ? 1u : 0u;
+    return cnt;
+}
+
 // The exact enumeration's split-pot lane code, kinds 0 and 1, walked as mcq_exact_ext_kernel<KIND, true> walks it.
 // -> 0, MCQ_XX_* (1..4), 5 = cannot be dealt, 6 = two random opponents.  weights: 22 words.
 int hs_exact_ext_ways(const mcq_query *q, const mcq_query_ext *x, int law, uint64_t *weights) {
