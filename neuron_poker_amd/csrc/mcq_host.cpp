@@ -60,7 +60,11 @@ void pick_geometry(const mcq_ctx *c, int mode, uint64_t total_tasks, uint32_t *g
     const uint32_t full = (uint32_t)c->n_cu * (uint32_t)c->occ[mode];
     if (split) *split = 0;
     if (work_wpb) *work_wpb = 0;
-    if (total_tasks == 0) { *block = kBlock; *grid = full; return; }
+    if (total_tasks == 0) {
+        *block = kBlock;
+        *grid = c->grid_cap && full > c->grid_cap ? c->grid_cap : full;
+        return;
+    }
     if (split) { /* small batches are cut finer, see mcq_pick_split */
         *split = mcq_pick_split(total_tasks, max_tasks ? max_tasks : total_tasks, (uint32_t)c->n_cu, c->split_max);
         total_tasks <<= *split;
@@ -78,6 +82,9 @@ void pick_geometry(const mcq_ctx *c, int mode, uint64_t total_tasks, uint32_t *g
     if (work_wpb && launch != wpb) *work_wpb = (uint32_t)wpb;
     else launch = wpb < 4 ? 4 : wpb, wpb = launch;
     *block = (uint32_t)(64 * launch);
+    /* tests: fewer blocks than the work asks for, so that a wave's slice is many tasks of one query (streams are keyed by
+     * query id and iteration: the tallies do not depend on the number of blocks) */
+    if (c->grid_cap && *grid > c->grid_cap) *grid = c->grid_cap;
 }
 
 /* is stream s being captured into a graph? (a failing query counts as "no") */
@@ -440,6 +447,7 @@ mcq_ctx *mcq_ctx_clone(const mcq_ctx *c) {
         d->law = c->law;
         d->split_max = c->split_max;
         d->load_waves = c->load_waves;
+        d->grid_cap = c->grid_cap;
         d->direct_max_tasks = c->direct_max_tasks;
         d->direct_poll = c->direct_poll;
         d->direct_sleep = c->direct_sleep;
@@ -554,6 +562,10 @@ mcq_ctx *mcq_create(int device, int flags) {
     if (const char *e = getenv("MCQ_LOAD_WAVES")) { /* tuning knob, see pick_geometry */
         const int v = atoi(e);
         c->load_waves = (uint32_t)(v < 1 ? 1 : (v > 16 ? 16 : v));
+    }
+    if (const char *e = getenv("MCQ_GRID_CAP")) { /* at most this many blocks in a sliced launch (tests), see pick_geometry */
+        const long v = atol(e);
+        if (v >= 1) c->grid_cap = (uint32_t)(v > 0x7fffffffL ? 0x7fffffffL : v);
     }
     if (const char *e = getenv("MCQ_REPLAY_DEVICE_BYTES")) { /* chunking of the parity mode's draw buffer (tests) */
         const long long v = atoll(e);

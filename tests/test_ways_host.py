@@ -37,6 +37,22 @@ def test_lane_code_on_random_hands_every_player_count_and_street(mode):
                 assert np.array_equal(got, exp), (mode, n, nb, general, got, exp)
 
 
+@pytest.mark.parametrize("mode", W.MODES)
+def test_vectorised_recount_equals_the_pairwise_one(mode):
+    """ways_expect.expected_row_fast (packed scores compared in numpy: what the long-query GPU tests expect rows from)
+    against expected_row (oracle.compare per pair of hands), word for word, on the cases in which k varies -- and on the
+    two further boards the long-query tests take from tests/hot_boards.py, where the reference's quads rule and the wheel
+    decide what compares equal."""
+    from tests import hot_boards as HB
+    for i, (hero, board, n) in enumerate(W.CASES):
+        fast = W.expected_row_fast(mode, hero, board, n, W.RUNS, W.SEED, W.QID, threads=4)
+        assert np.array_equal(fast, W.expected_case(mode, i)), (mode, i, fast, W.expected_case(mode, i))
+    for s in (8, 16):
+        hero, board = HB.SITUATIONS[s]
+        fast = W.expected_row_fast(mode, hero, board, 6, 1000, W.SEED, W.QID + s, threads=4)
+        assert np.array_equal(fast, W.expected_row(mode, hero, board, 6, 1000, W.SEED, W.QID + s)), (mode, s)
+
+
 def test_sanity_against_arithmetic():
     """Heads-up every tie is two-way; alone at the table hero wins every iteration."""
     for mode in W.MODES:

@@ -42,6 +42,23 @@ def expected_row(mode, hero, board, n_players, runs, seed, qid):
     return np.concatenate([r["tallies"], ways[2:]]).astype(np.uint64)
 
 
+def expected_row_fast(mode, hero, board, n_players, runs, seed, qid, threads=1):
+    """expected_row for long queries: the same trace, scored in one oracle.score_batch call (calc_score of every hand as an
+    order-preserving integer) and compared in numpy instead of one oracle.compare per pair of hands.
+    tests/test_ways_host.py holds it equal to expected_row, word for word."""
+    if mode == O.MODE_MT:
+        seed, qid = (seed + qid) & 0xFFFFFFFF, 0
+    r = O.run(mode, hero, board, n_players, runs, seed, qid, keep=runs)
+    score = O.score_batch(r["trace"].reshape(-1, 7), threads).reshape(runs, n_players)
+    mine, theirs = score[:, :1], score[:, 1:]
+    best = ~(theirs > mine).any(axis=1)                    # no opponent's hand is greater
+    k = 1 + (theirs == mine).sum(axis=1)                   # hands that share the pot
+    ways = np.bincount(k[best], minlength=11).astype(np.uint64)
+    assert int(ways[1]) == r["win"] and int(ways[2:].sum()) == r["tie"], (ways, r["win"], r["tie"])
+    assert not ways[n_players + 1:].any()
+    return np.concatenate([r["tallies"], ways[2:]]).astype(np.uint64)
+
+
 _cache = {}
 
 
