@@ -567,6 +567,10 @@ mcq_ctx *mcq_create(int device, int flags) {
         const long v = atol(e);
         if (v >= 1) c->grid_cap = (uint32_t)(v > 0x7fffffffL ? 0x7fffffffL : v);
     }
+    if (const char *e = getenv("MCQ_EXACT_CU")) { /* the CU count the exact plans size their grids by, capped (tests), see exact_cu */
+        const long v = atol(e);
+        if (v >= 1) c->exact_cu = (uint32_t)(v > 0x7fffffffL ? 0x7fffffffL : v);
+    }
     if (const char *e = getenv("MCQ_REPLAY_DEVICE_BYTES")) { /* chunking of the parity mode's draw buffer (tests) */
         const long long v = atoll(e);
         if (v > 0) c->replay_device_bytes = (uint64_t)v;
@@ -1229,6 +1233,12 @@ int mcq_showdown(mcq_ctx *c, const uint8_t *hands, size_t n_tables, int n_player
     ABI_GUARD_END("mcq_showdown")
 }
 
+/* the CU count mcq_exact_plan and mcq_exact_ext_plan size a grid by: the device's, or MCQ_EXACT_CU where that is smaller */
+static uint32_t exact_cu(const mcq_ctx *c) {
+    const uint32_t n_cu = (uint32_t)c->n_cu;
+    return c->exact_cu && c->exact_cu < n_cu ? c->exact_cu : n_cu;
+}
+
 int mcq_exact_batch(mcq_ctx *c, const mcq_query *q, size_t n, int law, mcq_result *out) {
     ABI_GUARD_BEGIN
     if (!c) return mcq_fail(MCQ_EINVAL, "mcq_exact_batch: null context");
@@ -1254,10 +1264,10 @@ int mcq_exact_batch(mcq_ctx *c, const mcq_query *q, size_t n, int law, mcq_resul
     const McqExactJob *d_jobs = static_cast<const McqExactJob *>(c->h_misc.dev);
     size_t n_two = 0;
     for (size_t i = 0; i < n; i++) /* the two-opponent queries first, the others behind them */
-        if (q[i].n_players == 3) mcq_exact_plan(&q[i], (uint32_t)i, (uint32_t)c->n_cu, &jobs[n_two++]);
+        if (q[i].n_players == 3) mcq_exact_plan(&q[i], (uint32_t)i, exact_cu(c), &jobs[n_two++]);
     size_t at = n_two;
     for (size_t i = 0; i < n; i++)
-        if (q[i].n_players != 3) mcq_exact_plan(&q[i], (uint32_t)i, (uint32_t)c->n_cu, &jobs[at++]);
+        if (q[i].n_players != 3) mcq_exact_plan(&q[i], (uint32_t)i, exact_cu(c), &jobs[at++]);
     for (size_t a = 0; a < n;) {
         const bool two = a < n_two;
         const size_t end = two ? n_two : n, b = a + 65535u < end ? a + 65535u : end;
@@ -1352,7 +1362,7 @@ static int exact_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_
             if (xq[i].b.n_opp != kind) continue;
             h1_off[i] = off;
             const uint32_t g = mcq_exact_ext_plan(&q[i], (uint32_t)i, (uint32_t)i, kind, xq[i].b.L, (uint32_t)off,
-                                                  (uint32_t)c->n_cu, &jobs[at++]);
+                                                  exact_cu(c), &jobs[at++]);
             max_grid = g > max_grid ? g : max_grid;
             if (kind == 2u) off += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
         }
