@@ -137,6 +137,33 @@ int main(int argc, char **argv) {
         for (s = 0; s < 3; s++) printf(" %.6f", (double)seats.seat[s].share / ((double)MCQ_SHARE_UNIT * (double)seats.runs));
         printf("\n");
     }
+    { /* a hero RANGE on the flop: every hand of {AA, AKs} against a random hand from one enumeration */
+        static mcq_result rows[MCQ_HAND_ROWS];
+        mcq_query_ext x;
+        mcq_exact_prob agg;
+        const mcq_result *h;
+        memset(&x, 0, sizeof x);
+        x.ghost[0] = x.ghost[1] = 0xFF;
+        x.hero_is_range = 1;
+        x.hero_range[(14 * 12) >> 5] |= 1u << ((14 * 12) & 31);           /* AA: pair -> 14 * rank */
+        x.hero_range[(13 * 11 + 12) >> 5] |= 1u << ((13 * 11 + 12) & 31); /* AKs: suited -> 13 * min + max */
+        for (k = 0; k < 5; k++) x.opp_range[k] = 0xFFFFFFFFu;
+        x.opp_range[5] = 0x1FFu; /* every class */
+        memset(&q, 0, sizeof q);
+        q.board[0] = (uint8_t)card("2C");
+        q.board[1] = (uint8_t)card("7D");
+        q.board[2] = (uint8_t)card("9H");
+        q.n_board = 3;
+        q.n_players = 2;
+        rc = mcq_exact_batch_hero_range(ctx, &q, &x, 1, MCQ_LAW_REFERENCE, rows, &agg);
+        if (rc) {
+            fprintf(stderr, "mcq_exact_batch_hero_range: %d %s\n", rc, mcq_last_error());
+            return 1;
+        }
+        h = &rows[MCQ_HAND_INDEX((unsigned)card("AH"), (unsigned)card("AS"))];
+        printf("{AA, AKs} on 2c7d9h against a random hand: range equity %.6f, AhAs alone %.6f\n", agg.win + agg.tie,
+               (double)(h->win + h->tie) / (double)h->runs);
+    }
     mcq_destroy(ctx);
     return 0;
 }

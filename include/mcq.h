@@ -269,9 +269,10 @@ MCQ_API int mcq_exact_batch(mcq_ctx *ctx, const mcq_query *q, size_t n, int law,
  * range.  Accepted: hero given as two cards, 0..9 further known hands each given as two cards (is_range == 0), optional
  * ghost cards, 0, 1 or 2 random opponents (n_players - 1 - n_known) drawn from opp_range, both laws.  Refused with
  * MCQ_EINVAL, nothing launched: whatever mcq_eval_batch_ext refuses, hero_is_range, a known hand given as a range, more
- * than two random opponents, and a range that cannot be dealt on some branch of positive probability.  A hero range (an
- * outer sum over the hero's hands: out of reach preflop) and ranged known hands (the reference's pop-by-value quirk,
- * montecarlo_python.py:154-161) are left out on purpose.
+ * than two random opponents, and a range that cannot be dealt on some branch of positive probability.  A hero range is
+ * an outer sum over the hero's hands -- out of reach preflop, and postflop, heads-up, the business of
+ * mcq_exact_batch_hero_range below, which shares the ranking of the opponent's hands among all hero hands; ranged known
+ * hands (the reference's pop-by-value quirk, montecarlo_python.py:154-161) are left out on purpose.
  * MCQ_LAW_REFERENCE: every ordered pair (A, B) of the current deck is equally likely provided A != B, B is not the
  * deck's highest card and class(A, B) is allowed; A is dealt, then B if B < A, else the card that follows B
  * (montecarlo_python.py:165-181); a table card is never the highest card left.  MCQ_LAW_UNIFORM: every allowed
@@ -330,6 +331,30 @@ MCQ_API int mcq_exact_batch_seats(mcq_ctx *ctx, const mcq_query *q, const mcq_qu
  * of every seat. */
 MCQ_API int mcq_exact_batch_ext_seats(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
                                       mcq_result_seats *weights);
+
+/* Exact RANGE against RANGE, postflop and heads-up: every hand of the hero's range from ONE enumeration per record.
+ * Accepted: ext[i].hero_is_range == 1 with hero_range (q[i].hole is ignored), n_known == 0, n_players == 2 -- one random
+ * opponent drawn from opp_range, restricted or not --, 3, 4 or 5 table cards, optional ghost cards, both laws.
+ * D = the 52 cards minus table and ghost.  For every hand {a < b} of D whose class is in hero_range,
+ * rows[i * MCQ_HAND_ROWS + MCQ_HAND_INDEX(a, b)] is bit for bit the weights row mcq_exact_batch_ext writes for the same
+ * record with the hero given as those two cards (runs = total weight, passes = 0; under MCQ_LAW_REFERENCE the opponent's
+ * index bias on the deck without the hero's cards and the rule that a table card is never the highest card left
+ * included); every other row is zero.  Heads-up pot share of that hand: (win + tie / 2) / runs.
+ * agg[i] (agg may be NULL) = sum_h w_h x_h / runs_h / sum_h w_h over the allowed hands, x = win, tie, by_type[t], combined
+ * on the host in ascending row order; w_h = how often the law deals hero that hand: 1 under MCQ_LAW_UNIFORM, and
+ * 2 - [b is the highest card of D] under MCQ_LAW_REFERENCE (montecarlo_python.py:136-148: the ordered pairs (A, B) with B
+ * not the deck's highest card, the hand leaves by value) -- what mcq_eval_batch_ext with hero_is_range == 1 converges to.
+ * Refused with MCQ_EINVAL, rows and agg untouched: whatever mcq_eval_batch_ext refuses, hero_is_range == 0, n_known != 0,
+ * n_players != 2, fewer than three table cards (preflop every hero hand meets C(50, 5) completions), a bad law, more
+ * than MCQ_HERO_RANGE_MAX_BATCH records, no allowed hero hand in D -- all before anything is launched -- and an allowed
+ * hero hand against which the opponent's range cannot be dealt (mcq_exact_batch_ext's "cannot be dealt on some branch of
+ * positive probability"; seen as a row without weight, before anything is copied to the caller).
+ * Deterministic: integer sums per hero hand.  Each record costs MCQ_HAND_ROWS * sizeof(mcq_result) = 138 KB of rows. */
+#define MCQ_HAND_ROWS 1326u /* C(52, 2) */
+#define MCQ_HAND_INDEX(a, b) /* a < b card ids */ ((b) * ((b) - 1u) / 2u + (a))
+#define MCQ_HERO_RANGE_MAX_BATCH 1024u
+MCQ_API int mcq_exact_batch_hero_range(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                                       mcq_result *rows /* [n][MCQ_HAND_ROWS] */, mcq_exact_prob *agg /* [n], may be NULL */);
 
 /* Select the dealing law used by MCQ_MODE_PHILOX on this context (MCQ_LAW_*).  Extended queries
  * (mcq_eval_batch_ext) are dealt by the reference's law only: under MCQ_LAW_UNIFORM that call gives MCQ_EINVAL. */

@@ -135,6 +135,8 @@ def load_library():
         L.mcq_exact_batch.restype = C.c_int
         L.mcq_exact_batch_ext.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
         L.mcq_exact_batch_ext.restype = C.c_int
+        L.mcq_exact_batch_hero_range.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
+        L.mcq_exact_batch_hero_range.restype = C.c_int
         L.mcq_set_dealing_law.argtypes = [vp, C.c_int]
         L.mcq_set_dealing_law.restype = C.c_int
         L.mcq_set_kernel_timing.argtypes = [vp, C.c_int]
@@ -259,6 +261,18 @@ def pack_query_one(hole, board, n_players, runs):
     except struct.error as e:
         raise ValueError("card id, n_players or runs out of range: %s" % e)
     return np.frombuffer(bytearray(raw), QUERY_DTYPE)  # writable
+
+
+HAND_ROWS = 1326   # C(52, 2): MCQ_HAND_ROWS
+
+
+def hand_index(a, b):
+    """Row of the two-card hand {a, b} (card ids) among the HAND_ROWS rows of Engine.exact_hero_range: MCQ_HAND_INDEX."""
+    a, b = int(a), int(b)
+    if a == b or not (0 <= a < 52 and 0 <= b < 52):
+        raise ValueError("a hand is two different card ids below 52")
+    lo, hi = min(a, b), max(a, b)
+    return hi * (hi - 1) // 2 + lo
 
 
 def class_bit(name):
@@ -416,6 +430,27 @@ class Engine:
         if rc:
             _raise(rc)
         return prob, weights
+
+    def exact_hero_range(self, queries, ext, law="reference"):
+        """Exact range against range, postflop and heads-up (mcq_exact_batch_hero_range): records with hero_is_range = 1,
+        no known hands, one random opponent drawn from opp_range, 3 to 5 table cards.  -> (rows, agg): rows[n, HAND_ROWS]
+        of RESULT_DTYPE -- row hand_index(a, b) holds, for every hand of the hero's range that the deck can make, the
+        integer weights exact_ext gives the same record with the hero holding a and b, every other row is zero -- and
+        agg[n] of EXACT_PROB_DTYPE, the rows combined with the weights by which the law deals hero his hands."""
+        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
+        if code is None:
+            raise ValueError("law must be 'reference' or 'uniform'")
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        rows = np.zeros((len(q), HAND_ROWS), RESULT_DTYPE)
+        agg = np.zeros(len(q), EXACT_PROB_DTYPE)
+        rc = self._lib.mcq_exact_batch_hero_range(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, rows.ctypes.data,
+                                                  agg.ctypes.data)
+        if rc:
+            _raise(rc)
+        return rows, agg
 
     def exact_ext_ways(self, queries, ext, law="reference"):
         """exact_ext with the ties split by the hands that share the pot (mcq_exact_batch_ext_ways; at most ONE random

@@ -19,6 +19,7 @@
 #include "mcq_ctx.hpp"
 #include "mcq_device.hpp"
 #include "mcq_exact_ext.hpp"
+#include "mcq_exact_hero.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt_blocks.hpp"
 #include "mcq_replay.hpp"
@@ -1421,6 +1422,83 @@ int mcq_exact_batch_ext_seats(mcq_ctx *c, const mcq_query *q, const mcq_query_ex
     ABI_GUARD_BEGIN
     return exact_batch_ext_impl(c, q, ext, n, law, nullptr, weights, kSeatsWords, "mcq_exact_batch_ext_seats", 1u);
     ABI_GUARD_END("mcq_exact_batch_ext_seats")
+}
+
+}  // extern "C"
+
+extern "C" {
+
+/* every hero hand of a range against one random opponent from one enumeration per query (mcq_exact_hero.hpp) */
+int mcq_exact_batch_hero_range(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, mcq_result *rows,
+                               mcq_exact_prob *agg) {
+    ABI_GUARD_BEGIN
+    const char *who = "mcq_exact_batch_hero_range";
+    if (n == 0) return MCQ_OK; /* (nothing to do: not even a context is needed) */
+    if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
+    if (!q || !ext || !rows) return mcq_fail(MCQ_EINVAL, who, "null buffer");
+    if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return mcq_fail(MCQ_EINVAL, who, "bad law");
+    if (n > MCQ_HERO_RANGE_MAX_BATCH) return mcq_fail(MCQ_EINVAL, who, "at most MCQ_HERO_RANGE_MAX_BATCH queries per call");
+    /* validation first: nothing is launched for a batch with one query that cannot be enumerated */
+    std::vector<McqExactHeroQuery> xq(n);
+    std::vector<uint8_t> rid(n * 64u);
+    char buf[200];
+    for (size_t i = 0; i < n; i++) {
+        const McqExtRec er = {reinterpret_cast<const uint32_t *>(&ext[i])};
+        int why = mcq_exact_hero_query(mcq_query_words(q[i]), er, law, xq[i]);
+        if (why == MCQ_XH_OK) {
+            mcq_exact_ext_r_ids(xq[i].x, &rid[64u * i]);
+            xq[i].n_allowed = mcq_exact_hero_count(xq[i], &rid[64u * i], nullptr);
+            if (xq[i].n_allowed == 0u) why = MCQ_XH_EMPTY;
+        }
+        if (why != MCQ_XH_OK) {
+            static const char *const reason[] = {
+                "", "invalid extended query (as mcq_eval_batch_ext: distinct card ids < 52, at most 9 known hands, used ranges not empty)",
+                "the hero is given as two cards (hero_is_range == 0): mcq_exact_batch_ext enumerates that",
+                "known hands beside a hero range are not enumerated (n_known must be 0)",
+                "a hero range is enumerated heads-up only (n_players must be 2)",
+                "a hero range is enumerated postflop only (3 to 5 table cards): preflop every hero hand meets C(50, 5) table "
+                "completions",
+                "no hand of the hero's range can be made of the cards left"};
+            snprintf(buf, sizeof buf, "query %zu: %s", i, reason[why]);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+    }
+    MCQ_ENTER(c, who);
+    McqDeviceScope dev_(c->device);
+    HIP_TRY(dev_.err);
+    const size_t q_bytes = (size_t)MCQ_XH_ROWS * sizeof(mcq_result);
+    HIP_TRY(c->d_res.reserve(n * q_bytes));
+    c->res_clean = 0;
+    HIP_TRY(c->h_res.reserve(n * q_bytes));
+    HIP_TRY(hipMemsetAsync(c->d_res.p, 0, n * q_bytes, c->stream));
+    /* jobs and extension records travel in pinned memory */
+    const size_t job_bytes = (n * sizeof(McqExactExtJob) + 255u) & ~(size_t)255u;
+    HIP_TRY(c->h_misc.reserve(job_bytes + n * sizeof(mcq_query_ext)));
+    McqExactExtJob *jobs = static_cast<McqExactExtJob *>(c->h_misc.p);
+    const McqExactExtJob *d_jobs = static_cast<const McqExactExtJob *>(c->h_misc.dev);
+    memcpy(static_cast<uint8_t *>(c->h_misc.p) + job_bytes, ext, n * sizeof(mcq_query_ext));
+    const uint32_t *d_ext = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(c->h_misc.dev) + job_bytes);
+    uint32_t max_grid = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t g = mcq_exact_hero_plan(&q[i], (uint32_t)i, (uint32_t)i, xq[i].x.b.L, xq[i].n_allowed, exact_cu(c), &jobs[i]);
+        max_grid = g > max_grid ? g : max_grid;
+    }
+    HIP_TRY(mcq_launch_exact_hero(d_jobs, (uint32_t)n, max_grid, d_ext, law, (mcq_result *)c->d_res.p, c->d_luts, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * q_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    /* the aggregates first: a row without weight (the opponent's range cannot be dealt against that hero hand) refuses the
+     * whole call before anything reaches the caller */
+    const mcq_result *hr = static_cast<const mcq_result *>(c->h_res.p);
+    std::vector<mcq_exact_prob> p(n);
+    for (size_t i = 0; i < n; i++)
+        if (!mcq_exact_hero_finish(xq[i], &rid[64u * i], hr + i * MCQ_XH_ROWS, p[i])) {
+            snprintf(buf, sizeof buf, "query %zu: the opponent's range cannot be dealt against some hand of the hero's range", i);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+    memcpy(rows, hr, n * q_bytes);
+    if (agg) memcpy(agg, p.data(), n * sizeof(mcq_exact_prob));
+    return MCQ_OK;
+    ABI_GUARD_END("mcq_exact_batch_hero_range")
 }
 
 }  // extern "C"

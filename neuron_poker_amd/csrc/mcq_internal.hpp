@@ -40,6 +40,12 @@ hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, u
                                 const McqTables *d_luts, hipStream_t s,
                                 bool ways = false /* kinds 0 and 1: d_rows holds zeroed mcq_result_ways rows */,
                                 bool seats = false /* kind 0: d_rows holds zeroed mcq_result_seats rows */);
+/* hero-range enumeration (mcq_exact_hero.hpp): one job per query, L = |D|, n_allowed = its allowed hero hands (> 0); d_rows
+ * holds zeroed [MCQ_HAND_ROWS] mcq_result rows per query, job->row = the query's index */
+uint32_t mcq_exact_hero_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed, uint32_t n_cu,
+                             McqExactExtJob *job);
+hipError_t mcq_launch_exact_hero(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
+                                 mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
 hipError_t mcq_launch_exact(const McqExactJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, bool two_opp, int law,
                             mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
 /* hands / winner / wtype / keys: device-visible memory (pinned host memory or HBM), 16-byte aligned and padded to whole

@@ -17,6 +17,7 @@
 #include "mcq_device.hpp"
 #include "mcq_exact.hpp"
 #include "mcq_exact_ext.hpp"
+#include "mcq_exact_hero.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt.hpp"
 #include "mcq_mt_ext.hpp"
@@ -2274,6 +2275,106 @@ __global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJo
     }
 }
 
+// ---------------------------------------------------------------------------------------------- exact enumeration, hero range
+// See mcq_exact_hero.hpp; one job per query (blockIdx.y), the shape of mcq_exact_ext_kernel's kind 2 with the first hand
+// being the HERO's: a BLOCK per table completion -- its 1024 threads rank the C(m, 2) <= 1081 candidate hands once
+// (LDS), then thread t of group g owns the (g * 1024 + t)-th ALLOWED hero hand (a D-pair, fixed across completions; the
+// hands outside the range or the deck are not on the list and cost no walk) and walks every candidate as the
+// opponent's hand with broadcast LDS reads.  Its twelve 32-bit sums stay in registers until the block's last completion
+// and go to row mcq_exact_hero_row of the query's zeroed [1326][13] rows (integer atomics: deterministic).
+// LDS: 97 KB of tables + 8.7 KB of keys and records + 6 KB of lists, one block of 16 waves per CU.
+__global__ __launch_bounds__(1024) void mcq_exact_hero_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
+                                                              int law, unsigned long long *__restrict__ rows,
+                                                              const McqTables *__restrict__ g_tab) {
+    const McqExactExtJob job = jobs[blockIdx.y];
+    if (blockIdx.x >= job.grid) return;
+    constexpr uint32_t kChunks = (MCQ_XH_MAX_HANDS + 63u) / 64u;
+    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ uint16_t pair_xy[MCQ_XH_MAX_HANDS]; /* every D-pair; the candidate hands are its first n_pairs entries */
+    __shared__ uint32_t xw[MCQ_EXT_WORDS];
+    __shared__ McqExactHeroQuery xq;
+    __shared__ uint8_t r_id[64];
+    __shared__ uint8_t cb_tab[MCQ_XX_MAX_RP + 3u];
+    __shared__ uint16_t own_list[MCQ_XH_MAX_HANDS];
+    __shared__ uint32_t chunk_cnt[kChunks];
+    __shared__ McqCard rem_card[64];
+    __shared__ uint32_t rem_pos[64];
+    __shared__ uint32_t keys[MCQ_XH_MAX_PAIRS + 3u];
+    __shared__ uint32_t recs[MCQ_XH_MAX_PAIRS + 3u];
+    static_assert(MCQ_XH_MAX_PAIRS <= MCQ_XH_MAX_HANDS, "pair_xy covers the candidate hands");
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
+    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
+    for (uint32_t i = tid; i < MCQ_XH_MAX_HANDS; i += blockDim.x) {
+        uint32_t x, y;
+        mcq_exact_pair_xy(i, x, y);
+        pair_xy[i] = (uint16_t)(x | (y << 8));
+    }
+    load_tables(tab, g_tab); /* ends with a barrier */
+    if (tid == 0) {
+        const McqExtRec er = {xw};
+        (void)mcq_exact_hero_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, law, xq); /* validated by the host */
+        mcq_exact_ext_r_ids(xq.x, r_id);
+    }
+    __syncthreads();
+    const McqExactHeroQuery &e = xq;
+    mcq_exact_ext_cb_table(e.x, r_id, tid, blockDim.x, cb_tab);
+    /* the allowed hero hands in ascending order (every block makes the same list): 64 D-pairs per wave and pass */
+    for (uint32_t c = wib; c < kChunks; c += 16u) {
+        const uint32_t rp = c * 64u + lane, xy = pair_xy[rp < MCQ_XH_MAX_HANDS ? rp : 0u];
+        const bool on = rp < e.x.n_rp && mcq_exact_hero_allowed(e, r_id, xy & 0xFFu, xy >> 8);
+        const unsigned long long mask = __ballot(on);
+        if (lane == 0u) chunk_cnt[c] = (uint32_t)__popcll(mask);
+    }
+    __syncthreads();
+    for (uint32_t c = wib; c < kChunks; c += 16u) {
+        const uint32_t rp = c * 64u + lane, xy = pair_xy[rp < MCQ_XH_MAX_HANDS ? rp : 0u];
+        const bool on = rp < e.x.n_rp && mcq_exact_hero_allowed(e, r_id, xy & 0xFFu, xy >> 8);
+        const unsigned long long mask = __ballot(on);
+        uint32_t base = 0;
+        for (uint32_t j = 0; j < c; j++) base += chunk_cnt[j];
+        if (on) own_list[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (uint16_t)rp;
+    }
+    uint32_t n_own = 0;
+    for (uint32_t j = 0; j < kChunks; j++) n_own += chunk_cnt[j];
+    __syncthreads();
+
+    const uint32_t groups = job.groups, group = blockIdx.x % groups, idx = group * blockDim.x + tid;
+    const bool own = idx < n_own;
+    const uint32_t hxy = pair_xy[own ? own_list[idx] : 0u], qa = hxy & 0xFFu, qb = hxy >> 8;
+    McqExactHeroSums s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+    for (uint32_t board = blockIdx.x / groups; board < job.n_boards; board += job.grid / groups) {
+        uint32_t pos[5];
+        mcq_exact_unrank(board, e.x.b.L, e.x.b.k, pos);
+        McqExactBoard bd;
+        mcq_exact_hero_board(e.x.b, pos, r_id, bd);
+        __syncthreads(); /* the previous completion's walk is done with keys and records */
+        if (tid < e.x.m) {
+            const uint32_t rp = mcq_exact_rem_pos(pos, tid);
+            rem_pos[tid] = rp;
+            rem_card[tid] = mcq_card(r_id[rp]);
+        }
+        __syncthreads();
+        mcq_exact_hero_rank(e, bd, tid, blockDim.x, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, keys, recs);
+        __syncthreads();
+        const uint32_t mi = own ? mcq_exact_ext_m_index(e.x, pos, qa, qb) : e.x.n_pairs;
+        if (mi < e.x.n_pairs) {
+            McqExactAcc acc = {0, 0, 0};
+            const uint32_t type = mcq_exact_hero_walk(e, bd, qa, qb, mi, keys, recs, acc);
+            mcq_exact_hero_add(s, acc, type);
+        }
+    }
+    if (own) {
+        unsigned long long *dst = rows + ((size_t)job.row * MCQ_XH_ROWS + mcq_exact_hero_row(r_id, qa, qb)) * 13u;
+        /* an mcq_result row: runs, passes, win, tie, by_type[9] */
+        if (s.tot) atomicAdd(dst + 0, (unsigned long long)s.tot);
+        if (s.win) atomicAdd(dst + 2, (unsigned long long)s.win);
+        if (s.tie) atomicAdd(dst + 3, (unsigned long long)s.tie);
+#pragma unroll
+        for (uint32_t t = 0; t < 9; t++)
+            if (s.type[t]) atomicAdd(dst + 4 + t, (unsigned long long)s.type[t]);
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- launchers
@@ -2567,6 +2668,30 @@ hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, u
         MCQ_LAUNCH_XX(2u, MCQ_ROW_PLAIN);
     }
 #undef MCQ_LAUNCH_XX
+    return hipGetLastError();
+}
+
+uint32_t mcq_exact_hero_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed, uint32_t n_cu,
+                             McqExactExtJob *job) {
+    __builtin_memcpy(job->rec, q, 16);
+    job->ext = ext;
+    job->n_boards = mcq_exact_binom(L, 5u - q->n_board);
+    job->row = row;
+    job->h1_off = 0u;
+    job->groups = (n_allowed + 1023u) / 1024u;
+    uint32_t per = n_cu / job->groups;
+    if (per < 1u) per = 1u;
+    if (per > job->n_boards) per = job->n_boards;
+    job->grid = per * job->groups;
+    return job->grid;
+}
+
+hipError_t mcq_launch_exact_hero(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
+                                 mcq_result *d_rows, const McqTables *d_luts, hipStream_t s) {
+    if (n_jobs == 0) return hipSuccess;
+    if (n_jobs > 65535u || max_grid == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mcq_exact_hero_kernel, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law,
+                       reinterpret_cast<unsigned long long *>(d_rows), d_luts);
     return hipGetLastError();
 }
 

@@ -32,9 +32,9 @@ from collections import Counter
 import numpy as np
 
 from . import _lib
-from .cards import TYPES, card_id
+from .cards import TYPES, card_id, card_str
 
-__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "MonteCarlo", "seed",
+__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "MonteCarlo", "seed",
            "configure"]
 
 _state = {"couple_numpy": False,
@@ -492,3 +492,50 @@ def get_equity_exact(player_cards, table_cards, players, dealing="reference", en
     ext = _ext_record(list(player_cards), False, known_hands, ghost_cards, opponent_range, opp_bits)
     prob, weights = eng.exact_ext(q, ext, dealing)
     return float(prob[0]["win"] + prob[0]["tie"]), weights[0]
+
+
+_ROW_HANDS = [(a, b) for b in range(52) for a in range(b)]   # row _lib.hand_index(a, b) -> (a, b)
+
+
+def get_range_equity_exact(hero_range, table_cards, opponent_range=1, dealing="reference", ghost_cards='', engine=None,
+                           ties="credited"):
+    """Exact equity of a hero RANGE against one random opponent, ranged or not, on the flop, turn or river: every hand
+    of the range from one enumeration on the GPU (mcq_exact_batch_hero_range).
+
+    hero_range and opponent_range follow run_montecarlo's conventions: a set of preflop class strings, or a number that
+    keeps the top fraction of the 169 classes.  -> (equity, {(card, card): (equity_h, weight_h)}): per hand of the range
+    that the remaining cards can make (card strings, lower card id first) its exact equity -- ties="credited": (win + tie) /
+    runs as the reference credits a tie; ties="split": the heads-up pot share (win + tie / 2) / runs -- and how often
+    `dealing` deals hero that hand in proportion; `equity` is their weighted mean, what run_montecarlo with a hero range
+    converges to under dealing='reference'.  Preflop, further players and known hands raise ValueError."""
+    if ties not in ("credited", "split"):
+        raise ValueError("ties must be 'credited' or 'split'")
+    hero_bits = _opponent_range_bits(hero_range)
+    if hero_bits is None:
+        hero_bits = _lib.ALL_CLASSES
+    opp_bits = _opponent_range_bits(opponent_range)
+    board = [card_id(c) for c in table_cards]
+    if len(board) > 5:
+        raise ValueError("table_cards holds more than five cards")
+    ghost = None
+    if ghost_cards != '' and ghost_cards is not None:
+        ghost = [card_id(ghost_cards[0]), card_id(ghost_cards[1])]
+    q = _lib.pack_query_one([0, 0], board, 2, 1)
+    ext = _lib.pack_query_ext(1, ghost=ghost, hero_range=hero_bits, opp_range=opp_bits)
+    eng = engine or _lib.default_engine()
+    rows, _ = eng.exact_hero_range(q, ext, dealing)
+    r = rows[0]
+    live = np.flatnonzero(r["runs"])
+    gone = set(board) | set(ghost or [])
+    top = max(c for c in range(52) if c not in gone)
+    uniform = dealing in ("uniform", 1)
+    tie = r["tie"][live].astype(np.float64)
+    eq = (r["win"][live] + (tie / 2.0 if ties == "split" else tie)) / r["runs"][live]
+    hands, num, den = {}, 0.0, 0.0
+    for i, e in zip(live, eq):
+        a, b = _ROW_HANDS[i]
+        w = 1 if uniform or b == top else 2
+        hands[(card_str(a), card_str(b))] = (float(e), w)
+        num += w * float(e)
+        den += w
+    return num / den, hands
