@@ -123,6 +123,14 @@ MCQ_HD uint32_t mcq_bfe(uint32_t x, uint32_t off, uint32_t width) { /* (x >> off
     return (x >> off) & (width >= 32 ? 0xFFFFFFFFu : ((1u << width) - 1u));
 #endif
 }
+MCQ_HD uint32_t mcq_mul24(uint32_t a, uint32_t b) { /* a, b < 2^24: one v_mul_u32_u24 */
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul24(a, b);
+#else
+    return a * b;
+#endif
+}
+MCQ_HD uint32_t mcq_mad24(uint32_t a, uint32_t b, uint32_t c) { return mcq_mul24(a, b) + c; } /* one v_mad_u32_u24 */
 MCQ_HD uint32_t mcq_sad_u8(uint32_t bytes, uint32_t acc) { /* acc + sum of the four bytes */
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_sad_u8(bytes, 0u, acc);
@@ -542,9 +550,11 @@ struct McqFlushSel {
     uint32_t psel, bfl4;
     template <class Board>
     MCQ_HDM void from_board(const Board &b) {
-        const uint32_t f = (b.cnt + 0x5555u) & 0x8888u; /* bit 4s+3 <=> suit s has >= 3 table cards */
-        psel = 0x0C0C0100u + ((f & 0x8800u) != 0 ? 0x0404u : 0u) /* hearts or spades: his */
-               + ((f & 0x8080u) != 0 ? 0x0202u : 0u);            /* diamonds or spades: upper half-word */
+        const uint32_t f = (b.cnt + 0x5555u) & 0x8888u; /* bit 4s+3 <=> suit s has >= 3 table cards: one bit at most */
+        /* f * 0x0123 = 0x0123 << (4s + 3): its bits 15-16 are nibble 3 - s of the constant = s, and 0 for f = 0.  No compare,
+         * no select (those went through VCC and its wait states): and, 24-bit multiply, bit-field extract, multiply-add */
+        const uint32_t s = mcq_bfe(mcq_mul24(f, 0x0123u), 15u, 2u);
+        psel = mcq_mad24(s, 0x0202u, 0x0C0C0100u); /* + 0x0404: hearts or spades, his; + 0x0202: diamonds or spades, upper half-word */
         bfl4 = mcq_perm(b.his, b.los, psel);
     }
 };
@@ -623,7 +633,7 @@ MCQ_HD uint32_t mcq_eval_key(const McqBoard &b, const McqFlushSel &fs, const Mcq
 // (McqCard::rb), so the table is one add per card and a hand one add and two dependent 16-bit LDS reads.
 MCQ_HD McqCard mcq_card_sum(uint32_t c) { /* c < 52 */
     McqCard e = mcq_card(c);
-    e.rb = mcq_rank_weight(c >> 2);
+    e.rb = 2u * mcq_rank_weight(c >> 2); /* doubled: the sum's low bits are the byte offset of a 16-bit hoff entry as they are */
     return e;
 }
 struct McqSumBoard {
@@ -658,7 +668,18 @@ MCQ_HD uint32_t mcq_ld_u16(const uint16_t *t, uint32_t byte_off) {
     return *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(t) + byte_off);
 }
 // The two ids of table + hole: of the rank multiset (never 0) and of the flush suit (0 without a flush); the hand's
-// id is the greater one.
+// id is the greater one.  In two steps, so that a caller with several hands can send every hand's first reads before any
+// second one (mcq_iteration_sum): mcq_sum_first sends the flush lookup and the row's displacement, mcq_sum_rank the
+// slot's id.
+MCQ_HD void mcq_sum_first(const McqSumBoard &b, const McqFlushSel &fs, const McqSumHole &h, const McqSumTabs &t,
+                          uint32_t &s, uint32_t &d, uint32_t &flush_id) {
+    s = b.sum + h.ksum; /* twice the multiset's sum (mcq_card_sum) */
+    flush_id = mcq_ld_u32(t.tfid, fs.bfl4 | mcq_perm(h.his, h.los, fs.psel));
+    d = mcq_ld_u16(t.hoff, s & (MCQ_SUM_MASK << 1));
+}
+MCQ_HD uint32_t mcq_sum_rank(const McqSumTabs &t, uint32_t s, uint32_t d) {
+    return mcq_ld_u16(t.hrank, (d + (s >> (MCQ_SUM_SHIFT + 1u))) << 1);
+}
 MCQ_HD void mcq_sum_ids(const McqSumBoard &b, const McqFlushSel &fs, const McqSumHole &h, const McqSumTabs &t,
                         uint32_t &rank_id, uint32_t &flush_id) {
 #ifdef MCQ_ABLATE_EVAL /* diagnostic timing build: wrong results */
@@ -666,10 +687,9 @@ MCQ_HD void mcq_sum_ids(const McqSumBoard &b, const McqFlushSel &fs, const McqSu
     flush_id = 0u;
     return;
 #endif
-    const uint32_t s = b.sum + h.ksum;
-    flush_id = mcq_ld_u32(t.tfid, fs.bfl4 | mcq_perm(h.his, h.los, fs.psel));
-    const uint32_t d = mcq_ld_u16(t.hoff, (s & MCQ_SUM_MASK) << 1);
-    rank_id = mcq_ld_u16(t.hrank, (d + (s >> MCQ_SUM_SHIFT)) << 1);
+    uint32_t s, d;
+    mcq_sum_first(b, fs, h, t, s, d, flush_id);
+    rank_id = mcq_sum_rank(t, s, d);
 }
 MCQ_HD uint32_t mcq_sum_key(const McqSumBoard &b, const McqFlushSel &fs, const McqSumHole &h, const McqSumTabs &t) {
     uint32_t r, f;
@@ -1022,12 +1042,20 @@ MCQ_HD void mcq_hole_reg(uint32_t rb, uint32_t &h, uint32_t &k) {
     h = h + f - 0x01010101u;                          /* every other hole moves down by one */
 }
 
-// Store t = r in byte SLOT.  rb7 = r (optionally with bit 7 set) in every byte, as the scan needs it anyway, so
-// the insertion is a single bit-field insert of the low seven bits (the slot's bit 7 is always clear).
+// Store t = r in byte SLOT of a register whose slots fill in rising order: the slot still holds the sentinel, moved down
+// once by each scan the register has seen since its slot 0 was filled -- SLOT scans, so 0x7F - SLOT exactly -- and the
+// insert is the ADD of (r - that) at the slot's place.  rp = r | 0x80, the draw as it arrives (one byte).  After a scan
+// the constant joins the scan's own (h + f - 0x01010101 + constant: one v_add3_u32) and the insert is one v_lshl_add_u32;
+// slot 0 of a fresh register is one add of a constant to rp.  (A bit-field insert with the mask as a literal is not
+// encodable in the three-operand form: the compiler splits it into an and and a three-operand logic instruction.)
 template <int SLOT>
-MCQ_HD void mcq_hole_put(uint32_t &h, uint32_t rb7) {
+MCQ_HD void mcq_hole_put(uint32_t &h, uint32_t rp) {
     constexpr uint32_t sh = 8u * (SLOT & 3);
-    h = mcq_bfi(0x7Fu << sh, rb7, h);
+#ifdef MCQ_ABLATE_HOLES /* diagnostic timing build (wrong results): its scans do not move the sentinel */
+    h = mcq_bfi(0x7Fu << sh, rp << sh, h);
+    return;
+#endif
+    h = h + (rp << sh) - ((0x80u + 0x7Fu - (uint32_t)(SLOT & 3)) << sh);
 }
 
 // Draws arrive as rp = r | 0x80 (r < 64).  Returned: base position + 128 (the caller's table pointer is biased).
@@ -1039,7 +1067,7 @@ MCQ_HD uint32_t mcq_draw_opp(uint32_t rp, uint32_t (&H)[5]) {
         const uint32_t rb = mcq_splat_byte(rp);
 #pragma unroll
         for (int i = 0; i < (J + 3) / 4; i++) mcq_hole_reg(rb, H[i], k);
-        mcq_hole_put<J>(H[J / 4], rb);
+        mcq_hole_put<J>(H[J / 4], rp);
     } else {
         mcq_hole_put<0>(H[0], rp);
     }
@@ -1069,7 +1097,7 @@ MCQ_HD uint32_t mcq_draw_table(uint32_t rp, const uint32_t (&H)[5], uint32_t &hb
     if (K > 0) {
         const uint32_t rb = mcq_splat_byte(rp);
         mcq_hole_reg(rb, hb, p);
-        if (K < 4) mcq_hole_put<K>(hb, rb); /* the hole of a fifth table card is never looked at */
+        if (K < 4) mcq_hole_put<K>(hb, rp); /* the hole of a fifth table card is never looked at */
     } else {
         mcq_hole_put<0>(hb, rp);
     }
@@ -1134,6 +1162,7 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
     MCQ_OPP(0) MCQ_OPP(1) MCQ_OPP(2) MCQ_OPP(3) MCQ_OPP(4) MCQ_OPP(5) MCQ_OPP(6) MCQ_OPP(7) MCQ_OPP(8)
 #undef MCQ_OPP
     McqSumBoard b = qc.board_s;
+    if (NDEAL == 5) b.clear(); /* all five to come: the known table is empty, nothing to add the cards to */
     if (NOPP >= 0) {
         mcq_deal_table<(NOPP >= 0 ? (2 * NOPP + 3) / 4 : 0), Draws, NDEAL>(qc, dr, deck, H, L, b);
     } else switch (mcq_opaque_uniform((2u * qc.n_opp + 3u) / 4u)) { /* registers holding the opponents' holes: wave-uniform */
@@ -1162,7 +1191,24 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
             best = mcq_max3(best, rid, fid);                               \
         }                                                                  \
     }
-    MCQ_EVAL(0) MCQ_EVAL(1) MCQ_EVAL(2) MCQ_EVAL(3) MCQ_EVAL(4) MCQ_EVAL(5) MCQ_EVAL(6) MCQ_EVAL(7) MCQ_EVAL(8)
+#ifndef MCQ_ABLATE_EVAL
+    if constexpr (NOPP >= 1 && !Acc::kWays) {
+        /* Straight form: the hands' lookups in sweeps -- every hand's first reads, then every second-level read, then the
+         * maxima -- so that the order of the source already overlaps the hands' dependent read pairs.  (The compiler
+         * leaves the 6-max preflop block in the order of the source since its table starts empty, as the disassembly
+         * shows; hand by hand, that order waits for every read where it is sent: 3.67 ms against 3.53 in sweeps.) */
+        uint32_t s[MCQ_MAX_OPP], d[MCQ_MAX_OPP], fid[MCQ_MAX_OPP], rid[MCQ_MAX_OPP];
+#pragma unroll
+        for (int P = 0; P < NOPP; P++) mcq_sum_first(b, fs, opp[P], tabs, s[P], d[P], fid[P]);
+#pragma unroll
+        for (int P = 0; P < NOPP; P++) rid[P] = mcq_sum_rank(tabs, s[P], d[P]);
+#pragma unroll
+        for (int P = 0; P < NOPP; P++) best = mcq_max3(best, rid[P], fid[P]);
+    } else
+#endif
+    {
+        MCQ_EVAL(0) MCQ_EVAL(1) MCQ_EVAL(2) MCQ_EVAL(3) MCQ_EVAL(4) MCQ_EVAL(5) MCQ_EVAL(6) MCQ_EVAL(7) MCQ_EVAL(8)
+    }
 #undef MCQ_EVAL
     uint64_t won = hk >= best ? 1u : 0u; /* ties go to hero (hand_evaluator.py:23) */
     acc.types += won << (6u * (hk >> MCQ_ID_SHIFT));
