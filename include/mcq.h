@@ -356,6 +356,39 @@ MCQ_API int mcq_exact_batch_ext_seats(mcq_ctx *ctx, const mcq_query *q, const mc
 MCQ_API int mcq_exact_batch_hero_range(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
                                        mcq_result *rows /* [n][MCQ_HAND_ROWS] */, mcq_exact_prob *agg /* [n], may be NULL */);
 
+/* Exact equity PER RUNOUT, on the flop and the turn: which cards help and how much, from ONE enumeration per record.
+ * Accepted: whatever mcq_exact_batch_ext_ways accepts -- hero given as two cards, 0..9 known hands each given as two cards,
+ * optional ghost cards, at most one random opponent, ranged or not, both laws -- with 3 or 4 table cards; a batch may mix
+ * the shapes.  R = the cards the opponent and the table are dealt from, k = 5 - n_board cards to come.
+ * Every row is an mcq_result_ways weight row exactly as mcq_exact_batch_ext_ways writes it (runs = weight, passes = 0,
+ * sum(tie_ways) == r.tie), restricted to part of the table completions:
+ *   k = 1 (turn)  cards[i * 52 + c] = the row of the single completion "river = card id c"; pairs[i][*] all zero;
+ *   k = 2 (flop)  pairs[i * MCQ_HAND_ROWS + MCQ_HAND_INDEX(a, b)] = the row of the completion {a < b};
+ *                 cards[i * 52 + c] = the sum of the pair rows that contain c.
+ * The row of a card or pair that cannot come -- not in R, or impossible under MCQ_LAW_REFERENCE, where a table card is
+ * never the highest card left -- is zero.  The rows of a record add up, word for word, to its mcq_exact_batch_ext_ways
+ * weights row: the card rows for k = 1, the pair rows for k = 2 (the card rows of a flop add up to twice that row).
+ * Hero's hand type is fixed by the completion, so a completion row has at most one non-zero by_type entry, win + tie.
+ * Equity given that c comes next: (win + tie) / runs of cards[i * 52 + c] (pot share: the tie_ways formula of
+ * mcq_result_ways); P(c is the next card) = cards[i * 52 + c].runs / (k * total runs).  That holds under
+ * MCQ_LAW_REFERENCE too: for a fixed opponent hand a pair {a < b} is allowed in both dealing orders or in neither -- it is
+ * refused exactly when b is the highest card left (a then b: b would be the last card of the deck without a; b then a: b
+ * would be the last card of the deck; a itself is never the highest while b is there, and once b has gone a card above b
+ * remains) --, every allowed ORDERED draw is equally likely, and the number of allowed ordered draws, (d - 1) (d - 2) or d - 1
+ * with d cards left after the opponent's hand, does not depend on that hand.  So each order of an allowed
+ * pair carries half its weight, and the first card's weight is the sum over its pairs of one half: the card row over k.
+ * pairs may be NULL (the pair rows are then not copied back).  Refused with MCQ_EINVAL, nothing launched, cards and pairs
+ * untouched for the whole batch: whatever mcq_exact_batch_ext_ways refuses (a hero range, a ranged known hand, two random
+ * opponents, a range that cannot be dealt, a bad law, an invalid record), 0 table cards (C(50, 5) rows per record), 5 table
+ * cards (no card to come), n > MCQ_RUNOUT_MAX_BATCH.  Deterministic: every completion has one owner that stores its row
+ * once, the card rows are integer sums in a fixed order; a batch gives what the single calls give.  Device scratch:
+ * (52 + MCQ_HAND_ROWS) rows of 176 bytes = 243 KB per record. */
+#define MCQ_RUNOUT_CARD_ROWS 52u
+#define MCQ_RUNOUT_MAX_BATCH 1024u
+MCQ_API int mcq_exact_batch_ext_runouts(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                                        mcq_result_ways *cards /* [n][52] */,
+                                        mcq_result_ways *pairs /* [n][MCQ_HAND_ROWS], may be NULL */);
+
 /* Select the dealing law used by MCQ_MODE_PHILOX on this context (MCQ_LAW_*).  Extended queries
  * (mcq_eval_batch_ext) are dealt by the reference's law only: under MCQ_LAW_UNIFORM that call gives MCQ_EINVAL. */
 MCQ_API int mcq_set_dealing_law(mcq_ctx *ctx, int law);

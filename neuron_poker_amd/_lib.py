@@ -137,6 +137,8 @@ def load_library():
         L.mcq_exact_batch_ext.restype = C.c_int
         L.mcq_exact_batch_hero_range.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
         L.mcq_exact_batch_hero_range.restype = C.c_int
+        L.mcq_exact_batch_ext_runouts.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
+        L.mcq_exact_batch_ext_runouts.restype = C.c_int
         L.mcq_set_dealing_law.argtypes = [vp, C.c_int]
         L.mcq_set_dealing_law.restype = C.c_int
         L.mcq_set_kernel_timing.argtypes = [vp, C.c_int]
@@ -264,6 +266,8 @@ def pack_query_one(hole, board, n_players, runs):
 
 
 HAND_ROWS = 1326   # C(52, 2): MCQ_HAND_ROWS
+RUNOUT_CARD_ROWS = 52     # MCQ_RUNOUT_CARD_ROWS
+RUNOUT_MAX_BATCH = 1024   # MCQ_RUNOUT_MAX_BATCH
 
 
 def hand_index(a, b):
@@ -470,6 +474,27 @@ class Engine:
         if rc:
             _raise(rc)
         return prob, weights
+
+    def exact_ext_runouts(self, queries, ext, law="reference", want_pairs=True):
+        """Exact equity per runout on the flop and the turn (mcq_exact_batch_ext_runouts; what exact_ext_ways accepts, with 3
+        or 4 table cards).  -> (cards[n, 52], pairs[n, HAND_ROWS] or None) of RESULT_WAYS_DTYPE: the integer weights of
+        exact_ext_ways restricted to the table completions that hold the card (flop: the pair; the card rows are the sums
+        of their pair rows).  The rows of what cannot come are zero; a turn record's pair rows are all zero.  Equity given
+        that card c comes next: (win + tie) / runs of cards[i, c], or pot_share of that row."""
+        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
+        if code is None:
+            raise ValueError("law must be 'reference' or 'uniform'")
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        cards = np.zeros((len(q), RUNOUT_CARD_ROWS), RESULT_WAYS_DTYPE)
+        pairs = np.zeros((len(q), HAND_ROWS), RESULT_WAYS_DTYPE) if want_pairs else None
+        rc = self._lib.mcq_exact_batch_ext_runouts(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, cards.ctypes.data,
+                                                   pairs.ctypes.data if want_pairs else None)
+        if rc:
+            _raise(rc)
+        return cards, pairs
 
     def eval_batch_ext_ways(self, queries, ext, seed, first_query_id=0, mode=MODE_PHILOX):
         """eval_batch_ext with the ties split by the hands that share the pot (mcq_eval_batch_ext_ways).  -> array of

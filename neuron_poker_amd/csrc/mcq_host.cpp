@@ -20,6 +20,7 @@
 #include "mcq_device.hpp"
 #include "mcq_exact_ext.hpp"
 #include "mcq_exact_hero.hpp"
+#include "mcq_exact_runout.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt_blocks.hpp"
 #include "mcq_replay.hpp"
@@ -1499,6 +1500,80 @@ int mcq_exact_batch_hero_range(mcq_ctx *c, const mcq_query *q, const mcq_query_e
     if (agg) memcpy(agg, p.data(), n * sizeof(mcq_exact_prob));
     return MCQ_OK;
     ABI_GUARD_END("mcq_exact_batch_hero_range")
+}
+
+/* flop and turn records, at most one random opponent: the weights row of every table completion (mcq_exact_runout.hpp) */
+int mcq_exact_batch_ext_runouts(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                                mcq_result_ways *cards, mcq_result_ways *pairs) {
+    ABI_GUARD_BEGIN
+    const char *who = "mcq_exact_batch_ext_runouts";
+    if (n == 0) return MCQ_OK; /* (nothing to do: not even a context is needed) */
+    if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
+    if (!q || !ext || !cards) return mcq_fail(MCQ_EINVAL, who, "null buffer");
+    if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return mcq_fail(MCQ_EINVAL, who, "bad law");
+    if (n > MCQ_RUNOUT_MAX_BATCH) return mcq_fail(MCQ_EINVAL, who, "at most MCQ_RUNOUT_MAX_BATCH queries per call");
+    /* validation first, as mcq_exact_batch_ext_ways: nothing is launched for a batch with one record that is refused */
+    std::vector<McqExactExtQuery> xq(n);
+    char buf[200];
+    for (size_t i = 0; i < n; i++) {
+        const McqExtRec er = {reinterpret_cast<const uint32_t *>(&ext[i])};
+        const int why = mcq_exact_runout_query(mcq_query_words(q[i]), er, law, xq[i]);
+        if (why != MCQ_XX_OK) {
+            static const char *const reason[] = {
+                "", "invalid extended query (as mcq_eval_batch_ext: distinct card ids < 52, at most 9 known hands, used ranges not empty)",
+                "a hero range is not enumerated (rotate a known hand into the hero's seat)",
+                "a known hand given as a range is not enumerated", "at most two random opponents",
+                "two random opponents have no split-pot enumeration, so none per runout",
+                "runouts are enumerated on the flop and the turn only (3 or 4 table cards): preflop a record has C(50, 5) "
+                "completions",
+                "five table cards: no card to come"};
+            snprintf(buf, sizeof buf, "query %zu: %s", i, reason[why]);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+        uint8_t rid[64];
+        mcq_exact_ext_r_ids(xq[i], rid);
+        if (!mcq_exact_ext_dealable(xq[i], rid)) {
+            snprintf(buf, sizeof buf, "query %zu: the opponents' range cannot be dealt from the remaining cards", i);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+    }
+    MCQ_ENTER(c, who);
+    McqDeviceScope dev_(c->device);
+    HIP_TRY(dev_.err);
+    /* device rows: the card rows of all records, then their pair rows -- each part is handed back with one copy */
+    const size_t card_bytes = n * MCQ_XR_CARD_ROWS * sizeof(mcq_result_ways), pair_bytes = n * MCQ_XR_PAIR_ROWS * sizeof(mcq_result_ways);
+    const size_t back_bytes = card_bytes + (pairs ? pair_bytes : 0u);
+    HIP_TRY(c->d_res.reserve(card_bytes + pair_bytes));
+    c->res_clean = 0;
+    HIP_TRY(c->h_res.reserve(back_bytes));
+    HIP_TRY(hipMemsetAsync(c->d_res.p, 0, card_bytes + pair_bytes, c->stream));
+    mcq_result_ways *d_cards = static_cast<mcq_result_ways *>(c->d_res.p), *d_pairs = d_cards + n * MCQ_XR_CARD_ROWS;
+    /* jobs and extension records travel in pinned memory, the jobs grouped by kind */
+    const size_t job_bytes = (n * sizeof(McqExactExtJob) + 255u) & ~(size_t)255u;
+    HIP_TRY(c->h_misc.reserve(job_bytes + n * sizeof(mcq_query_ext)));
+    McqExactExtJob *jobs = static_cast<McqExactExtJob *>(c->h_misc.p);
+    const McqExactExtJob *d_jobs = static_cast<const McqExactExtJob *>(c->h_misc.dev);
+    memcpy(static_cast<uint8_t *>(c->h_misc.p) + job_bytes, ext, n * sizeof(mcq_query_ext));
+    const uint32_t *d_ext = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(c->h_misc.dev) + job_bytes);
+    size_t at = 0;
+    for (uint32_t kind = 0; kind < 2u; kind++) {
+        const size_t first = at;
+        uint32_t max_grid = 0;
+        for (size_t i = 0; i < n; i++) {
+            if (xq[i].b.n_opp != kind) continue;
+            const uint32_t g = mcq_exact_ext_plan(&q[i], (uint32_t)i, (uint32_t)i, kind, xq[i].b.L, 0u, exact_cu(c), &jobs[at++]);
+            max_grid = g > max_grid ? g : max_grid;
+        }
+        HIP_TRY(mcq_launch_exact_runouts(d_jobs + first, (uint32_t)(at - first), max_grid, kind, d_ext, law, d_cards, d_pairs,
+                                         c->d_luts, c->stream));
+    }
+    HIP_TRY(mcq_launch_exact_runout_cards(d_jobs, (uint32_t)n, d_cards, d_pairs, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, back_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(cards, c->h_res.p, card_bytes);
+    if (pairs) memcpy(pairs, static_cast<const uint8_t *>(c->h_res.p) + card_bytes, pair_bytes);
+    return MCQ_OK;
+    ABI_GUARD_END("mcq_exact_batch_ext_runouts")
 }
 
 }  // extern "C"

@@ -46,6 +46,15 @@ uint32_t mcq_exact_hero_plan(const mcq_query *q, uint32_t ext, uint32_t row, uin
                              McqExactExtJob *job);
 hipError_t mcq_launch_exact_hero(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
                                  mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
+/* per-runout enumeration (mcq_exact_runout.hpp): flop and turn records with at most one random opponent, jobs planned by
+ * mcq_exact_ext_plan (kind 0 or 1, job->row = the record's index); d_cards holds 52 and d_pairs MCQ_HAND_ROWS zeroed
+ * mcq_result_ways rows per record.  The second launch takes the jobs of both kinds and fills the card rows of the flop
+ * records from their pair rows. */
+hipError_t mcq_launch_exact_runouts(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, uint32_t kind,
+                                    const uint32_t *d_ext, int law, mcq_result_ways *d_cards, mcq_result_ways *d_pairs,
+                                    const McqTables *d_luts, hipStream_t s);
+hipError_t mcq_launch_exact_runout_cards(const McqExactExtJob *d_jobs, uint32_t n_jobs, mcq_result_ways *d_cards,
+                                         const mcq_result_ways *d_pairs, hipStream_t s);
 hipError_t mcq_launch_exact(const McqExactJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, bool two_opp, int law,
                             mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
 /* hands / winner / wtype / keys: device-visible memory (pinned host memory or HBM), 16-byte aligned and padded to whole

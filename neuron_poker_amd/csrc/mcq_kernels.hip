@@ -18,6 +18,7 @@
 #include "mcq_exact.hpp"
 #include "mcq_exact_ext.hpp"
 #include "mcq_exact_hero.hpp"
+#include "mcq_exact_runout.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt.hpp"
 #include "mcq_mt_ext.hpp"
@@ -2375,6 +2376,110 @@ __global__ __launch_bounds__(1024) void mcq_exact_hero_kernel(const McqExactExtJ
     }
 }
 
+// ---------------------------------------------------------------------------------------------- exact enumeration, per runout
+// See mcq_exact_runout.hpp; the shape of mcq_exact_ext_kernel<KIND, MCQ_ROW_WAYS>, kinds 0 and 1 (LDS: the same 97 KB
+// table image, pair list, range bits and per-wave rem_card / rem_pos), with flop and turn records only.  The sums of a
+// completion are not folded: its owner -- a lane (kind 0), a wave after its wave sums (kind 1) -- stores the completion's
+// 22 words once into the zeroed row of its slot among the record's MCQ_XR_ROWS rows.  One owner per completion and one
+// completion per slot: plain stores, no atomics.
+template <uint32_t KIND>
+__global__ __launch_bounds__(1024) void mcq_exact_runout_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
+                                                                int law, unsigned long long *__restrict__ card_rows,
+                                                                unsigned long long *__restrict__ pair_rows,
+                                                                const McqTables *__restrict__ g_tab) {
+    const McqExactExtJob job = jobs[blockIdx.y];
+    if (blockIdx.x >= job.grid) return;
+    constexpr uint32_t kWaves = 16u, kRem = KIND == 1u ? kWaves : 1u;
+    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ uint16_t pair_xy[MCQ_EXACT_PAIRS + 2];
+    __shared__ uint32_t xw[MCQ_EXT_WORDS];
+    __shared__ McqExactExtQuery xq;
+    __shared__ uint8_t r_id[64];
+    __shared__ uint8_t cb_tab[KIND != 0u ? MCQ_XX_MAX_RP : 1u];
+    __shared__ McqCard rem_card_all[kRem][64];
+    __shared__ uint32_t rem_pos_all[kRem][64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
+    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
+    if (tid < 64u) r_id[tid] = 0; /* (positions at or above L are never owners; their ids stay defined) */
+    for (uint32_t i = tid; i < MCQ_EXACT_PAIRS; i += blockDim.x) {
+        uint32_t x, y;
+        mcq_exact_pair_xy(i, x, y);
+        pair_xy[i] = (uint16_t)(x | (y << 8));
+    }
+    load_tables(tab, g_tab); /* ends with a barrier */
+    if (tid == 0) {
+        const McqExtRec er = {xw};
+        (void)mcq_exact_runout_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, law, xq); /* validated by the host */
+        mcq_exact_ext_r_ids(xq, r_id);
+    }
+    __syncthreads();
+    const McqExactExtQuery &e = xq;
+    if (KIND != 0u) {
+        mcq_exact_ext_cb_table(e, r_id, tid, blockDim.x, cb_tab);
+        __syncthreads();
+    }
+    const uint32_t n_boards = job.n_boards;
+    /* the record's rows: slots below MCQ_XR_CARD_ROWS among the card rows, the others among the pair rows */
+    unsigned long long *rec_cards = card_rows + (size_t)job.row * (MCQ_XR_CARD_ROWS * MCQ_XR_WORDS);
+    unsigned long long *rec_pairs = pair_rows + (size_t)job.row * (MCQ_XR_PAIR_ROWS * MCQ_XR_WORDS);
+
+    if constexpr (KIND == 0u) {
+        for (uint32_t idx = blockIdx.x * blockDim.x + tid; idx < n_boards; idx += job.grid * blockDim.x) {
+            McqExactAcc a = {0, 0, 0};
+            uint32_t type, n_eq;
+            const uint32_t slot = mcq_exact_runout_lone(e, idx, r_id, tab.sel8, g_tab->tf, tab.tops, tab.sd, a, type, n_eq);
+            if (a.tot == 0u || slot >= MCQ_XR_ROWS) continue; /* no weight: the row stays zero */
+            ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(mcq_exact_runout_row(rec_cards, rec_pairs, slot)); /* 176-byte rows: 16-byte aligned */
+#pragma unroll
+            for (uint32_t w = 0; w < MCQ_XR_WORDS; w += 2u)
+                dst[w / 2u] = make_ulonglong2(mcq_exact_runout_word(w, a.win, a.tie, a.tot, 0u, type, n_eq),
+                                              mcq_exact_runout_word(w + 1u, a.win, a.tie, a.tot, 0u, type, n_eq));
+        }
+    } else {
+        McqCard *rem_card = rem_card_all[wib];
+        uint32_t *rem_pos = rem_pos_all[wib];
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wib), n_waves = job.grid * kWaves;
+        for (uint32_t board = wave; board < n_boards; board += n_waves) {
+            uint32_t pos[5];
+            mcq_exact_unrank(board, e.b.L, e.b.k, pos);
+            McqExactBoard bd;
+            mcq_exact_board(e.b, pos, tab.sel8, g_tab->tf, tab.tops, tab.sd, bd);
+            uint32_t n_eq;
+            const uint32_t kb = mcq_exact_ext_known_best_eq(e, bd, g_tab->tf, tab.tops, tab.sd, n_eq);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* the previous completion's reads are done (same wave) */
+            if (lane < e.m) {
+                const uint32_t rp = mcq_exact_rem_pos(pos, lane);
+                rem_pos[lane] = rp;
+                rem_card[lane] = mcq_card(r_id[rp]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            McqExactAccWays acc = {0, 0, 0, 0};
+            mcq_exact_ext_pass_a(e, bd, kb, lane, 64u, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, nullptr,
+                                 nullptr, acc);
+            const uint32_t win = wave_sum(acc.win), tie = wave_sum(acc.tie), tot = wave_sum(acc.tot), tie_c = wave_sum(acc.tie_c);
+            const uint32_t slot = mcq_exact_runout_slot(e, r_id, pos);
+            /* lane l stores word l of the row; one random opponent leaves at most eight known hands: 13 + n_eq <= 21 */
+            if (tot != 0u && slot < MCQ_XR_ROWS && lane < MCQ_XR_WORDS)
+                mcq_exact_runout_row(rec_cards, rec_pairs, slot)[lane] =
+                    mcq_exact_runout_word(lane, win, tie, tot, tie_c, mcq_key_type(bd.hero_key), n_eq);
+        }
+    }
+}
+
+// k = 2: the record's 52 card rows from its pair rows, thread (card, word); a turn record's card rows are the
+// completion rows themselves and stay as they are.
+__global__ __launch_bounds__(256) void mcq_exact_runout_cards_kernel(const McqExactExtJob *__restrict__ jobs,
+                                                                     unsigned long long *__restrict__ card_rows,
+                                                                     const unsigned long long *__restrict__ pair_rows) {
+    const McqExactExtJob job = jobs[blockIdx.y];
+    const McqQueryWords q = {job.rec[0], job.rec[1], job.rec[2], job.rec[3]};
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q.n_board() != 3u || t >= MCQ_XR_CARD_ROWS * MCQ_XR_WORDS) return;
+    card_rows[(size_t)job.row * (MCQ_XR_CARD_ROWS * MCQ_XR_WORDS) + t] = mcq_exact_runout_card_word(
+        pair_rows + (size_t)job.row * (MCQ_XR_PAIR_ROWS * MCQ_XR_WORDS), t / MCQ_XR_WORDS, t % MCQ_XR_WORDS);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- launchers
@@ -2692,6 +2797,28 @@ hipError_t mcq_launch_exact_hero(const McqExactExtJob *d_jobs, uint32_t n_jobs, 
     if (n_jobs > 65535u || max_grid == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mcq_exact_hero_kernel, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law,
                        reinterpret_cast<unsigned long long *>(d_rows), d_luts);
+    return hipGetLastError();
+}
+
+hipError_t mcq_launch_exact_runouts(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, uint32_t kind,
+                                    const uint32_t *d_ext, int law, mcq_result_ways *d_cards, mcq_result_ways *d_pairs,
+                                    const McqTables *d_luts, hipStream_t s) {
+    if (n_jobs == 0) return hipSuccess;
+    if (n_jobs > 65535u || max_grid == 0 || kind > 1u) return hipErrorInvalidValue;
+    unsigned long long *cards = reinterpret_cast<unsigned long long *>(d_cards), *pairs = reinterpret_cast<unsigned long long *>(d_pairs);
+    if (kind == 0u)
+        hipLaunchKernelGGL(mcq_exact_runout_kernel<0u>, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, cards, pairs, d_luts);
+    else
+        hipLaunchKernelGGL(mcq_exact_runout_kernel<1u>, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, cards, pairs, d_luts);
+    return hipGetLastError();
+}
+
+hipError_t mcq_launch_exact_runout_cards(const McqExactExtJob *d_jobs, uint32_t n_jobs, mcq_result_ways *d_cards,
+                                         const mcq_result_ways *d_pairs, hipStream_t s) {
+    if (n_jobs == 0) return hipSuccess;
+    if (n_jobs > 65535u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mcq_exact_runout_cards_kernel, dim3((MCQ_XR_CARD_ROWS * MCQ_XR_WORDS + 255u) / 256u, n_jobs), dim3(256), 0, s,
+                       d_jobs, reinterpret_cast<unsigned long long *>(d_cards), reinterpret_cast<const unsigned long long *>(d_pairs));
     return hipGetLastError();
 }
 

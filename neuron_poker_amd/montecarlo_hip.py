@@ -34,7 +34,7 @@ import numpy as np
 from . import _lib
 from .cards import TYPES, card_id, card_str
 
-__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "MonteCarlo", "seed",
+__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_runout_equities", "MonteCarlo", "seed",
            "configure"]
 
 _state = {"couple_numpy": False,
@@ -539,3 +539,55 @@ def get_range_equity_exact(hero_range, table_cards, opponent_range=1, dealing="r
         num += w * float(e)
         den += w
     return num / den, hands
+
+
+def get_runout_equities(player_cards, table_cards, players, dealing="reference", engine=None, *, known_hands=(),
+                        ghost_cards=None, opponent_range=None, ties="credited", pairs=False):
+    """Exact equity per RUNOUT on the flop or the turn: which cards help and how much, from one enumeration on the GPU
+    (mcq_exact_batch_ext_runouts).
+
+    The arguments are get_equity_exact's: known_hands (further hands of two cards), ghost_cards and opponent_range (None:
+    every class) follow run_montecarlo's conventions, `players` counts every hand, and at most ONE of them may be a random
+    opponent.  -> (equity, by_card): `equity` is what get_equity_exact returns for the same arguments, and by_card maps the
+    card string of every card that can come next to (equity given that it comes next, probability that it comes next).
+    pairs=True adds a third value that maps (card, card) -- lower card id first -- to (equity, probability) of that turn
+    and river (empty on the turn, where by_card says it all).  ties="credited": (win + tie) / runs as the reference
+    credits a tie; ties="split": hero's exact pot share.  Under dealing='reference' a card that would be the highest card
+    left never comes (montecarlo_python.py:188) and is not listed.  Preflop, the river, two random opponents and ranged
+    hands raise ValueError."""
+    if ties not in ("credited", "split"):
+        raise ValueError("ties must be 'credited' or 'split'")
+    if opponent_range is None:
+        opponent_range = 1
+    if ghost_cards is None:
+        ghost_cards = ''
+    known_hands = [list(h) for h in known_hands]
+    for h in known_hands:
+        if len(h) != 2:
+            raise ValueError("a known hand is two cards here (ranged known hands are not enumerated)")
+    opp_bits = _opponent_range_bits(opponent_range)
+    q = _query(list(player_cards), list(table_cards), players, 1)
+    k = 5 - int(q["n_board"][0])
+    ext = _ext_record(list(player_cards), False, known_hands, ghost_cards, opponent_range, opp_bits)
+    eng = engine or _lib.default_engine()
+    card_rows, pair_rows = eng.exact_ext_runouts(q, ext, dealing, want_pairs=bool(pairs))
+    card_rows = card_rows[0].view(np.uint64).reshape(52, 22)
+
+    def value(rows):
+        """Equity of every weight row, exactly: the reference's credit or the pot share."""
+        if ties == "split":
+            return [float(v) for v in _lib.pot_share(rows, exact=True)]
+        return [(int(r[2]) + int(r[3])) / max(int(r[0]), 1) for r in rows]
+
+    total = card_rows.sum(axis=0) // np.uint64(k)       # the card rows of a flop hold every completion twice
+    runs = int(total[0])
+    equity = value(total.reshape(1, 22))[0]
+    live = np.flatnonzero(card_rows[:, 0])
+    by_card = {card_str(int(c)): (e, int(card_rows[c, 0]) / (k * runs)) for c, e in zip(live, value(card_rows[live]))}
+    if not pairs:
+        return equity, by_card
+    pair_rows = pair_rows[0].view(np.uint64).reshape(_lib.HAND_ROWS, 22)
+    live = np.flatnonzero(pair_rows[:, 0])
+    by_pair = {(card_str(_ROW_HANDS[i][0]), card_str(_ROW_HANDS[i][1])): (e, int(pair_rows[i, 0]) / runs)
+               for i, e in zip(live, value(pair_rows[live]))}
+    return equity, by_card, by_pair

@@ -1,0 +1,188 @@
+"""The per-runout exact enumeration's lane code (csrc/mcq_exact_runout.hpp) on the host, no GPU: every completion's row
+against an independent literal walk of the reference, the probability of the next card against that walk's ORDERED table
+draws, the rows' sums against the host build of the existing split-pot enumeration, and the identities between card rows,
+pair rows and hand types.  Both laws."""
+import os
+import subprocess
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+from neuron_poker_amd import _lib
+from tests import hostsim_ext_ways as WS
+from tests import hostsim_runouts as HS
+from tests import runout_literal as RL
+
+LAWS = [0, 1]   # MCQ_LAW_REFERENCE, MCQ_LAW_UNIFORM
+HERE = os.path.dirname(os.path.abspath(__file__))
+_rows, _lit = {}, {}
+
+
+def rows_of(name, law):
+    """The host build's (cards, pairs) of a case, computed once and left unchanged."""
+    key = (name, law)
+    if key not in _rows:
+        c, p = HS.runouts(*RL.records(RL.CASES[name]), law)
+        c.setflags(write=False)
+        p.setflags(write=False)
+        _rows[key] = (c, p)
+    return _rows[key]
+
+
+def literal_of(name, law):
+    key = (name, law)
+    if key not in _lit:
+        _lit[key] = RL.literal(RL.CASES[name], bool(law))
+    return _lit[key]
+
+
+def k_of(name):
+    return 5 - len(RL.CASES[name][1])
+
+
+def completion_rows(name, law):
+    """The rows that hold ONE completion each: the card rows of a turn, the pair rows of a flop."""
+    cards, pairs = rows_of(name, law)
+    return cards if k_of(name) == 1 else pairs
+
+
+@pytest.mark.parametrize("law", LAWS)
+@pytest.mark.parametrize("name", RL.LITERAL_CASES)
+def test_every_row_is_the_literal_walk(name, law):
+    cards, pairs = rows_of(name, law)
+    per, _ = literal_of(name, law)
+    k = k_of(name)
+    total = int(completion_rows(name, law)[:, 0].sum())
+    assert total > 0 and sum(o.p for o in per.values()) == 1
+    if k == 1:
+        for c in range(52):
+            assert RL.row_fractions(cards[c], total) == RL.outcome_fractions(per.get((c,))), (name, law, c)
+        return
+    seen = 0
+    for b in range(1, 52):
+        for a in range(b):
+            o = per.get((a, b))
+            seen += o is not None
+            assert RL.row_fractions(pairs[_lib.hand_index(a, b)], total) == RL.outcome_fractions(o), (name, law, a, b)
+    assert seen == len(per)
+    for c in range(52):     # a card row: the literal outcomes of the completions that hold the card
+        want = [RL.outcome_fractions(o) for t, o in sorted(per.items()) if c in t]
+        got = RL.row_fractions(cards[c], total)
+        assert got[:3] == tuple(sum((w[i] for w in want), Fraction(0)) for i in range(3)), (name, law, c)
+        for j in (3, 4):
+            assert got[j] == [sum((w[j][t] for w in want), Fraction(0)) for t in range(9)], (name, law, c)
+
+
+@pytest.mark.parametrize("law", LAWS)
+@pytest.mark.parametrize("name", RL.LITERAL_CASES)
+def test_probability_of_the_next_card_is_the_ordered_walk(name, law):
+    cards, _ = rows_of(name, law)
+    _, first = literal_of(name, law)
+    k = k_of(name)
+    total = int(completion_rows(name, law)[:, 0].sum())
+    assert sum(first.values()) == 1
+    for c in range(52):
+        assert Fraction(int(cards[c, 0]), k * total) == first.get(c, Fraction(0)), (name, law, c)
+
+
+@pytest.mark.parametrize("law", LAWS)
+@pytest.mark.parametrize("name", RL.HOST_CASES)
+def test_sums_and_identities(name, law):
+    cards, pairs = rows_of(name, law)
+    k = k_of(name)
+    q, x = RL.records(RL.CASES[name])
+    whole = WS.exact(q, x, law)                       # the existing enumeration, folded into one row
+    one = completion_rows(name, law)
+    assert np.array_equal(one.sum(axis=0), whole), (name, law)
+    assert int(whole[1]) == 0 and int(whole[13:].sum()) == int(whole[3])
+    if k == 1:
+        assert not pairs.any()
+    else:
+        want = np.zeros_like(cards)
+        for b in range(1, 52):
+            for a in range(b):
+                r = pairs[_lib.hand_index(a, b)]
+                want[a] += r
+                want[b] += r
+        assert np.array_equal(cards, want), (name, law)
+        assert np.array_equal(cards.sum(axis=0), 2 * whole)
+    deck = RL.deck(RL.CASES[name])
+    live = one[:, 0] != 0
+    assert (one[~live] == 0).all()
+    for r in one[live]:        # hero's hand type is fixed per completion
+        by_type = r[4:13]
+        assert int(r[1]) == 0 and int((by_type != 0).sum()) == (1 if int(r[2] + r[3]) else 0), (name, law, r)
+        assert int(by_type.sum()) == int(r[2] + r[3]) and int(r[13:].sum()) == int(r[3])
+        assert int(r[2] + r[3]) <= int(r[0])
+    # only cards of R come
+    for c in range(52):
+        if c not in deck:
+            assert not cards[c].any(), (name, law, c)
+    if name == "flop_any":
+        assert len(deck) == 47 and int(live.sum()) == (1081 if law else 1081 - 46)   # the reference never deals R's top card
+    if name == "flop_allin":
+        assert int(one[:, 14].sum()) > 0     # a straight on the table side: ties shared three ways
+
+
+@pytest.mark.parametrize("name", RL.HOST_CASES)
+def test_reference_law_differs_where_it_must(name):
+    top = max(RL.deck(RL.CASES[name]))
+    ref_c, ref_p = rows_of(name, 0)
+    uni_c, uni_p = rows_of(name, 1)
+    assert not ref_c[top].any() and uni_c[top].any()      # a table card is never the highest card left
+    if k_of(name) == 2:
+        for a in range(top):
+            assert not ref_p[_lib.hand_index(a, top)].any()
+    # some other row differs as well, as a share of its record's total: the completions' chances, the opponent's index bias
+    k = k_of(name)
+    t_ref, t_uni = int(ref_c[:, 0].sum()) // k, int(uni_c[:, 0].sum()) // k
+    others = [c for c in range(52) if c != top]
+    assert any(RL.row_fractions(ref_c[c], t_ref) != RL.row_fractions(uni_c[c], t_uni) for c in others)
+    if name == "turn_known_ghost":
+        assert top == 50                                  # AS is a ghost card: AH is the highest card left
+
+
+def _refused(q, x, law=0):
+    with pytest.raises(ValueError) as e:
+        HS.runouts(q, x, law)     # (checks that the outputs were left untouched)
+    return str(e.value)
+
+
+def test_refusals():
+    hero, table, n_players, known, ghost, opp = RL.parts(RL.CASES["turn_known_ghost"])
+    q, x = RL.records(RL.CASES["turn_known_ghost"])
+    assert _refused(q, x, law=2) == "bad law"
+    assert _refused(_lib.pack_query_one(hero, [], n_players, 1), x) == "preflop"
+    assert _refused(_lib.pack_query_one(hero, table + [RL.C("2D")], n_players, 1), x) == "river"
+    assert _refused(_lib.pack_query_one(hero, table, n_players + 1, 1), x) == "two random opponents"
+    assert _refused(_lib.pack_query_one(hero, table, n_players + 2, 1), x) == "too many opponents"
+    xh = _lib.pack_query_ext(1, ghost=ghost, known=known, opp_range=opp, hero_range=_lib.range_bits(["AA"]))
+    assert _refused(q, xh) == "hero range"
+    xk = _lib.pack_query_ext(1, ghost=ghost, known=[_lib.range_bits(["AA", "KK"])], opp_range=opp)
+    assert _refused(q, xk) == "ranged known hand"
+    qd = q.copy()
+    qd["board"][0, 1] = qd["board"][0, 0]
+    assert _refused(qd, x) == "invalid"
+    # the opponent holds AA only and three aces are gone
+    qa = _lib.pack_query_one([RL.C("AD"), RL.C("AC")], [RL.C("AH"), RL.C("7H"), RL.C("2S")], 2, 1)
+    for law in LAWS:
+        assert _refused(qa, _lib.pack_query_ext(1, opp_range=_lib.range_bits(["AA"])), law) == "range cannot be dealt"
+
+
+def test_stand_alone_program_under_the_host_sanitizers(tmp_path):
+    """hs_main.cpp -- cases (b) and (c), both laws -- built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a
+    program of its own."""
+    exe = str(tmp_path / "hs_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           os.path.join(HERE, "hostsim_runouts", "hs_main.cpp"), "-o", exe])
+    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert res.returncode == 0, res.stdout
+    lines = res.stdout.strip().splitlines()
+    assert len(lines) == 4 and all(" rc 0," in ln for ln in lines), res.stdout
+    # the program's sums are the host build's
+    for ln, (name, law) in zip(lines, [("turn_known_ghost", 0), ("turn_known_ghost", 1), ("flop_allin", 0), ("flop_allin", 1)]):
+        cards, pairs = rows_of(name, law)
+        assert "card rows hold %d, pair rows %d in %d rows" % (int(cards[:, 0].sum()), int(pairs[:, 0].sum()),
+                                                              int((pairs[:, 0] != 0).sum())) in ln, (ln, name, law)
