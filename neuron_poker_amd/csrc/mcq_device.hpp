@@ -1058,18 +1058,50 @@ MCQ_HD void mcq_hole_put(uint32_t &h, uint32_t rp) {
     h = h + (rp << sh) - ((0x80u + 0x7Fu - (uint32_t)(SLOT & 3)) << sh);
 }
 
+// A hole that is ALONE in its register is one comparison, not a scan.  The first draw into a register leaves itself
+// there as it arrived (h = rp0 = t0 | 0x80: a copy, no instruction); the second draw finds f = [t0 <= r], k += f, and
+// writes the register whole, as a fresh one looks after the insert of rp0 at slot 0, the scan and the insert of rp at
+// slot 1: bytes 3 and 2 the sentinel moved down once, byte 1 = r, byte 0 = t0 + f - 1.  Both draws carry the same
+// | 0x80, so they compare as they arrive, and their two biases and the -1 fold into the literal: v_cmp_le_u32,
+// v_addc_co_u32 (k), v_lshl_add_u32, v_addc_co_u32 (h) -- four instructions for the eight of the scan and the two
+// inserts, and the VCC of a vector compare is read at once.
+MCQ_HD void mcq_hole_pair(uint32_t rp, uint32_t &h, uint32_t &k) {
+    const uint32_t rp0 = h;
+#ifdef MCQ_ABLATE_HOLES /* diagnostic timing build: wrong results */
+    k += (rp ^ rp0) & 1u;
+    h = (rp << 8) + rp0;
+    return;
+#endif
+    const uint32_t f = rp0 <= rp ? 1u : 0u;
+    k = k + f;
+    const uint32_t t = mcq_opaque((rp << 8) + rp0);
+    uint32_t c = MCQ_HOLE_SENTINEL - 0x01010101u - 0x7E7Eu - 0x8080u - 1u; /* 0x7E7D7F7F */
+#if defined(__HIP_DEVICE_COMPILE__)
+    /* t and the literal pinned in registers, the flag as a carry: left to itself the compiler selects between the literal
+     * and the literal + 1 and adds (five instructions, two registers for the pair of constants).  Not volatile: the
+     * literal's register is set outside the loop where the compiler finds room. */
+    asm("" : "+v"(c));
+    unsigned carry_out; /* never set (the sum stays below 2^31) and never read: __builtin_addc is here for its carry IN */
+    h = __builtin_addc(t, c, f, &carry_out);
+#else
+    h = t + c + f;
+#endif
+}
+
 // Draws arrive as rp = r | 0x80 (r < 64).  Returned: base position + 128 (the caller's table pointer is biased).
-// opponent draw number J (0-based; J holes precede it, all in H[0 .. (J+3)/4))
+// opponent draw number J (0-based; J holes precede it, all in H[0 .. (J+3)/4)).  The first draw into a register (J = 0,
+// 4, 8: the first card of a pair) scans the full registers before it and leaves itself in its own, where the pair's
+// second card -- the only draw that meets a register holding one hole -- finds it (mcq_hole_pair).
 template <int J>
 MCQ_HD uint32_t mcq_draw_opp(uint32_t rp, uint32_t (&H)[5]) {
     uint32_t k = rp;
-    if (J > 0) {
+    if (J % 4 == 1) mcq_hole_pair(rp, H[J / 4], k);
+    if (J % 4 == 0) H[J / 4] = rp;
+    if (J >= 2) {
         const uint32_t rb = mcq_splat_byte(rp);
 #pragma unroll
-        for (int i = 0; i < (J + 3) / 4; i++) mcq_hole_reg(rb, H[i], k);
-        mcq_hole_put<J>(H[J / 4], rp);
-    } else {
-        mcq_hole_put<0>(H[0], rp);
+        for (int i = 0; i < (J % 4 < 2 ? J / 4 : J / 4 + 1); i++) mcq_hole_reg(rb, H[i], k);
+        if (J % 4 >= 2) mcq_hole_put<J>(H[J / 4], rp);
     }
     return mcq_opaque(k); /* materialise k so that the table address is one shift-add */
 }
@@ -1091,15 +1123,18 @@ MCQ_HD void mcq_hole_count(uint32_t rb, uint32_t h, uint32_t &k) {
 // against p (3 instructions per register instead of 5) and never moved again.
 // NREGS is a template parameter: with a run-time bound the compiler scans all five registers and discards the
 // unused ones with selects (7 instructions per register instead of 0).
+// The first table draw leaves itself in hb as it arrived; the second one meets it alone there (mcq_hole_pair).
 template <int K, int NREGS>
 MCQ_HD uint32_t mcq_draw_table(uint32_t rp, const uint32_t (&H)[5], uint32_t &hb) {
     uint32_t p = rp; /* r | 0x80 */
-    if (K > 0) {
+    if (K == 0) {
+        hb = rp;
+    } else if (K == 1) {
+        mcq_hole_pair(rp, hb, p);
+    } else {
         const uint32_t rb = mcq_splat_byte(rp);
         mcq_hole_reg(rb, hb, p);
         if (K < 4) mcq_hole_put<K>(hb, rp); /* the hole of a fifth table card is never looked at */
-    } else {
-        mcq_hole_put<0>(hb, rp);
     }
     uint32_t k = p; /* position among the cards the opponents left, still | 0x80 */
     if (NREGS > 0) {
