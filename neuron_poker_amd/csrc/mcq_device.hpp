@@ -1167,6 +1167,15 @@ MCQ_HD void mcq_deal_table(const McqQueryCtx &qc, Draws &dr, const Deck &deck, c
     if (n_deal > 0u) b.add(pend);
 }
 
+// The late join of an opponent pair (mcq_iteration_sum): where the second card's suit masks may be used from.  Device: an
+// empty volatile asm on the two registers; a host build has no scheduler to hold.
+MCQ_HD void mcq_join_hold(McqCard &c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(c.los), "+v"(c.his));
+#else
+    (void)c;
+#endif
+}
 // One Monte-Carlo iteration of one lane.  The opponents' hole cards stay in registers (statically indexed:
 // everything below is unrolled over the opponent number) until the table is complete: the reference deals
 // ALL opponents before any table card (montecarlo_python.py:215-217).
@@ -1185,13 +1194,34 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
     uint32_t L = qc.L0;
     McqSumHole opp[MCQ_MAX_OPP];
     const uint32_t n_opp_d = NOPP >= 0 ? (uint32_t)NOPP : mcq_opaque_uniform(qc.n_opp);
+    /* Straight forms: a pair joins its hand one pair late, as a table card joins the table one draw late (mcq_deal_table).
+     * opp[P].set -- one add of the rank weights, two v_or of the suit masks -- is the first use of the pair's four LDS
+     * reads, and where it follows them the wave waits there with lgkmcnt(0).  Held back behind the NEXT pair's reads (the
+     * last pair's behind the table's draws) the wait becomes lgkmcnt(4) and the next pair's arithmetic covers it.  The
+     * iteration is one basic block here and the compiler's scheduler ignores the order of the source for plain
+     * arithmetic, so mcq_join_hold ties the second card's masks to the place in the source: an empty volatile asm, which
+     * keeps its order among the volatile asms of the draws (mcq_opaque) before and behind it.  The general form keeps
+     * the old order: its wave-uniform branches already separate the blocks -- and with it every caller of the general
+     * form: the one-launch kernel (mcq_eval_direct_kernel, which has no straight dispatch), parity mode with split-pot
+     * rows and parity mode with six or more opponents (mcq_iterations_replay4). */
+    constexpr bool kLate = NOPP >= 1; /* every straight form, both accumulators, every draw policy: none needs a register more */
+    McqCard j1 = {0u, 0u, 0u, 0u}, j2 = {0u, 0u, 0u, 0u}; /* the pair that has not joined yet */
 #define MCQ_OPP(P)                                                                                             \
     if (P < n_opp_d) {                                                                                         \
         uint32_t r1, r2;                                                                                       \
         dr.template pair<P>(L, r1, r2); /* r1 in [0,L-1], r2 in [0,L-2], r1 != r2 (l.167-176), both | 0x80 */  \
         const McqCard c1 = deck.hole_card(mcq_draw_opp<2 * P>(r1, H));     /* deck.pop(r1) (l.178) */          \
         const McqCard c2 = deck.hole_card(mcq_draw_opp<2 * P + 1>(r2, H)); /* deck.pop(r2), shrunk list (l.179) */ \
-        opp[P].set(c1, c2);                                                                                    \
+        if constexpr (kLate) {                                                                                 \
+            if (P > 0) {                                                                                       \
+                mcq_join_hold(j2);                                                                             \
+                opp[P > 0 ? P - 1 : 0].set(j1, j2);                                                            \
+            }                                                                                                  \
+            j1 = c1;                                                                                           \
+            j2 = c2;                                                                                           \
+        } else {                                                                                               \
+            opp[P].set(c1, c2);                                                                                \
+        }                                                                                                      \
         L -= 2;                                                                                                \
     }
     MCQ_OPP(0) MCQ_OPP(1) MCQ_OPP(2) MCQ_OPP(3) MCQ_OPP(4) MCQ_OPP(5) MCQ_OPP(6) MCQ_OPP(7) MCQ_OPP(8)
@@ -1207,6 +1237,10 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
         case 3: mcq_deal_table<3, Draws>(qc, dr, deck, H, L, b); break;
         case 4: mcq_deal_table<4, Draws>(qc, dr, deck, H, L, b); break;
         default: mcq_deal_table<5, Draws>(qc, dr, deck, H, L, b); break;
+    }
+    if constexpr (kLate) { /* the last pair, behind the table's draws */
+        mcq_join_hold(j2);
+        opp[NOPP >= 1 ? NOPP - 1 : 0].set(j1, j2);
     }
     McqFlushSel fs;
     fs.from_board(b);
