@@ -356,6 +356,30 @@ MCQ_API int mcq_exact_batch_ext_seats(mcq_ctx *ctx, const mcq_query *q, const mc
 MCQ_API int mcq_exact_batch_hero_range(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
                                        mcq_result *rows /* [n][MCQ_HAND_ROWS] */, mcq_exact_prob *agg /* [n], may be NULL */);
 
+/* Exact RANGE against RANGE BEFORE THE FLOP, heads-up: every hand of the hero's range from ONE enumeration of the
+ * C(|D|, 5) table completions per record.  An entry of its own because a record takes from tens of milliseconds (narrow
+ * ranges) to seconds (every hand against every hand), not the millisecond of mcq_exact_batch_hero_range.
+ * Accepted: n_board == 0, ext[i].hero_is_range == 1 with hero_range (q[i].hole is ignored), n_known == 0, n_players == 2 --
+ * one random opponent drawn from opp_range, restricted or not --, optional ghost cards, both laws.
+ * D = the 52 cards minus the ghost cards (52 or 50).  rows and agg are laid out and defined exactly as
+ * mcq_exact_batch_hero_range's: rows[i * MCQ_HAND_ROWS + MCQ_HAND_INDEX(a, b)] is bit for bit the weights row
+ * mcq_exact_batch_ext writes for the same record with the hero given as those two cards (runs = total weight, passes = 0),
+ * every other row is zero, and agg[i] (agg may be NULL) combines the allowed rows with w_h = 1 under MCQ_LAW_UNIFORM and
+ * 2 - [b is the highest card of D] under MCQ_LAW_REFERENCE, on the host in ascending row order.
+ * Cost: only the hands that a range allows are ranked and walked (hero's hands and the hands the opponent can hold), so a
+ * call scales with the ranges.  The completions are sent in slices, several kernel launches per call (262 144 completions
+ * each unless MCQ_HERO_PRE_SLICE says otherwise): no single launch holds the GPU for the whole call.
+ * Refused with MCQ_EINVAL, rows and agg untouched: a bad law, any table card (mcq_exact_batch_hero_range enumerates the
+ * flop, turn and river), whatever that entry refuses otherwise (what mcq_eval_batch_ext refuses, hero_is_range == 0,
+ * n_known != 0, n_players != 2, no allowed hero hand in D), more than MCQ_HERO_PREFLOP_MAX_BATCH records -- all before
+ * anything is launched -- and an allowed hero hand against which the opponent's range cannot be dealt (seen as a row
+ * without weight, before anything is copied to the caller).  MCQ_EBUSY as everywhere.
+ * Deterministic: integer sums per hero hand.  Each record costs MCQ_HAND_ROWS * sizeof(mcq_result) = 138 KB of rows. */
+#define MCQ_HERO_PREFLOP_MAX_BATCH 64u
+MCQ_API int mcq_exact_batch_hero_range_preflop(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                                               mcq_result *rows /* [n][MCQ_HAND_ROWS] */,
+                                               mcq_exact_prob *agg /* [n], may be NULL */);
+
 /* Exact equity PER RUNOUT, on the flop and the turn: which cards help and how much, from ONE enumeration per record.
  * Accepted: whatever mcq_exact_batch_ext_ways accepts -- hero given as two cards, 0..9 known hands each given as two cards,
  * optional ghost cards, at most one random opponent, ranged or not, both laws -- with 3 or 4 table cards; a batch may mix

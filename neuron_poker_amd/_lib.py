@@ -137,6 +137,8 @@ def load_library():
         L.mcq_exact_batch_ext.restype = C.c_int
         L.mcq_exact_batch_hero_range.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
         L.mcq_exact_batch_hero_range.restype = C.c_int
+        L.mcq_exact_batch_hero_range_preflop.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
+        L.mcq_exact_batch_hero_range_preflop.restype = C.c_int
         L.mcq_exact_batch_ext_runouts.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
         L.mcq_exact_batch_ext_runouts.restype = C.c_int
         L.mcq_set_dealing_law.argtypes = [vp, C.c_int]
@@ -266,6 +268,7 @@ def pack_query_one(hole, board, n_players, runs):
 
 
 HAND_ROWS = 1326   # C(52, 2): MCQ_HAND_ROWS
+HERO_PREFLOP_MAX_BATCH = 64   # MCQ_HERO_PREFLOP_MAX_BATCH
 RUNOUT_CARD_ROWS = 52     # MCQ_RUNOUT_CARD_ROWS
 RUNOUT_MAX_BATCH = 1024   # MCQ_RUNOUT_MAX_BATCH
 
@@ -452,6 +455,26 @@ class Engine:
         agg = np.zeros(len(q), EXACT_PROB_DTYPE)
         rc = self._lib.mcq_exact_batch_hero_range(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, rows.ctypes.data,
                                                   agg.ctypes.data)
+        if rc:
+            _raise(rc)
+        return rows, agg
+
+    def exact_hero_range_preflop(self, queries, ext, law="reference"):
+        """Exact range against range BEFORE THE FLOP, heads-up (mcq_exact_batch_hero_range_preflop): records without
+        table cards, hero_is_range = 1, no known hands, one random opponent drawn from opp_range; at most
+        HERO_PREFLOP_MAX_BATCH of them.  -> (rows, agg) laid out as exact_hero_range's.  A record takes from tens of
+        milliseconds (narrow ranges) to seconds (every hand against every hand)."""
+        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
+        if code is None:
+            raise ValueError("law must be 'reference' or 'uniform'")
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        rows = np.zeros((len(q), HAND_ROWS), RESULT_DTYPE)
+        agg = np.zeros(len(q), EXACT_PROB_DTYPE)
+        rc = self._lib.mcq_exact_batch_hero_range_preflop(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code,
+                                                          rows.ctypes.data, agg.ctypes.data)
         if rc:
             _raise(rc)
         return rows, agg

@@ -1,0 +1,199 @@
+// mcq_exact_hero_pre.hpp -- exact enumeration with the HERO given as a range BEFORE THE FLOP: every hero hand against one
+// random opponent (ranged or not) from ONE enumeration of the C(|D|, 5) table completions; lane code shared by
+// mcq_exact_hero_pre_kernel (mcq_kernels.hip) and the host build of the tests (tests/hostsim_hero_preflop).
+//
+// The mathematics is mcq_exact_hero.hpp's -- its opening comment is the specification: the opponent's weight is
+// mcq_exact_ext_w2 with the hero's hand as the hand that left the deck, under MCQ_LAW_REFERENCE a completion counts iff
+// above(h) + above(o) < u, and a hero hand's sums are win, tie, tot and by_type[9].  mcq_exact.hpp, mcq_exact_ext.hpp and
+// mcq_exact_hero.hpp are included and reused unchanged.  The code is generic in k = 0..5 new table cards (the C entry takes
+// k = 5 only), so that the tests can pin it against mcq_exact_hero.hpp on the flop, turn and river.
+//
+// What differs.  D = 52 cards minus table and ghost, |D| <= 52: up to C(52, 2) = 1326 hero hands, up to C(52, 5) =
+// 2 598 960 completions, each leaving C(|D| - k, 2) <= 1081 hands.  Nothing is indexed by the per-completion m-index:
+// every hand is a D-PAIR (D-positions pa < pb, index pb (pb - 1) / 2 + pa), fixed across the completions, and a
+// completion only marks the pairs that touch one of its table cards as dead (key 0 -- every hand's key is > 0 -- and
+// record 0, whose range bits give weight 0 under both laws).  Three ascending lists per query:
+//   ranked   the D-pairs that are ranked per completion = allowed + live, as D-pair indices;
+//   allowed  the hero hands whose class is in hero_range, as SLOTS of `ranked`;
+//   live     the D-pairs whose range bits (mcq_exact_ext_cbits) are not 0 -- the only hands the opponent can ever hold,
+//            whatever hero holds: mcq_exact_ext_w2 of range bits 0 is 0 --, as slots of `ranked`.
+// Keys and records are kept per slot; a hero hand walks `live` only and finds its own key at its own slot, so rank and walk
+// cost what the ranges leave, not 1326 x 1081.  A group of few hero hands shares each hand's walk among several threads
+// (mcq_exact_hero_pre_share).
+// Sums.  A hero hand's twelve sums stay 32-bit while one block owns at most MCQ_XP_MAX_OWNED completions (one completion
+// adds at most 2 x 1081 to tot); the host sends the completions in slices of at most that many per launch and the rows are
+// accumulated across launches with 64-bit integer atomics.
+#ifndef MCQ_EXACT_HERO_PRE_HPP
+#define MCQ_EXACT_HERO_PRE_HPP
+
+#include "mcq_exact_hero.hpp"
+
+#define MCQ_XP_MAX_D 52u        /* |D|: before the flop, no ghost cards */
+#define MCQ_XP_MAX_PAIRS 1326u  /* C(52, 2) D-pairs = hero hands = MCQ_XH_ROWS */
+#define MCQ_XP_MAX_CAND 1081u   /* C(47, 2) hands that a completion leaves alive */
+#define MCQ_XP_MAX_BOARDS 2598960u /* C(52, 5) */
+#define MCQ_XP_MAX_OWNED 1500000u  /* completions whose sums one thread may keep in 32 bits */
+#define MCQ_XP_DEFAULT_SLICE 262144u /* completions per launch: ten launches for C(52, 5) */
+
+static_assert(MCQ_XP_MAX_PAIRS == MCQ_XH_ROWS, "one row per D-pair of the full deck");
+static_assert(MCQ_XP_MAX_PAIRS > MCQ_XX_MAX_RP && MCQ_XP_MAX_D > MCQ_XX_MAX_L,
+              "mcq_exact_ext.hpp's sizes (50 cards, 1225 pairs) do not cover |D| = 52: this header sizes its own arrays");
+static_assert((MCQ_XP_MAX_D - 5u) * (MCQ_XP_MAX_D - 6u) / 2u == MCQ_XP_MAX_CAND, "hands left by a completion");
+static_assert((uint64_t)MCQ_XP_MAX_OWNED * 2u * MCQ_XP_MAX_CAND < (1ull << 32), "a hero hand's sums of one launch fit 32 bits");
+static_assert(MCQ_XP_DEFAULT_SLICE <= MCQ_XP_MAX_OWNED, "the default slice keeps that bound whatever the grid");
+static_assert(MCQ_XP_MAX_D - 1u < 64u, "D-positions fit the 6-bit fields of mcq_exact_ext_pack");
+/* mcq_exact_binom and mcq_exact_unrank say "n <= 50"; at L = 52, k = 5 their intermediates still fit 32 bits: the largest
+ * binomial met is C(51, 5) = 2 349 060, and it is multiplied by at most 51 before the exact division. */
+static_assert(2349060ull * 51ull < (1ull << 32), "mcq_exact_unrank at L = 52, k = 5");
+
+// The query of a record with ANY number of table cards (mcq_exact_hero_query refuses fewer than three); the other
+// refusals are its own, in its order.
+MCQ_HD int mcq_exact_hero_pre_query(const McqQueryWords &q, const McqExtRec &er, int law, McqExactHeroQuery &e) {
+    if (!mcq_query_ext_valid(q, er)) return MCQ_XH_INVALID;
+    if (!er.hero_is_range()) return MCQ_XH_NOT_RANGE;
+    if (er.n_known() != 0u) return MCQ_XH_KNOWN;
+    if (q.n_players() != 2u) return MCQ_XH_PLAYERS;
+    const uint64_t deck = mcq_ext_base_deck(q, er);
+    McqExactExtQuery &x = e.x;
+    x.n_known = 0u;
+    for (uint32_t h = 0; h < MCQ_MAX_KNOWN; h++) x.known[h] = 0u;
+    x.b.deck_lo = (uint32_t)deck;
+    x.b.deck_hi = (uint32_t)(deck >> 32);
+    x.b.L = mcq_popc(x.b.deck_lo) + mcq_popc(x.b.deck_hi);
+    x.b.k = 5u - q.n_board();
+    x.b.n_opp = 1u;
+    x.b.ref_law = law == MCQ_LAW_REFERENCE;
+    x.b.known.clear();
+    for (uint32_t i = 0; i < q.n_board(); i++) x.b.known.add(mcq_card(q.card(2u + i)));
+    x.b.hero.set(mcq_card(0u), mcq_card(1u)); /* (nobody's: every hero hand is a D-pair) */
+    x.m = x.b.L - x.b.k;
+    x.n_pairs = x.m * (x.m - 1u) / 2u;
+    x.n_rp = x.b.L * (x.b.L - 1u) / 2u;
+    x.ranged = !mcq_ext_opp_all(er);
+    for (uint32_t i = 0; i < 6; i++) {
+        x.bits[i] = er.w[er.opp_set() + i];
+        e.hero_bits[i] = er.w[er.hero_set() + i];
+    }
+    e.n_allowed = 0u; /* the host counts them: mcq_exact_hero_pre_lists */
+    return MCQ_XH_OK;
+}
+
+// is D-pair (qa < qb) on the lists?  bit 0: allowed, bit 1: live
+MCQ_HD uint32_t mcq_exact_hero_pre_on(const McqExactHeroQuery &e, const uint8_t *r_id, const uint8_t *cb_tab, uint32_t rp,
+                                      uint32_t qa, uint32_t qb) {
+    return (mcq_exact_hero_allowed(e, r_id, qa, qb) ? 1u : 0u) | (cb_tab[rp] != 0u ? 2u : 0u);
+}
+
+// The three lists, one D-pair after the other (the kernel makes the same lists with ballots); cb_tab from
+// mcq_exact_ext_cb_table, MCQ_XP_MAX_PAIRS entries each.  n[0..3) = allowed, live, ranked.
+MCQ_HD void mcq_exact_hero_pre_lists(const McqExactHeroQuery &e, const uint8_t *r_id, const uint8_t *cb_tab, uint16_t *allowed,
+                                     uint16_t *live, uint16_t *ranked, uint32_t n[3]) {
+    n[0] = n[1] = n[2] = 0u;
+    uint32_t rp = 0;
+    for (uint32_t qb = 1; qb < e.x.b.L; qb++)
+        for (uint32_t qa = 0; qa < qb; qa++, rp++) {
+            const uint32_t on = mcq_exact_hero_pre_on(e, r_id, cb_tab, rp, qa, qb);
+            if (on == 0u) continue;
+            if (on & 1u) allowed[n[0]++] = (uint16_t)n[2];
+            if (on & 2u) live[n[1]++] = (uint16_t)n[2];
+            ranked[n[2]++] = (uint16_t)rp;
+        }
+}
+
+// the D-positions of a completion's table cards as a mask
+MCQ_HD uint64_t mcq_exact_hero_pre_mask(const McqExactQuery &b, const uint32_t pos[5]) {
+    uint64_t m = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 5; i++)
+        if (i < b.k) m |= 1ull << pos[i];
+    return m;
+}
+
+// The completion that follows pos[0..k) (ascending D-positions) in the order of mcq_exact_unrank's index: a block unranks
+// the first completion of its share once and steps from there -- scalar work of a few instructions where unranking walks
+// down the deck with a division per step.  Unused entries (i >= k) stay 255.
+MCQ_HD void mcq_exact_hero_pre_next(uint32_t pos[5], uint32_t k) {
+    bool carry = true;
+#pragma unroll
+    for (uint32_t i = 0; i < 5; i++)
+        if (i < k && carry) {
+            if (i + 1u < k && pos[i] + 1u == pos[i + 1u < 5u ? i + 1u : 4u]) {
+                pos[i] = i; /* the lowest cards start over */
+            } else {
+                pos[i]++;
+                carry = false;
+            }
+        }
+}
+
+// Ranking pass, lane `lane` of `n_lanes`: key and packed record of the slots lane, lane + n_lanes, ... of `ranked`
+// (pair_xy[rp] = qa | qb << 8, d_card[p] = mcq_card(r_id[p]), taken = mcq_exact_hero_pre_mask).
+MCQ_HD void mcq_exact_hero_pre_rank(const McqExactHeroQuery &e, const McqExactBoard &bd, uint64_t taken, uint32_t lane,
+                                    uint32_t n_lanes, const uint16_t *ranked, uint32_t n_ranked, const uint16_t *pair_xy,
+                                    const McqCard *d_card, const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops,
+                                    const uint32_t *sd, uint32_t *keys, uint32_t *rec) {
+    for (uint32_t i = lane; i < n_ranked; i += n_lanes) {
+        const uint32_t rp = ranked[i], xy = pair_xy[rp], pa = xy & 0xFFu, pb = xy >> 8;
+        uint32_t key = 0u, r = 0u; /* dead: a table card took one of its cards */
+        if ((((taken >> pa) | (taken >> pb)) & 1ull) == 0ull) {
+            McqHole h;
+            h.set(d_card[pa], d_card[pb]);
+            key = mcq_eval_key(bd.b, bd.fs, h, tf, tops, sd);
+            r = mcq_exact_ext_pack(pa, pb, bd.top, e.x.b.k != 0u, cb_tab[rp]);
+        }
+        keys[i] = key;
+        rec[i] = r;
+    }
+}
+
+// A group of blocks owns n_g <= 1024 hero hands.  Where they leave threads idle, `share` threads walk for ONE hero hand,
+// thread `sub` of them the live hands sub, sub + share, ...: a narrow hero range would otherwise leave its walk to a
+// single wave, one step after the other.  Each thread keeps its own sums; they meet in the row's atomics.
+MCQ_HD uint32_t mcq_exact_hero_pre_share(uint32_t n_g) {
+    const uint32_t s = 1024u / (n_g ? n_g : 1u);
+    return s > 64u ? 64u : s < 1u ? 1u : s;
+}
+
+// The walk of ONE hero hand h = D-positions qa < qb at slot `own` (keys[own] != 0: the completion left it alive): the
+// live hands j0, j0 + step, ... as the opponent's.  Returns the hero hand's type.
+MCQ_HD uint32_t mcq_exact_hero_pre_walk_as(const bool ref, const McqExactBoard &bd, uint32_t qa, uint32_t qb, uint32_t own,
+                                           const uint16_t *live, uint32_t n_live, uint32_t j0, uint32_t step, const uint32_t *keys,
+                                           const uint32_t *rec, McqExactAcc &acc) {
+    const uint32_t kh = keys[own], ah = mcq_exact_ext_above(rec[own]);
+    for (uint32_t j = j0; j < n_live; j += step) {
+        const uint32_t s = live[j], r = rec[s], pa = r & 63u, pb = (r >> 6) & 63u;
+        const bool shared = pa == qa || pa == qb || pb == qa || pb == qb; /* (hero's own hand among them) */
+        const bool ok = !shared && (!ref || ah + mcq_exact_ext_above(r) < bd.u);
+        const uint32_t w = ok ? mcq_exact_ext_w2(ref, mcq_exact_ext_cb(r), pa, pb, qa, qb) : 0u; /* a dead hand: r == 0, w == 0 */
+        const uint32_t kj = keys[s];
+        acc.win += kj < kh ? w : 0u;
+        acc.tie += kj == kh ? w : 0u;
+        acc.tot += w;
+    }
+    return mcq_key_type(kh);
+}
+
+// ... with the law and the commonest stride (1: a group of more than 512 hands) as constants of four copies of the loop
+MCQ_HD uint32_t mcq_exact_hero_pre_walk(const McqExactHeroQuery &e, const McqExactBoard &bd, uint32_t qa, uint32_t qb, uint32_t own,
+                                        const uint16_t *live, uint32_t n_live, uint32_t j0, uint32_t step, const uint32_t *keys,
+                                        const uint32_t *rec, McqExactAcc &acc) {
+    if (e.x.b.ref_law)
+        return step == 1u ? mcq_exact_hero_pre_walk_as(true, bd, qa, qb, own, live, n_live, j0, 1u, keys, rec, acc)
+                          : mcq_exact_hero_pre_walk_as(true, bd, qa, qb, own, live, n_live, j0, step, keys, rec, acc);
+    return step == 1u ? mcq_exact_hero_pre_walk_as(false, bd, qa, qb, own, live, n_live, j0, 1u, keys, rec, acc)
+                      : mcq_exact_hero_pre_walk_as(false, bd, qa, qb, own, live, n_live, j0, step, keys, rec, acc);
+}
+
+// ---- host side
+// The completions go out in launches of `slice`; a launch's grid gives every group of blocks `per` blocks, each of which
+// owns a run of consecutive completions of this length (the last ones fewer) -- the plan is sound iff it is at most
+// MCQ_XP_MAX_OWNED.
+MCQ_HD uint32_t mcq_exact_hero_pre_owned(uint32_t slice, uint32_t per) { return (slice + per - 1u) / per; }
+
+// clamps a requested slice (0: the default) to what the 32-bit sums allow with a single block per group
+MCQ_HD uint32_t mcq_exact_hero_pre_slice(uint64_t want) {
+    if (want == 0u) return MCQ_XP_DEFAULT_SLICE;
+    return want > MCQ_XP_MAX_OWNED ? MCQ_XP_MAX_OWNED : (uint32_t)want;
+}
+
+#endif /* MCQ_EXACT_HERO_PRE_HPP */

@@ -20,6 +20,7 @@
 #include "mcq_device.hpp"
 #include "mcq_exact_ext.hpp"
 #include "mcq_exact_hero.hpp"
+#include "mcq_exact_hero_pre.hpp"
 #include "mcq_exact_runout.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt_blocks.hpp"
@@ -572,6 +573,10 @@ mcq_ctx *mcq_create(int device, int flags) {
     if (const char *e = getenv("MCQ_EXACT_CU")) { /* the CU count the exact plans size their grids by, capped (tests), see exact_cu */
         const long v = atol(e);
         if (v >= 1) c->exact_cu = (uint32_t)(v > 0x7fffffffL ? 0x7fffffffL : v);
+    }
+    if (const char *e = getenv("MCQ_HERO_PRE_SLICE")) { /* table completions per launch of the preflop hero-range enumeration (tests) */
+        const long long v = atoll(e);
+        if (v >= 1) c->hero_pre_slice = mcq_exact_hero_pre_slice((uint64_t)v);
     }
     if (const char *e = getenv("MCQ_REPLAY_DEVICE_BYTES")) { /* chunking of the parity mode's draw buffer (tests) */
         const long long v = atoll(e);
@@ -1500,6 +1505,91 @@ int mcq_exact_batch_hero_range(mcq_ctx *c, const mcq_query *q, const mcq_query_e
     if (agg) memcpy(agg, p.data(), n * sizeof(mcq_exact_prob));
     return MCQ_OK;
     ABI_GUARD_END("mcq_exact_batch_hero_range")
+}
+
+/* ... before the flop: the C(|D|, 5) completions go out in slices, several launches per call (mcq_exact_hero_pre.hpp) */
+int mcq_exact_batch_hero_range_preflop(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                                       mcq_result *rows, mcq_exact_prob *agg) {
+    ABI_GUARD_BEGIN
+    const char *who = "mcq_exact_batch_hero_range_preflop";
+    if (n == 0) return MCQ_OK; /* (nothing to do: not even a context is needed) */
+    if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
+    if (!q || !ext || !rows) return mcq_fail(MCQ_EINVAL, who, "null buffer");
+    if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return mcq_fail(MCQ_EINVAL, who, "bad law");
+    if (n > MCQ_HERO_PREFLOP_MAX_BATCH) return mcq_fail(MCQ_EINVAL, who, "at most MCQ_HERO_PREFLOP_MAX_BATCH queries per call");
+    /* validation first: nothing is launched for a batch with one query that cannot be enumerated */
+    std::vector<McqExactHeroQuery> xq(n);
+    std::vector<uint8_t> rid(n * 64u);
+    char buf[200];
+    for (size_t i = 0; i < n; i++) {
+        const McqExtRec er = {reinterpret_cast<const uint32_t *>(&ext[i])};
+        int why = mcq_exact_hero_pre_query(mcq_query_words(q[i]), er, law, xq[i]);
+        if (why == MCQ_XH_OK && q[i].n_board != 0) {
+            snprintf(buf, sizeof buf, "query %zu: table cards: this entry enumerates before the flop only (n_board must be 0); "
+                     "mcq_exact_batch_hero_range takes the flop, turn and river", i);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+        if (why == MCQ_XH_OK) {
+            mcq_exact_ext_r_ids(xq[i].x, &rid[64u * i]);
+            xq[i].n_allowed = mcq_exact_hero_count(xq[i], &rid[64u * i], nullptr);
+            if (xq[i].n_allowed == 0u) why = MCQ_XH_EMPTY;
+        }
+        if (why != MCQ_XH_OK) {
+            static const char *const reason[] = {
+                "", "invalid extended query (as mcq_eval_batch_ext: distinct card ids < 52, at most 9 known hands, used ranges not empty)",
+                "the hero is given as two cards (hero_is_range == 0): mcq_exact_batch_ext enumerates that",
+                "known hands beside a hero range are not enumerated (n_known must be 0)",
+                "a hero range is enumerated heads-up only (n_players must be 2)", "",
+                "no hand of the hero's range can be made of the cards left"};
+            snprintf(buf, sizeof buf, "query %zu: %s", i, reason[why]);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+    }
+    MCQ_ENTER(c, who);
+    McqDeviceScope dev_(c->device);
+    HIP_TRY(dev_.err);
+    const size_t q_bytes = (size_t)MCQ_XH_ROWS * sizeof(mcq_result);
+    HIP_TRY(c->d_res.reserve(n * q_bytes));
+    c->res_clean = 0;
+    HIP_TRY(c->h_res.reserve(n * q_bytes));
+    /* jobs and extension records travel in pinned memory */
+    const size_t job_bytes = (n * sizeof(McqExactExtJob) + 255u) & ~(size_t)255u;
+    HIP_TRY(c->h_misc.reserve(job_bytes + n * sizeof(mcq_query_ext)));
+    McqExactExtJob *jobs = static_cast<McqExactExtJob *>(c->h_misc.p);
+    const McqExactExtJob *d_jobs = static_cast<const McqExactExtJob *>(c->h_misc.dev);
+    memcpy(static_cast<uint8_t *>(c->h_misc.p) + job_bytes, ext, n * sizeof(mcq_query_ext));
+    const uint32_t *d_ext = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(c->h_misc.dev) + job_bytes);
+    const uint32_t slice = mcq_exact_hero_pre_slice(c->hero_pre_slice);
+    uint32_t max_grid = 0, max_boards = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t g = mcq_exact_hero_pre_plan(&q[i], (uint32_t)i, (uint32_t)i, xq[i].x.b.L, xq[i].n_allowed, exact_cu(c), slice,
+                                                   &jobs[i]);
+        if (g == 0u) return mcq_fail(MCQ_EINVAL, who, "MCQ_HERO_PRE_SLICE: a block would own more completions than its 32-bit sums allow");
+        max_grid = g > max_grid ? g : max_grid;
+        max_boards = jobs[i].n_boards > max_boards ? jobs[i].n_boards : max_boards;
+    }
+    HIP_TRY(hipMemsetAsync(c->d_res.p, 0, n * q_bytes, c->stream));
+    for (uint32_t lo = 0; lo < max_boards;) { /* (a record with ghost cards has fewer completions: its blocks leave at once) */
+        const uint32_t hi = max_boards - lo > slice ? lo + slice : max_boards;
+        HIP_TRY(mcq_launch_exact_hero_pre(d_jobs, (uint32_t)n, max_grid, d_ext, law, lo, hi, (mcq_result *)c->d_res.p, c->d_luts,
+                                          c->stream));
+        lo = hi;
+    }
+    HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * q_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    /* the aggregates first: a row without weight (the opponent's range cannot be dealt against that hero hand) refuses the
+     * whole call before anything reaches the caller */
+    const mcq_result *hr = static_cast<const mcq_result *>(c->h_res.p);
+    std::vector<mcq_exact_prob> p(n);
+    for (size_t i = 0; i < n; i++)
+        if (!mcq_exact_hero_finish(xq[i], &rid[64u * i], hr + i * MCQ_XH_ROWS, p[i])) {
+            snprintf(buf, sizeof buf, "query %zu: the opponent's range cannot be dealt against some hand of the hero's range", i);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+    memcpy(rows, hr, n * q_bytes);
+    if (agg) memcpy(agg, p.data(), n * sizeof(mcq_exact_prob));
+    return MCQ_OK;
+    ABI_GUARD_END("mcq_exact_batch_hero_range_preflop")
 }
 
 /* flop and turn records, at most one random opponent: the weights row of every table completion (mcq_exact_runout.hpp) */

@@ -46,6 +46,13 @@ uint32_t mcq_exact_hero_plan(const mcq_query *q, uint32_t ext, uint32_t row, uin
                              McqExactExtJob *job);
 hipError_t mcq_launch_exact_hero(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
                                  mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
+/* ... before the flop (mcq_exact_hero_pre.hpp): the completions go out in launches of `slice`, each over [lo, hi) with
+ * hi - lo <= slice, all adding into the same zeroed rows.  The plan returns 0 when a block would own more completions per
+ * launch than a thread's 32-bit sums allow (MCQ_XP_MAX_OWNED). */
+uint32_t mcq_exact_hero_pre_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed, uint32_t n_cu,
+                                 uint32_t slice, McqExactExtJob *job);
+hipError_t mcq_launch_exact_hero_pre(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
+                                     uint32_t lo, uint32_t hi, mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
 /* per-runout enumeration (mcq_exact_runout.hpp): flop and turn records with at most one random opponent, jobs planned by
  * mcq_exact_ext_plan (kind 0 or 1, job->row = the record's index); d_cards holds 52 and d_pairs MCQ_HAND_ROWS zeroed
  * mcq_result_ways rows per record.  The second launch takes the jobs of both kinds and fills the card rows of the flop

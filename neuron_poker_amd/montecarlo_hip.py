@@ -34,7 +34,7 @@ import numpy as np
 from . import _lib
 from .cards import TYPES, card_id, card_str
 
-__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_runout_equities", "MonteCarlo", "seed",
+__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_preflop_range_equity_exact", "preflop_class_table", "get_runout_equities", "MonteCarlo", "seed",
            "configure"]
 
 _state = {"couple_numpy": False,
@@ -524,11 +524,14 @@ def get_range_equity_exact(hero_range, table_cards, opponent_range=1, dealing="r
     ext = _lib.pack_query_ext(1, ghost=ghost, hero_range=hero_bits, opp_range=opp_bits)
     eng = engine or _lib.default_engine()
     rows, _ = eng.exact_hero_range(q, ext, dealing)
-    r = rows[0]
+    return _range_rows_to_hands(rows[0], set(board) | set(ghost or []), dealing in ("uniform", 1), ties)
+
+
+def _range_rows_to_hands(r, gone, uniform, ties):
+    """The HAND_ROWS rows of one record -> (equity, {(card, card): (equity_h, weight_h)}); gone = the card ids that left
+    the deck (table and ghost cards)."""
     live = np.flatnonzero(r["runs"])
-    gone = set(board) | set(ghost or [])
     top = max(c for c in range(52) if c not in gone)
-    uniform = dealing in ("uniform", 1)
     tie = r["tie"][live].astype(np.float64)
     eq = (r["win"][live] + (tie / 2.0 if ties == "split" else tie)) / r["runs"][live]
     hands, num, den = {}, 0.0, 0.0
@@ -539,6 +542,60 @@ def get_range_equity_exact(hero_range, table_cards, opponent_range=1, dealing="r
         num += w * float(e)
         den += w
     return num / den, hands
+
+
+def _hand_class(a, b):
+    """Preflop class string of the hand of card ids a, b: 'AA', 'AKS', 'AKO' -- the higher rank first."""
+    from .cards import RANKS
+    lo, hi = sorted((a >> 2, b >> 2))
+    if lo == hi:
+        return RANKS[hi] * 2
+    return RANKS[hi] + RANKS[lo] + ("S" if (a & 3) == (b & 3) else "O")
+
+
+def preflop_class_table(hands):
+    """{(card, card): (equity, weight)} as get_preflop_range_equity_exact returns it -> {class string: (equity, weight)}:
+    per preflop class its hands' total weight and their weighted mean equity."""
+    num, den = {}, {}
+    for (a, b), (e, w) in hands.items():
+        c = _hand_class(card_id(a), card_id(b))
+        num[c] = num.get(c, 0.0) + w * e
+        den[c] = den.get(c, 0) + w
+    return {c: (num[c] / den[c], den[c]) for c in den}
+
+
+def get_preflop_range_equity_exact(hero_range, opponent_range=1, dealing="reference", ghost_cards='', engine=None,
+                                   ties="credited", by_class=False):
+    """Exact equity of a hero RANGE against one random opponent, ranged or not, BEFORE THE FLOP: every hand of the range
+    from one enumeration of all table completions on the GPU (mcq_exact_batch_hero_range_preflop).  Narrow ranges take
+    tens of milliseconds, every hand against every hand takes seconds.
+
+    The arguments and the result are get_range_equity_exact's without table cards: -> (equity, {(card, card): (equity_h,
+    weight_h)}).  by_class=True adds a third value, the 169-class table {class string: (equity, weight)}: per class of
+    the range its hands' weighted mean equity and total weight under `dealing` (preflop_class_table)."""
+    if ties not in ("credited", "split"):
+        raise ValueError("ties must be 'credited' or 'split'")
+    if dealing not in ("reference", "uniform", 0, 1):
+        raise ValueError("dealing must be 'reference' or 'uniform'")
+    hero_bits = _opponent_range_bits(hero_range)
+    if hero_bits is None:
+        hero_bits = _lib.ALL_CLASSES
+    if not np.asarray(hero_bits).any():
+        raise ValueError("hero_range names no preflop class")
+    opp_bits = _opponent_range_bits(opponent_range)
+    ghost = None
+    if ghost_cards != '' and ghost_cards is not None:
+        if len(ghost_cards) != 2:
+            raise ValueError("ghost_cards is two cards or ''")
+        ghost = [card_id(ghost_cards[0]), card_id(ghost_cards[1])]
+    q = _lib.pack_query_one([0, 0], [], 2, 1)
+    ext = _lib.pack_query_ext(1, ghost=ghost, hero_range=hero_bits, opp_range=opp_bits)
+    eng = engine or _lib.default_engine()
+    rows, _ = eng.exact_hero_range_preflop(q, ext, dealing)
+    equity, hands = _range_rows_to_hands(rows[0], set(ghost or []), dealing in ("uniform", 1), ties)
+    if by_class:
+        return equity, hands, preflop_class_table(hands)
+    return equity, hands
 
 
 def get_runout_equities(player_cards, table_cards, players, dealing="reference", engine=None, *, known_hands=(),
