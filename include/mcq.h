@@ -356,6 +356,42 @@ MCQ_API int mcq_exact_batch_ext_seats(mcq_ctx *ctx, const mcq_query *q, const mc
 MCQ_API int mcq_exact_batch_hero_range(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
                                        mcq_result *rows /* [n][MCQ_HAND_ROWS] */, mcq_exact_prob *agg /* [n], may be NULL */);
 
+/* Exact range against range with WEIGHTED HANDS, postflop and heads-up: mcq_exact_batch_hero_range with a weight per
+ * two-card hand on both sides -- "calls with AQo half of the time", a reach probability per combo, "AhKh but not AsKs" --
+ * in place of the in-or-out of a preflop class.  Weights are integers 0..MCQ_COMBO_WEIGHT_MAX; a caller with probabilities
+ * scales them (only the ratios matter).
+ * Accepted: exactly what mcq_exact_batch_hero_range accepts -- hero_is_range == 1, n_known == 0, n_players == 2, 3, 4 or 5
+ * table cards, optional ghost cards, at most MCQ_HERO_RANGE_MAX_BATCH records.
+ * The law is always MCQ_LAW_UNIFORM, so there is no law argument: the reference's law tests the class of the drawn index
+ * pair (A, B) and then deals "the card after B", and a weight per dealt hand has no meaning there.
+ * Definitions.  D = the 52 cards minus table and ghost cards, k = 5 - n_board.  Both tables hold MCQ_HAND_ROWS entries per
+ * record, indexed by MCQ_HAND_INDEX(a, b):
+ *   eff_opp(g)  = opp_weights[i][MCQ_HAND_INDEX(g)]                      if class(g) is in opp_range,  else 0
+ *   eff_hero(h) = hero_weights ? hero_weights[i][MCQ_HAND_INDEX(h)] : 1  if class(h) is in hero_range, else 0
+ * The class sets stay in force; "every class" in both sets leaves the weights alone to define the ranges.  Entries of
+ * either table for a hand that holds a table or ghost card are ignored (they need not be zero).
+ * Rows.  A hero hand h of D is allowed iff eff_hero(h) > 0; the rows of all other hands are zero.  For an allowed hand,
+ * with T over the k-subsets of D minus h and g over the two-card hands of D minus h minus T:
+ *   runs       = sum_T sum_g eff_opp(g)                     (at most 1081 * 990 * 65535, about 7.0e10)
+ *   win        = the same sum over the g that lose to h on T,   tie = over the g level with h
+ *   by_type[t] = the part of win + tie in which h makes hand type t,   passes = 0
+ * -- integers, deterministic.  The rows are linear in opp_weights word for word, and with every opp_weights entry 1 and
+ * hero_weights == NULL rows and agg equal mcq_exact_batch_hero_range(..., MCQ_LAW_UNIFORM, ...) bit for bit.
+ * agg[i] (agg may be NULL) = sum_h eff_hero(h) x_h / runs_h / sum_h eff_hero(h) over the allowed hands, x = win, tie,
+ * by_type[t], in doubles on the host in ascending row order.
+ * Refused with MCQ_EINVAL, nothing launched, rows and agg untouched: whatever mcq_exact_batch_hero_range refuses,
+ * opp_weights == NULL, no allowed hero hand (eff_hero is 0 everywhere in D); and -- before anything is copied to the
+ * caller -- an allowed hero hand whose row has no weight (eff_opp is 0 for every hand that shares no card with it).
+ * MCQ_EBUSY as everywhere.
+ * Not covered: before the flop (mcq_exact_batch_hero_range_preflop keeps class sets), the reference's law, weighted
+ * ranges in the Monte-Carlo entries, more than one opponent. */
+#define MCQ_COMBO_WEIGHT_MAX 65535u
+MCQ_API int mcq_exact_batch_hero_range_weighted(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n,
+                                                const uint16_t *opp_weights /* [n][MCQ_HAND_ROWS] */,
+                                                const uint16_t *hero_weights /* [n][MCQ_HAND_ROWS], may be NULL: every allowed hand weighs 1 */,
+                                                mcq_result *rows /* [n][MCQ_HAND_ROWS] */,
+                                                mcq_exact_prob *agg /* [n], may be NULL */);
+
 /* Exact RANGE against RANGE BEFORE THE FLOP, heads-up: every hand of the hero's range from ONE enumeration of the
  * C(|D|, 5) table completions per record.  An entry of its own because a record takes from tens of milliseconds (narrow
  * ranges) to seconds (every hand against every hand), not the millisecond of mcq_exact_batch_hero_range.

@@ -137,6 +137,8 @@ def load_library():
         L.mcq_exact_batch_ext.restype = C.c_int
         L.mcq_exact_batch_hero_range.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
         L.mcq_exact_batch_hero_range.restype = C.c_int
+        L.mcq_exact_batch_hero_range_weighted.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
+        L.mcq_exact_batch_hero_range_weighted.restype = C.c_int
         L.mcq_exact_batch_hero_range_preflop.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
         L.mcq_exact_batch_hero_range_preflop.restype = C.c_int
         L.mcq_exact_batch_ext_runouts.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
@@ -269,6 +271,7 @@ def pack_query_one(hole, board, n_players, runs):
 
 HAND_ROWS = 1326   # C(52, 2): MCQ_HAND_ROWS
 HERO_PREFLOP_MAX_BATCH = 64   # MCQ_HERO_PREFLOP_MAX_BATCH
+COMBO_WEIGHT_MAX = 65535      # MCQ_COMBO_WEIGHT_MAX
 RUNOUT_CARD_ROWS = 52     # MCQ_RUNOUT_CARD_ROWS
 RUNOUT_MAX_BATCH = 1024   # MCQ_RUNOUT_MAX_BATCH
 
@@ -455,6 +458,34 @@ class Engine:
         agg = np.zeros(len(q), EXACT_PROB_DTYPE)
         rc = self._lib.mcq_exact_batch_hero_range(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, rows.ctypes.data,
                                                   agg.ctypes.data)
+        if rc:
+            _raise(rc)
+        return rows, agg
+
+    def exact_hero_range_weighted(self, queries, ext, opp_weights, hero_weights=None):
+        """exact_hero_range with a weight per HAND on both sides, under the uniform law
+        (mcq_exact_batch_hero_range_weighted).  opp_weights and hero_weights are uint16 arrays [n, HAND_ROWS] indexed by
+        hand_index(a, b); hero_weights=None weighs every hand of the hero's classes 1.  The class sets of the records stay
+        in force (a hand outside its set weighs 0).  -> (rows, agg) laid out as exact_hero_range's: per hero hand of
+        positive weight runs = the opponent's total weight, win, tie and by_type its parts; agg combines the rows with the
+        hero's weights.  A wrong shape or dtype raises ValueError."""
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        tables = []
+        for name, w in (("opp_weights", opp_weights), ("hero_weights", hero_weights)):
+            if w is None and name == "hero_weights":
+                tables.append(None)
+                continue
+            if not isinstance(w, np.ndarray) or w.dtype != np.uint16 or w.shape != (len(q), HAND_ROWS):
+                raise ValueError("%s is a uint16 array of shape [n, HAND_ROWS] = (%d, %d)" % (name, len(q), HAND_ROWS))
+            tables.append(np.ascontiguousarray(w))
+        rows = np.zeros((len(q), HAND_ROWS), RESULT_DTYPE)
+        agg = np.zeros(len(q), EXACT_PROB_DTYPE)
+        rc = self._lib.mcq_exact_batch_hero_range_weighted(self._ctx, q.ctypes.data, e.ctypes.data, len(q), tables[0].ctypes.data,
+                                                           None if tables[1] is None else tables[1].ctypes.data,
+                                                           rows.ctypes.data, agg.ctypes.data)
         if rc:
             _raise(rc)
         return rows, agg

@@ -194,4 +194,114 @@ MCQ_HD bool mcq_exact_hero_finish(const McqExactHeroQuery &e, const uint8_t *r_i
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------- weighted hands
+// mcq_exact_batch_hero_range_weighted: the same enumeration with an integer weight per HAND in place of the class bit,
+// MCQ_LAW_UNIFORM only (the reference's law tests the class of the drawn index pair and deals "the card after B": a
+// weight per dealt hand has no meaning there, so its terms are not compiled in).  Both ranges keep their class sets;
+// the tables are indexed by row (mcq_exact_hero_row) and folded once into tables per D-pair:
+//   ow_tab[rp] = eff_opp  = opp_w[row]                 if the pair's class is in the opponent's range, else 0
+//   hw_tab[rp] = eff_hero = hero_w ? hero_w[row] : 1   if the pair's class is in the hero's range,     else 0
+// A hero hand is allowed iff eff_hero > 0 (host and kernel make the list from hw_tab alike).  The ranking pass stores a
+// candidate's eff_opp in the 16 bits above its positions (the `above` and range-bit fields are not needed under the
+// uniform law), so the walk's weight is one shift.
+#define MCQ_XH_WEIGHT_MAX 65535u /* MCQ_COMBO_WEIGHT_MAX */
+
+static_assert(MCQ_XH_MAX_PAIRS * MCQ_XH_WEIGHT_MAX < (1u << 27), "a completion's weighted sums (McqExactAcc) fit 32 bits");
+static_assert((uint64_t)MCQ_XH_MAX_PAIRS * MCQ_EXACT_PAIRS * MCQ_XH_WEIGHT_MAX > 0xFFFFFFFFull,
+              "a hero hand's weighted sums over the flop's 1081 completions do NOT fit 32 bits: McqExactHeroSumsW is 64-bit");
+static_assert((uint64_t)MCQ_XH_MAX_HANDS * MCQ_XH_MAX_PAIRS * MCQ_XH_WEIGHT_MAX < (1ull << 37), "... and 64 bits hold them with room");
+
+// the two tables per D-pair; entries rp0, rp0 + step, ...
+MCQ_HD void mcq_exact_hero_w_tables(const McqExactHeroQuery &e, const uint8_t *r_id, const uint16_t *opp_w, const uint16_t *hero_w,
+                                    uint32_t rp0, uint32_t step, uint16_t *ow_tab, uint16_t *hw_tab) {
+    for (uint32_t rp = rp0; rp < e.x.n_rp; rp += step) {
+        uint32_t pa, pb;
+        mcq_exact_pair_xy(rp, pa, pb);
+        const uint32_t row = mcq_exact_hero_row(r_id, pa, pb);
+        ow_tab[rp] = mcq_in_range(e.x.bits, r_id[pa], r_id[pb]) ? opp_w[row] : (uint16_t)0u;
+        hw_tab[rp] = mcq_in_range(e.hero_bits, r_id[pa], r_id[pb]) ? (hero_w ? hero_w[row] : (uint16_t)1u) : (uint16_t)0u;
+    }
+}
+
+// The allowed hero hands as D-pair indices, ascending -> their number.  (The kernel makes the same list with ballots.)
+MCQ_HD uint32_t mcq_exact_hero_w_count(const McqExactHeroQuery &e, const uint16_t *hw_tab, uint16_t *list) {
+    uint32_t n = 0;
+    for (uint32_t rp = 0; rp < e.x.n_rp; rp++) {
+        if (hw_tab[rp] == 0u) continue;
+        if (list) list[n] = (uint16_t)rp;
+        n++;
+    }
+    return n;
+}
+
+// packed record of a candidate hand: D-positions, eff_opp
+MCQ_HD uint32_t mcq_exact_hero_w_pack(uint32_t pa, uint32_t pb, uint32_t w) { return pa | (pb << 6) | (w << 16); }
+
+// Ranking pass, as mcq_exact_hero_rank.
+MCQ_HD void mcq_exact_hero_w_rank(const McqExactHeroQuery &e, const McqExactBoard &bd, uint32_t lane, uint32_t n_lanes,
+                                  const uint16_t *pair_xy, const McqCard *rem_card, const uint32_t *rem_pos, const uint16_t *ow_tab,
+                                  const uint32_t *tf, const uint32_t *tops, const uint32_t *sd, uint32_t *keys, uint32_t *rec) {
+    for (uint32_t i = lane; i < e.x.n_pairs; i += n_lanes) {
+        const uint32_t xy = pair_xy[i], x = xy & 0xFFu, y = xy >> 8;
+        McqHole h;
+        h.set(rem_card[x], rem_card[y]);
+        keys[i] = mcq_eval_key(bd.b, bd.fs, h, tf, tops, sd);
+        const uint32_t pa = rem_pos[x], pb = rem_pos[y];
+        rec[i] = mcq_exact_hero_w_pack(pa, pb, ow_tab[pb * (pb - 1u) / 2u + pa]);
+    }
+}
+
+// The walk of ONE hero hand, as mcq_exact_hero_walk: a completion's sums stay 32-bit.  Returns the hero hand's type.
+MCQ_HD uint32_t mcq_exact_hero_w_walk(const McqExactHeroQuery &e, uint32_t qa, uint32_t qb, uint32_t mi, const uint32_t *keys,
+                                      const uint32_t *rec, McqExactAcc &acc) {
+    const uint32_t kh = keys[mi];
+    for (uint32_t j = 0; j < e.x.n_pairs; j++) {
+        const uint32_t r = rec[j], pa = r & 63u, pb = (r >> 6) & 63u;
+        const bool shared = pa == qa || pa == qb || pb == qa || pb == qb; /* (hero's own hand among them) */
+        const uint32_t w = !shared ? r >> 16 : 0u;
+        const uint32_t kj = keys[j];
+        acc.win += kj < kh ? w : 0u;
+        acc.tie += kj == kh ? w : 0u;
+        acc.tot += w;
+    }
+    return mcq_key_type(kh);
+}
+
+struct McqExactHeroSumsW { /* 64-bit: a hero hand's weighted sums over all completions (see the static_asserts above) */
+    unsigned long long win, tie, tot, type[9];
+};
+MCQ_HD void mcq_exact_hero_w_add(McqExactHeroSumsW &s, const McqExactAcc &a, uint32_t type) { /* once per completion */
+    s.win += a.win;
+    s.tie += a.tie;
+    s.tot += a.tot;
+#pragma unroll
+    for (uint32_t t = 0; t < 9; t++) s.type[t] += t == type ? a.win + a.tie : 0u;
+}
+
+// ---- host side
+// The aggregate, as mcq_exact_hero_finish: the allowed rows combined with eff_hero, in ascending row order.
+MCQ_HD bool mcq_exact_hero_w_finish(const McqExactHeroQuery &e, const uint8_t *r_id, const uint16_t *hw_tab, const mcq_result *rows,
+                                    mcq_exact_prob &p) {
+    uint8_t pos_of[52];
+    for (uint32_t c = 0; c < 52; c++) pos_of[c] = 255;
+    for (uint32_t i = 0; i < e.x.b.L; i++) pos_of[r_id[i]] = (uint8_t)i;
+    double num[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, den = 0;
+    for (uint32_t b = 1; b < 52; b++)
+        for (uint32_t a = 0; a < b; a++) {
+            const uint32_t qa = pos_of[a], qb = pos_of[b];
+            if (qa == 255u || qb == 255u || hw_tab[qb * (qb - 1u) / 2u + qa] == 0u) continue;
+            const mcq_result &r = rows[b * (b - 1u) / 2u + a];
+            if (r.runs == 0) return false;
+            const double w = (double)hw_tab[qb * (qb - 1u) / 2u + qa], runs = (double)r.runs;
+            num[0] += w * (double)r.win / runs;
+            num[1] += w * (double)r.tie / runs;
+            for (uint32_t t = 0; t < 9; t++) num[2 + t] += w * (double)r.by_type[t] / runs;
+            den += w;
+        }
+    p.win = num[0] / den;
+    p.tie = num[1] / den;
+    for (uint32_t t = 0; t < 9; t++) p.by_type[t] = num[2 + t] / den;
+    return true;
+}
+
 #endif /* MCQ_EXACT_HERO_HPP */

@@ -46,6 +46,10 @@ uint32_t mcq_exact_hero_plan(const mcq_query *q, uint32_t ext, uint32_t row, uin
                              McqExactExtJob *job);
 hipError_t mcq_launch_exact_hero(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
                                  mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
+/* ... with a weight per hand, uniform law (mcq_exact_hero_w_kernel): the same jobs; d_wts holds 2 * MCQ_HAND_ROWS uint16 per
+ * query -- the opponent's table, then the hero's, which is read only with hero_w (else every hand of his classes weighs 1) */
+hipError_t mcq_launch_exact_hero_w(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext,
+                                   const uint16_t *d_wts, bool hero_w, mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
 /* ... before the flop (mcq_exact_hero_pre.hpp): the completions go out in launches of `slice`, each over [lo, hi) with
  * hi - lo <= slice, all adding into the same zeroed rows.  The plan returns 0 when a block would own more completions per
  * launch than a thread's 32-bit sums allow (MCQ_XP_MAX_OWNED). */

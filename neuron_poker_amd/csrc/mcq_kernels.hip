@@ -2377,6 +2377,108 @@ __global__ __launch_bounds__(1024) void mcq_exact_hero_kernel(const McqExactExtJ
     }
 }
 
+// ---------------------------------------------------------------------------------------------- exact enumeration, hero range, weighted hands
+// mcq_exact_hero_kernel with an integer weight per hand (mcq_exact_hero.hpp, "weighted hands"): the uniform law only.
+// wts holds per query row the opponent's [1326] uint16 table and then the hero's; hero_w == 0: the hero's table is not
+// there and every hand of the hero's classes weighs 1.  The tables are folded once per block into ow_tab / hw_tab (LDS,
+// per D-pair, 4.7 KB in place of the 1.2 KB of range bits); the allowed list is made from hw_tab, so every block makes the
+// same one.  A completion's sums are 32-bit as before; they are added ONCE per completion into twelve 64-bit sums, which
+// go out by the same integer atomics.
+__global__ __launch_bounds__(1024) void mcq_exact_hero_w_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
+                                                                const uint16_t *__restrict__ wts, uint32_t hero_w,
+                                                                unsigned long long *__restrict__ rows,
+                                                                const McqTables *__restrict__ g_tab) {
+    const McqExactExtJob job = jobs[blockIdx.y];
+    if (blockIdx.x >= job.grid) return;
+    constexpr uint32_t kChunks = (MCQ_XH_MAX_HANDS + 63u) / 64u;
+    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ uint16_t pair_xy[MCQ_XH_MAX_HANDS]; /* every D-pair; the candidate hands are its first n_pairs entries */
+    __shared__ uint32_t xw[MCQ_EXT_WORDS];
+    __shared__ McqExactHeroQuery xq;
+    __shared__ uint8_t r_id[64];
+    __shared__ uint16_t ow_tab[MCQ_XH_MAX_HANDS];
+    __shared__ uint16_t hw_tab[MCQ_XH_MAX_HANDS];
+    __shared__ uint16_t own_list[MCQ_XH_MAX_HANDS];
+    __shared__ uint32_t chunk_cnt[kChunks];
+    __shared__ McqCard rem_card[64];
+    __shared__ uint32_t rem_pos[64];
+    __shared__ uint32_t keys[MCQ_XH_MAX_PAIRS + 3u];
+    __shared__ uint32_t recs[MCQ_XH_MAX_PAIRS + 3u];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
+    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
+    for (uint32_t i = tid; i < MCQ_XH_MAX_HANDS; i += blockDim.x) {
+        uint32_t x, y;
+        mcq_exact_pair_xy(i, x, y);
+        pair_xy[i] = (uint16_t)(x | (y << 8));
+    }
+    load_tables(tab, g_tab); /* ends with a barrier */
+    if (tid == 0) {
+        const McqExtRec er = {xw};
+        (void)mcq_exact_hero_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, MCQ_LAW_UNIFORM, xq); /* validated by the host */
+        mcq_exact_ext_r_ids(xq.x, r_id);
+    }
+    __syncthreads();
+    const McqExactHeroQuery &e = xq;
+    const uint16_t *w_opp = wts + (size_t)job.row * 2u * MCQ_XH_ROWS;
+    mcq_exact_hero_w_tables(e, r_id, w_opp, hero_w ? w_opp + MCQ_XH_ROWS : nullptr, tid, blockDim.x, ow_tab, hw_tab);
+    __syncthreads();
+    /* the allowed hero hands in ascending order (every block makes the same list): 64 D-pairs per wave and pass */
+    for (uint32_t c = wib; c < kChunks; c += 16u) {
+        const uint32_t rp = c * 64u + lane;
+        const bool on = rp < e.x.n_rp && hw_tab[rp] != 0u;
+        const unsigned long long mask = __ballot(on);
+        if (lane == 0u) chunk_cnt[c] = (uint32_t)__popcll(mask);
+    }
+    __syncthreads();
+    for (uint32_t c = wib; c < kChunks; c += 16u) {
+        const uint32_t rp = c * 64u + lane;
+        const bool on = rp < e.x.n_rp && hw_tab[rp] != 0u;
+        const unsigned long long mask = __ballot(on);
+        uint32_t base = 0;
+        for (uint32_t j = 0; j < c; j++) base += chunk_cnt[j];
+        if (on) own_list[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (uint16_t)rp;
+    }
+    uint32_t n_own = 0;
+    for (uint32_t j = 0; j < kChunks; j++) n_own += chunk_cnt[j];
+    __syncthreads();
+
+    const uint32_t groups = job.groups, group = blockIdx.x % groups, idx = group * blockDim.x + tid;
+    const bool own = idx < n_own;
+    const uint32_t hxy = pair_xy[own ? own_list[idx] : 0u], qa = hxy & 0xFFu, qb = hxy >> 8;
+    McqExactHeroSumsW s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+    for (uint32_t board = blockIdx.x / groups; board < job.n_boards; board += job.grid / groups) {
+        uint32_t pos[5];
+        mcq_exact_unrank(board, e.x.b.L, e.x.b.k, pos);
+        McqExactBoard bd;
+        mcq_exact_hero_board(e.x.b, pos, r_id, bd);
+        __syncthreads(); /* the previous completion's walk is done with keys and records */
+        if (tid < e.x.m) {
+            const uint32_t rp = mcq_exact_rem_pos(pos, tid);
+            rem_pos[tid] = rp;
+            rem_card[tid] = mcq_card(r_id[rp]);
+        }
+        __syncthreads();
+        mcq_exact_hero_w_rank(e, bd, tid, blockDim.x, pair_xy, rem_card, rem_pos, ow_tab, g_tab->tf, tab.tops, tab.sd, keys, recs);
+        __syncthreads();
+        const uint32_t mi = own ? mcq_exact_ext_m_index(e.x, pos, qa, qb) : e.x.n_pairs;
+        if (mi < e.x.n_pairs) {
+            McqExactAcc acc = {0, 0, 0};
+            const uint32_t type = mcq_exact_hero_w_walk(e, qa, qb, mi, keys, recs, acc);
+            mcq_exact_hero_w_add(s, acc, type);
+        }
+    }
+    if (own) {
+        unsigned long long *dst = rows + ((size_t)job.row * MCQ_XH_ROWS + mcq_exact_hero_row(r_id, qa, qb)) * 13u;
+        /* an mcq_result row: runs, passes, win, tie, by_type[9] */
+        if (s.tot) atomicAdd(dst + 0, s.tot);
+        if (s.win) atomicAdd(dst + 2, s.win);
+        if (s.tie) atomicAdd(dst + 3, s.tie);
+#pragma unroll
+        for (uint32_t t = 0; t < 9; t++)
+            if (s.type[t]) atomicAdd(dst + 4 + t, s.type[t]);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- exact enumeration, hero range, preflop
 // See mcq_exact_hero_pre.hpp; one job per query (blockIdx.y), the shape of mcq_exact_hero_kernel with everything indexed by
 // D-pair: a BLOCK per table completion; the blocks of a group share the launch's slice [lo, hi) in runs of consecutive
@@ -2922,6 +3024,15 @@ hipError_t mcq_launch_exact_hero(const McqExactExtJob *d_jobs, uint32_t n_jobs, 
     if (n_jobs == 0) return hipSuccess;
     if (n_jobs > 65535u || max_grid == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mcq_exact_hero_kernel, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law,
+                       reinterpret_cast<unsigned long long *>(d_rows), d_luts);
+    return hipGetLastError();
+}
+
+hipError_t mcq_launch_exact_hero_w(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext,
+                                   const uint16_t *d_wts, bool hero_w, mcq_result *d_rows, const McqTables *d_luts, hipStream_t s) {
+    if (n_jobs == 0) return hipSuccess;
+    if (n_jobs > 65535u || max_grid == 0 || !d_wts) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mcq_exact_hero_w_kernel, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, d_wts, hero_w ? 1u : 0u,
                        reinterpret_cast<unsigned long long *>(d_rows), d_luts);
     return hipGetLastError();
 }

@@ -34,7 +34,7 @@ import numpy as np
 from . import _lib
 from .cards import TYPES, card_id, card_str
 
-__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_preflop_range_equity_exact", "preflop_class_table", "get_runout_equities", "MonteCarlo", "seed",
+__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_range_equity_exact_weighted", "quantise_weight", "get_preflop_range_equity_exact", "preflop_class_table", "get_runout_equities", "MonteCarlo", "seed",
            "configure"]
 
 _state = {"couple_numpy": False,
@@ -525,6 +525,84 @@ def get_range_equity_exact(hero_range, table_cards, opponent_range=1, dealing="r
     eng = engine or _lib.default_engine()
     rows, _ = eng.exact_hero_range(q, ext, dealing)
     return _range_rows_to_hands(rows[0], set(board) | set(ghost or []), dealing in ("uniform", 1), ties)
+
+
+def quantise_weight(w):
+    """A hand's weight in [0, 1] -> the integer 0..65535 the library works with: round(w * 65535).  A non-zero weight that
+    would round to 0 (below 1 / 131070) raises ValueError: the hand would silently leave the range."""
+    w = float(w)
+    if not 0.0 <= w <= 1.0:
+        raise ValueError("a weight is a number in [0, 1], not %r" % (w,))
+    v = int(round(w * _lib.COMBO_WEIGHT_MAX))
+    if v == 0 and w != 0.0:
+        raise ValueError("the weight %r rounds to 0 of %d: give 0 to leave the hand out" % (w, _lib.COMBO_WEIGHT_MAX))
+    return v
+
+
+def _weighted_range(rng, what):
+    """A range of get_range_equity_exact_weighted -> (class bits, weights[1, HAND_ROWS] uint16 or None for "every hand 1").
+    A dict maps class strings ('AQO') and hands (('AH', 'KH')) to weights in [0, 1]: a hand's entry overrides its class's,
+    whatever is not named weighs 0, and the class set is "every class" -- the weights alone define the range."""
+    if not isinstance(rng, dict):
+        bits = _opponent_range_bits(rng)
+        return (_lib.ALL_CLASSES if bits is None else bits), None
+    by_class, by_hand = {}, {}
+    for key, w in rng.items():
+        if isinstance(key, str):
+            bit = _lib.class_bit(key)
+            if bit is None:
+                raise ValueError("%s: %r is no preflop class" % (what, key))
+            by_class[bit] = quantise_weight(w)
+        else:
+            if len(key) != 2:
+                raise ValueError("%s: a hand is two cards, not %r" % (what, key))
+            by_hand[_lib.hand_index(card_id(key[0]), card_id(key[1]))] = quantise_weight(w)
+    table = np.zeros((1, _lib.HAND_ROWS), np.uint16)
+    for i, (a, b) in enumerate(_ROW_HANDS):
+        table[0, i] = by_hand.get(i, by_class.get(_lib.class_bit(_hand_class(a, b)), 0))
+    return _lib.ALL_CLASSES, table
+
+
+def get_range_equity_exact_weighted(hero, table_cards, opponent, ghost_cards='', engine=None, ties="credited"):
+    """Exact equity of a WEIGHTED hero range against one opponent with a weighted range, on the flop, turn or river, every
+    hand equally likely but for its weight (mcq_exact_batch_hero_range_weighted; the uniform law).
+
+    hero and opponent are each a range as run_montecarlo takes it -- a set of class strings or a top fraction: every hand
+    of it weighs 1 -- or a dict of weights in [0, 1] keyed by class string ('AQO': 0.5) or by hand (('AH', 'KH'): 1.0).  A
+    hand's entry overrides its class's; whatever is not named weighs 0.  Weights are quantised to round(w * 65535)
+    (quantise_weight; a non-zero weight that would become 0 raises ValueError).
+    -> (equity, {(card, card): (equity_h, weight_h)}): per hero hand of positive weight that the remaining cards can make
+    its exact equity against the weighted opponent -- ties as in get_range_equity_exact -- and its weight (the quantised
+    one / 65535; 1.0 in a plain range); `equity` is their weighted mean.  Preflop raises ValueError, and so does a hero
+    hand against which no opponent hand of positive weight is left."""
+    if ties not in ("credited", "split"):
+        raise ValueError("ties must be 'credited' or 'split'")
+    hero_bits, hero_w = _weighted_range(hero, "hero")
+    opp_bits, opp_w = _weighted_range(opponent, "opponent")
+    if opp_w is None:
+        opp_w = np.ones((1, _lib.HAND_ROWS), np.uint16)
+    board = [card_id(c) for c in table_cards]
+    if len(board) > 5:
+        raise ValueError("table_cards holds more than five cards")
+    ghost = None
+    if ghost_cards != '' and ghost_cards is not None:
+        ghost = [card_id(ghost_cards[0]), card_id(ghost_cards[1])]
+    q = _lib.pack_query_one([0, 0], board, 2, 1)
+    ext = _lib.pack_query_ext(1, ghost=ghost, hero_range=hero_bits, opp_range=opp_bits)
+    eng = engine or _lib.default_engine()
+    rows, _ = eng.exact_hero_range_weighted(q, ext, opp_w, hero_w)
+    r = rows[0]
+    live = np.flatnonzero(r["runs"])
+    tie = r["tie"][live].astype(np.float64)
+    eq = (r["win"][live] + (tie / 2.0 if ties == "split" else tie)) / r["runs"][live]
+    hands, num, den = {}, 0.0, 0.0
+    for i, e in zip(live, eq):
+        a, b = _ROW_HANDS[i]
+        w = 1.0 if hero_w is None else int(hero_w[0, i]) / float(_lib.COMBO_WEIGHT_MAX)
+        hands[(card_str(a), card_str(b))] = (float(e), w)
+        num += w * float(e)
+        den += w
+    return num / den, hands
 
 
 def _range_rows_to_hands(r, gone, uniform, ties):
