@@ -383,8 +383,8 @@ MCQ_API int mcq_exact_batch_hero_range(mcq_ctx *ctx, const mcq_query *q, const m
  * opp_weights == NULL, no allowed hero hand (eff_hero is 0 everywhere in D); and -- before anything is copied to the
  * caller -- an allowed hero hand whose row has no weight (eff_opp is 0 for every hand that shares no card with it).
  * MCQ_EBUSY as everywhere.
- * Not covered: before the flop (mcq_exact_batch_hero_range_preflop keeps class sets), the reference's law, weighted
- * ranges in the Monte-Carlo entries, more than one opponent. */
+ * Not covered: the reference's law, weighted ranges in the Monte-Carlo entries, more than one opponent.  Before the flop:
+ * mcq_exact_batch_hero_range_preflop_weighted below. */
 #define MCQ_COMBO_WEIGHT_MAX 65535u
 MCQ_API int mcq_exact_batch_hero_range_weighted(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n,
                                                 const uint16_t *opp_weights /* [n][MCQ_HAND_ROWS] */,
@@ -415,6 +415,35 @@ MCQ_API int mcq_exact_batch_hero_range_weighted(mcq_ctx *ctx, const mcq_query *q
 MCQ_API int mcq_exact_batch_hero_range_preflop(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
                                                mcq_result *rows /* [n][MCQ_HAND_ROWS] */,
                                                mcq_exact_prob *agg /* [n], may be NULL */);
+
+/* Exact range against range with WEIGHTED HANDS BEFORE THE FLOP, heads-up: mcq_exact_batch_hero_range_preflop with a weight
+ * per two-card hand on both sides -- opening, 3-bet and calling ranges as mixed strategies ("raise A5s 40 % of the time"),
+ * a reach probability per combo.  Weights are integers 0..MCQ_COMBO_WEIGHT_MAX.
+ * Accepted: exactly what mcq_exact_batch_hero_range_preflop accepts -- n_board == 0, hero_is_range == 1, n_known == 0,
+ * n_players == 2, optional ghost cards (|D| = 52 or 50), at most MCQ_HERO_PREFLOP_MAX_BATCH records.
+ * The law is always MCQ_LAW_UNIFORM, so there is no law argument, for the reason mcq_exact_batch_hero_range_weighted states.
+ * Definitions: word for word those of mcq_exact_batch_hero_range_weighted with k = 5 and D = the 52 cards minus the ghost
+ * cards.  eff_opp and eff_hero fold the class sets and the tables (entries for a hand that holds a ghost card are ignored);
+ * a hero hand h of D is allowed iff eff_hero(h) > 0, every other row is zero, and for an allowed hand, with T over the
+ * 5-subsets of D minus h and g over the two-card hands of D minus h minus T,
+ *   runs = sum_T sum_g eff_opp(g)          (at most C(48, 5) * 1081 * 65535, about 1.2e14)
+ * win, tie, by_type[9] its parts as there, passes = 0 -- integers, deterministic, linear in opp_weights.  With every
+ * opp_weights entry 1 and hero_weights == NULL rows and agg equal mcq_exact_batch_hero_range_preflop(..., MCQ_LAW_UNIFORM,
+ * ...) bit for bit.  agg[i] (agg may be NULL) = sum_h eff_hero(h) x_h / runs_h / sum_h eff_hero(h) over the allowed hands,
+ * in doubles on the host in ascending row order.
+ * Cost and launches: as mcq_exact_batch_hero_range_preflop's -- only hands of positive weight are ranked and walked, the
+ * completions go out in the same slices (MCQ_HERO_PRE_SLICE).
+ * Refused with MCQ_EINVAL, nothing launched, rows and agg untouched: whatever mcq_exact_batch_hero_range_preflop refuses
+ * (any table card and more than MCQ_HERO_PREFLOP_MAX_BATCH records among it), opp_weights == NULL, no hero hand of positive
+ * effective weight in D, and an allowed hero hand against which no opponent hand of positive effective weight is left.
+ * The last is decided on the host before the enumeration: before the flop it is exact, because a hand g with eff_opp(g) > 0
+ * that shares no card with h leaves |D| - 4 >= 5 cards for a completion that avoids both.  MCQ_EBUSY as everywhere.
+ * Not covered: the reference's law, weighted ranges in the Monte-Carlo entries, more than one opponent. */
+MCQ_API int mcq_exact_batch_hero_range_preflop_weighted(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n,
+                                                        const uint16_t *opp_weights /* [n][MCQ_HAND_ROWS] */,
+                                                        const uint16_t *hero_weights /* [n][MCQ_HAND_ROWS], may be NULL: every allowed hand weighs 1 */,
+                                                        mcq_result *rows /* [n][MCQ_HAND_ROWS] */,
+                                                        mcq_exact_prob *agg /* [n], may be NULL */);
 
 /* Exact equity PER RUNOUT, on the flop and the turn: which cards help and how much, from ONE enumeration per record.
  * Accepted: whatever mcq_exact_batch_ext_ways accepts -- hero given as two cards, 0..9 known hands each given as two cards,

@@ -141,6 +141,8 @@ def load_library():
         L.mcq_exact_batch_hero_range_weighted.restype = C.c_int
         L.mcq_exact_batch_hero_range_preflop.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
         L.mcq_exact_batch_hero_range_preflop.restype = C.c_int
+        L.mcq_exact_batch_hero_range_preflop_weighted.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
+        L.mcq_exact_batch_hero_range_preflop_weighted.restype = C.c_int
         L.mcq_exact_batch_ext_runouts.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
         L.mcq_exact_batch_ext_runouts.restype = C.c_int
         L.mcq_set_dealing_law.argtypes = [vp, C.c_int]
@@ -506,6 +508,36 @@ class Engine:
         agg = np.zeros(len(q), EXACT_PROB_DTYPE)
         rc = self._lib.mcq_exact_batch_hero_range_preflop(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code,
                                                           rows.ctypes.data, agg.ctypes.data)
+        if rc:
+            _raise(rc)
+        return rows, agg
+
+    def exact_hero_range_preflop_weighted(self, queries, ext, opp_weights, hero_weights=None):
+        """exact_hero_range_preflop with a weight per HAND on both sides, under the uniform law
+        (mcq_exact_batch_hero_range_preflop_weighted): records without table cards, at most HERO_PREFLOP_MAX_BATCH of
+        them; opp_weights and hero_weights as exact_hero_range_weighted takes them -- uint16 arrays [n, HAND_ROWS] indexed
+        by hand_index(a, b), hero_weights=None weighs every hand of the hero's classes 1, the class sets stay in force.
+        -> (rows, agg) laid out as exact_hero_range_weighted's.  A wrong shape or dtype raises ValueError, and so does a
+        hero hand of positive weight against which no opponent hand of positive weight is left (seen before anything is
+        launched)."""
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+        if len(e) != len(q):
+            raise ValueError("one mcq_query_ext per query")
+        tables = []
+        for name, w in (("opp_weights", opp_weights), ("hero_weights", hero_weights)):
+            if w is None and name == "hero_weights":
+                tables.append(None)
+                continue
+            if not isinstance(w, np.ndarray) or w.dtype != np.uint16 or w.shape != (len(q), HAND_ROWS):
+                raise ValueError("%s is a uint16 array of shape [n, HAND_ROWS] = (%d, %d)" % (name, len(q), HAND_ROWS))
+            tables.append(np.ascontiguousarray(w))
+        rows = np.zeros((len(q), HAND_ROWS), RESULT_DTYPE)
+        agg = np.zeros(len(q), EXACT_PROB_DTYPE)
+        rc = self._lib.mcq_exact_batch_hero_range_preflop_weighted(self._ctx, q.ctypes.data, e.ctypes.data, len(q),
+                                                                   tables[0].ctypes.data,
+                                                                   None if tables[1] is None else tables[1].ctypes.data,
+                                                                   rows.ctypes.data, agg.ctypes.data)
         if rc:
             _raise(rc)
         return rows, agg

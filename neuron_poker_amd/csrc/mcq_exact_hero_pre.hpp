@@ -23,6 +23,8 @@
 // Sums.  A hero hand's twelve sums stay 32-bit while one block owns at most MCQ_XP_MAX_OWNED completions (one completion
 // adds at most 2 x 1081 to tot); the host sends the completions in slices of at most that many per launch and the rows are
 // accumulated across launches with 64-bit integer atomics.
+// Weighted hands (mcq_exact_hero_pre_w_kernel, tests/hostsim_hero_preflop_weighted): the section of that name below -- the
+// same lists made from two weight tables per D-pair, the weight in the record, 64-bit sums per thread.
 #ifndef MCQ_EXACT_HERO_PRE_HPP
 #define MCQ_EXACT_HERO_PRE_HPP
 
@@ -184,7 +186,105 @@ MCQ_HD uint32_t mcq_exact_hero_pre_walk(const McqExactHeroQuery &e, const McqExa
                       : mcq_exact_hero_pre_walk_as(false, bd, qa, qb, own, live, n_live, j0, step, keys, rec, acc);
 }
 
+// ---------------------------------------------------------------------------------------------- weighted hands
+// mcq_exact_batch_hero_range_preflop_weighted: the same enumeration with an integer weight per HAND in place of the class
+// bit, MCQ_LAW_UNIFORM only -- mcq_exact_hero.hpp's "weighted hands" on D-pairs.  ow_tab / hw_tab (eff_opp / eff_hero per
+// D-pair, MCQ_XP_MAX_PAIRS entries each) are made by mcq_exact_hero_w_tables, and the three lists are made from THEM:
+//   allowed  hw_tab[rp] != 0;   live  ow_tab[rp] != 0;   ranked  their union
+// (host planning counts `allowed` from the same table, so host and every block agree).  A ranked slot's record is
+// mcq_exact_hero_w_pack(pa, pb, eff_opp); a pair that a table card touches keeps key 0 and record 0, whose weight is 0.
+// Sums.  A thread's sums of ONE completion stay 32-bit (McqExactAcc) whatever its share of the walk; they are added once
+// per completion into McqExactHeroSumsW (64-bit), so MCQ_XP_MAX_OWNED bounds nothing here -- plan and slices are kept only
+// so that launch lengths and grids stay what callers know.
+static_assert(MCQ_XP_MAX_CAND * MCQ_XH_WEIGHT_MAX < (1u << 27), "a completion's weighted sums (McqExactAcc) fit 32 bits");
+static_assert((uint64_t)MCQ_XP_MAX_OWNED * MCQ_XP_MAX_CAND * MCQ_XH_WEIGHT_MAX > 0xFFFFFFFFull,
+              "a thread's weighted sums of one launch do NOT fit 32 bits: McqExactHeroSumsW is 64-bit");
+static_assert((uint64_t)MCQ_XP_MAX_BOARDS * MCQ_XP_MAX_CAND * MCQ_XH_WEIGHT_MAX < (1ull << 48),
+              "... and 64 bits hold a hero hand's sums over all C(52, 5) completions with room");
+
+// is D-pair rp on the lists?  bit 0: allowed, bit 1: live
+MCQ_HD uint32_t mcq_exact_hero_pre_w_on(const uint16_t *ow_tab, const uint16_t *hw_tab, uint32_t rp) {
+    return (hw_tab[rp] != 0u ? 1u : 0u) | (ow_tab[rp] != 0u ? 2u : 0u);
+}
+
+// The three lists, as mcq_exact_hero_pre_lists (the kernel makes the same lists with ballots).  n[0..3) = allowed, live, ranked.
+MCQ_HD void mcq_exact_hero_pre_w_lists(const McqExactHeroQuery &e, const uint16_t *ow_tab, const uint16_t *hw_tab, uint16_t *allowed,
+                                       uint16_t *live, uint16_t *ranked, uint32_t n[3]) {
+    n[0] = n[1] = n[2] = 0u;
+    for (uint32_t rp = 0; rp < e.x.n_rp; rp++) {
+        const uint32_t on = mcq_exact_hero_pre_w_on(ow_tab, hw_tab, rp);
+        if (on == 0u) continue;
+        if (on & 1u) allowed[n[0]++] = (uint16_t)n[2];
+        if (on & 2u) live[n[1]++] = (uint16_t)n[2];
+        ranked[n[2]++] = (uint16_t)rp;
+    }
+}
+
+// Ranking pass, as mcq_exact_hero_pre_rank.
+MCQ_HD void mcq_exact_hero_pre_w_rank(const McqExactBoard &bd, uint64_t taken, uint32_t lane, uint32_t n_lanes, const uint16_t *ranked,
+                                      uint32_t n_ranked, const uint16_t *pair_xy, const McqCard *d_card, const uint16_t *ow_tab,
+                                      const uint32_t *tf, const uint32_t *tops, const uint32_t *sd, uint32_t *keys, uint32_t *rec) {
+    for (uint32_t i = lane; i < n_ranked; i += n_lanes) {
+        const uint32_t rp = ranked[i], xy = pair_xy[rp], pa = xy & 0xFFu, pb = xy >> 8;
+        uint32_t key = 0u, r = 0u; /* dead: a table card took one of its cards */
+        if ((((taken >> pa) | (taken >> pb)) & 1ull) == 0ull) {
+            McqHole h;
+            h.set(d_card[pa], d_card[pb]);
+            key = mcq_eval_key(bd.b, bd.fs, h, tf, tops, sd);
+            r = mcq_exact_hero_w_pack(pa, pb, ow_tab[rp]);
+        }
+        keys[i] = key;
+        rec[i] = r;
+    }
+}
+
+// The walk of ONE hero hand, as mcq_exact_hero_pre_walk_as: the live hands j0, j0 + step, ... as the opponent's, the
+// weight one shift.  Returns the hero hand's type.
+MCQ_HD uint32_t mcq_exact_hero_pre_w_walk_as(uint32_t qa, uint32_t qb, uint32_t own, const uint16_t *live, uint32_t n_live, uint32_t j0,
+                                             uint32_t step, const uint32_t *keys, const uint32_t *rec, McqExactAcc &acc) {
+    const uint32_t kh = keys[own];
+    for (uint32_t j = j0; j < n_live; j += step) {
+        const uint32_t s = live[j], r = rec[s], pa = r & 63u, pb = (r >> 6) & 63u;
+        const bool shared = pa == qa || pa == qb || pb == qa || pb == qb; /* (hero's own hand among them) */
+        const uint32_t w = shared ? 0u : r >> 16;                         /* a dead hand: r == 0, w == 0 */
+        const uint32_t kj = keys[s];
+        acc.win += kj < kh ? w : 0u;
+        acc.tie += kj == kh ? w : 0u;
+        acc.tot += w;
+    }
+    return mcq_key_type(kh);
+}
+
+// ... with the commonest stride (1: a group of more than 512 hands) as a constant of a copy of the loop
+MCQ_HD uint32_t mcq_exact_hero_pre_w_walk(uint32_t qa, uint32_t qb, uint32_t own, const uint16_t *live, uint32_t n_live, uint32_t j0,
+                                          uint32_t step, const uint32_t *keys, const uint32_t *rec, McqExactAcc &acc) {
+    return step == 1u ? mcq_exact_hero_pre_w_walk_as(qa, qb, own, live, n_live, j0, 1u, keys, rec, acc)
+                      : mcq_exact_hero_pre_w_walk_as(qa, qb, own, live, n_live, j0, step, keys, rec, acc);
+}
+
 // ---- host side
+// Is some opponent hand of positive weight left against EVERY allowed hero hand?  Exact whatever k: a live D-pair g that
+// shares no card with h leaves |D| - 4 >= k cards, so a completion that avoids both exists and h's row gets weight; without
+// such a g it gets none.  One pass over allowed x live D-pairs, at most 1326^2 steps, before anything is launched.
+// -> MCQ_XP_MAX_PAIRS if so, else the D-pair index of the first hero hand left without an opponent.
+MCQ_HD uint32_t mcq_exact_hero_pre_w_undealable(const McqExactHeroQuery &e, const uint16_t *ow_tab, const uint16_t *hw_tab) {
+    uint32_t rp = 0;
+    for (uint32_t qb = 1; qb < e.x.b.L; qb++)
+        for (uint32_t qa = 0; qa < qb; qa++, rp++) {
+            if (hw_tab[rp] == 0u) continue;
+            bool found = false;
+            uint32_t g = 0;
+            for (uint32_t pb = 1; pb < e.x.b.L && !found; pb++)
+                for (uint32_t pa = 0; pa < pb; pa++, g++)
+                    if (ow_tab[g] != 0u && pa != qa && pa != qb && pb != qa && pb != qb) {
+                        found = true;
+                        break;
+                    }
+            if (!found) return rp;
+        }
+    return MCQ_XP_MAX_PAIRS;
+}
+
 // The completions go out in launches of `slice`; a launch's grid gives every group of blocks `per` blocks, each of which
 // owns a run of consecutive completions of this length (the last ones fewer) -- the plan is sound iff it is at most
 // MCQ_XP_MAX_OWNED.

@@ -57,6 +57,12 @@ uint32_t mcq_exact_hero_pre_plan(const mcq_query *q, uint32_t ext, uint32_t row,
                                  uint32_t slice, McqExactExtJob *job);
 hipError_t mcq_launch_exact_hero_pre(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
                                      uint32_t lo, uint32_t hi, mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
+/* ... before the flop with a weight per hand, uniform law (mcq_exact_hero_pre_w_kernel): the jobs of mcq_exact_hero_pre_plan
+ * (n_allowed counted from the hero's folded table), the slices of mcq_launch_exact_hero_pre and the weight tables of
+ * mcq_launch_exact_hero_w.  The 64-bit sums per thread need no bound on the completions a block owns. */
+hipError_t mcq_launch_exact_hero_pre_w(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext,
+                                       const uint16_t *d_wts, bool hero_w, uint32_t lo, uint32_t hi, mcq_result *d_rows,
+                                       const McqTables *d_luts, hipStream_t s);
 /* per-runout enumeration (mcq_exact_runout.hpp): flop and turn records with at most one random opponent, jobs planned by
  * mcq_exact_ext_plan (kind 0 or 1, job->row = the record's index); d_cards holds 52 and d_pairs MCQ_HAND_ROWS zeroed
  * mcq_result_ways rows per record.  The second launch takes the jobs of both kinds and fills the card rows of the flop

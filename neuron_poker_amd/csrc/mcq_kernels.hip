@@ -2604,6 +2604,127 @@ __global__ __launch_bounds__(1024) void mcq_exact_hero_pre_kernel(const McqExact
     }
 }
 
+// ---------------------------------------------------------------------------------------------- exact enumeration, hero range, preflop, weighted hands
+// mcq_exact_hero_pre_kernel with an integer weight per hand (mcq_exact_hero_pre.hpp, "weighted hands"): the uniform law
+// only.  The same block shape, runs of consecutive completions, ballot-made lists, two barriers per completion and shared
+// walks; wts as mcq_exact_hero_w_kernel's (per query row the opponent's [1326] uint16 table, then the hero's; hero_w == 0:
+// every hand of the hero's classes weighs 1).  The tables are folded once per block into ow_tab / hw_tab (LDS, per D-pair)
+// and the lists' two predicates are read from them.  A completion's sums are 32-bit; they are added ONCE per completion
+// into twelve 64-bit sums per thread, which go out by the same integer atomics -- so no bound on the completions a block
+// owns is needed.
+// LDS: 97 KB of tables + 10.6 KB of keys and records + 8 KB of lists + 2.6 KB of D-pairs + 5.3 KB of weights, one block of
+// 16 waves per CU.
+__global__ __launch_bounds__(1024) void mcq_exact_hero_pre_w_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
+                                                                    const uint16_t *__restrict__ wts, uint32_t hero_w, uint32_t lo,
+                                                                    uint32_t hi, unsigned long long *__restrict__ rows,
+                                                                    const McqTables *__restrict__ g_tab) {
+    const McqExactExtJob job = jobs[blockIdx.y];
+    if (blockIdx.x >= job.grid || lo >= job.n_boards) return;
+    constexpr uint32_t kChunks = (MCQ_XP_MAX_PAIRS + 63u) / 64u;
+    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ uint16_t pair_xy[MCQ_XP_MAX_PAIRS]; /* every D-pair: qa | qb << 8 */
+    __shared__ uint32_t xw[MCQ_EXT_WORDS];
+    __shared__ McqExactHeroQuery xq;
+    __shared__ uint8_t r_id[64];
+    __shared__ McqCard d_card[64];
+    __shared__ uint16_t ow_tab[MCQ_XP_MAX_PAIRS], hw_tab[MCQ_XP_MAX_PAIRS];
+    __shared__ uint16_t allowed[MCQ_XP_MAX_PAIRS], live[MCQ_XP_MAX_PAIRS], ranked[MCQ_XP_MAX_PAIRS];
+    __shared__ uint32_t chunk_cnt[3][kChunks];
+    __shared__ uint32_t keys[MCQ_XP_MAX_PAIRS + 2u];
+    __shared__ uint32_t recs[MCQ_XP_MAX_PAIRS + 2u];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
+    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
+    for (uint32_t i = tid; i < MCQ_XP_MAX_PAIRS; i += blockDim.x) {
+        uint32_t x, y;
+        mcq_exact_pair_xy(i, x, y);
+        pair_xy[i] = (uint16_t)(x | (y << 8));
+    }
+    load_tables(tab, g_tab); /* ends with a barrier */
+    if (tid == 0) {
+        const McqExtRec er = {xw};
+        (void)mcq_exact_hero_pre_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, MCQ_LAW_UNIFORM, xq); /* validated by the host */
+        mcq_exact_ext_r_ids(xq.x, r_id);
+    }
+    __syncthreads();
+    const McqExactHeroQuery &e = xq;
+    if (tid < e.x.b.L) d_card[tid] = mcq_card(r_id[tid]);
+    const uint16_t *w_opp = wts + (size_t)job.row * 2u * MCQ_XH_ROWS;
+    mcq_exact_hero_w_tables(e, r_id, w_opp, hero_w ? w_opp + MCQ_XH_ROWS : nullptr, tid, blockDim.x, ow_tab, hw_tab);
+    __syncthreads();
+    /* the lists in ascending order (every block makes the same ones): 64 D-pairs per wave and pass */
+    for (uint32_t c = wib; c < kChunks; c += 16u) {
+        const uint32_t rp = c * 64u + lane;
+        const uint32_t on = rp < e.x.n_rp ? mcq_exact_hero_pre_w_on(ow_tab, hw_tab, rp) : 0u;
+        const unsigned long long ma = __ballot((on & 1u) != 0u), ml = __ballot((on & 2u) != 0u);
+        if (lane == 0u) {
+            chunk_cnt[0][c] = (uint32_t)__popcll(ma);
+            chunk_cnt[1][c] = (uint32_t)__popcll(ml);
+            chunk_cnt[2][c] = (uint32_t)__popcll(ma | ml);
+        }
+    }
+    __syncthreads();
+    for (uint32_t c = wib; c < kChunks; c += 16u) {
+        const uint32_t rp = c * 64u + lane;
+        const uint32_t on = rp < e.x.n_rp ? mcq_exact_hero_pre_w_on(ow_tab, hw_tab, rp) : 0u;
+        const unsigned long long ma = __ballot((on & 1u) != 0u), ml = __ballot((on & 2u) != 0u), below = (1ull << lane) - 1ull;
+        uint32_t base_a = 0, base_l = 0, base_r = 0;
+        for (uint32_t j = 0; j < c; j++) {
+            base_a += chunk_cnt[0][j];
+            base_l += chunk_cnt[1][j];
+            base_r += chunk_cnt[2][j];
+        }
+        const uint32_t slot = base_r + (uint32_t)__popcll((ma | ml) & below);
+        if (on != 0u) ranked[slot] = (uint16_t)rp;
+        if (on & 1u) allowed[base_a + (uint32_t)__popcll(ma & below)] = (uint16_t)slot;
+        if (on & 2u) live[base_l + (uint32_t)__popcll(ml & below)] = (uint16_t)slot;
+    }
+    uint32_t n_allowed = 0, n_live = 0, n_ranked = 0;
+    for (uint32_t j = 0; j < kChunks; j++) {
+        n_allowed += chunk_cnt[0][j];
+        n_live += chunk_cnt[1][j];
+        n_ranked += chunk_cnt[2][j];
+    }
+    __syncthreads();
+
+    const uint32_t groups = job.groups, group = blockIdx.x % groups, first = group * blockDim.x;
+    const uint32_t n_g = n_allowed > first ? (n_allowed - first < blockDim.x ? n_allowed - first : blockDim.x) : 0u;
+    const uint32_t share = mcq_exact_hero_pre_share(n_g), hand = tid / share, sub = tid - hand * share;
+    const bool own = hand < n_g;
+    const uint32_t own_slot = own ? allowed[first + hand] : 0u;
+    const uint32_t hxy = pair_xy[n_ranked ? ranked[own_slot] : 0u], qa = hxy & 0xFFu, qb = hxy >> 8;
+    /* the block's run of consecutive completions: the first one unranked, the others by stepping */
+    const uint32_t end = hi < job.n_boards ? hi : job.n_boards, run = mcq_exact_hero_pre_owned(end - lo, job.grid / groups);
+    const uint32_t b0 = lo + (blockIdx.x / groups) * run, b1 = end - b0 < run ? end : b0 + run;
+    McqExactHeroSumsW s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+    uint32_t pos[5];
+    if (b0 < end) mcq_exact_unrank(b0, e.x.b.L, e.x.b.k, pos);
+    for (uint32_t board = b0; board < b1 && b0 < end; board++) {
+        if (board != b0) mcq_exact_hero_pre_next(pos, e.x.b.k);
+        McqExactBoard bd;
+        mcq_exact_hero_board(e.x.b, pos, r_id, bd);
+        const uint64_t taken = mcq_exact_hero_pre_mask(e.x.b, pos);
+        __syncthreads(); /* the previous completion's walk is done with keys and records */
+        mcq_exact_hero_pre_w_rank(bd, taken, tid, blockDim.x, ranked, n_ranked, pair_xy, d_card, ow_tab, g_tab->tf, tab.tops, tab.sd, keys,
+                                  recs);
+        __syncthreads();
+        if (own && keys[own_slot] != 0u) {
+            McqExactAcc acc = {0, 0, 0};
+            const uint32_t type = mcq_exact_hero_pre_w_walk(qa, qb, own_slot, live, n_live, sub, share, keys, recs, acc);
+            mcq_exact_hero_w_add(s, acc, type);
+        }
+    }
+    if (own) {
+        unsigned long long *dst = rows + ((size_t)job.row * MCQ_XH_ROWS + mcq_exact_hero_row(r_id, qa, qb)) * 13u;
+        /* an mcq_result row: runs, passes, win, tie, by_type[9] */
+        if (s.tot) atomicAdd(dst + 0, s.tot);
+        if (s.win) atomicAdd(dst + 2, s.win);
+        if (s.tie) atomicAdd(dst + 3, s.tie);
+#pragma unroll
+        for (uint32_t t = 0; t < 9; t++)
+            if (s.type[t]) atomicAdd(dst + 4 + t, s.type[t]);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- exact enumeration, per runout
 // See mcq_exact_runout.hpp; the shape of mcq_exact_ext_kernel<KIND, MCQ_ROW_WAYS>, kinds 0 and 1 (LDS: the same 97 KB
 // table image, pair list, range bits and per-wave rem_card / rem_pos), with flop and turn records only.  The sums of a
@@ -3061,6 +3182,16 @@ hipError_t mcq_launch_exact_hero_pre(const McqExactExtJob *d_jobs, uint32_t n_jo
     if (n_jobs > 65535u || max_grid == 0 || lo >= hi || hi - lo > MCQ_XP_MAX_OWNED) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mcq_exact_hero_pre_kernel, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, lo, hi,
                        reinterpret_cast<unsigned long long *>(d_rows), d_luts);
+    return hipGetLastError();
+}
+
+hipError_t mcq_launch_exact_hero_pre_w(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext,
+                                       const uint16_t *d_wts, bool hero_w, uint32_t lo, uint32_t hi, mcq_result *d_rows,
+                                       const McqTables *d_luts, hipStream_t s) {
+    if (n_jobs == 0) return hipSuccess;
+    if (n_jobs > 65535u || max_grid == 0 || !d_wts || lo >= hi || hi - lo > MCQ_XP_MAX_OWNED) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mcq_exact_hero_pre_w_kernel, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, d_wts, hero_w ? 1u : 0u, lo,
+                       hi, reinterpret_cast<unsigned long long *>(d_rows), d_luts);
     return hipGetLastError();
 }
 

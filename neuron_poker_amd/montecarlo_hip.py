@@ -34,7 +34,7 @@ import numpy as np
 from . import _lib
 from .cards import TYPES, card_id, card_str
 
-__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_range_equity_exact_weighted", "quantise_weight", "get_preflop_range_equity_exact", "preflop_class_table", "get_runout_equities", "MonteCarlo", "seed",
+__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_range_equity_exact_weighted", "quantise_weight", "get_preflop_range_equity_exact", "get_preflop_range_equity_exact_weighted", "preflop_class_table", "get_runout_equities", "MonteCarlo", "seed",
            "configure"]
 
 _state = {"couple_numpy": False,
@@ -591,7 +591,12 @@ def get_range_equity_exact_weighted(hero, table_cards, opponent, ghost_cards='',
     ext = _lib.pack_query_ext(1, ghost=ghost, hero_range=hero_bits, opp_range=opp_bits)
     eng = engine or _lib.default_engine()
     rows, _ = eng.exact_hero_range_weighted(q, ext, opp_w, hero_w)
-    r = rows[0]
+    return _weighted_rows_to_hands(rows[0], hero_w, ties)
+
+
+def _weighted_rows_to_hands(r, hero_w, ties):
+    """The HAND_ROWS rows of one weighted record -> (equity, {(card, card): (equity_h, weight_h)}); hero_w = the hero's
+    table [1, HAND_ROWS] or None (every hand 1)."""
     live = np.flatnonzero(r["runs"])
     tie = r["tie"][live].astype(np.float64)
     eq = (r["win"][live] + (tie / 2.0 if ties == "split" else tie)) / r["runs"][live]
@@ -671,6 +676,39 @@ def get_preflop_range_equity_exact(hero_range, opponent_range=1, dealing="refere
     eng = engine or _lib.default_engine()
     rows, _ = eng.exact_hero_range_preflop(q, ext, dealing)
     equity, hands = _range_rows_to_hands(rows[0], set(ghost or []), dealing in ("uniform", 1), ties)
+    if by_class:
+        return equity, hands, preflop_class_table(hands)
+    return equity, hands
+
+
+def get_preflop_range_equity_exact_weighted(hero, opponent, ghost_cards='', engine=None, ties="credited", by_class=False):
+    """Exact equity of a WEIGHTED hero range against one opponent with a weighted range BEFORE THE FLOP, every hand equally
+    likely but for its weight (mcq_exact_batch_hero_range_preflop_weighted; the uniform law): opening, 3-bet and calling
+    ranges as mixed strategies.
+
+    hero and opponent are given exactly as get_range_equity_exact_weighted takes them -- a set of class strings or a top
+    fraction (every hand of it weighs 1), or a dict of weights in [0, 1] keyed by class string ('A5S': 0.4) or by hand
+    (('AH', 'KH'): 1.0), quantised by quantise_weight.  -> (equity, {(card, card): (equity_h, weight_h)}) as that function
+    returns it; by_class=True adds the class table {class string: (equity, weight)} of preflop_class_table.  A hero hand
+    against which no opponent hand of positive weight is left raises ValueError."""
+    if ties not in ("credited", "split"):
+        raise ValueError("ties must be 'credited' or 'split'")
+    hero_bits, hero_w = _weighted_range(hero, "hero")
+    opp_bits, opp_w = _weighted_range(opponent, "opponent")
+    if not np.asarray(hero_bits).any():
+        raise ValueError("hero names no preflop class")
+    if opp_w is None:
+        opp_w = np.ones((1, _lib.HAND_ROWS), np.uint16)
+    ghost = None
+    if ghost_cards != '' and ghost_cards is not None:
+        if len(ghost_cards) != 2:
+            raise ValueError("ghost_cards is two cards or ''")
+        ghost = [card_id(ghost_cards[0]), card_id(ghost_cards[1])]
+    q = _lib.pack_query_one([0, 0], [], 2, 1)
+    ext = _lib.pack_query_ext(1, ghost=ghost, hero_range=hero_bits, opp_range=opp_bits)
+    eng = engine or _lib.default_engine()
+    rows, _ = eng.exact_hero_range_preflop_weighted(q, ext, opp_w, hero_w)
+    equity, hands = _weighted_rows_to_hands(rows[0], hero_w, ties)
     if by_class:
         return equity, hands, preflop_class_table(hands)
     return equity, hands
