@@ -339,6 +339,39 @@ def pack_query_ext(n, ghost=None, known2=None, hero_range=None, opp_range=None, 
     return e
 
 
+def _hero_weight_table(name, w, n):
+    """a weight table of exact_hero_range*_weighted: uint16 [n, HAND_ROWS], contiguous"""
+    if not isinstance(w, np.ndarray) or w.dtype != np.uint16 or w.shape != (n, HAND_ROWS):
+        raise ValueError("%s is a uint16 array of shape [n, HAND_ROWS] = (%d, %d)" % (name, n, HAND_ROWS))
+    return np.ascontiguousarray(w)
+
+
+def _hero_range(eng, entry, queries, ext, law=None, weights=None):
+    """What the four Engine.exact_hero_range* methods share: the law (weights is None) or the (opp_weights, hero_weights)
+    tables, the records, the output arrays, the call of the library's `entry`.  Every ValueError is raised before the
+    engine is touched.  -> (rows, agg)"""
+    if weights is None:
+        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
+        if code is None:
+            raise ValueError("law must be 'reference' or 'uniform'")
+    q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+    e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
+    if len(e) != len(q):
+        raise ValueError("one mcq_query_ext per query")
+    if weights is None:
+        mid = (code,)
+    else:
+        opp = _hero_weight_table("opp_weights", weights[0], len(q))
+        hero = None if weights[1] is None else _hero_weight_table("hero_weights", weights[1], len(q))
+        mid = (opp.ctypes.data, None if hero is None else hero.ctypes.data)
+    rows = np.zeros((len(q), HAND_ROWS), RESULT_DTYPE)
+    agg = np.zeros(len(q), EXACT_PROB_DTYPE)
+    rc = getattr(eng._lib, entry)(eng._ctx, q.ctypes.data, e.ctypes.data, len(q), *mid, rows.ctypes.data, agg.ctypes.data)
+    if rc:
+        _raise(rc)
+    return rows, agg
+
+
 class Engine:
     """One mcq_ctx: an equity engine bound to one GPU.  Not re-entrant: one call in flight per engine -- a second thread
     calling into the same Engine meanwhile gets McqBusyError (the library checks).  One Engine per thread."""
@@ -449,20 +482,7 @@ class Engine:
         of RESULT_DTYPE -- row hand_index(a, b) holds, for every hand of the hero's range that the deck can make, the
         integer weights exact_ext gives the same record with the hero holding a and b, every other row is zero -- and
         agg[n] of EXACT_PROB_DTYPE, the rows combined with the weights by which the law deals hero his hands."""
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
-        rows = np.zeros((len(q), HAND_ROWS), RESULT_DTYPE)
-        agg = np.zeros(len(q), EXACT_PROB_DTYPE)
-        rc = self._lib.mcq_exact_batch_hero_range(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, rows.ctypes.data,
-                                                  agg.ctypes.data)
-        if rc:
-            _raise(rc)
-        return rows, agg
+        return _hero_range(self, "mcq_exact_batch_hero_range", queries, ext, law=law)
 
     def exact_hero_range_weighted(self, queries, ext, opp_weights, hero_weights=None):
         """exact_hero_range with a weight per HAND on both sides, under the uniform law
@@ -471,46 +491,14 @@ class Engine:
         in force (a hand outside its set weighs 0).  -> (rows, agg) laid out as exact_hero_range's: per hero hand of
         positive weight runs = the opponent's total weight, win, tie and by_type its parts; agg combines the rows with the
         hero's weights.  A wrong shape or dtype raises ValueError."""
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
-        tables = []
-        for name, w in (("opp_weights", opp_weights), ("hero_weights", hero_weights)):
-            if w is None and name == "hero_weights":
-                tables.append(None)
-                continue
-            if not isinstance(w, np.ndarray) or w.dtype != np.uint16 or w.shape != (len(q), HAND_ROWS):
-                raise ValueError("%s is a uint16 array of shape [n, HAND_ROWS] = (%d, %d)" % (name, len(q), HAND_ROWS))
-            tables.append(np.ascontiguousarray(w))
-        rows = np.zeros((len(q), HAND_ROWS), RESULT_DTYPE)
-        agg = np.zeros(len(q), EXACT_PROB_DTYPE)
-        rc = self._lib.mcq_exact_batch_hero_range_weighted(self._ctx, q.ctypes.data, e.ctypes.data, len(q), tables[0].ctypes.data,
-                                                           None if tables[1] is None else tables[1].ctypes.data,
-                                                           rows.ctypes.data, agg.ctypes.data)
-        if rc:
-            _raise(rc)
-        return rows, agg
+        return _hero_range(self, "mcq_exact_batch_hero_range_weighted", queries, ext, weights=(opp_weights, hero_weights))
 
     def exact_hero_range_preflop(self, queries, ext, law="reference"):
         """Exact range against range BEFORE THE FLOP, heads-up (mcq_exact_batch_hero_range_preflop): records without
         table cards, hero_is_range = 1, no known hands, one random opponent drawn from opp_range; at most
         HERO_PREFLOP_MAX_BATCH of them.  -> (rows, agg) laid out as exact_hero_range's.  A record takes from tens of
         milliseconds (narrow ranges) to seconds (every hand against every hand)."""
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
-        rows = np.zeros((len(q), HAND_ROWS), RESULT_DTYPE)
-        agg = np.zeros(len(q), EXACT_PROB_DTYPE)
-        rc = self._lib.mcq_exact_batch_hero_range_preflop(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code,
-                                                          rows.ctypes.data, agg.ctypes.data)
-        if rc:
-            _raise(rc)
-        return rows, agg
+        return _hero_range(self, "mcq_exact_batch_hero_range_preflop", queries, ext, law=law)
 
     def exact_hero_range_preflop_weighted(self, queries, ext, opp_weights, hero_weights=None):
         """exact_hero_range_preflop with a weight per HAND on both sides, under the uniform law
@@ -520,27 +508,8 @@ class Engine:
         -> (rows, agg) laid out as exact_hero_range_weighted's.  A wrong shape or dtype raises ValueError, and so does a
         hero hand of positive weight against which no opponent hand of positive weight is left (seen before anything is
         launched)."""
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
-        tables = []
-        for name, w in (("opp_weights", opp_weights), ("hero_weights", hero_weights)):
-            if w is None and name == "hero_weights":
-                tables.append(None)
-                continue
-            if not isinstance(w, np.ndarray) or w.dtype != np.uint16 or w.shape != (len(q), HAND_ROWS):
-                raise ValueError("%s is a uint16 array of shape [n, HAND_ROWS] = (%d, %d)" % (name, len(q), HAND_ROWS))
-            tables.append(np.ascontiguousarray(w))
-        rows = np.zeros((len(q), HAND_ROWS), RESULT_DTYPE)
-        agg = np.zeros(len(q), EXACT_PROB_DTYPE)
-        rc = self._lib.mcq_exact_batch_hero_range_preflop_weighted(self._ctx, q.ctypes.data, e.ctypes.data, len(q),
-                                                                   tables[0].ctypes.data,
-                                                                   None if tables[1] is None else tables[1].ctypes.data,
-                                                                   rows.ctypes.data, agg.ctypes.data)
-        if rc:
-            _raise(rc)
-        return rows, agg
+        return _hero_range(self, "mcq_exact_batch_hero_range_preflop_weighted", queries, ext,
+                           weights=(opp_weights, hero_weights))
 
     def exact_ext_ways(self, queries, ext, law="reference"):
         """exact_ext with the ties split by the hands that share the pot (mcq_exact_batch_ext_ways; at most ONE random

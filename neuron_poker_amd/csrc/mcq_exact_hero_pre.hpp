@@ -1,6 +1,7 @@
 // mcq_exact_hero_pre.hpp -- exact enumeration with the HERO given as a range BEFORE THE FLOP: every hero hand against one
 // random opponent (ranged or not) from ONE enumeration of the C(|D|, 5) table completions; lane code shared by
-// mcq_exact_hero_pre_kernel (mcq_kernels.hip) and the host build of the tests (tests/hostsim_hero_preflop).
+// mcq_exact_hero_pre_kernel and mcq_exact_hero_pre_w_kernel (mcq_kernels.hip) and the host builds of the tests
+// (tests/hostsim_hero_preflop, tests/hostsim_hero_preflop_weighted).
 //
 // The mathematics is mcq_exact_hero.hpp's -- its opening comment is the specification: the opponent's weight is
 // mcq_exact_ext_w2 with the hero's hand as the hand that left the deck, under MCQ_LAW_REFERENCE a completion counts iff
@@ -15,16 +16,17 @@
 // record 0, whose range bits give weight 0 under both laws).  Three ascending lists per query:
 //   ranked   the D-pairs that are ranked per completion = allowed + live, as D-pair indices;
 //   allowed  the hero hands whose class is in hero_range, as SLOTS of `ranked`;
-//   live     the D-pairs whose range bits (mcq_exact_ext_cbits) are not 0 -- the only hands the opponent can ever hold,
-//            whatever hero holds: mcq_exact_ext_w2 of range bits 0 is 0 --, as slots of `ranked`.
+//   live     the D-pairs whose entry in the opponent's table (McqHeroKind<W>::opp_t: the range bits of mcq_exact_ext_cbits,
+//            or eff_opp) is not 0 -- the only hands the opponent can ever hold, whatever hero holds: mcq_exact_ext_w2 of
+//            range bits 0 is 0 --, as slots of `ranked`.
 // Keys and records are kept per slot; a hero hand walks `live` only and finds its own key at its own slot, so rank and walk
 // cost what the ranges leave, not 1326 x 1081.  A group of few hero hands shares each hand's walk among several threads
 // (mcq_exact_hero_pre_share).
 // Sums.  A hero hand's twelve sums stay 32-bit while one block owns at most MCQ_XP_MAX_OWNED completions (one completion
 // adds at most 2 x 1081 to tot); the host sends the completions in slices of at most that many per launch and the rows are
 // accumulated across launches with 64-bit integer atomics.
-// Weighted hands (mcq_exact_hero_pre_w_kernel, tests/hostsim_hero_preflop_weighted): the section of that name below -- the
-// same lists made from two weight tables per D-pair, the weight in the record, 64-bit sums per thread.
+// Weighted hands (McqHeroKind<true>: mcq_exact_hero_pre_w_kernel): the same lists made from the two weight tables per
+// D-pair, the weight in the record, 64-bit sums per thread -- see "weighted hands" below for what that changes.
 #ifndef MCQ_EXACT_HERO_PRE_HPP
 #define MCQ_EXACT_HERO_PRE_HPP
 
@@ -48,56 +50,22 @@ static_assert(MCQ_XP_MAX_D - 1u < 64u, "D-positions fit the 6-bit fields of mcq_
  * binomial met is C(51, 5) = 2 349 060, and it is multiplied by at most 51 before the exact division. */
 static_assert(2349060ull * 51ull < (1ull << 32), "mcq_exact_unrank at L = 52, k = 5");
 
-// The query of a record with ANY number of table cards (mcq_exact_hero_query refuses fewer than three); the other
-// refusals are its own, in its order.
-MCQ_HD int mcq_exact_hero_pre_query(const McqQueryWords &q, const McqExtRec &er, int law, McqExactHeroQuery &e) {
-    if (!mcq_query_ext_valid(q, er)) return MCQ_XH_INVALID;
-    if (!er.hero_is_range()) return MCQ_XH_NOT_RANGE;
-    if (er.n_known() != 0u) return MCQ_XH_KNOWN;
-    if (q.n_players() != 2u) return MCQ_XH_PLAYERS;
-    const uint64_t deck = mcq_ext_base_deck(q, er);
-    McqExactExtQuery &x = e.x;
-    x.n_known = 0u;
-    for (uint32_t h = 0; h < MCQ_MAX_KNOWN; h++) x.known[h] = 0u;
-    x.b.deck_lo = (uint32_t)deck;
-    x.b.deck_hi = (uint32_t)(deck >> 32);
-    x.b.L = mcq_popc(x.b.deck_lo) + mcq_popc(x.b.deck_hi);
-    x.b.k = 5u - q.n_board();
-    x.b.n_opp = 1u;
-    x.b.ref_law = law == MCQ_LAW_REFERENCE;
-    x.b.known.clear();
-    for (uint32_t i = 0; i < q.n_board(); i++) x.b.known.add(mcq_card(q.card(2u + i)));
-    x.b.hero.set(mcq_card(0u), mcq_card(1u)); /* (nobody's: every hero hand is a D-pair) */
-    x.m = x.b.L - x.b.k;
-    x.n_pairs = x.m * (x.m - 1u) / 2u;
-    x.n_rp = x.b.L * (x.b.L - 1u) / 2u;
-    x.ranged = !mcq_ext_opp_all(er);
-    for (uint32_t i = 0; i < 6; i++) {
-        x.bits[i] = er.w[er.opp_set() + i];
-        e.hero_bits[i] = er.w[er.hero_set() + i];
-    }
-    e.n_allowed = 0u; /* the host counts them: mcq_exact_hero_pre_lists */
-    return MCQ_XH_OK;
-}
+// The query of a record with ANY number of table cards is mcq_exact_hero_query without need_flop.
 
-// is D-pair (qa < qb) on the lists?  bit 0: allowed, bit 1: live
-MCQ_HD uint32_t mcq_exact_hero_pre_on(const McqExactHeroQuery &e, const uint8_t *r_id, const uint8_t *cb_tab, uint32_t rp,
-                                      uint32_t qa, uint32_t qb) {
-    return (mcq_exact_hero_allowed(e, r_id, qa, qb) ? 1u : 0u) | (cb_tab[rp] != 0u ? 2u : 0u);
-}
-
-// The three lists, one D-pair after the other (the kernel makes the same lists with ballots); cb_tab from
-// mcq_exact_ext_cb_table, MCQ_XP_MAX_PAIRS entries each.  n[0..3) = allowed, live, ranked.
-MCQ_HD void mcq_exact_hero_pre_lists(const McqExactHeroQuery &e, const uint8_t *r_id, const uint8_t *cb_tab, uint16_t *allowed,
-                                     uint16_t *live, uint16_t *ranked, uint32_t n[3]) {
+// The three lists, one D-pair after the other (the kernel makes the same lists with ballots); opp_tab from
+// mcq_exact_ext_cb_table or ow_tab, hw_tab for W = true only, MCQ_XP_MAX_PAIRS entries each.  n[0..3) = allowed, live,
+// ranked.  (Host planning counts `allowed` by mcq_exact_hero_count, from the same predicate: host and every block agree.)
+template <bool W>
+MCQ_HD void mcq_exact_hero_pre_lists(const McqExactHeroQuery &e, const uint8_t *r_id, const typename McqHeroKind<W>::opp_t *opp_tab,
+                                     const uint16_t *hw_tab, uint16_t *allowed, uint16_t *live, uint16_t *ranked, uint32_t n[3]) {
     n[0] = n[1] = n[2] = 0u;
     uint32_t rp = 0;
     for (uint32_t qb = 1; qb < e.x.b.L; qb++)
         for (uint32_t qa = 0; qa < qb; qa++, rp++) {
-            const uint32_t on = mcq_exact_hero_pre_on(e, r_id, cb_tab, rp, qa, qb);
-            if (on == 0u) continue;
-            if (on & 1u) allowed[n[0]++] = (uint16_t)n[2];
-            if (on & 2u) live[n[1]++] = (uint16_t)n[2];
+            const bool is_allowed = McqHeroKind<W>::allowed(e, r_id, hw_tab, rp, qa, qb), is_live = opp_tab[rp] != 0u;
+            if (!is_allowed && !is_live) continue;
+            if (is_allowed) allowed[n[0]++] = (uint16_t)n[2];
+            if (is_live) live[n[1]++] = (uint16_t)n[2];
             ranked[n[2]++] = (uint16_t)rp;
         }
 }
@@ -128,12 +96,13 @@ MCQ_HD void mcq_exact_hero_pre_next(uint32_t pos[5], uint32_t k) {
         }
 }
 
-// Ranking pass, lane `lane` of `n_lanes`: key and packed record of the slots lane, lane + n_lanes, ... of `ranked`
-// (pair_xy[rp] = qa | qb << 8, d_card[p] = mcq_card(r_id[p]), taken = mcq_exact_hero_pre_mask).
+// Ranking pass, lane `lane` of `n_lanes`: key and packed record (McqHeroKind<W>::pack) of the slots lane, lane + n_lanes,
+// ... of `ranked` (pair_xy[rp] = qa | qb << 8, d_card[p] = mcq_card(r_id[p]), taken = mcq_exact_hero_pre_mask).
+template <bool W>
 MCQ_HD void mcq_exact_hero_pre_rank(const McqExactHeroQuery &e, const McqExactBoard &bd, uint64_t taken, uint32_t lane,
                                     uint32_t n_lanes, const uint16_t *ranked, uint32_t n_ranked, const uint16_t *pair_xy,
-                                    const McqCard *d_card, const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops,
-                                    const uint32_t *sd, uint32_t *keys, uint32_t *rec) {
+                                    const McqCard *d_card, const typename McqHeroKind<W>::opp_t *opp_tab, const uint32_t *tf,
+                                    const uint32_t *tops, const uint32_t *sd, uint32_t *keys, uint32_t *rec) {
     for (uint32_t i = lane; i < n_ranked; i += n_lanes) {
         const uint32_t rp = ranked[i], xy = pair_xy[rp], pa = xy & 0xFFu, pb = xy >> 8;
         uint32_t key = 0u, r = 0u; /* dead: a table card took one of its cards */
@@ -141,7 +110,7 @@ MCQ_HD void mcq_exact_hero_pre_rank(const McqExactHeroQuery &e, const McqExactBo
             McqHole h;
             h.set(d_card[pa], d_card[pb]);
             key = mcq_eval_key(bd.b, bd.fs, h, tf, tops, sd);
-            r = mcq_exact_ext_pack(pa, pb, bd.top, e.x.b.k != 0u, cb_tab[rp]);
+            r = McqHeroKind<W>::pack(pa, pb, bd.top, e.x.b.k != 0u, opp_tab[rp]);
         }
         keys[i] = key;
         rec[i] = r;
@@ -156,17 +125,20 @@ MCQ_HD uint32_t mcq_exact_hero_pre_share(uint32_t n_g) {
     return s > 64u ? 64u : s < 1u ? 1u : s;
 }
 
-// The walk of ONE hero hand h = D-positions qa < qb at slot `own` (keys[own] != 0: the completion left it alive): the
-// live hands j0, j0 + step, ... as the opponent's.  Returns the hero hand's type.
-MCQ_HD uint32_t mcq_exact_hero_pre_walk_as(const bool ref, const McqExactBoard &bd, uint32_t qa, uint32_t qb, uint32_t own,
-                                           const uint16_t *live, uint32_t n_live, uint32_t j0, uint32_t step, const uint32_t *keys,
-                                           const uint32_t *rec, McqExactAcc &acc) {
+// The class-bit walk of ONE hero hand h = D-positions qa < qb at slot `own` (keys[own] != 0: the completion left it alive):
+// the live hands j0, j0 + step, ... as the opponent's (a dead one: record 0, weight 0).  A loop of its own beside
+// mcq_exact_hero_walk_as: through that one it was measured 0.2 to 2.8 % FASTER on the two larger shapes under both laws,
+// below what the same code gives against itself (profiles/hero_refactor_ab.txt, "discarded variants") -- a loop that the
+// compiler laid out anew, whose other shapes nobody has measured.  Returns the hero hand's type.
+MCQ_HD uint32_t mcq_exact_hero_pre_walk_bits(const bool ref, const McqExactBoard &bd, uint32_t qa, uint32_t qb, uint32_t own,
+                                             const uint16_t *live, uint32_t n_live, uint32_t j0, uint32_t step, const uint32_t *keys,
+                                             const uint32_t *rec, McqExactAcc &acc) {
     const uint32_t kh = keys[own], ah = mcq_exact_ext_above(rec[own]);
     for (uint32_t j = j0; j < n_live; j += step) {
         const uint32_t s = live[j], r = rec[s], pa = r & 63u, pb = (r >> 6) & 63u;
         const bool shared = pa == qa || pa == qb || pb == qa || pb == qb; /* (hero's own hand among them) */
         const bool ok = !shared && (!ref || ah + mcq_exact_ext_above(r) < bd.u);
-        const uint32_t w = ok ? mcq_exact_ext_w2(ref, mcq_exact_ext_cb(r), pa, pb, qa, qb) : 0u; /* a dead hand: r == 0, w == 0 */
+        const uint32_t w = ok ? mcq_exact_ext_w2(ref, mcq_exact_ext_cb(r), pa, pb, qa, qb) : 0u;
         const uint32_t kj = keys[s];
         acc.win += kj < kh ? w : 0u;
         acc.tie += kj == kh ? w : 0u;
@@ -175,92 +147,36 @@ MCQ_HD uint32_t mcq_exact_hero_pre_walk_as(const bool ref, const McqExactBoard &
     return mcq_key_type(kh);
 }
 
-// ... with the law and the commonest stride (1: a group of more than 512 hands) as constants of four copies of the loop
+// The walk of one hero hand, with the commonest stride (1: a group of more than 512 hands) and, W = false, the law as
+// constants of two or four copies of the loop (W = true: mcq_exact_hero_walk_as over `live`, the uniform law only).
+template <bool W>
 MCQ_HD uint32_t mcq_exact_hero_pre_walk(const McqExactHeroQuery &e, const McqExactBoard &bd, uint32_t qa, uint32_t qb, uint32_t own,
                                         const uint16_t *live, uint32_t n_live, uint32_t j0, uint32_t step, const uint32_t *keys,
                                         const uint32_t *rec, McqExactAcc &acc) {
-    if (e.x.b.ref_law)
-        return step == 1u ? mcq_exact_hero_pre_walk_as(true, bd, qa, qb, own, live, n_live, j0, 1u, keys, rec, acc)
-                          : mcq_exact_hero_pre_walk_as(true, bd, qa, qb, own, live, n_live, j0, step, keys, rec, acc);
-    return step == 1u ? mcq_exact_hero_pre_walk_as(false, bd, qa, qb, own, live, n_live, j0, 1u, keys, rec, acc)
-                      : mcq_exact_hero_pre_walk_as(false, bd, qa, qb, own, live, n_live, j0, step, keys, rec, acc);
+    if constexpr (W) {
+        return step == 1u ? mcq_exact_hero_walk_as<W, true>(false, bd.u, qa, qb, own, live, n_live, j0, 1u, keys, rec, acc)
+                          : mcq_exact_hero_walk_as<W, true>(false, bd.u, qa, qb, own, live, n_live, j0, step, keys, rec, acc);
+    } else {
+        if (e.x.b.ref_law)
+            return step == 1u ? mcq_exact_hero_pre_walk_bits(true, bd, qa, qb, own, live, n_live, j0, 1u, keys, rec, acc)
+                              : mcq_exact_hero_pre_walk_bits(true, bd, qa, qb, own, live, n_live, j0, step, keys, rec, acc);
+        return step == 1u ? mcq_exact_hero_pre_walk_bits(false, bd, qa, qb, own, live, n_live, j0, 1u, keys, rec, acc)
+                          : mcq_exact_hero_pre_walk_bits(false, bd, qa, qb, own, live, n_live, j0, step, keys, rec, acc);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------- weighted hands
-// mcq_exact_batch_hero_range_preflop_weighted: the same enumeration with an integer weight per HAND in place of the class
-// bit, MCQ_LAW_UNIFORM only -- mcq_exact_hero.hpp's "weighted hands" on D-pairs.  ow_tab / hw_tab (eff_opp / eff_hero per
-// D-pair, MCQ_XP_MAX_PAIRS entries each) are made by mcq_exact_hero_w_tables, and the three lists are made from THEM:
-//   allowed  hw_tab[rp] != 0;   live  ow_tab[rp] != 0;   ranked  their union
-// (host planning counts `allowed` from the same table, so host and every block agree).  A ranked slot's record is
-// mcq_exact_hero_w_pack(pa, pb, eff_opp); a pair that a table card touches keeps key 0 and record 0, whose weight is 0.
+// mcq_exact_batch_hero_range_preflop_weighted: mcq_exact_hero.hpp's McqHeroKind<true> on D-pairs.  What differs from the
+// above: a ranked slot's record is mcq_exact_hero_w_pack(pa, pb, eff_opp); a pair that a table card touches keeps key 0 and
+// record 0, whose weight is 0.
 // Sums.  A thread's sums of ONE completion stay 32-bit (McqExactAcc) whatever its share of the walk; they are added once
-// per completion into McqExactHeroSumsW (64-bit), so MCQ_XP_MAX_OWNED bounds nothing here -- plan and slices are kept only
-// so that launch lengths and grids stay what callers know.
+// per completion into McqHeroKind<true>::Sums (64-bit), so MCQ_XP_MAX_OWNED bounds nothing here -- plan and slices are kept
+// only so that launch lengths and grids stay what callers know.
 static_assert(MCQ_XP_MAX_CAND * MCQ_XH_WEIGHT_MAX < (1u << 27), "a completion's weighted sums (McqExactAcc) fit 32 bits");
 static_assert((uint64_t)MCQ_XP_MAX_OWNED * MCQ_XP_MAX_CAND * MCQ_XH_WEIGHT_MAX > 0xFFFFFFFFull,
-              "a thread's weighted sums of one launch do NOT fit 32 bits: McqExactHeroSumsW is 64-bit");
+              "a thread's weighted sums of one launch do NOT fit 32 bits: McqHeroKind<true>::Sums is 64-bit");
 static_assert((uint64_t)MCQ_XP_MAX_BOARDS * MCQ_XP_MAX_CAND * MCQ_XH_WEIGHT_MAX < (1ull << 48),
               "... and 64 bits hold a hero hand's sums over all C(52, 5) completions with room");
-
-// is D-pair rp on the lists?  bit 0: allowed, bit 1: live
-MCQ_HD uint32_t mcq_exact_hero_pre_w_on(const uint16_t *ow_tab, const uint16_t *hw_tab, uint32_t rp) {
-    return (hw_tab[rp] != 0u ? 1u : 0u) | (ow_tab[rp] != 0u ? 2u : 0u);
-}
-
-// The three lists, as mcq_exact_hero_pre_lists (the kernel makes the same lists with ballots).  n[0..3) = allowed, live, ranked.
-MCQ_HD void mcq_exact_hero_pre_w_lists(const McqExactHeroQuery &e, const uint16_t *ow_tab, const uint16_t *hw_tab, uint16_t *allowed,
-                                       uint16_t *live, uint16_t *ranked, uint32_t n[3]) {
-    n[0] = n[1] = n[2] = 0u;
-    for (uint32_t rp = 0; rp < e.x.n_rp; rp++) {
-        const uint32_t on = mcq_exact_hero_pre_w_on(ow_tab, hw_tab, rp);
-        if (on == 0u) continue;
-        if (on & 1u) allowed[n[0]++] = (uint16_t)n[2];
-        if (on & 2u) live[n[1]++] = (uint16_t)n[2];
-        ranked[n[2]++] = (uint16_t)rp;
-    }
-}
-
-// Ranking pass, as mcq_exact_hero_pre_rank.
-MCQ_HD void mcq_exact_hero_pre_w_rank(const McqExactBoard &bd, uint64_t taken, uint32_t lane, uint32_t n_lanes, const uint16_t *ranked,
-                                      uint32_t n_ranked, const uint16_t *pair_xy, const McqCard *d_card, const uint16_t *ow_tab,
-                                      const uint32_t *tf, const uint32_t *tops, const uint32_t *sd, uint32_t *keys, uint32_t *rec) {
-    for (uint32_t i = lane; i < n_ranked; i += n_lanes) {
-        const uint32_t rp = ranked[i], xy = pair_xy[rp], pa = xy & 0xFFu, pb = xy >> 8;
-        uint32_t key = 0u, r = 0u; /* dead: a table card took one of its cards */
-        if ((((taken >> pa) | (taken >> pb)) & 1ull) == 0ull) {
-            McqHole h;
-            h.set(d_card[pa], d_card[pb]);
-            key = mcq_eval_key(bd.b, bd.fs, h, tf, tops, sd);
-            r = mcq_exact_hero_w_pack(pa, pb, ow_tab[rp]);
-        }
-        keys[i] = key;
-        rec[i] = r;
-    }
-}
-
-// The walk of ONE hero hand, as mcq_exact_hero_pre_walk_as: the live hands j0, j0 + step, ... as the opponent's, the
-// weight one shift.  Returns the hero hand's type.
-MCQ_HD uint32_t mcq_exact_hero_pre_w_walk_as(uint32_t qa, uint32_t qb, uint32_t own, const uint16_t *live, uint32_t n_live, uint32_t j0,
-                                             uint32_t step, const uint32_t *keys, const uint32_t *rec, McqExactAcc &acc) {
-    const uint32_t kh = keys[own];
-    for (uint32_t j = j0; j < n_live; j += step) {
-        const uint32_t s = live[j], r = rec[s], pa = r & 63u, pb = (r >> 6) & 63u;
-        const bool shared = pa == qa || pa == qb || pb == qa || pb == qb; /* (hero's own hand among them) */
-        const uint32_t w = shared ? 0u : r >> 16;                         /* a dead hand: r == 0, w == 0 */
-        const uint32_t kj = keys[s];
-        acc.win += kj < kh ? w : 0u;
-        acc.tie += kj == kh ? w : 0u;
-        acc.tot += w;
-    }
-    return mcq_key_type(kh);
-}
-
-// ... with the commonest stride (1: a group of more than 512 hands) as a constant of a copy of the loop
-MCQ_HD uint32_t mcq_exact_hero_pre_w_walk(uint32_t qa, uint32_t qb, uint32_t own, const uint16_t *live, uint32_t n_live, uint32_t j0,
-                                          uint32_t step, const uint32_t *keys, const uint32_t *rec, McqExactAcc &acc) {
-    return step == 1u ? mcq_exact_hero_pre_w_walk_as(qa, qb, own, live, n_live, j0, 1u, keys, rec, acc)
-                      : mcq_exact_hero_pre_w_walk_as(qa, qb, own, live, n_live, j0, step, keys, rec, acc);
-}
 
 // ---- host side
 // Is some opponent hand of positive weight left against EVERY allowed hero hand?  Exact whatever k: a live D-pair g that
@@ -294,6 +210,45 @@ MCQ_HD uint32_t mcq_exact_hero_pre_owned(uint32_t slice, uint32_t per) { return 
 MCQ_HD uint32_t mcq_exact_hero_pre_slice(uint64_t want) {
     if (want == 0u) return MCQ_XP_DEFAULT_SLICE;
     return want > MCQ_XP_MAX_OWNED ? MCQ_XP_MAX_OWNED : (uint32_t)want;
+}
+
+// ---- the two preflop entries by name
+// mcq_exact_batch_hero_range_preflop (_pre) and ..._preflop_weighted (_pre_w) as fixed instances of the code above, as in
+// mcq_exact_hero.hpp: the names the host builds of the tests walk an entry through.
+MCQ_HD int mcq_exact_hero_pre_query(const McqQueryWords &q, const McqExtRec &er, int law, McqExactHeroQuery &e) {
+    return mcq_exact_hero_query(q, er, law, false, e);
+}
+MCQ_HD void mcq_exact_hero_pre_lists(const McqExactHeroQuery &e, const uint8_t *r_id, const uint8_t *cb_tab, uint16_t *allowed,
+                                     uint16_t *live, uint16_t *ranked, uint32_t n[3]) {
+    mcq_exact_hero_pre_lists<false>(e, r_id, cb_tab, nullptr, allowed, live, ranked, n);
+}
+MCQ_HD void mcq_exact_hero_pre_w_lists(const McqExactHeroQuery &e, const uint16_t *ow_tab, const uint16_t *hw_tab, uint16_t *allowed,
+                                       uint16_t *live, uint16_t *ranked, uint32_t n[3]) {
+    mcq_exact_hero_pre_lists<true>(e, nullptr, ow_tab, hw_tab, allowed, live, ranked, n);
+}
+MCQ_HD void mcq_exact_hero_pre_rank(const McqExactHeroQuery &e, const McqExactBoard &bd, uint64_t taken, uint32_t lane,
+                                    uint32_t n_lanes, const uint16_t *ranked, uint32_t n_ranked, const uint16_t *pair_xy,
+                                    const McqCard *d_card, const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops,
+                                    const uint32_t *sd, uint32_t *keys, uint32_t *rec) {
+    mcq_exact_hero_pre_rank<false>(e, bd, taken, lane, n_lanes, ranked, n_ranked, pair_xy, d_card, cb_tab, tf, tops, sd, keys, rec);
+}
+MCQ_HD uint32_t mcq_exact_hero_pre_walk(const McqExactHeroQuery &e, const McqExactBoard &bd, uint32_t qa, uint32_t qb, uint32_t own,
+                                        const uint16_t *live, uint32_t n_live, uint32_t j0, uint32_t step, const uint32_t *keys,
+                                        const uint32_t *rec, McqExactAcc &acc) {
+    return mcq_exact_hero_pre_walk<false>(e, bd, qa, qb, own, live, n_live, j0, step, keys, rec, acc);
+}
+/* (a weighted record packs nothing of the query and the uniform law asks nothing of the completion) */
+MCQ_HD void mcq_exact_hero_pre_w_rank(const McqExactBoard &bd, uint64_t taken, uint32_t lane, uint32_t n_lanes, const uint16_t *ranked,
+                                      uint32_t n_ranked, const uint16_t *pair_xy, const McqCard *d_card, const uint16_t *ow_tab,
+                                      const uint32_t *tf, const uint32_t *tops, const uint32_t *sd, uint32_t *keys, uint32_t *rec) {
+    const McqExactHeroQuery e = McqExactHeroQuery();
+    mcq_exact_hero_pre_rank<true>(e, bd, taken, lane, n_lanes, ranked, n_ranked, pair_xy, d_card, ow_tab, tf, tops, sd, keys, rec);
+}
+MCQ_HD uint32_t mcq_exact_hero_pre_w_walk(uint32_t qa, uint32_t qb, uint32_t own, const uint16_t *live, uint32_t n_live, uint32_t j0,
+                                          uint32_t step, const uint32_t *keys, const uint32_t *rec, McqExactAcc &acc) {
+    const McqExactHeroQuery e = McqExactHeroQuery();
+    const McqExactBoard bd = McqExactBoard();
+    return mcq_exact_hero_pre_walk<true>(e, bd, qa, qb, own, live, n_live, j0, step, keys, rec, acc);
 }
 
 #endif /* MCQ_EXACT_HERO_PRE_HPP */

@@ -1432,36 +1432,48 @@ int mcq_exact_batch_ext_seats(mcq_ctx *c, const mcq_query *q, const mcq_query_ex
 
 }  // extern "C"
 
-/* every hero hand of a range against one random opponent from one enumeration per query (mcq_exact_hero.hpp).  weighted:
- * opp_w (and hero_w, or null: every hand 1) hold a weight per hand, the law is the uniform one (mcq_exact_hero_w_kernel). */
-static int exact_hero_range_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, bool weighted,
-                                 const uint16_t *opp_w, const uint16_t *hero_w, mcq_result *rows, mcq_exact_prob *agg,
+/* every hero hand of a range against one random opponent from one enumeration per query (mcq_exact_hero.hpp).
+ * preflop: the C(|D|, 5) completions go out in slices, several launches per call (mcq_exact_hero_pre.hpp).
+ * weighted: opp_w (and hero_w, or null: every hand 1) hold a weight per hand, the law is the uniform one; before the flop the
+ * opponent's range is then checked against every allowed hero hand BEFORE anything is launched. */
+static int exact_hero_range_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, bool preflop,
+                                 bool weighted, const uint16_t *opp_w, const uint16_t *hero_w, mcq_result *rows, mcq_exact_prob *agg,
                                  const char *who) {
     if (n == 0) return MCQ_OK; /* (nothing to do: not even a context is needed) */
     if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
     if (!q || !ext || !rows) return mcq_fail(MCQ_EINVAL, who, "null buffer");
     if (weighted && !opp_w) return mcq_fail(MCQ_EINVAL, who, "null opp_weights");
     if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return mcq_fail(MCQ_EINVAL, who, "bad law");
-    if (n > MCQ_HERO_RANGE_MAX_BATCH) return mcq_fail(MCQ_EINVAL, who, "at most MCQ_HERO_RANGE_MAX_BATCH queries per call");
+    if (preflop ? n > MCQ_HERO_PREFLOP_MAX_BATCH : n > MCQ_HERO_RANGE_MAX_BATCH)
+        return mcq_fail(MCQ_EINVAL, who, preflop ? "at most MCQ_HERO_PREFLOP_MAX_BATCH queries per call"
+                                                 : "at most MCQ_HERO_RANGE_MAX_BATCH queries per call");
     /* validation first: nothing is launched for a batch with one query that cannot be enumerated */
     std::vector<McqExactHeroQuery> xq(n);
     std::vector<uint8_t> rid(n * 64u);
-    std::vector<uint16_t> hw_tab(weighted ? n * (size_t)MCQ_XH_MAX_HANDS : 0u), ow_tab(weighted ? MCQ_XH_MAX_HANDS : 0u);
+    std::vector<uint16_t> hw_tab(weighted ? n * (size_t)MCQ_XP_MAX_PAIRS : 0u), ow_tab(weighted ? MCQ_XP_MAX_PAIRS : 0u);
     char buf[200];
     for (size_t i = 0; i < n; i++) {
         const McqExtRec er = {reinterpret_cast<const uint32_t *>(&ext[i])};
-        int why = mcq_exact_hero_query(mcq_query_words(q[i]), er, law, xq[i]);
+        int why = mcq_exact_hero_query(mcq_query_words(q[i]), er, law, !preflop, xq[i]);
+        if (preflop && why == MCQ_XH_OK && q[i].n_board != 0) {
+            snprintf(buf, sizeof buf, "query %zu: table cards: this entry enumerates before the flop only (n_board must be 0); "
+                     "%s takes the flop, turn and river", i, weighted ? "mcq_exact_batch_hero_range_weighted" : "mcq_exact_batch_hero_range");
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
         if (why == MCQ_XH_OK) {
+            const uint8_t *r_id = &rid[64u * i];
+            uint16_t *hw = weighted ? &hw_tab[i * MCQ_XP_MAX_PAIRS] : nullptr;
             mcq_exact_ext_r_ids(xq[i].x, &rid[64u * i]);
-            if (weighted) {
-                uint16_t *hw = &hw_tab[i * MCQ_XH_MAX_HANDS];
-                mcq_exact_hero_w_tables(xq[i], &rid[64u * i], opp_w + i * MCQ_XH_ROWS, hero_w ? hero_w + i * MCQ_XH_ROWS : nullptr, 0u,
-                                        1u, ow_tab.data(), hw);
-                xq[i].n_allowed = mcq_exact_hero_w_count(xq[i], hw, nullptr);
-            } else {
-                xq[i].n_allowed = mcq_exact_hero_count(xq[i], &rid[64u * i], nullptr);
-            }
-            if (xq[i].n_allowed == 0u) why = MCQ_XH_EMPTY;
+            if (weighted)
+                mcq_exact_hero_w_tables(xq[i], r_id, opp_w + i * MCQ_XH_ROWS, hero_w ? hero_w + i * MCQ_XH_ROWS : nullptr, 0u, 1u,
+                                        ow_tab.data(), hw);
+            xq[i].n_allowed = weighted ? mcq_exact_hero_count<true>(xq[i], r_id, hw, nullptr)
+                                       : mcq_exact_hero_count<false>(xq[i], r_id, nullptr, nullptr);
+            if (xq[i].n_allowed == 0u)
+                why = MCQ_XH_EMPTY;
+            /* exact before the flop (mcq_exact_hero_pre_w_undealable): the enumeration is not paid for to be thrown away */
+            else if (preflop && weighted && mcq_exact_hero_pre_w_undealable(xq[i], ow_tab.data(), hw) != MCQ_XP_MAX_PAIRS)
+                why = MCQ_XH_UNDEALABLE;
         }
         if (why != MCQ_XH_OK) {
             static const char *const reason[] = {
@@ -1471,131 +1483,6 @@ static int exact_hero_range_impl(mcq_ctx *c, const mcq_query *q, const mcq_query
                 "a hero range is enumerated heads-up only (n_players must be 2)",
                 "a hero range is enumerated postflop only (3 to 5 table cards): preflop every hero hand meets C(50, 5) table "
                 "completions",
-                "no hand of the hero's range can be made of the cards left"};
-            snprintf(buf, sizeof buf, "query %zu: %s%s", i, reason[why],
-                     weighted && why == MCQ_XH_EMPTY ? " with a positive weight" : "");
-            return mcq_fail(MCQ_EINVAL, who, buf);
-        }
-    }
-    MCQ_ENTER(c, who);
-    McqDeviceScope dev_(c->device);
-    HIP_TRY(dev_.err);
-    const size_t q_bytes = (size_t)MCQ_XH_ROWS * sizeof(mcq_result);
-    HIP_TRY(c->d_res.reserve(n * q_bytes));
-    c->res_clean = 0;
-    HIP_TRY(c->h_res.reserve(n * q_bytes));
-    HIP_TRY(hipMemsetAsync(c->d_res.p, 0, n * q_bytes, c->stream));
-    /* jobs and extension records travel in pinned memory */
-    const size_t job_bytes = (n * sizeof(McqExactExtJob) + 255u) & ~(size_t)255u;
-    /* ... and behind them the weight tables: per query the opponent's, then the hero's (left out: never read) */
-    const size_t ext_bytes = (n * sizeof(mcq_query_ext) + 255u) & ~(size_t)255u, w_bytes = 2u * MCQ_XH_ROWS * sizeof(uint16_t);
-    HIP_TRY(c->h_misc.reserve(job_bytes + ext_bytes + (weighted ? n * w_bytes : 0u)));
-    McqExactExtJob *jobs = static_cast<McqExactExtJob *>(c->h_misc.p);
-    const McqExactExtJob *d_jobs = static_cast<const McqExactExtJob *>(c->h_misc.dev);
-    memcpy(static_cast<uint8_t *>(c->h_misc.p) + job_bytes, ext, n * sizeof(mcq_query_ext));
-    const uint32_t *d_ext = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(c->h_misc.dev) + job_bytes);
-    uint32_t max_grid = 0;
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t g = mcq_exact_hero_plan(&q[i], (uint32_t)i, (uint32_t)i, xq[i].x.b.L, xq[i].n_allowed, exact_cu(c), &jobs[i]);
-        max_grid = g > max_grid ? g : max_grid;
-    }
-    if (weighted) {
-        uint16_t *w = reinterpret_cast<uint16_t *>(static_cast<uint8_t *>(c->h_misc.p) + job_bytes + ext_bytes);
-        for (size_t i = 0; i < n; i++) {
-            memcpy(w + i * 2u * MCQ_XH_ROWS, opp_w + i * MCQ_XH_ROWS, w_bytes / 2u);
-            if (hero_w) memcpy(w + (i * 2u + 1u) * MCQ_XH_ROWS, hero_w + i * MCQ_XH_ROWS, w_bytes / 2u);
-        }
-        const uint16_t *d_wts = reinterpret_cast<const uint16_t *>(static_cast<uint8_t *>(c->h_misc.dev) + job_bytes + ext_bytes);
-        HIP_TRY(mcq_launch_exact_hero_w(d_jobs, (uint32_t)n, max_grid, d_ext, d_wts, hero_w != nullptr, (mcq_result *)c->d_res.p,
-                                        c->d_luts, c->stream));
-    } else {
-        HIP_TRY(mcq_launch_exact_hero(d_jobs, (uint32_t)n, max_grid, d_ext, law, (mcq_result *)c->d_res.p, c->d_luts, c->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * q_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    /* the aggregates first: a row without weight (the opponent's range cannot be dealt against that hero hand) refuses the
-     * whole call before anything reaches the caller */
-    const mcq_result *hr = static_cast<const mcq_result *>(c->h_res.p);
-    std::vector<mcq_exact_prob> p(n);
-    for (size_t i = 0; i < n; i++)
-        if (!(weighted ? mcq_exact_hero_w_finish(xq[i], &rid[64u * i], &hw_tab[i * MCQ_XH_MAX_HANDS], hr + i * MCQ_XH_ROWS, p[i])
-                       : mcq_exact_hero_finish(xq[i], &rid[64u * i], hr + i * MCQ_XH_ROWS, p[i]))) {
-            snprintf(buf, sizeof buf, "query %zu: the opponent's range cannot be dealt against some hand of the hero's range", i);
-            return mcq_fail(MCQ_EINVAL, who, buf);
-        }
-    memcpy(rows, hr, n * q_bytes);
-    if (agg) memcpy(agg, p.data(), n * sizeof(mcq_exact_prob));
-    return MCQ_OK;
-}
-
-extern "C" {
-
-int mcq_exact_batch_hero_range(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, mcq_result *rows,
-                               mcq_exact_prob *agg) {
-    ABI_GUARD_BEGIN
-    return exact_hero_range_impl(c, q, ext, n, law, false, nullptr, nullptr, rows, agg, "mcq_exact_batch_hero_range");
-    ABI_GUARD_END("mcq_exact_batch_hero_range")
-}
-
-/* ... with a weight per hand on both sides, under the uniform law */
-int mcq_exact_batch_hero_range_weighted(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n,
-                                        const uint16_t *opp_weights, const uint16_t *hero_weights, mcq_result *rows,
-                                        mcq_exact_prob *agg) {
-    ABI_GUARD_BEGIN
-    return exact_hero_range_impl(c, q, ext, n, MCQ_LAW_UNIFORM, true, opp_weights, hero_weights, rows, agg,
-                                 "mcq_exact_batch_hero_range_weighted");
-    ABI_GUARD_END("mcq_exact_batch_hero_range_weighted")
-}
-
-}  // extern "C"
-
-/* ... before the flop: the C(|D|, 5) completions go out in slices, several launches per call (mcq_exact_hero_pre.hpp).
- * weighted: as exact_hero_range_impl's, with the lists made from the folded tables (mcq_exact_hero_pre_w_kernel) and the
- * opponent's range checked against every allowed hero hand BEFORE anything is launched. */
-static int exact_hero_range_preflop_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, bool weighted,
-                                         const uint16_t *opp_w, const uint16_t *hero_w, mcq_result *rows, mcq_exact_prob *agg,
-                                         const char *who) {
-    if (n == 0) return MCQ_OK; /* (nothing to do: not even a context is needed) */
-    if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
-    if (!q || !ext || !rows) return mcq_fail(MCQ_EINVAL, who, "null buffer");
-    if (weighted && !opp_w) return mcq_fail(MCQ_EINVAL, who, "null opp_weights");
-    if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return mcq_fail(MCQ_EINVAL, who, "bad law");
-    if (n > MCQ_HERO_PREFLOP_MAX_BATCH) return mcq_fail(MCQ_EINVAL, who, "at most MCQ_HERO_PREFLOP_MAX_BATCH queries per call");
-    /* validation first: nothing is launched for a batch with one query that cannot be enumerated */
-    std::vector<McqExactHeroQuery> xq(n);
-    std::vector<uint8_t> rid(n * 64u);
-    std::vector<uint16_t> hw_tab(weighted ? n * (size_t)MCQ_XP_MAX_PAIRS : 0u), ow_tab(weighted ? MCQ_XP_MAX_PAIRS : 0u);
-    char buf[200];
-    for (size_t i = 0; i < n; i++) {
-        const McqExtRec er = {reinterpret_cast<const uint32_t *>(&ext[i])};
-        int why = mcq_exact_hero_pre_query(mcq_query_words(q[i]), er, law, xq[i]);
-        if (why == MCQ_XH_OK && q[i].n_board != 0) {
-            snprintf(buf, sizeof buf, "query %zu: table cards: this entry enumerates before the flop only (n_board must be 0); "
-                     "%s takes the flop, turn and river", i, weighted ? "mcq_exact_batch_hero_range_weighted" : "mcq_exact_batch_hero_range");
-            return mcq_fail(MCQ_EINVAL, who, buf);
-        }
-        if (why == MCQ_XH_OK) {
-            mcq_exact_ext_r_ids(xq[i].x, &rid[64u * i]);
-            if (weighted) {
-                uint16_t *hw = &hw_tab[i * MCQ_XP_MAX_PAIRS];
-                mcq_exact_hero_w_tables(xq[i], &rid[64u * i], opp_w + i * MCQ_XH_ROWS, hero_w ? hero_w + i * MCQ_XH_ROWS : nullptr, 0u,
-                                        1u, ow_tab.data(), hw);
-                xq[i].n_allowed = mcq_exact_hero_w_count(xq[i], hw, nullptr);
-            } else {
-                xq[i].n_allowed = mcq_exact_hero_count(xq[i], &rid[64u * i], nullptr);
-            }
-            if (xq[i].n_allowed == 0u)
-                why = MCQ_XH_EMPTY;
-            /* exact before the flop (mcq_exact_hero_pre_w_undealable): the enumeration is not paid for to be thrown away */
-            else if (weighted && mcq_exact_hero_pre_w_undealable(xq[i], ow_tab.data(), &hw_tab[i * MCQ_XP_MAX_PAIRS]) != MCQ_XP_MAX_PAIRS)
-                why = MCQ_XH_UNDEALABLE;
-        }
-        if (why != MCQ_XH_OK) {
-            static const char *const reason[] = {
-                "", "invalid extended query (as mcq_eval_batch_ext: distinct card ids < 52, at most 9 known hands, used ranges not empty)",
-                "the hero is given as two cards (hero_is_range == 0): mcq_exact_batch_ext enumerates that",
-                "known hands beside a hero range are not enumerated (n_known must be 0)",
-                "a hero range is enumerated heads-up only (n_players must be 2)", "",
                 "no hand of the hero's range can be made of the cards left",
                 "the opponent's range cannot be dealt against some hand of the hero's range (no hand of positive weight shares no "
                 "card with it)"};
@@ -1610,11 +1497,13 @@ static int exact_hero_range_preflop_impl(mcq_ctx *c, const mcq_query *q, const m
     HIP_TRY(c->d_res.reserve(n * q_bytes));
     c->res_clean = 0;
     HIP_TRY(c->h_res.reserve(n * q_bytes));
+    /* the rows are zeroed here postflop, where no plan fails; preflop only once every plan stands (below) */
+    if (!preflop) HIP_TRY(hipMemsetAsync(c->d_res.p, 0, n * q_bytes, c->stream));
     /* jobs and extension records travel in pinned memory */
     const size_t job_bytes = (n * sizeof(McqExactExtJob) + 255u) & ~(size_t)255u;
     /* ... and behind them the weight tables: per query the opponent's, then the hero's (left out: never read) */
     const size_t ext_bytes = (n * sizeof(mcq_query_ext) + 255u) & ~(size_t)255u, w_bytes = 2u * MCQ_XH_ROWS * sizeof(uint16_t);
-    HIP_TRY(c->h_misc.reserve(weighted ? job_bytes + ext_bytes + n * w_bytes : job_bytes + n * sizeof(mcq_query_ext)));
+    HIP_TRY(c->h_misc.reserve(job_bytes + ext_bytes + (weighted ? n * w_bytes : 0u)));
     McqExactExtJob *jobs = static_cast<McqExactExtJob *>(c->h_misc.p);
     const McqExactExtJob *d_jobs = static_cast<const McqExactExtJob *>(c->h_misc.dev);
     memcpy(static_cast<uint8_t *>(c->h_misc.p) + job_bytes, ext, n * sizeof(mcq_query_ext));
@@ -1628,37 +1517,33 @@ static int exact_hero_range_preflop_impl(mcq_ctx *c, const mcq_query *q, const m
         }
         d_wts = reinterpret_cast<const uint16_t *>(static_cast<uint8_t *>(c->h_misc.dev) + job_bytes + ext_bytes);
     }
-    const uint32_t slice = mcq_exact_hero_pre_slice(c->hero_pre_slice);
+    const uint32_t slice = mcq_exact_hero_pre_slice(c->hero_pre_slice); /* (preflop only) */
     uint32_t max_grid = 0, max_boards = 0;
     for (size_t i = 0; i < n; i++) {
-        const uint32_t g = mcq_exact_hero_pre_plan(&q[i], (uint32_t)i, (uint32_t)i, xq[i].x.b.L, xq[i].n_allowed, exact_cu(c), slice,
-                                                   &jobs[i]);
-        if (g == 0u)
+        const uint32_t g = mcq_exact_hero_plan(preflop, &q[i], (uint32_t)i, (uint32_t)i, xq[i].x.b.L, xq[i].n_allowed, exact_cu(c), slice,
+                                               &jobs[i]);
+        if (g == 0u) /* (preflop only) */
             return mcq_fail(MCQ_EINVAL, who, weighted ? "MCQ_HERO_PRE_SLICE: a launch would be longer than the plan allows"
                                                       : "MCQ_HERO_PRE_SLICE: a block would own more completions than its 32-bit sums allow");
         max_grid = g > max_grid ? g : max_grid;
         max_boards = jobs[i].n_boards > max_boards ? jobs[i].n_boards : max_boards;
     }
-    HIP_TRY(hipMemsetAsync(c->d_res.p, 0, n * q_bytes, c->stream));
-    for (uint32_t lo = 0; lo < max_boards;) { /* (a record with ghost cards has fewer completions: its blocks leave at once) */
-        const uint32_t hi = max_boards - lo > slice ? lo + slice : max_boards;
-        if (weighted)
-            HIP_TRY(mcq_launch_exact_hero_pre_w(d_jobs, (uint32_t)n, max_grid, d_ext, d_wts, hero_w != nullptr, lo, hi,
-                                                (mcq_result *)c->d_res.p, c->d_luts, c->stream));
-        else
-            HIP_TRY(mcq_launch_exact_hero_pre(d_jobs, (uint32_t)n, max_grid, d_ext, law, lo, hi, (mcq_result *)c->d_res.p, c->d_luts,
-                                              c->stream));
+    if (preflop) HIP_TRY(hipMemsetAsync(c->d_res.p, 0, n * q_bytes, c->stream));
+    /* postflop: one launch.  preflop: a launch per slice (a record with ghost cards has fewer completions: its blocks leave at once) */
+    for (uint32_t lo = 0; lo < max_boards;) {
+        const uint32_t hi = preflop && max_boards - lo > slice ? lo + slice : max_boards;
+        HIP_TRY(mcq_launch_exact_hero(preflop, weighted, d_jobs, (uint32_t)n, max_grid, d_ext, law, d_wts, hero_w != nullptr, lo, hi,
+                                      (mcq_result *)c->d_res.p, c->d_luts, c->stream));
         lo = hi;
     }
     HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * q_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     /* the aggregates first: a row without weight (the opponent's range cannot be dealt against that hero hand) refuses the
-     * whole call before anything reaches the caller (weighted: a backstop, the check above has seen it) */
+     * whole call before anything reaches the caller (preflop weighted: a backstop, the check above has seen it) */
     const mcq_result *hr = static_cast<const mcq_result *>(c->h_res.p);
     std::vector<mcq_exact_prob> p(n);
     for (size_t i = 0; i < n; i++)
-        if (!(weighted ? mcq_exact_hero_w_finish(xq[i], &rid[64u * i], &hw_tab[i * MCQ_XP_MAX_PAIRS], hr + i * MCQ_XH_ROWS, p[i])
-                       : mcq_exact_hero_finish(xq[i], &rid[64u * i], hr + i * MCQ_XH_ROWS, p[i]))) {
+        if (!mcq_exact_hero_finish(xq[i], &rid[64u * i], weighted ? &hw_tab[i * MCQ_XP_MAX_PAIRS] : nullptr, hr + i * MCQ_XH_ROWS, p[i])) {
             snprintf(buf, sizeof buf, "query %zu: the opponent's range cannot be dealt against some hand of the hero's range", i);
             return mcq_fail(MCQ_EINVAL, who, buf);
         }
@@ -1669,20 +1554,38 @@ static int exact_hero_range_preflop_impl(mcq_ctx *c, const mcq_query *q, const m
 
 extern "C" {
 
-int mcq_exact_batch_hero_range_preflop(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
-                                       mcq_result *rows, mcq_exact_prob *agg) {
+int mcq_exact_batch_hero_range(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law, mcq_result *rows,
+                               mcq_exact_prob *agg) {
     ABI_GUARD_BEGIN
-    return exact_hero_range_preflop_impl(c, q, ext, n, law, false, nullptr, nullptr, rows, agg, "mcq_exact_batch_hero_range_preflop");
-    ABI_GUARD_END("mcq_exact_batch_hero_range_preflop")
+    return exact_hero_range_impl(c, q, ext, n, law, false, false, nullptr, nullptr, rows, agg, "mcq_exact_batch_hero_range");
+    ABI_GUARD_END("mcq_exact_batch_hero_range")
 }
 
 /* ... with a weight per hand on both sides, under the uniform law */
+int mcq_exact_batch_hero_range_weighted(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n,
+                                        const uint16_t *opp_weights, const uint16_t *hero_weights, mcq_result *rows,
+                                        mcq_exact_prob *agg) {
+    ABI_GUARD_BEGIN
+    return exact_hero_range_impl(c, q, ext, n, MCQ_LAW_UNIFORM, false, true, opp_weights, hero_weights, rows, agg,
+                                 "mcq_exact_batch_hero_range_weighted");
+    ABI_GUARD_END("mcq_exact_batch_hero_range_weighted")
+}
+
+/* ... before the flop */
+int mcq_exact_batch_hero_range_preflop(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n, int law,
+                                       mcq_result *rows, mcq_exact_prob *agg) {
+    ABI_GUARD_BEGIN
+    return exact_hero_range_impl(c, q, ext, n, law, true, false, nullptr, nullptr, rows, agg, "mcq_exact_batch_hero_range_preflop");
+    ABI_GUARD_END("mcq_exact_batch_hero_range_preflop")
+}
+
+/* ... before the flop with a weight per hand on both sides, under the uniform law */
 int mcq_exact_batch_hero_range_preflop_weighted(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n,
                                                 const uint16_t *opp_weights, const uint16_t *hero_weights, mcq_result *rows,
                                                 mcq_exact_prob *agg) {
     ABI_GUARD_BEGIN
-    return exact_hero_range_preflop_impl(c, q, ext, n, MCQ_LAW_UNIFORM, true, opp_weights, hero_weights, rows, agg,
-                                         "mcq_exact_batch_hero_range_preflop_weighted");
+    return exact_hero_range_impl(c, q, ext, n, MCQ_LAW_UNIFORM, true, true, opp_weights, hero_weights, rows, agg,
+                                 "mcq_exact_batch_hero_range_preflop_weighted");
     ABI_GUARD_END("mcq_exact_batch_hero_range_preflop_weighted")
 }
 

@@ -40,29 +40,20 @@ hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, u
                                 const McqTables *d_luts, hipStream_t s,
                                 bool ways = false /* kinds 0 and 1: d_rows holds zeroed mcq_result_ways rows */,
                                 bool seats = false /* kind 0: d_rows holds zeroed mcq_result_seats rows */);
-/* hero-range enumeration (mcq_exact_hero.hpp): one job per query, L = |D|, n_allowed = its allowed hero hands (> 0); d_rows
- * holds zeroed [MCQ_HAND_ROWS] mcq_result rows per query, job->row = the query's index */
-uint32_t mcq_exact_hero_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed, uint32_t n_cu,
-                             McqExactExtJob *job);
-hipError_t mcq_launch_exact_hero(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
+/* hero-range enumeration (mcq_exact_hero.hpp, preflop: mcq_exact_hero_pre.hpp): one job per query, L = |D|, n_allowed = its
+ * allowed hero hands (> 0); d_rows holds zeroed [MCQ_HAND_ROWS] mcq_result rows per query, job->row = the query's index.
+ * preflop: the completions go out in launches of `slice`, each over [lo, hi) with hi - lo <= slice, all adding into the same
+ * rows; the plan returns 0 when a block would own more completions per launch than a thread's 32-bit sums allow
+ * (MCQ_XP_MAX_OWNED; the 64-bit sums of the weighted kernel need no bound, the plan is the same).  Postflop: one launch,
+ * slice, lo and hi are not read. */
+uint32_t mcq_exact_hero_plan(bool preflop, const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed,
+                             uint32_t n_cu, uint32_t slice, McqExactExtJob *job);
+/* weighted: a weight per hand, uniform law (law is not read); d_wts holds 2 * MCQ_HAND_ROWS uint16 per query -- the opponent's
+ * table, then the hero's, which is read only with hero_w (else every hand of his classes weighs 1).  n_allowed is then
+ * counted from the hero's folded table. */
+hipError_t mcq_launch_exact_hero(bool preflop, bool weighted, const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid,
+                                 const uint32_t *d_ext, int law, const uint16_t *d_wts, bool hero_w, uint32_t lo, uint32_t hi,
                                  mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
-/* ... with a weight per hand, uniform law (mcq_exact_hero_w_kernel): the same jobs; d_wts holds 2 * MCQ_HAND_ROWS uint16 per
- * query -- the opponent's table, then the hero's, which is read only with hero_w (else every hand of his classes weighs 1) */
-hipError_t mcq_launch_exact_hero_w(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext,
-                                   const uint16_t *d_wts, bool hero_w, mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
-/* ... before the flop (mcq_exact_hero_pre.hpp): the completions go out in launches of `slice`, each over [lo, hi) with
- * hi - lo <= slice, all adding into the same zeroed rows.  The plan returns 0 when a block would own more completions per
- * launch than a thread's 32-bit sums allow (MCQ_XP_MAX_OWNED). */
-uint32_t mcq_exact_hero_pre_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed, uint32_t n_cu,
-                                 uint32_t slice, McqExactExtJob *job);
-hipError_t mcq_launch_exact_hero_pre(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
-                                     uint32_t lo, uint32_t hi, mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
-/* ... before the flop with a weight per hand, uniform law (mcq_exact_hero_pre_w_kernel): the jobs of mcq_exact_hero_pre_plan
- * (n_allowed counted from the hero's folded table), the slices of mcq_launch_exact_hero_pre and the weight tables of
- * mcq_launch_exact_hero_w.  The 64-bit sums per thread need no bound on the completions a block owns. */
-hipError_t mcq_launch_exact_hero_pre_w(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext,
-                                       const uint16_t *d_wts, bool hero_w, uint32_t lo, uint32_t hi, mcq_result *d_rows,
-                                       const McqTables *d_luts, hipStream_t s);
 /* per-runout enumeration (mcq_exact_runout.hpp): flop and turn records with at most one random opponent, jobs planned by
  * mcq_exact_ext_plan (kind 0 or 1, job->row = the record's index); d_cards holds 52 and d_pairs MCQ_HAND_ROWS zeroed
  * mcq_result_ways rows per record.  The second launch takes the jobs of both kinds and fills the card rows of the flop

@@ -2278,72 +2278,163 @@ __global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJo
 }
 
 // ---------------------------------------------------------------------------------------------- exact enumeration, hero range
-// See mcq_exact_hero.hpp; one job per query (blockIdx.y), the shape of mcq_exact_ext_kernel's kind 2 with the first hand
-// being the HERO's: a BLOCK per table completion -- its 1024 threads rank the C(m, 2) <= 1081 candidate hands once
-// (LDS), then thread t of group g owns the (g * 1024 + t)-th ALLOWED hero hand (a D-pair, fixed across completions; the
-// hands outside the range or the deck are not on the list and cost no walk) and walks every candidate as the
-// opponent's hand with broadcast LDS reads.  Its twelve 32-bit sums stay in registers until the block's last completion
-// and go to row mcq_exact_hero_row of the query's zeroed [1326][13] rows (integer atomics: deterministic).
-// LDS: 97 KB of tables + 8.7 KB of keys and records + 6 KB of lists, one block of 16 waves per CU.
-__global__ __launch_bounds__(1024) void mcq_exact_hero_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
-                                                              int law, unsigned long long *__restrict__ rows,
-                                                              const McqTables *__restrict__ g_tab) {
+// Four kernels -- postflop or preflop, class bits or a weight per hand (McqHeroKind<W>, mcq_exact_hero.hpp) -- made of two
+// bodies, one per street, and of the four helpers below, which both bodies share.  One job per query (blockIdx.y), a BLOCK
+// of 1024 threads per table completion, one block of 16 waves per CU.
+
+// Block prologue: the record's extension words, every D-pair as qa | qb << 8 (N_PAIRS entries), the evaluator's tables, the
+// query (built by thread 0; the host has validated it) and the deck's card ids.  Ends with a barrier.
+template <uint32_t N_PAIRS>
+__device__ __forceinline__ void hero_prologue(const McqExactExtJob &job, const uint32_t *__restrict__ ext, int law,
+                                              const McqTables *__restrict__ g_tab, LdsTablesEval &tab, uint16_t *pair_xy, uint32_t *xw,
+                                              McqExactHeroQuery &xq, uint8_t *r_id) {
+    const uint32_t tid = threadIdx.x;
+    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
+    for (uint32_t i = tid; i < N_PAIRS; i += blockDim.x) {
+        uint32_t x, y;
+        mcq_exact_pair_xy(i, x, y);
+        pair_xy[i] = (uint16_t)(x | (y << 8));
+    }
+    load_tables(tab, g_tab); /* ends with a barrier */
+    if (tid == 0) {
+        const McqExtRec er = {xw};
+        (void)mcq_exact_hero_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, law, false, xq);
+        mcq_exact_ext_r_ids(xq.x, r_id);
+    }
+    __syncthreads();
+}
+
+// W = true: the block's two weight tables per D-pair, folded from the query row's tables in wts -- the opponent's [1326]
+// uint16, then the hero's; hero_w == 0: the hero's is not there and every hand of the hero's classes weighs 1.
+__device__ __forceinline__ void hero_fold_weights(const McqExactHeroQuery &e, const uint8_t *r_id, const uint16_t *__restrict__ wts,
+                                                  uint32_t row, uint32_t hero_w, uint16_t *ow_tab, uint16_t *hw_tab) {
+    const uint16_t *w_opp = wts + (size_t)row * 2u * MCQ_XH_ROWS;
+    mcq_exact_hero_w_tables(e, r_id, w_opp, hero_w ? w_opp + MCQ_XH_ROWS : nullptr, threadIdx.x, blockDim.x, ow_tab, hw_tab);
+}
+
+// Ballot compaction: on(rp) says of D-pair rp < n_rp whether it is allowed (bit 0) and live (bit 1).  `ranked` gets the
+// D-pairs with a bit set, ascending; LISTS: `allowed` and `live` get their slots in `ranked`.  n[0..3) = allowed, live,
+// ranked (without LISTS the caller sets no live bit: `ranked` is the allowed list and only n[2] is counted).  Two passes of
+// 64 D-pairs per wave -- count per chunk, barrier, prefix and scatter, barrier --, so every block makes the same lists.
+// chunk_cnt: [LISTS ? 3 : 1][(MAX_PAIRS + 63) / 64].
+template <uint32_t MAX_PAIRS, bool LISTS, class On>
+__device__ __forceinline__ void hero_compact(uint32_t n_rp, On on, uint32_t *chunk_cnt, uint16_t *ranked, uint16_t *allowed,
+                                             uint16_t *live, uint32_t n[3]) {
+    constexpr uint32_t kChunks = (MAX_PAIRS + 63u) / 64u;
+    const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
+    uint32_t *cnt_r = chunk_cnt, *cnt_a = chunk_cnt + (LISTS ? kChunks : 0u), *cnt_l = chunk_cnt + (LISTS ? 2u * kChunks : 0u);
+#pragma unroll
+    for (uint32_t pass = 0; pass < 2u; pass++) {
+        for (uint32_t c = wib; c < kChunks; c += 16u) {
+            const uint32_t rp = c * 64u + lane, bits = on(rp);
+            const unsigned long long ma = __ballot((bits & 1u) != 0u), ml = LISTS ? __ballot((bits & 2u) != 0u) : 0ull;
+            if (pass == 0u) {
+                if (lane == 0u) {
+                    if (LISTS) {
+                        cnt_a[c] = (uint32_t)__popcll(ma);
+                        cnt_l[c] = (uint32_t)__popcll(ml);
+                    }
+                    cnt_r[c] = (uint32_t)__popcll(ma | ml);
+                }
+                continue;
+            }
+            const unsigned long long below = (1ull << lane) - 1ull;
+            uint32_t base_a = 0, base_l = 0, base_r = 0;
+            for (uint32_t j = 0; j < c; j++) {
+                if (LISTS) {
+                    base_a += cnt_a[j];
+                    base_l += cnt_l[j];
+                }
+                base_r += cnt_r[j];
+            }
+            const uint32_t slot = base_r + (uint32_t)__popcll((ma | ml) & below);
+            if (bits != 0u) ranked[slot] = (uint16_t)rp;
+            if (LISTS) {
+                if (bits & 1u) allowed[base_a + (uint32_t)__popcll(ma & below)] = (uint16_t)slot;
+                if (bits & 2u) live[base_l + (uint32_t)__popcll(ml & below)] = (uint16_t)slot;
+            }
+        }
+        if (pass == 0u) __syncthreads();
+    }
+    n[0] = n[1] = n[2] = 0u;
+    for (uint32_t j = 0; j < kChunks; j++) {
+        if (LISTS) {
+            n[0] += cnt_a[j];
+            n[1] += cnt_l[j];
+        }
+        n[2] += cnt_r[j];
+    }
+    __syncthreads();
+}
+
+// Row flush: a hero hand's twelve sums into its mcq_result row (runs, passes, win, tie, by_type[9]) among the query's zeroed
+// [1326][13] rows -- 64-bit integer atomics, so the result is deterministic.
+template <class Sums>
+__device__ __forceinline__ void hero_flush(unsigned long long *__restrict__ rows, uint32_t q_row, uint32_t row, const Sums &s) {
+    unsigned long long *dst = rows + ((size_t)q_row * MCQ_XH_ROWS + row) * 13u;
+    if (s.tot) atomicAdd(dst + 0, (unsigned long long)s.tot);
+    if (s.win) atomicAdd(dst + 2, (unsigned long long)s.win);
+    if (s.tie) atomicAdd(dst + 3, (unsigned long long)s.tie);
+#pragma unroll
+    for (uint32_t t = 0; t < 9; t++)
+        if (s.type[t]) atomicAdd(dst + 4 + t, (unsigned long long)s.type[t]);
+}
+
+// Postflop (mcq_exact_hero.hpp): the shape of mcq_exact_ext_kernel's kind 2 with the first hand being the HERO's.  Per
+// completion the 1024 threads rank the C(m, 2) <= 1081 candidate hands once (LDS), then thread t of group g owns the
+// (g * 1024 + t)-th ALLOWED hero hand (a D-pair, fixed across completions; the hands outside the range or the deck are not
+// on the list and cost no walk) and walks every candidate as the opponent's hand with broadcast LDS reads: three barriers
+// per completion.  Its twelve sums stay in registers until the block's last completion.
+// W = true: the uniform law only.  The opponent's table is ow_tab (4.7 KB with hw_tab, in place of the 1.2 KB of range
+// bits), the allowed list is made from hw_tab; a completion's sums are 32-bit as before and are added ONCE per completion
+// into twelve 64-bit sums.
+// LDS: 97 KB of tables + 8.7 KB of keys and records + 6 KB of lists.
+template <bool W>
+__device__ __forceinline__ void hero_body(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext, int law,
+                                          const uint16_t *__restrict__ wts, uint32_t hero_w, unsigned long long *__restrict__ rows,
+                                          const McqTables *__restrict__ g_tab) {
+    typedef McqHeroKind<W> Kind;
     const McqExactExtJob job = jobs[blockIdx.y];
     if (blockIdx.x >= job.grid) return;
-    constexpr uint32_t kChunks = (MCQ_XH_MAX_HANDS + 63u) / 64u;
     __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
     __shared__ uint16_t pair_xy[MCQ_XH_MAX_HANDS]; /* every D-pair; the candidate hands are its first n_pairs entries */
     __shared__ uint32_t xw[MCQ_EXT_WORDS];
     __shared__ McqExactHeroQuery xq;
     __shared__ uint8_t r_id[64];
-    __shared__ uint8_t cb_tab[MCQ_XX_MAX_RP + 3u];
+    __shared__ typename Kind::opp_t opp_tab[W ? MCQ_XH_MAX_HANDS : MCQ_XX_MAX_RP + 3u];
     __shared__ uint16_t own_list[MCQ_XH_MAX_HANDS];
-    __shared__ uint32_t chunk_cnt[kChunks];
+    __shared__ uint32_t chunk_cnt[(MCQ_XH_MAX_HANDS + 63u) / 64u];
     __shared__ McqCard rem_card[64];
     __shared__ uint32_t rem_pos[64];
     __shared__ uint32_t keys[MCQ_XH_MAX_PAIRS + 3u];
     __shared__ uint32_t recs[MCQ_XH_MAX_PAIRS + 3u];
     static_assert(MCQ_XH_MAX_PAIRS <= MCQ_XH_MAX_HANDS, "pair_xy covers the candidate hands");
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
-    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
-    for (uint32_t i = tid; i < MCQ_XH_MAX_HANDS; i += blockDim.x) {
-        uint32_t x, y;
-        mcq_exact_pair_xy(i, x, y);
-        pair_xy[i] = (uint16_t)(x | (y << 8));
-    }
-    load_tables(tab, g_tab); /* ends with a barrier */
-    if (tid == 0) {
-        const McqExtRec er = {xw};
-        (void)mcq_exact_hero_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, law, xq); /* validated by the host */
-        mcq_exact_ext_r_ids(xq.x, r_id);
-    }
-    __syncthreads();
+    const uint32_t tid = threadIdx.x;
+    hero_prologue<MCQ_XH_MAX_HANDS>(job, ext, law, g_tab, tab, pair_xy, xw, xq, r_id);
     const McqExactHeroQuery &e = xq;
-    mcq_exact_ext_cb_table(e.x, r_id, tid, blockDim.x, cb_tab);
-    /* the allowed hero hands in ascending order (every block makes the same list): 64 D-pairs per wave and pass */
-    for (uint32_t c = wib; c < kChunks; c += 16u) {
-        const uint32_t rp = c * 64u + lane, xy = pair_xy[rp < MCQ_XH_MAX_HANDS ? rp : 0u];
-        const bool on = rp < e.x.n_rp && mcq_exact_hero_allowed(e, r_id, xy & 0xFFu, xy >> 8);
-        const unsigned long long mask = __ballot(on);
-        if (lane == 0u) chunk_cnt[c] = (uint32_t)__popcll(mask);
+    const uint16_t *hw_tab = nullptr;
+    if constexpr (W) {
+        __shared__ uint16_t hw[MCQ_XH_MAX_HANDS];
+        hero_fold_weights(e, r_id, wts, job.row, hero_w, opp_tab, hw);
+        hw_tab = hw;
+        __syncthreads();
+    } else {
+        mcq_exact_ext_cb_table(e.x, r_id, tid, blockDim.x, opp_tab); /* (the list does not read it: no barrier yet) */
     }
-    __syncthreads();
-    for (uint32_t c = wib; c < kChunks; c += 16u) {
-        const uint32_t rp = c * 64u + lane, xy = pair_xy[rp < MCQ_XH_MAX_HANDS ? rp : 0u];
-        const bool on = rp < e.x.n_rp && mcq_exact_hero_allowed(e, r_id, xy & 0xFFu, xy >> 8);
-        const unsigned long long mask = __ballot(on);
-        uint32_t base = 0;
-        for (uint32_t j = 0; j < c; j++) base += chunk_cnt[j];
-        if (on) own_list[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (uint16_t)rp;
-    }
-    uint32_t n_own = 0;
-    for (uint32_t j = 0; j < kChunks; j++) n_own += chunk_cnt[j];
-    __syncthreads();
+    uint32_t n[3];
+    hero_compact<MCQ_XH_MAX_HANDS, false>(
+        e.x.n_rp,
+        [&](uint32_t rp) -> uint32_t {
+            const uint32_t xy = pair_xy[rp < MCQ_XH_MAX_HANDS ? rp : 0u];
+            return rp < e.x.n_rp && Kind::allowed(e, r_id, hw_tab, rp, xy & 0xFFu, xy >> 8) ? 1u : 0u;
+        },
+        chunk_cnt, own_list, nullptr, nullptr, n);
+    const uint32_t n_own = n[2];
 
     const uint32_t groups = job.groups, group = blockIdx.x % groups, idx = group * blockDim.x + tid;
     const bool own = idx < n_own;
     const uint32_t hxy = pair_xy[own ? own_list[idx] : 0u], qa = hxy & 0xFFu, qb = hxy >> 8;
-    McqExactHeroSums s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+    typename Kind::Sums s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
     for (uint32_t board = blockIdx.x / groups; board < job.n_boards; board += job.grid / groups) {
         uint32_t pos[5];
         mcq_exact_unrank(board, e.x.b.L, e.x.b.k, pos);
@@ -2356,373 +2447,131 @@ __global__ __launch_bounds__(1024) void mcq_exact_hero_kernel(const McqExactExtJ
             rem_card[tid] = mcq_card(r_id[rp]);
         }
         __syncthreads();
-        mcq_exact_hero_rank(e, bd, tid, blockDim.x, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, keys, recs);
+        mcq_exact_hero_rank<W>(e, bd, tid, blockDim.x, pair_xy, rem_card, rem_pos, opp_tab, g_tab->tf, tab.tops, tab.sd, keys, recs);
         __syncthreads();
         const uint32_t mi = own ? mcq_exact_ext_m_index(e.x, pos, qa, qb) : e.x.n_pairs;
         if (mi < e.x.n_pairs) {
             McqExactAcc acc = {0, 0, 0};
-            const uint32_t type = mcq_exact_hero_walk(e, bd, qa, qb, mi, keys, recs, acc);
+            const uint32_t type = mcq_exact_hero_walk<W>(e, bd, qa, qb, mi, keys, recs, acc);
             mcq_exact_hero_add(s, acc, type);
         }
     }
-    if (own) {
-        unsigned long long *dst = rows + ((size_t)job.row * MCQ_XH_ROWS + mcq_exact_hero_row(r_id, qa, qb)) * 13u;
-        /* an mcq_result row: runs, passes, win, tie, by_type[9] */
-        if (s.tot) atomicAdd(dst + 0, (unsigned long long)s.tot);
-        if (s.win) atomicAdd(dst + 2, (unsigned long long)s.win);
-        if (s.tie) atomicAdd(dst + 3, (unsigned long long)s.tie);
-#pragma unroll
-        for (uint32_t t = 0; t < 9; t++)
-            if (s.type[t]) atomicAdd(dst + 4 + t, (unsigned long long)s.type[t]);
-    }
+    if (own) hero_flush(rows, job.row, mcq_exact_hero_row(r_id, qa, qb), s);
 }
 
-// ---------------------------------------------------------------------------------------------- exact enumeration, hero range, weighted hands
-// mcq_exact_hero_kernel with an integer weight per hand (mcq_exact_hero.hpp, "weighted hands"): the uniform law only.
-// wts holds per query row the opponent's [1326] uint16 table and then the hero's; hero_w == 0: the hero's table is not
-// there and every hand of the hero's classes weighs 1.  The tables are folded once per block into ow_tab / hw_tab (LDS,
-// per D-pair, 4.7 KB in place of the 1.2 KB of range bits); the allowed list is made from hw_tab, so every block makes the
-// same one.  A completion's sums are 32-bit as before; they are added ONCE per completion into twelve 64-bit sums, which
-// go out by the same integer atomics.
+__global__ __launch_bounds__(1024) void mcq_exact_hero_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
+                                                              int law, unsigned long long *__restrict__ rows,
+                                                              const McqTables *__restrict__ g_tab) {
+    hero_body<false>(jobs, ext, law, nullptr, 0u, rows, g_tab);
+}
+
 __global__ __launch_bounds__(1024) void mcq_exact_hero_w_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
                                                                 const uint16_t *__restrict__ wts, uint32_t hero_w,
                                                                 unsigned long long *__restrict__ rows,
                                                                 const McqTables *__restrict__ g_tab) {
-    const McqExactExtJob job = jobs[blockIdx.y];
-    if (blockIdx.x >= job.grid) return;
-    constexpr uint32_t kChunks = (MCQ_XH_MAX_HANDS + 63u) / 64u;
-    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
-    __shared__ uint16_t pair_xy[MCQ_XH_MAX_HANDS]; /* every D-pair; the candidate hands are its first n_pairs entries */
-    __shared__ uint32_t xw[MCQ_EXT_WORDS];
-    __shared__ McqExactHeroQuery xq;
-    __shared__ uint8_t r_id[64];
-    __shared__ uint16_t ow_tab[MCQ_XH_MAX_HANDS];
-    __shared__ uint16_t hw_tab[MCQ_XH_MAX_HANDS];
-    __shared__ uint16_t own_list[MCQ_XH_MAX_HANDS];
-    __shared__ uint32_t chunk_cnt[kChunks];
-    __shared__ McqCard rem_card[64];
-    __shared__ uint32_t rem_pos[64];
-    __shared__ uint32_t keys[MCQ_XH_MAX_PAIRS + 3u];
-    __shared__ uint32_t recs[MCQ_XH_MAX_PAIRS + 3u];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
-    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
-    for (uint32_t i = tid; i < MCQ_XH_MAX_HANDS; i += blockDim.x) {
-        uint32_t x, y;
-        mcq_exact_pair_xy(i, x, y);
-        pair_xy[i] = (uint16_t)(x | (y << 8));
-    }
-    load_tables(tab, g_tab); /* ends with a barrier */
-    if (tid == 0) {
-        const McqExtRec er = {xw};
-        (void)mcq_exact_hero_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, MCQ_LAW_UNIFORM, xq); /* validated by the host */
-        mcq_exact_ext_r_ids(xq.x, r_id);
-    }
-    __syncthreads();
-    const McqExactHeroQuery &e = xq;
-    const uint16_t *w_opp = wts + (size_t)job.row * 2u * MCQ_XH_ROWS;
-    mcq_exact_hero_w_tables(e, r_id, w_opp, hero_w ? w_opp + MCQ_XH_ROWS : nullptr, tid, blockDim.x, ow_tab, hw_tab);
-    __syncthreads();
-    /* the allowed hero hands in ascending order (every block makes the same list): 64 D-pairs per wave and pass */
-    for (uint32_t c = wib; c < kChunks; c += 16u) {
-        const uint32_t rp = c * 64u + lane;
-        const bool on = rp < e.x.n_rp && hw_tab[rp] != 0u;
-        const unsigned long long mask = __ballot(on);
-        if (lane == 0u) chunk_cnt[c] = (uint32_t)__popcll(mask);
-    }
-    __syncthreads();
-    for (uint32_t c = wib; c < kChunks; c += 16u) {
-        const uint32_t rp = c * 64u + lane;
-        const bool on = rp < e.x.n_rp && hw_tab[rp] != 0u;
-        const unsigned long long mask = __ballot(on);
-        uint32_t base = 0;
-        for (uint32_t j = 0; j < c; j++) base += chunk_cnt[j];
-        if (on) own_list[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (uint16_t)rp;
-    }
-    uint32_t n_own = 0;
-    for (uint32_t j = 0; j < kChunks; j++) n_own += chunk_cnt[j];
-    __syncthreads();
-
-    const uint32_t groups = job.groups, group = blockIdx.x % groups, idx = group * blockDim.x + tid;
-    const bool own = idx < n_own;
-    const uint32_t hxy = pair_xy[own ? own_list[idx] : 0u], qa = hxy & 0xFFu, qb = hxy >> 8;
-    McqExactHeroSumsW s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-    for (uint32_t board = blockIdx.x / groups; board < job.n_boards; board += job.grid / groups) {
-        uint32_t pos[5];
-        mcq_exact_unrank(board, e.x.b.L, e.x.b.k, pos);
-        McqExactBoard bd;
-        mcq_exact_hero_board(e.x.b, pos, r_id, bd);
-        __syncthreads(); /* the previous completion's walk is done with keys and records */
-        if (tid < e.x.m) {
-            const uint32_t rp = mcq_exact_rem_pos(pos, tid);
-            rem_pos[tid] = rp;
-            rem_card[tid] = mcq_card(r_id[rp]);
-        }
-        __syncthreads();
-        mcq_exact_hero_w_rank(e, bd, tid, blockDim.x, pair_xy, rem_card, rem_pos, ow_tab, g_tab->tf, tab.tops, tab.sd, keys, recs);
-        __syncthreads();
-        const uint32_t mi = own ? mcq_exact_ext_m_index(e.x, pos, qa, qb) : e.x.n_pairs;
-        if (mi < e.x.n_pairs) {
-            McqExactAcc acc = {0, 0, 0};
-            const uint32_t type = mcq_exact_hero_w_walk(e, qa, qb, mi, keys, recs, acc);
-            mcq_exact_hero_w_add(s, acc, type);
-        }
-    }
-    if (own) {
-        unsigned long long *dst = rows + ((size_t)job.row * MCQ_XH_ROWS + mcq_exact_hero_row(r_id, qa, qb)) * 13u;
-        /* an mcq_result row: runs, passes, win, tie, by_type[9] */
-        if (s.tot) atomicAdd(dst + 0, s.tot);
-        if (s.win) atomicAdd(dst + 2, s.win);
-        if (s.tie) atomicAdd(dst + 3, s.tie);
-#pragma unroll
-        for (uint32_t t = 0; t < 9; t++)
-            if (s.type[t]) atomicAdd(dst + 4 + t, s.type[t]);
-    }
+    hero_body<true>(jobs, ext, MCQ_LAW_UNIFORM, wts, hero_w, rows, g_tab);
 }
 
-// ---------------------------------------------------------------------------------------------- exact enumeration, hero range, preflop
-// See mcq_exact_hero_pre.hpp; one job per query (blockIdx.y), the shape of mcq_exact_hero_kernel with everything indexed by
-// D-pair: a BLOCK per table completion; the blocks of a group share the launch's slice [lo, hi) in runs of consecutive
-// completions (the first one unranked, the others by mcq_exact_hero_pre_next).  Once per block the three lists are made with wave ballots -- `ranked` (D-pairs), `allowed` and `live` (slots of
+// Preflop (mcq_exact_hero_pre.hpp): the shape of hero_body with everything indexed by D-pair.  The blocks of a group share
+// the launch's slice [lo, hi) in runs of consecutive completions (the first one unranked, the others by
+// mcq_exact_hero_pre_next).  Once per block the three lists are made -- `ranked` (D-pairs), `allowed` and `live` (slots of
 // `ranked`).  Per completion the 1024 threads rank the slots of `ranked` (a pair that a table card touches: key 0, record
 // 0), then thread t of group g owns the (g * 1024 + t)-th allowed hero hand and walks `live` with broadcast LDS reads; its
 // own key waits at its own slot.  A group of n_g < 513 hands gives each hand 1024 / n_g threads (64 at most), which share
-// its walk and keep sums of their own (mcq_exact_hero_pre_share).  Two barriers per completion: ranking may start only after the last walk, the walk only
-// after the ranking.  Twelve 32-bit sums per thread (the host bounds the completions a block owns per launch:
-// MCQ_XP_MAX_OWNED) go to the query's [1326][13] rows, which the launches of a call share: 64-bit integer atomics.
-// LDS: 97 KB of tables + 10.6 KB of keys and records + 8 KB of lists + 2.6 KB of D-pairs + 1.3 KB of range bits, one block
-// of 16 waves per CU.
+// its walk and keep sums of their own (mcq_exact_hero_pre_share).  Two barriers per completion: ranking may start only after
+// the last walk, the walk only after the ranking.  The rows are shared by the launches of a call.
+// W = false: twelve 32-bit sums per thread -- the host bounds the completions a block owns per launch (MCQ_XP_MAX_OWNED).
+// W = true: the uniform law only; the lists' two predicates are read from ow_tab / hw_tab; a completion's 32-bit sums are
+// added ONCE per completion into twelve 64-bit sums per thread, so no bound on the completions a block owns is needed.
+// LDS: 97 KB of tables + 10.6 KB of keys and records + 8 KB of lists + 2.6 KB of D-pairs + 1.3 KB of range bits or 5.3 KB
+// of weights.
+template <bool W>
+__device__ __forceinline__ void hero_pre_body(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext, int law,
+                                              const uint16_t *__restrict__ wts, uint32_t hero_w, uint32_t lo, uint32_t hi,
+                                              unsigned long long *__restrict__ rows, const McqTables *__restrict__ g_tab) {
+    typedef McqHeroKind<W> Kind;
+    const McqExactExtJob job = jobs[blockIdx.y];
+    if (blockIdx.x >= job.grid || lo >= job.n_boards) return;
+    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ uint16_t pair_xy[MCQ_XP_MAX_PAIRS]; /* every D-pair: qa | qb << 8 */
+    __shared__ uint32_t xw[MCQ_EXT_WORDS];
+    __shared__ McqExactHeroQuery xq;
+    __shared__ uint8_t r_id[64];
+    __shared__ McqCard d_card[64];
+    __shared__ typename Kind::opp_t opp_tab[W ? MCQ_XP_MAX_PAIRS : MCQ_XP_MAX_PAIRS + 2u];
+    __shared__ uint16_t allowed[MCQ_XP_MAX_PAIRS], live[MCQ_XP_MAX_PAIRS], ranked[MCQ_XP_MAX_PAIRS];
+    __shared__ uint32_t chunk_cnt[3u * ((MCQ_XP_MAX_PAIRS + 63u) / 64u)];
+    __shared__ uint32_t keys[MCQ_XP_MAX_PAIRS + 2u];
+    __shared__ uint32_t recs[MCQ_XP_MAX_PAIRS + 2u];
+    const uint32_t tid = threadIdx.x;
+    hero_prologue<MCQ_XP_MAX_PAIRS>(job, ext, law, g_tab, tab, pair_xy, xw, xq, r_id);
+    const McqExactHeroQuery &e = xq;
+    if (tid < e.x.b.L) d_card[tid] = mcq_card(r_id[tid]);
+    const uint16_t *hw_tab = nullptr;
+    if constexpr (W) {
+        __shared__ uint16_t hw[MCQ_XP_MAX_PAIRS];
+        hero_fold_weights(e, r_id, wts, job.row, hero_w, opp_tab, hw);
+        hw_tab = hw;
+    } else {
+        for (uint32_t rp = tid; rp < e.x.n_rp; rp += blockDim.x) {
+            const uint32_t xy = pair_xy[rp];
+            opp_tab[rp] = (uint8_t)mcq_exact_ext_cbits(e.x, r_id, xy & 0xFFu, xy >> 8);
+        }
+    }
+    __syncthreads();
+    uint32_t n[3];
+    hero_compact<MCQ_XP_MAX_PAIRS, true>(
+        e.x.n_rp,
+        [&](uint32_t rp) -> uint32_t {
+            const uint32_t xy = pair_xy[rp < MCQ_XP_MAX_PAIRS ? rp : 0u];
+            if (rp >= e.x.n_rp) return 0u;
+            return (Kind::allowed(e, r_id, hw_tab, rp, xy & 0xFFu, xy >> 8) ? 1u : 0u) | (opp_tab[rp] != 0u ? 2u : 0u);
+        },
+        chunk_cnt, ranked, allowed, live, n);
+    const uint32_t n_allowed = n[0], n_live = n[1], n_ranked = n[2];
+
+    const uint32_t groups = job.groups, group = blockIdx.x % groups, first = group * blockDim.x;
+    const uint32_t n_g = n_allowed > first ? (n_allowed - first < blockDim.x ? n_allowed - first : blockDim.x) : 0u;
+    const uint32_t share = mcq_exact_hero_pre_share(n_g), hand = tid / share, sub = tid - hand * share;
+    const bool own = hand < n_g;
+    const uint32_t own_slot = own ? allowed[first + hand] : 0u;
+    const uint32_t hxy = pair_xy[n_ranked ? ranked[own_slot] : 0u], qa = hxy & 0xFFu, qb = hxy >> 8;
+    /* the block's run of consecutive completions: the first one unranked, the others by stepping */
+    const uint32_t end = hi < job.n_boards ? hi : job.n_boards, run = mcq_exact_hero_pre_owned(end - lo, job.grid / groups);
+    const uint32_t b0 = lo + (blockIdx.x / groups) * run, b1 = end - b0 < run ? end : b0 + run;
+    typename Kind::Sums s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+    uint32_t pos[5];
+    if (b0 < end) mcq_exact_unrank(b0, e.x.b.L, e.x.b.k, pos);
+    for (uint32_t board = b0; board < b1 && b0 < end; board++) {
+        if (board != b0) mcq_exact_hero_pre_next(pos, e.x.b.k);
+        McqExactBoard bd;
+        mcq_exact_hero_board(e.x.b, pos, r_id, bd);
+        const uint64_t taken = mcq_exact_hero_pre_mask(e.x.b, pos);
+        __syncthreads(); /* the previous completion's walk is done with keys and records */
+        mcq_exact_hero_pre_rank<W>(e, bd, taken, tid, blockDim.x, ranked, n_ranked, pair_xy, d_card, opp_tab, g_tab->tf, tab.tops, tab.sd,
+                                   keys, recs);
+        __syncthreads();
+        if (own && keys[own_slot] != 0u) {
+            McqExactAcc acc = {0, 0, 0};
+            const uint32_t type = mcq_exact_hero_pre_walk<W>(e, bd, qa, qb, own_slot, live, n_live, sub, share, keys, recs, acc);
+            mcq_exact_hero_add(s, acc, type);
+        }
+    }
+    if (own) hero_flush(rows, job.row, mcq_exact_hero_row(r_id, qa, qb), s);
+}
+
 __global__ __launch_bounds__(1024) void mcq_exact_hero_pre_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
                                                                   int law, uint32_t lo, uint32_t hi,
                                                                   unsigned long long *__restrict__ rows,
                                                                   const McqTables *__restrict__ g_tab) {
-    const McqExactExtJob job = jobs[blockIdx.y];
-    if (blockIdx.x >= job.grid || lo >= job.n_boards) return;
-    constexpr uint32_t kChunks = (MCQ_XP_MAX_PAIRS + 63u) / 64u;
-    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
-    __shared__ uint16_t pair_xy[MCQ_XP_MAX_PAIRS]; /* every D-pair: qa | qb << 8 */
-    __shared__ uint32_t xw[MCQ_EXT_WORDS];
-    __shared__ McqExactHeroQuery xq;
-    __shared__ uint8_t r_id[64];
-    __shared__ McqCard d_card[64];
-    __shared__ uint8_t cb_tab[MCQ_XP_MAX_PAIRS + 2u];
-    __shared__ uint16_t allowed[MCQ_XP_MAX_PAIRS], live[MCQ_XP_MAX_PAIRS], ranked[MCQ_XP_MAX_PAIRS];
-    __shared__ uint32_t chunk_cnt[3][kChunks];
-    __shared__ uint32_t keys[MCQ_XP_MAX_PAIRS + 2u];
-    __shared__ uint32_t recs[MCQ_XP_MAX_PAIRS + 2u];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
-    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
-    for (uint32_t i = tid; i < MCQ_XP_MAX_PAIRS; i += blockDim.x) {
-        uint32_t x, y;
-        mcq_exact_pair_xy(i, x, y);
-        pair_xy[i] = (uint16_t)(x | (y << 8));
-    }
-    load_tables(tab, g_tab); /* ends with a barrier */
-    if (tid == 0) {
-        const McqExtRec er = {xw};
-        (void)mcq_exact_hero_pre_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, law, xq); /* validated by the host */
-        mcq_exact_ext_r_ids(xq.x, r_id);
-    }
-    __syncthreads();
-    const McqExactHeroQuery &e = xq;
-    if (tid < e.x.b.L) d_card[tid] = mcq_card(r_id[tid]);
-    for (uint32_t rp = tid; rp < e.x.n_rp; rp += blockDim.x) {
-        const uint32_t xy = pair_xy[rp];
-        cb_tab[rp] = (uint8_t)mcq_exact_ext_cbits(e.x, r_id, xy & 0xFFu, xy >> 8);
-    }
-    __syncthreads();
-    /* the lists in ascending order (every block makes the same ones): 64 D-pairs per wave and pass */
-    for (uint32_t c = wib; c < kChunks; c += 16u) {
-        const uint32_t rp = c * 64u + lane, xy = pair_xy[rp < MCQ_XP_MAX_PAIRS ? rp : 0u];
-        const uint32_t on = rp < e.x.n_rp ? mcq_exact_hero_pre_on(e, r_id, cb_tab, rp, xy & 0xFFu, xy >> 8) : 0u;
-        const unsigned long long ma = __ballot((on & 1u) != 0u), ml = __ballot((on & 2u) != 0u);
-        if (lane == 0u) {
-            chunk_cnt[0][c] = (uint32_t)__popcll(ma);
-            chunk_cnt[1][c] = (uint32_t)__popcll(ml);
-            chunk_cnt[2][c] = (uint32_t)__popcll(ma | ml);
-        }
-    }
-    __syncthreads();
-    for (uint32_t c = wib; c < kChunks; c += 16u) {
-        const uint32_t rp = c * 64u + lane, xy = pair_xy[rp < MCQ_XP_MAX_PAIRS ? rp : 0u];
-        const uint32_t on = rp < e.x.n_rp ? mcq_exact_hero_pre_on(e, r_id, cb_tab, rp, xy & 0xFFu, xy >> 8) : 0u;
-        const unsigned long long ma = __ballot((on & 1u) != 0u), ml = __ballot((on & 2u) != 0u), below = (1ull << lane) - 1ull;
-        uint32_t base_a = 0, base_l = 0, base_r = 0;
-        for (uint32_t j = 0; j < c; j++) {
-            base_a += chunk_cnt[0][j];
-            base_l += chunk_cnt[1][j];
-            base_r += chunk_cnt[2][j];
-        }
-        const uint32_t slot = base_r + (uint32_t)__popcll((ma | ml) & below);
-        if (on != 0u) ranked[slot] = (uint16_t)rp;
-        if (on & 1u) allowed[base_a + (uint32_t)__popcll(ma & below)] = (uint16_t)slot;
-        if (on & 2u) live[base_l + (uint32_t)__popcll(ml & below)] = (uint16_t)slot;
-    }
-    uint32_t n_allowed = 0, n_live = 0, n_ranked = 0;
-    for (uint32_t j = 0; j < kChunks; j++) {
-        n_allowed += chunk_cnt[0][j];
-        n_live += chunk_cnt[1][j];
-        n_ranked += chunk_cnt[2][j];
-    }
-    __syncthreads();
-
-    const uint32_t groups = job.groups, group = blockIdx.x % groups, first = group * blockDim.x;
-    const uint32_t n_g = n_allowed > first ? (n_allowed - first < blockDim.x ? n_allowed - first : blockDim.x) : 0u;
-    const uint32_t share = mcq_exact_hero_pre_share(n_g), hand = tid / share, sub = tid - hand * share;
-    const bool own = hand < n_g;
-    const uint32_t own_slot = own ? allowed[first + hand] : 0u;
-    const uint32_t hxy = pair_xy[n_ranked ? ranked[own_slot] : 0u], qa = hxy & 0xFFu, qb = hxy >> 8;
-    /* the block's run of consecutive completions: the first one unranked, the others by stepping */
-    const uint32_t end = hi < job.n_boards ? hi : job.n_boards, run = mcq_exact_hero_pre_owned(end - lo, job.grid / groups);
-    const uint32_t b0 = lo + (blockIdx.x / groups) * run, b1 = end - b0 < run ? end : b0 + run;
-    McqExactHeroSums s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-    uint32_t pos[5];
-    if (b0 < end) mcq_exact_unrank(b0, e.x.b.L, e.x.b.k, pos);
-    for (uint32_t board = b0; board < b1 && b0 < end; board++) {
-        if (board != b0) mcq_exact_hero_pre_next(pos, e.x.b.k);
-        McqExactBoard bd;
-        mcq_exact_hero_board(e.x.b, pos, r_id, bd);
-        const uint64_t taken = mcq_exact_hero_pre_mask(e.x.b, pos);
-        __syncthreads(); /* the previous completion's walk is done with keys and records */
-        mcq_exact_hero_pre_rank(e, bd, taken, tid, blockDim.x, ranked, n_ranked, pair_xy, d_card, cb_tab, g_tab->tf, tab.tops, tab.sd,
-                                keys, recs);
-        __syncthreads();
-        if (own && keys[own_slot] != 0u) {
-            McqExactAcc acc = {0, 0, 0};
-            const uint32_t type = mcq_exact_hero_pre_walk(e, bd, qa, qb, own_slot, live, n_live, sub, share, keys, recs, acc);
-            mcq_exact_hero_add(s, acc, type);
-        }
-    }
-    if (own) {
-        unsigned long long *dst = rows + ((size_t)job.row * MCQ_XH_ROWS + mcq_exact_hero_row(r_id, qa, qb)) * 13u;
-        /* an mcq_result row: runs, passes, win, tie, by_type[9] */
-        if (s.tot) atomicAdd(dst + 0, (unsigned long long)s.tot);
-        if (s.win) atomicAdd(dst + 2, (unsigned long long)s.win);
-        if (s.tie) atomicAdd(dst + 3, (unsigned long long)s.tie);
-#pragma unroll
-        for (uint32_t t = 0; t < 9; t++)
-            if (s.type[t]) atomicAdd(dst + 4 + t, (unsigned long long)s.type[t]);
-    }
+    hero_pre_body<false>(jobs, ext, law, nullptr, 0u, lo, hi, rows, g_tab);
 }
 
-// ---------------------------------------------------------------------------------------------- exact enumeration, hero range, preflop, weighted hands
-// mcq_exact_hero_pre_kernel with an integer weight per hand (mcq_exact_hero_pre.hpp, "weighted hands"): the uniform law
-// only.  The same block shape, runs of consecutive completions, ballot-made lists, two barriers per completion and shared
-// walks; wts as mcq_exact_hero_w_kernel's (per query row the opponent's [1326] uint16 table, then the hero's; hero_w == 0:
-// every hand of the hero's classes weighs 1).  The tables are folded once per block into ow_tab / hw_tab (LDS, per D-pair)
-// and the lists' two predicates are read from them.  A completion's sums are 32-bit; they are added ONCE per completion
-// into twelve 64-bit sums per thread, which go out by the same integer atomics -- so no bound on the completions a block
-// owns is needed.
-// LDS: 97 KB of tables + 10.6 KB of keys and records + 8 KB of lists + 2.6 KB of D-pairs + 5.3 KB of weights, one block of
-// 16 waves per CU.
 __global__ __launch_bounds__(1024) void mcq_exact_hero_pre_w_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
                                                                     const uint16_t *__restrict__ wts, uint32_t hero_w, uint32_t lo,
                                                                     uint32_t hi, unsigned long long *__restrict__ rows,
                                                                     const McqTables *__restrict__ g_tab) {
-    const McqExactExtJob job = jobs[blockIdx.y];
-    if (blockIdx.x >= job.grid || lo >= job.n_boards) return;
-    constexpr uint32_t kChunks = (MCQ_XP_MAX_PAIRS + 63u) / 64u;
-    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
-    __shared__ uint16_t pair_xy[MCQ_XP_MAX_PAIRS]; /* every D-pair: qa | qb << 8 */
-    __shared__ uint32_t xw[MCQ_EXT_WORDS];
-    __shared__ McqExactHeroQuery xq;
-    __shared__ uint8_t r_id[64];
-    __shared__ McqCard d_card[64];
-    __shared__ uint16_t ow_tab[MCQ_XP_MAX_PAIRS], hw_tab[MCQ_XP_MAX_PAIRS];
-    __shared__ uint16_t allowed[MCQ_XP_MAX_PAIRS], live[MCQ_XP_MAX_PAIRS], ranked[MCQ_XP_MAX_PAIRS];
-    __shared__ uint32_t chunk_cnt[3][kChunks];
-    __shared__ uint32_t keys[MCQ_XP_MAX_PAIRS + 2u];
-    __shared__ uint32_t recs[MCQ_XP_MAX_PAIRS + 2u];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
-    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
-    for (uint32_t i = tid; i < MCQ_XP_MAX_PAIRS; i += blockDim.x) {
-        uint32_t x, y;
-        mcq_exact_pair_xy(i, x, y);
-        pair_xy[i] = (uint16_t)(x | (y << 8));
-    }
-    load_tables(tab, g_tab); /* ends with a barrier */
-    if (tid == 0) {
-        const McqExtRec er = {xw};
-        (void)mcq_exact_hero_pre_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, MCQ_LAW_UNIFORM, xq); /* validated by the host */
-        mcq_exact_ext_r_ids(xq.x, r_id);
-    }
-    __syncthreads();
-    const McqExactHeroQuery &e = xq;
-    if (tid < e.x.b.L) d_card[tid] = mcq_card(r_id[tid]);
-    const uint16_t *w_opp = wts + (size_t)job.row * 2u * MCQ_XH_ROWS;
-    mcq_exact_hero_w_tables(e, r_id, w_opp, hero_w ? w_opp + MCQ_XH_ROWS : nullptr, tid, blockDim.x, ow_tab, hw_tab);
-    __syncthreads();
-    /* the lists in ascending order (every block makes the same ones): 64 D-pairs per wave and pass */
-    for (uint32_t c = wib; c < kChunks; c += 16u) {
-        const uint32_t rp = c * 64u + lane;
-        const uint32_t on = rp < e.x.n_rp ? mcq_exact_hero_pre_w_on(ow_tab, hw_tab, rp) : 0u;
-        const unsigned long long ma = __ballot((on & 1u) != 0u), ml = __ballot((on & 2u) != 0u);
-        if (lane == 0u) {
-            chunk_cnt[0][c] = (uint32_t)__popcll(ma);
-            chunk_cnt[1][c] = (uint32_t)__popcll(ml);
-            chunk_cnt[2][c] = (uint32_t)__popcll(ma | ml);
-        }
-    }
-    __syncthreads();
-    for (uint32_t c = wib; c < kChunks; c += 16u) {
-        const uint32_t rp = c * 64u + lane;
-        const uint32_t on = rp < e.x.n_rp ? mcq_exact_hero_pre_w_on(ow_tab, hw_tab, rp) : 0u;
-        const unsigned long long ma = __ballot((on & 1u) != 0u), ml = __ballot((on & 2u) != 0u), below = (1ull << lane) - 1ull;
-        uint32_t base_a = 0, base_l = 0, base_r = 0;
-        for (uint32_t j = 0; j < c; j++) {
-            base_a += chunk_cnt[0][j];
-            base_l += chunk_cnt[1][j];
-            base_r += chunk_cnt[2][j];
-        }
-        const uint32_t slot = base_r + (uint32_t)__popcll((ma | ml) & below);
-        if (on != 0u) ranked[slot] = (uint16_t)rp;
-        if (on & 1u) allowed[base_a + (uint32_t)__popcll(ma & below)] = (uint16_t)slot;
-        if (on & 2u) live[base_l + (uint32_t)__popcll(ml & below)] = (uint16_t)slot;
-    }
-    uint32_t n_allowed = 0, n_live = 0, n_ranked = 0;
-    for (uint32_t j = 0; j < kChunks; j++) {
-        n_allowed += chunk_cnt[0][j];
-        n_live += chunk_cnt[1][j];
-        n_ranked += chunk_cnt[2][j];
-    }
-    __syncthreads();
-
-    const uint32_t groups = job.groups, group = blockIdx.x % groups, first = group * blockDim.x;
-    const uint32_t n_g = n_allowed > first ? (n_allowed - first < blockDim.x ? n_allowed - first : blockDim.x) : 0u;
-    const uint32_t share = mcq_exact_hero_pre_share(n_g), hand = tid / share, sub = tid - hand * share;
-    const bool own = hand < n_g;
-    const uint32_t own_slot = own ? allowed[first + hand] : 0u;
-    const uint32_t hxy = pair_xy[n_ranked ? ranked[own_slot] : 0u], qa = hxy & 0xFFu, qb = hxy >> 8;
-    /* the block's run of consecutive completions: the first one unranked, the others by stepping */
-    const uint32_t end = hi < job.n_boards ? hi : job.n_boards, run = mcq_exact_hero_pre_owned(end - lo, job.grid / groups);
-    const uint32_t b0 = lo + (blockIdx.x / groups) * run, b1 = end - b0 < run ? end : b0 + run;
-    McqExactHeroSumsW s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-    uint32_t pos[5];
-    if (b0 < end) mcq_exact_unrank(b0, e.x.b.L, e.x.b.k, pos);
-    for (uint32_t board = b0; board < b1 && b0 < end; board++) {
-        if (board != b0) mcq_exact_hero_pre_next(pos, e.x.b.k);
-        McqExactBoard bd;
-        mcq_exact_hero_board(e.x.b, pos, r_id, bd);
-        const uint64_t taken = mcq_exact_hero_pre_mask(e.x.b, pos);
-        __syncthreads(); /* the previous completion's walk is done with keys and records */
-        mcq_exact_hero_pre_w_rank(bd, taken, tid, blockDim.x, ranked, n_ranked, pair_xy, d_card, ow_tab, g_tab->tf, tab.tops, tab.sd, keys,
-                                  recs);
-        __syncthreads();
-        if (own && keys[own_slot] != 0u) {
-            McqExactAcc acc = {0, 0, 0};
-            const uint32_t type = mcq_exact_hero_pre_w_walk(qa, qb, own_slot, live, n_live, sub, share, keys, recs, acc);
-            mcq_exact_hero_w_add(s, acc, type);
-        }
-    }
-    if (own) {
-        unsigned long long *dst = rows + ((size_t)job.row * MCQ_XH_ROWS + mcq_exact_hero_row(r_id, qa, qb)) * 13u;
-        /* an mcq_result row: runs, passes, win, tie, by_type[9] */
-        if (s.tot) atomicAdd(dst + 0, s.tot);
-        if (s.win) atomicAdd(dst + 2, s.win);
-        if (s.tie) atomicAdd(dst + 3, s.tie);
-#pragma unroll
-        for (uint32_t t = 0; t < 9; t++)
-            if (s.type[t]) atomicAdd(dst + 4 + t, s.type[t]);
-    }
+    hero_pre_body<true>(jobs, ext, MCQ_LAW_UNIFORM, wts, hero_w, lo, hi, rows, g_tab);
 }
 
 // ---------------------------------------------------------------------------------------------- exact enumeration, per runout
@@ -3125,8 +2974,8 @@ hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, u
     return hipGetLastError();
 }
 
-uint32_t mcq_exact_hero_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed, uint32_t n_cu,
-                             McqExactExtJob *job) {
+uint32_t mcq_exact_hero_plan(bool preflop, const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed,
+                             uint32_t n_cu, uint32_t slice, McqExactExtJob *job) {
     __builtin_memcpy(job->rec, q, 16);
     job->ext = ext;
     job->n_boards = mcq_exact_binom(L, 5u - q->n_board);
@@ -3135,63 +2984,27 @@ uint32_t mcq_exact_hero_plan(const mcq_query *q, uint32_t ext, uint32_t row, uin
     job->groups = (n_allowed + 1023u) / 1024u;
     uint32_t per = n_cu / job->groups;
     if (per < 1u) per = 1u;
+    if (preflop && per > slice) per = slice;
     if (per > job->n_boards) per = job->n_boards;
     job->grid = per * job->groups;
+    /* preflop, a thread's 32-bit sums: the completions one block owns in a launch */
+    if (preflop && (slice == 0u || mcq_exact_hero_pre_owned(slice, per) > MCQ_XP_MAX_OWNED)) return 0u;
     return job->grid;
 }
 
-hipError_t mcq_launch_exact_hero(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
+hipError_t mcq_launch_exact_hero(bool preflop, bool weighted, const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid,
+                                 const uint32_t *d_ext, int law, const uint16_t *d_wts, bool hero_w, uint32_t lo, uint32_t hi,
                                  mcq_result *d_rows, const McqTables *d_luts, hipStream_t s) {
     if (n_jobs == 0) return hipSuccess;
-    if (n_jobs > 65535u || max_grid == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mcq_exact_hero_kernel, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law,
-                       reinterpret_cast<unsigned long long *>(d_rows), d_luts);
-    return hipGetLastError();
-}
-
-hipError_t mcq_launch_exact_hero_w(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext,
-                                   const uint16_t *d_wts, bool hero_w, mcq_result *d_rows, const McqTables *d_luts, hipStream_t s) {
-    if (n_jobs == 0) return hipSuccess;
-    if (n_jobs > 65535u || max_grid == 0 || !d_wts) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mcq_exact_hero_w_kernel, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, d_wts, hero_w ? 1u : 0u,
-                       reinterpret_cast<unsigned long long *>(d_rows), d_luts);
-    return hipGetLastError();
-}
-
-uint32_t mcq_exact_hero_pre_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed, uint32_t n_cu,
-                                 uint32_t slice, McqExactExtJob *job) {
-    __builtin_memcpy(job->rec, q, 16);
-    job->ext = ext;
-    job->n_boards = mcq_exact_binom(L, 5u - q->n_board);
-    job->row = row;
-    job->h1_off = 0u;
-    job->groups = (n_allowed + 1023u) / 1024u;
-    uint32_t per = n_cu / job->groups;
-    if (per < 1u) per = 1u;
-    if (per > slice) per = slice;
-    if (per > job->n_boards) per = job->n_boards;
-    job->grid = per * job->groups;
-    /* a thread's 32-bit sums: the completions one block owns in a launch */
-    if (slice == 0u || mcq_exact_hero_pre_owned(slice, per) > MCQ_XP_MAX_OWNED) return 0u;
-    return job->grid;
-}
-
-hipError_t mcq_launch_exact_hero_pre(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext, int law,
-                                     uint32_t lo, uint32_t hi, mcq_result *d_rows, const McqTables *d_luts, hipStream_t s) {
-    if (n_jobs == 0) return hipSuccess;
-    if (n_jobs > 65535u || max_grid == 0 || lo >= hi || hi - lo > MCQ_XP_MAX_OWNED) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mcq_exact_hero_pre_kernel, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, law, lo, hi,
-                       reinterpret_cast<unsigned long long *>(d_rows), d_luts);
-    return hipGetLastError();
-}
-
-hipError_t mcq_launch_exact_hero_pre_w(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, const uint32_t *d_ext,
-                                       const uint16_t *d_wts, bool hero_w, uint32_t lo, uint32_t hi, mcq_result *d_rows,
-                                       const McqTables *d_luts, hipStream_t s) {
-    if (n_jobs == 0) return hipSuccess;
-    if (n_jobs > 65535u || max_grid == 0 || !d_wts || lo >= hi || hi - lo > MCQ_XP_MAX_OWNED) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mcq_exact_hero_pre_w_kernel, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, d_ext, d_wts, hero_w ? 1u : 0u, lo,
-                       hi, reinterpret_cast<unsigned long long *>(d_rows), d_luts);
+    if (n_jobs > 65535u || max_grid == 0 || (weighted && !d_wts)) return hipErrorInvalidValue;
+    if (preflop && (lo >= hi || hi - lo > MCQ_XP_MAX_OWNED)) return hipErrorInvalidValue;
+    const dim3 grid(max_grid, n_jobs), block(1024);
+    const uint32_t hw = hero_w ? 1u : 0u;
+    unsigned long long *rows = reinterpret_cast<unsigned long long *>(d_rows);
+    if (!preflop && !weighted) hipLaunchKernelGGL(mcq_exact_hero_kernel, grid, block, 0, s, d_jobs, d_ext, law, rows, d_luts);
+    else if (!preflop) hipLaunchKernelGGL(mcq_exact_hero_w_kernel, grid, block, 0, s, d_jobs, d_ext, d_wts, hw, rows, d_luts);
+    else if (!weighted) hipLaunchKernelGGL(mcq_exact_hero_pre_kernel, grid, block, 0, s, d_jobs, d_ext, law, lo, hi, rows, d_luts);
+    else hipLaunchKernelGGL(mcq_exact_hero_pre_w_kernel, grid, block, 0, s, d_jobs, d_ext, d_wts, hw, lo, hi, rows, d_luts);
     return hipGetLastError();
 }
 

@@ -17,6 +17,10 @@ made from them and the 64-bit sums cost or save against the class bits.
     python tools/hero_preflop_weighted_probe.py --kernels DIR/.../prew_kernel_trace.csv
                                 the launches of case (a), one call per entry: their number, the longest one and their
                                 sum (a run of its own: tracing slows the host; --kernels reads the file, no GPU)
+    timeout -k 10 540 python tools/hero_preflop_weighted_probe.py --ab PARENT_SO COPY_SO
+                                all FOUR hero-range entries, postflop and preflop, the unweighted ones under both
+                                laws, of this build beside the parent commit's build and a second copy of it (see
+                                ab()): exit status 1 unless every ratio lies inside the widened interval
 
 The rows and aggregates of the two entries are checked to be equal byte for byte before anything is timed.
 """
@@ -39,7 +43,7 @@ KERNELS = [("unweighted", "mcq_exact_hero_pre_kernel"), ("weighted", "mcq_exact_
 
 
 class Baseline:
-    """mcq_exact_batch_hero_range_preflop of another build of the library, through its C ABI alone."""
+    """The four hero-range entries of another build of the library, through its C ABI alone."""
 
     def __init__(self, path):
         self.lib = C.CDLL(os.path.abspath(path))
@@ -47,15 +51,23 @@ class Baseline:
         self.lib.mcq_create.argtypes = [C.c_int, C.c_uint]
         self.lib.mcq_destroy.argtypes = [C.c_void_p]
         vp = C.c_void_p
-        self.lib.mcq_exact_batch_hero_range_preflop.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, vp]
+        for street in ("", "_preflop"):
+            getattr(self.lib, "mcq_exact_batch_hero_range" + street).argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, vp]
+            getattr(self.lib, "mcq_exact_batch_hero_range%s_weighted" % street).argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp]
         self.ctx = self.lib.mcq_create(0, 0)
         assert self.ctx, "mcq_create of the baseline library failed"
 
-    def preflop(self, q, x, rows, agg):
-        rc = self.lib.mcq_exact_batch_hero_range_preflop(self.ctx, q.ctypes.data, x.ctypes.data, len(q), 1, rows.ctypes.data,
-                                                         agg.ctypes.data)
+    def call(self, entry, q, x, rows, agg, opp_w=None, law=1):
+        """mcq_exact_batch_<entry>: under `law` (0 reference, 1 uniform), or (a ..._weighted entry) with the opponent's table
+        opp_w alone"""
+        mid = (law,) if opp_w is None else (opp_w.ctypes.data, None)
+        rc = getattr(self.lib, "mcq_exact_batch_" + entry)(self.ctx, q.ctypes.data, x.ctypes.data, len(q), *mid, rows.ctypes.data,
+                                                           agg.ctypes.data)
         assert rc == 0, rc
         return rows, agg
+
+    def preflop(self, q, x, rows, agg):
+        return self.call("hero_range_preflop", q, x, rows, agg)
 
     def close(self):
         self.lib.mcq_destroy(self.ctx)
@@ -107,6 +119,74 @@ def run(keys, baseline_lib):
         base.close()
 
 
+# --ab: name, table cards, hero range, opponent range, timed rounds per call order -- the shapes of tools/hero_range_probe.py
+# and tools/hero_range_weighted_probe.py, then SHAPES above
+AB_SHAPES = [("flop, any vs any", ["2D", "9H", "JS"], None, None, 10),
+             ("flop, top 25% vs top 25%", ["2D", "9H", "JS"], 0.25, 0.25, 10),
+             ("turn, any vs any", ["2D", "9H", "JS", "5C"], None, None, 10)] + \
+            [("preflop, " + name, [], hero, opp, rounds // 3) for _, name, hero, opp, rounds in SHAPES]
+AB_PASSES = 4
+
+
+def ab(parent_so, copy_so):
+    """All four entries of this build beside the parent commit's build and beside a second copy of the parent's build (the
+    same file under a second name, so that it loads separately): what a refactor of these entries must leave alone.  Per
+    entry and shape the three libraries are called in turn, in one order and then in the reverse one, after a warm-up call
+    whose rows and aggregates are checked to be equal byte for byte.  Per order: this / parent and copy / parent, the
+    ratios of the median call times (the two long preflop shapes get ONE timed call per order and pass, so their "median"
+    is that call: a call of seconds, whose rounds differ by under 0.2 %, profiles/hero_preflop_weighted_probe.txt).  An
+    unweighted entry is timed under the reference's law, its default, and under the uniform one: the walks are separate
+    copies of the loop per law, or read the law per candidate.  The same code differs by up to a percent and more between two CONTEXTS, steadily
+    for as long as they live (the copy against the parent shows it), so the whole is done AB_PASSES times, each with fresh
+    contexts of all three libraries.  The copy / parent ratios of all passes and orders span the interval that the same
+    code gives against itself; an entry and shape passes when every this / parent ratio lies in that interval widened on
+    each side by its own width.  "faster" (the ones outside lie below it) is printed for information and fails like
+    "OUTSIDE": the rule is inside, and a loop that got faster on one shape has changed and may be slower on another."""
+    import neuron_poker_amd as npa
+    from neuron_poker_amd import _lib
+    from neuron_poker_amd.montecarlo_hip import _opponent_range_bits
+    _lib.load_library()
+    ones = np.ones((1, _lib.HAND_ROWS), np.uint16)
+    out = [(np.zeros((1, _lib.HAND_ROWS), _lib.RESULT_DTYPE), np.zeros(1, _lib.EXACT_PROB_DTYPE)) for _ in range(3)]
+    cases = []
+    for name, table, hero, opp, rounds in AB_SHAPES:
+        hb, ob = _opponent_range_bits(1 if hero is None else hero), _opponent_range_bits(1 if opp is None else opp)
+        q = _lib.pack_query_one([0, 0], [npa.card_id(c) for c in table], 2, 1)
+        x = _lib.pack_query_ext(1, hero_range=_lib.ALL_CLASSES if hb is None else hb, opp_range=ob)
+        street = "hero_range" + ("" if table else "_preflop")
+        cases += [(street, name + ", reference law", q, x, rounds, 0), (street, name, q, x, rounds, 1),
+                  (street + "_weighted", name, q, x, rounds, 1)]
+    ratios = {c[:2]: [] for c in cases}                                  # (this / parent, copy / parent, parent ms) per pass and order
+    for _p in range(AB_PASSES):
+        libs = [("this", Baseline(_lib.library_path())), ("parent", Baseline(parent_so)), ("copy", Baseline(copy_so))]
+        for entry, name, q, x, rounds, law in cases:
+            w = ones if entry.endswith("_weighted") else None
+            first = [b.call(entry, q, x, r, a, w, law) for (_, b), (r, a) in zip(libs, out)]  # warm-up, and the check
+            assert all(r.tobytes() == first[0][0].tobytes() and a.tobytes() == first[0][1].tobytes() for r, a in first), (entry, name)
+            for order in (libs, libs[::-1]):
+                t = {k: [] for k, _ in libs}
+                for _ in range(rounds):
+                    for k, b in order:
+                        t0 = time.perf_counter()
+                        b.call(entry, q, x, out[0][0], out[0][1], w, law)
+                        t[k].append((time.perf_counter() - t0) * 1e3)
+                med = {k: float(np.median(v)) for k, v in t.items()}
+                ratios[(entry, name)].append((med["this"] / med["parent"], med["copy"] / med["parent"], med["parent"]))
+        for _, b in libs:
+            b.close()
+        print("pass done", flush=True)
+    ok = True
+    for (entry, name), r in ratios.items():
+        lo, hi = min(v[1] for v in r), max(v[1] for v in r)
+        lo, hi = lo - (hi - lo), hi + (hi - lo)
+        verdict = "inside" if all(lo <= v[0] <= hi for v in r) else "faster" if all(v[0] <= hi for v in r) else "OUTSIDE"
+        ok = ok and verdict == "inside"
+        print("%-28s %-46s parent %9.3f ms  widened [%.4f, %.4f]  %s\n    this/parent %s\n    copy/parent %s" %
+              (entry, name, float(np.median([v[2] for v in r])), lo, hi, verdict, " ".join("%.4f" % v[0] for v in r),
+               " ".join("%.4f" % v[1] for v in r)), flush=True)
+    return ok
+
+
 def trace():
     """Case (a) alone, one call per entry and no warm-up call of it: every launch of a kernel belongs to that call."""
     import neuron_poker_amd as npa
@@ -134,11 +214,15 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="abc", help="which of the cases a, b, c to time (one per process under a time limit, see above)")
     ap.add_argument("--baseline-lib", metavar="SO", help="another build of libmcq_hip.so whose unweighted entry is timed too")
+    ap.add_argument("--ab", nargs=2, metavar=("PARENT_SO", "COPY_SO"),
+                    help="all four hero-range entries of this build beside the parent's build and a second copy of it, both call orders")
     ap.add_argument("--trace", action="store_true", help="case (a) once per entry, no timing: the run to put under rocprofv3 --kernel-trace")
     ap.add_argument("--kernels", metavar="CSV", help="read the launches' times from a kernel trace of a --trace run")
     a = ap.parse_args()
     if a.kernels:
         kernels(a.kernels)
+    elif a.ab:
+        sys.exit(0 if ab(*a.ab) else 1)
     elif a.trace:
         trace()
     else:
