@@ -2,6 +2,11 @@
 // an opponent range; lane code shared by mcq_exact_ext_kernel (mcq_kernels.hip) and the host build of the tests
 // (tests/hostsim_exact_ext).  The plain walk's pieces (mcq_exact.hpp) are reused unchanged.
 //
+// Every row form (plain, split-pot, per seat, per runout) is made of the same few pieces, each stated once: the known hands
+// of a completion (mcq_exact_ext_known), a completion without a random opponent (mcq_exact_ext_lone_known), the walk over the
+// candidate hands (mcq_exact_ext_candidates, with three small bodies) and the word of a row that a completion's sums give
+// (mcq_exact_ext_row_word, mcq_exact_ext_seats_word).
+//
 // What is enumerated.  R = the deck the random opponents are dealt from: 52 cards minus ghost, table, hero and the known
 // hands, ascending card id (montecarlo_python.py:121-163, 206-208); L = |R|.  Table-completion-major as the plain walk:
 // the k = 5 - n_board new table cards T are a k-subset of R, the m = L - k cards left hold the opponents' hands --
@@ -112,37 +117,36 @@ MCQ_HD uint32_t mcq_exact_ext_pack(uint32_t pa, uint32_t pb, uint32_t top, bool 
 MCQ_HD uint32_t mcq_exact_ext_cb(uint32_t r) { return r >> 14; }
 MCQ_HD uint32_t mcq_exact_ext_above(uint32_t r) { return (r >> 12) & 3u; }
 
-// the strongest known hand's key for this completion, 0 without known hands (every hand's key is > 0)
-MCQ_HD uint32_t mcq_exact_ext_known_best(const McqExactExtQuery &e, const McqExactBoard &bd, const uint32_t *tf,
+// The known hands of one completion in ONE pass (wave-uniform); a caller that ignores a part leaves it to the compiler to
+// drop after inlining.
+//   best   the strongest known hand's key, 0 without known hands (every hand's key is > 0);
+//   n_eq   the known hands whose key equals hero's (split-pot form: the pot of a tie is shared by 1 + n_eq hands, by
+//          2 + n_eq when the one candidate hand is level with hero too);
+//   top    the greatest key among hero (seat 0) and the known hands (seats 1..n_known), level = the mask of the seats
+//          that hold it (per-seat form).
+struct McqExactKnown {
+    uint32_t best, n_eq, top, level;
+};
+MCQ_HD McqExactKnown mcq_exact_ext_known(const McqExactExtQuery &e, const McqExactBoard &bd, const uint32_t *tf,
                                          const uint32_t *tops, const uint32_t *sd) {
-    uint32_t best = 0;
+    McqExactKnown kn = {0u, 0u, bd.hero_key, 1u};
     for (uint32_t h = 0; h < e.n_known; h++) {
         McqHole kh;
         kh.set(mcq_card(e.known[h] & 0xFFu), mcq_card(e.known[h] >> 8));
-        const uint32_t k = mcq_eval_key(bd.b, bd.fs, kh, tf, tops, sd);
-        best = k > best ? k : best;
+        const uint32_t key = mcq_eval_key(bd.b, bd.fs, kh, tf, tops, sd);
+        kn.best = key > kn.best ? key : kn.best;
+        kn.n_eq += key == bd.hero_key ? 1u : 0u;
+        kn.level = key > kn.top ? 0u : kn.level;
+        kn.level |= key >= kn.top ? 2u << h : 0u;
+        kn.top = key > kn.top ? key : kn.top;
     }
-    return best;
+    return kn;
 }
 
 // Split-pot form (kinds 0 and 1: at most one random opponent).  The tie weights are split by k = the hands that share
-// the pot, hero included: the known hands whose key equals hero's come from the same keys as the best of them, and the
-// one candidate hand adds itself when its own key equals hero's.  Per completion the known hands' count n_eq is
-// wave-uniform, so a lane keeps ONE further sum -- tie_c, the ties in which the candidate's key equals hero's: those are
-// shared by 2 + n_eq hands, the other ties (tie - tie_c: the candidate below hero, a known hand level) by 1 + n_eq.
-MCQ_HD uint32_t mcq_exact_ext_known_best_eq(const McqExactExtQuery &e, const McqExactBoard &bd, const uint32_t *tf,
-                                            const uint32_t *tops, const uint32_t *sd, uint32_t &n_eq) {
-    uint32_t best = 0;
-    n_eq = 0;
-    for (uint32_t h = 0; h < e.n_known; h++) {
-        McqHole kh;
-        kh.set(mcq_card(e.known[h] & 0xFFu), mcq_card(e.known[h] >> 8));
-        const uint32_t k = mcq_eval_key(bd.b, bd.fs, kh, tf, tops, sd);
-        best = k > best ? k : best;
-        n_eq += k == bd.hero_key ? 1u : 0u;
-    }
-    return best;
-}
+// the pot, hero included.  Per completion the known hands' count n_eq is wave-uniform, so a lane keeps ONE further sum --
+// tie_c, the ties in which the candidate's key equals hero's: those are shared by 2 + n_eq hands, the other ties
+// (tie - tie_c: the candidate below hero, a known hand level) by 1 + n_eq.
 struct McqExactAccWays {
     static constexpr bool kWays = true;
     uint32_t win, tie, tot;
@@ -153,74 +157,31 @@ struct McqExactExtSums { /* 64-bit: a first hand's sums over all completions */
     unsigned long long win, tie, tot, type[9];
 };
 
-// No random opponent: completion `idx` alone (one lane).  Adds its weight (0 or 1) to win / tie / tot and returns hero's
-// hand type.
-MCQ_HD uint32_t mcq_exact_ext_lone(const McqExactExtQuery &e, uint32_t idx, const uint32_t *sel8, const uint32_t *tf,
-                                   const uint32_t *tops, const uint32_t *sd, McqExactAcc &acc) {
-    uint32_t pos[5];
-    mcq_exact_unrank(idx, e.b.L, e.b.k, pos);
-    McqExactBoard bd;
-    mcq_exact_board(e.b, pos, sel8, tf, tops, sd, bd);
-    const uint32_t kb = mcq_exact_ext_known_best(e, bd, tf, tops, sd);
-    const uint32_t w = !e.b.ref_law || bd.u > 0u ? 1u : 0u;
-    acc.win += kb < bd.hero_key ? w : 0u;
-    acc.tie += kb == bd.hero_key ? w : 0u;
-    acc.tot += w;
-    return mcq_key_type(bd.hero_key);
-}
-// The same, split: n_eq = the known hands level with hero (the pot of a tie is shared by 1 + n_eq hands).
-MCQ_HD uint32_t mcq_exact_ext_lone_ways(const McqExactExtQuery &e, uint32_t idx, const uint32_t *sel8, const uint32_t *tf,
-                                        const uint32_t *tops, const uint32_t *sd, McqExactAcc &acc, uint32_t &n_eq) {
-    uint32_t pos[5];
-    mcq_exact_unrank(idx, e.b.L, e.b.k, pos);
-    McqExactBoard bd;
-    mcq_exact_board(e.b, pos, sel8, tf, tops, sd, bd);
-    const uint32_t kb = mcq_exact_ext_known_best_eq(e, bd, tf, tops, sd, n_eq);
-    const uint32_t w = !e.b.ref_law || bd.u > 0u ? 1u : 0u;
-    acc.win += kb < bd.hero_key ? w : 0u;
-    acc.tie += kb == bd.hero_key ? w : 0u;
-    acc.tot += w;
-    return mcq_key_type(bd.hero_key);
+// Word `word` of one completion's row from its sums over the candidate hands: runs, passes = 0, win, tie, by_type[9] --
+// hero's hand type is fixed per completion: one entry, win + tie --, then tie_ways[9] (22-word rows of mcq_result_ways
+// only; a plain row ends at word 13 and passes tie_c = n_eq = 0).  Those ties are shared by 2 + n_eq hands where the
+// candidate is level with hero (tie_c), the others by 1 + n_eq (n_eq >= 1 there).  No random opponent: tie_c = 0.
+MCQ_HD unsigned long long mcq_exact_ext_row_word(uint32_t word, uint32_t win, uint32_t tie, uint32_t tot, uint32_t tie_c,
+                                                 uint32_t type, uint32_t n_eq) {
+    if (word < 4u) return word == 0u ? tot : word == 2u ? win : word == 3u ? tie : 0u;
+    if (word < 13u) return word - 4u == type ? win + tie : 0u;
+    const uint32_t j = word - 13u;
+    return (j == n_eq ? tie_c : 0u) + (j + 1u == n_eq ? tie - tie_c : 0u);
 }
 
-// The same per SEAT (mcq_result_seats: no random opponent): the greatest key among hero (seat 0) and the known hands
-// (seats 1..n_known) of completion `idx`, level = the mask of the seats that hold it, k = how many they are.  Returns the
-// completion's weight (0 or 1).
-MCQ_HD uint32_t mcq_exact_ext_lone_seats(const McqExactExtQuery &e, uint32_t idx, const uint32_t *sel8, const uint32_t *tf,
-                                         const uint32_t *tops, const uint32_t *sd, uint32_t &level, uint32_t &k) {
-    uint32_t pos[5];
+// No random opponent: completion `idx` alone (one lane) -- its R-positions, board and known hands; returns its weight
+// (0 or 1).  The plain, split-pot, per-seat and per-runout forms all start here.
+MCQ_HD uint32_t mcq_exact_ext_lone_known(const McqExactExtQuery &e, uint32_t idx, const uint32_t *sel8, const uint32_t *tf,
+                                   const uint32_t *tops, const uint32_t *sd, uint32_t pos[5], McqExactBoard &bd,
+                                   McqExactKnown &kn) {
     mcq_exact_unrank(idx, e.b.L, e.b.k, pos);
-    McqExactBoard bd;
     mcq_exact_board(e.b, pos, sel8, tf, tops, sd, bd);
-    uint32_t best = bd.hero_key;
-    level = 1u;
-    for (uint32_t h = 0; h < e.n_known; h++) {
-        McqHole kh;
-        kh.set(mcq_card(e.known[h] & 0xFFu), mcq_card(e.known[h] >> 8));
-        const uint32_t key = mcq_eval_key(bd.b, bd.fs, kh, tf, tops, sd);
-        level = key > best ? 0u : level;
-        level |= key >= best ? 2u << h : 0u;
-        best = key > best ? key : best;
-    }
-    k = mcq_popc(level);
+    kn = mcq_exact_ext_known(e, bd, tf, tops, sd);
     return !e.b.ref_law || bd.u > 0u ? 1u : 0u;
 }
-// ... and for a completion whose board a whole wave shares (one random opponent: mcq_exact_ext_pass_seats below): that
-// greatest key itself, wave-uniform as `level` is.  (The loop is mcq_exact_ext_lone_seats's, kept apart so that the
-// all-in kernel's code stays what it was.)
-MCQ_HD uint32_t mcq_exact_ext_level_seats(const McqExactExtQuery &e, const McqExactBoard &bd, const uint32_t *tf,
-                                          const uint32_t *tops, const uint32_t *sd, uint32_t &level) {
-    uint32_t best = bd.hero_key;
-    level = 1u;
-    for (uint32_t h = 0; h < e.n_known; h++) {
-        McqHole kh;
-        kh.set(mcq_card(e.known[h] & 0xFFu), mcq_card(e.known[h] >> 8));
-        const uint32_t key = mcq_eval_key(bd.b, bd.fs, kh, tf, tops, sd);
-        level = key > best ? 0u : level;
-        level |= key >= best ? 2u << h : 0u;
-        best = key > best ? key : best;
-    }
-    return best;
+// ... and what it gives hero: a win above every known hand, a tie level with the best of them (shared by 1 + kn.n_eq hands)
+MCQ_HD McqExactAcc mcq_exact_ext_lone_acc(const McqExactBoard &bd, const McqExactKnown &kn, uint32_t w) {
+    return {kn.best < bd.hero_key ? w : 0u, kn.best == bd.hero_key ? w : 0u, w};
 }
 
 // the range bits of every R-pair (index pb (pb - 1) / 2 + pa): they do not depend on the completion; entries rp, rp + step, ...
@@ -232,51 +193,14 @@ MCQ_HD void mcq_exact_ext_cb_table(const McqExactExtQuery &e, const uint8_t *r_i
     }
 }
 
-// Pass A, lane `lane` of `n_lanes`: keys of the candidate hands lane, lane + n_lanes, ... of this completion (rem_card /
-// rem_pos: the m cards left, pair_xy as in mcq_exact.hpp), each raised to the known hands' best kb; cb_tab from
-// mcq_exact_ext_cb_table.  One opponent (keys == nullptr): the outcome is tallied.  Two opponents: key and packed record
-// are stored for pass B.
-// Acc = McqExactAccWays (one opponent only): tie_c is kept beside the tallies.
-template <class Acc>
-MCQ_HD void mcq_exact_ext_pass_a(const McqExactExtQuery &e, const McqExactBoard &bd, uint32_t kb, uint32_t lane,
-                                 uint32_t n_lanes, const uint16_t *pair_xy, const McqCard *rem_card, const uint32_t *rem_pos,
-                                 const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops, const uint32_t *sd,
-                                 uint32_t *keys, uint32_t *rec, Acc &acc) {
-    for (uint32_t i = lane; i < e.n_pairs; i += n_lanes) {
-        const uint32_t xy = pair_xy[i], x = xy & 0xFFu, y = xy >> 8;
-        McqHole h;
-        h.set(rem_card[x], rem_card[y]);
-        uint32_t key = mcq_eval_key(bd.b, bd.fs, h, tf, tops, sd);
-        const bool level = key == bd.hero_key; /* (split-pot form only) */
-        key = key > kb ? key : kb;
-        const uint32_t pa = rem_pos[x], pb = rem_pos[y];
-        const uint32_t r = mcq_exact_ext_pack(pa, pb, bd.top, e.b.k != 0u, cb_tab[pb * (pb - 1u) / 2u + pa]);
-        if (keys) {
-            keys[i] = key;
-            rec[i] = r;
-        } else {
-            const bool ok = !e.b.ref_law || mcq_exact_ext_above(r) < bd.u;
-            const uint32_t w = ok ? mcq_exact_ext_w1(e.b.ref_law, mcq_exact_ext_cb(r), pa, pb) : 0u;
-            acc.win += key < bd.hero_key ? w : 0u;
-            acc.tie += key == bd.hero_key ? w : 0u;
-            acc.tot += w;
-            if constexpr (Acc::kWays) acc.tie_c += level && key == bd.hero_key ? w : 0u;
-        }
-    }
-}
-
-// Per SEAT with ONE random opponent (mcq_exact_ext_kernel<1, MCQ_ROW_SEATS>).  Per completion the best key among hero and
-// the known hands, the mask `level` of the seats holding it and their number n are wave-uniform
-// (mcq_exact_ext_level_seats), and a candidate hand is above, level with or below that key: a lane keeps THREE sums, the
-// weight above (gt), level (eq) and in all (tot); the weight below is tot - gt - eq.  Candidates, weights and the
-// reference law's completion condition are those of mcq_exact_ext_pass_a's tallying form.
-struct McqExactAccSeats {
-    uint32_t gt, eq, tot;
-};
-MCQ_HD void mcq_exact_ext_pass_seats(const McqExactExtQuery &e, const McqExactBoard &bd, uint32_t best, uint32_t lane,
-                                     uint32_t n_lanes, const uint16_t *pair_xy, const McqCard *rem_card,
-                                     const uint32_t *rem_pos, const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops,
-                                     const uint32_t *sd, McqExactAccSeats &acc) {
+// The candidate hands lane, lane + n_lanes, ... of one completion (rem_card / rem_pos: the m cards left, pair_xy as in
+// mcq_exact.hpp; cb_tab from mcq_exact_ext_cb_table): on(i, pa, pb, key, r, w) gets candidate i's R-positions, its own key,
+// its packed record and its weight as the FIRST opponent's hand (0 where the reference law's completion condition fails).
+// The three bodies below say only what they do with a candidate.
+template <class On>
+MCQ_HD void mcq_exact_ext_candidates(const McqExactExtQuery &e, const McqExactBoard &bd, uint32_t lane, uint32_t n_lanes,
+                                     const uint16_t *pair_xy, const McqCard *rem_card, const uint32_t *rem_pos,
+                                     const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops, const uint32_t *sd, On on) {
     for (uint32_t i = lane; i < e.n_pairs; i += n_lanes) {
         const uint32_t xy = pair_xy[i], x = xy & 0xFFu, y = xy >> 8;
         McqHole h;
@@ -285,11 +209,54 @@ MCQ_HD void mcq_exact_ext_pass_seats(const McqExactExtQuery &e, const McqExactBo
         const uint32_t pa = rem_pos[x], pb = rem_pos[y];
         const uint32_t r = mcq_exact_ext_pack(pa, pb, bd.top, e.b.k != 0u, cb_tab[pb * (pb - 1u) / 2u + pa]);
         const bool ok = !e.b.ref_law || mcq_exact_ext_above(r) < bd.u;
-        const uint32_t w = ok ? mcq_exact_ext_w1(e.b.ref_law, mcq_exact_ext_cb(r), pa, pb) : 0u;
-        acc.gt += key > best ? w : 0u;
-        acc.eq += key == best ? w : 0u;
-        acc.tot += w;
+        on(i, pa, pb, key, r, ok ? mcq_exact_ext_w1(e.b.ref_law, mcq_exact_ext_cb(r), pa, pb) : 0u);
     }
+}
+
+// Pass A, one opponent: the outcome of every candidate, its key raised to the known hands' best kb, is tallied.
+// Acc = McqExactAccWays: tie_c is kept beside the tallies.
+template <class Acc>
+MCQ_HD void mcq_exact_ext_pass_a_tally(const McqExactExtQuery &e, const McqExactBoard &bd, uint32_t kb, uint32_t lane,
+                                 uint32_t n_lanes, const uint16_t *pair_xy, const McqCard *rem_card, const uint32_t *rem_pos,
+                                 const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops, const uint32_t *sd, Acc &acc) {
+    mcq_exact_ext_candidates(e, bd, lane, n_lanes, pair_xy, rem_card, rem_pos, cb_tab, tf, tops, sd,
+                             [&](uint32_t, uint32_t, uint32_t, uint32_t own, uint32_t, uint32_t w) {
+                                 const uint32_t key = own > kb ? own : kb;
+                                 acc.win += key < bd.hero_key ? w : 0u;
+                                 acc.tie += key == bd.hero_key ? w : 0u;
+                                 acc.tot += w;
+                                 if constexpr (Acc::kWays) acc.tie_c += own == bd.hero_key && key == bd.hero_key ? w : 0u;
+                             });
+}
+// Pass A, two opponents: the raised key and the packed record are stored for pass B.
+MCQ_HD void mcq_exact_ext_pass_a_store(const McqExactExtQuery &e, const McqExactBoard &bd, uint32_t kb, uint32_t lane,
+                                       uint32_t n_lanes, const uint16_t *pair_xy, const McqCard *rem_card,
+                                       const uint32_t *rem_pos, const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops,
+                                       const uint32_t *sd, uint32_t *keys, uint32_t *rec) {
+    mcq_exact_ext_candidates(e, bd, lane, n_lanes, pair_xy, rem_card, rem_pos, cb_tab, tf, tops, sd,
+                             [&](uint32_t i, uint32_t, uint32_t, uint32_t own, uint32_t r, uint32_t) {
+                                 keys[i] = own > kb ? own : kb;
+                                 rec[i] = r;
+                             });
+}
+
+// Per SEAT with ONE random opponent (mcq_exact_ext_kernel<1, MCQ_ROW_SEATS>).  Per completion the best key among hero and
+// the known hands, the mask `level` of the seats holding it and their number n are wave-uniform (McqExactKnown: top,
+// level), and a candidate hand is above, level with or below that key: a lane keeps THREE sums, the weight above (gt),
+// level (eq) and in all (tot); the weight below is tot - gt - eq.
+struct McqExactAccSeats {
+    uint32_t gt, eq, tot;
+};
+MCQ_HD void mcq_exact_ext_pass_seats(const McqExactExtQuery &e, const McqExactBoard &bd, uint32_t best, uint32_t lane,
+                                     uint32_t n_lanes, const uint16_t *pair_xy, const McqCard *rem_card,
+                                     const uint32_t *rem_pos, const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops,
+                                     const uint32_t *sd, McqExactAccSeats &acc) {
+    mcq_exact_ext_candidates(e, bd, lane, n_lanes, pair_xy, rem_card, rem_pos, cb_tab, tf, tops, sd,
+                             [&](uint32_t, uint32_t, uint32_t, uint32_t key, uint32_t, uint32_t w) {
+                                 acc.gt += key > best ? w : 0u;
+                                 acc.eq += key == best ? w : 0u;
+                                 acc.tot += w;
+                             });
 }
 // What one completion adds to word `word` of the mcq_result_seats row, from its three sums over all candidates: word 0 is
 // runs, word 2 + 3 s + f is win / tie / share (f = 0, 1, 2) of seat s; the random opponent sits at seat 1 + n_known.
@@ -415,6 +382,65 @@ MCQ_HD void mcq_exact_ext_finish(const McqExactExtQuery &e, const uint8_t *r_id,
     p.win = (double)w.win / runs;
     p.tie = (double)w.tie / runs;
     for (uint32_t t = 0; t < 9; t++) p.by_type[t] = (double)w.by_type[t] / runs;
+}
+
+// ---- the pieces above BY THE NAMES and with the argument lists that the host simulators of the tests call (one-line
+// instances, as in mcq_exact_hero.hpp: the simulators' sources stay what they were, so the host tests pin the shared code
+// as they pinned the copies).  The kernels call the pieces themselves.
+MCQ_HD uint32_t mcq_exact_ext_known_best(const McqExactExtQuery &e, const McqExactBoard &bd, const uint32_t *tf,
+                                         const uint32_t *tops, const uint32_t *sd) {
+    return mcq_exact_ext_known(e, bd, tf, tops, sd).best;
+}
+MCQ_HD uint32_t mcq_exact_ext_known_best_eq(const McqExactExtQuery &e, const McqExactBoard &bd, const uint32_t *tf,
+                                            const uint32_t *tops, const uint32_t *sd, uint32_t &n_eq) {
+    const McqExactKnown kn = mcq_exact_ext_known(e, bd, tf, tops, sd);
+    n_eq = kn.n_eq;
+    return kn.best;
+}
+MCQ_HD uint32_t mcq_exact_ext_level_seats(const McqExactExtQuery &e, const McqExactBoard &bd, const uint32_t *tf,
+                                          const uint32_t *tops, const uint32_t *sd, uint32_t &level) {
+    const McqExactKnown kn = mcq_exact_ext_known(e, bd, tf, tops, sd);
+    level = kn.level;
+    return kn.top;
+}
+// completion `idx` alone: its tallies added to acc, -> hero's hand type; n_eq as above
+MCQ_HD uint32_t mcq_exact_ext_lone_ways(const McqExactExtQuery &e, uint32_t idx, const uint32_t *sel8, const uint32_t *tf,
+                                        const uint32_t *tops, const uint32_t *sd, McqExactAcc &acc, uint32_t &n_eq) {
+    uint32_t pos[5];
+    McqExactBoard bd;
+    McqExactKnown kn;
+    const uint32_t w = mcq_exact_ext_lone_known(e, idx, sel8, tf, tops, sd, pos, bd, kn);
+    const McqExactAcc a = mcq_exact_ext_lone_acc(bd, kn, w);
+    acc.win += a.win;
+    acc.tie += a.tie;
+    acc.tot += a.tot;
+    n_eq = kn.n_eq;
+    return mcq_key_type(bd.hero_key);
+}
+MCQ_HD uint32_t mcq_exact_ext_lone(const McqExactExtQuery &e, uint32_t idx, const uint32_t *sel8, const uint32_t *tf,
+                                   const uint32_t *tops, const uint32_t *sd, McqExactAcc &acc) {
+    uint32_t n_eq;
+    return mcq_exact_ext_lone_ways(e, idx, sel8, tf, tops, sd, acc, n_eq);
+}
+// ... per seat: -> its weight, the level seats' mask and their number k
+MCQ_HD uint32_t mcq_exact_ext_lone_seats(const McqExactExtQuery &e, uint32_t idx, const uint32_t *sel8, const uint32_t *tf,
+                                         const uint32_t *tops, const uint32_t *sd, uint32_t &level, uint32_t &k) {
+    uint32_t pos[5];
+    McqExactBoard bd;
+    McqExactKnown kn;
+    const uint32_t w = mcq_exact_ext_lone_known(e, idx, sel8, tf, tops, sd, pos, bd, kn);
+    level = kn.level;
+    k = mcq_popc(level);
+    return w;
+}
+// pass A with both forms behind one argument list: keys == nullptr tallies, else key and record are stored
+template <class Acc>
+MCQ_HD void mcq_exact_ext_pass_a(const McqExactExtQuery &e, const McqExactBoard &bd, uint32_t kb, uint32_t lane,
+                                 uint32_t n_lanes, const uint16_t *pair_xy, const McqCard *rem_card, const uint32_t *rem_pos,
+                                 const uint8_t *cb_tab, const uint32_t *tf, const uint32_t *tops, const uint32_t *sd,
+                                 uint32_t *keys, uint32_t *rec, Acc &acc) {
+    if (keys) mcq_exact_ext_pass_a_store(e, bd, kb, lane, n_lanes, pair_xy, rem_card, rem_pos, cb_tab, tf, tops, sd, keys, rec);
+    else mcq_exact_ext_pass_a_tally(e, bd, kb, lane, n_lanes, pair_xy, rem_card, rem_pos, cb_tab, tf, tops, sd, acc);
 }
 
 #endif /* MCQ_EXACT_EXT_HPP */

@@ -1,7 +1,8 @@
 // mcq_exact_runout.hpp -- exact equity PER RUNOUT (mcq_exact_batch_ext_runouts): the split-pot enumeration of
 // mcq_exact_ext.hpp, kinds 0 and 1, with the sums of every table completion kept apart instead of folded into one row;
 // lane code shared by mcq_exact_runout_kernel / mcq_exact_runout_cards_kernel (mcq_kernels.hip) and the host build of the
-// tests (tests/hostsim_runouts).  mcq_exact.hpp and mcq_exact_ext.hpp are reused unchanged.
+// tests (tests/hostsim_runouts).  mcq_exact.hpp and mcq_exact_ext.hpp are reused unchanged: a completion's row words are
+// mcq_exact_ext_row_word's, the same function that gives the folded rows of mcq_exact_ext_kernel.
 //
 // Flop (k = 2 cards to come) and turn (k = 1) only.  Per record the device keeps MCQ_XR_ROWS zeroed rows of 22 words
 // (mcq_result_ways): 52 card rows and MCQ_HAND_ROWS pair rows (slots 0..51 and 52..1377).  A completion has exactly ONE
@@ -49,25 +50,23 @@ MCQ_HD unsigned long long *mcq_exact_runout_row(unsigned long long *cards, unsig
     return slot < MCQ_XR_CARD_ROWS ? cards + (size_t)slot * MCQ_XR_WORDS : pairs + (size_t)(slot - MCQ_XR_CARD_ROWS) * MCQ_XR_WORDS;
 }
 
-// Word `word` (< MCQ_XR_WORDS) of one completion's row from its sums over the candidate hands: runs, passes = 0, win, tie,
-// by_type[9] -- hero's hand type is fixed per completion: one entry, win + tie --, tie_ways[9].  n_eq = the known hands
-// level with hero, tie_c = the part of `tie` in which the candidate's key equals hero's too (mcq_exact_ext.hpp): those
-// ties are shared by 2 + n_eq hands, the others by 1 + n_eq (n_eq >= 1 there).  Kind 0 has no candidate: tie_c = 0.
+// a completion's row words, by the name the host simulator of the tests calls
 MCQ_HD unsigned long long mcq_exact_runout_word(uint32_t word, uint32_t win, uint32_t tie, uint32_t tot, uint32_t tie_c,
                                                 uint32_t type, uint32_t n_eq) {
-    if (word < 4u) return word == 0u ? tot : word == 2u ? win : word == 3u ? tie : 0u;
-    if (word < 13u) return word - 4u == type ? win + tie : 0u;
-    const uint32_t j = word - 13u;
-    return (j == n_eq ? tie_c : 0u) + (j + 1u == n_eq ? tie - tie_c : 0u);
+    return mcq_exact_ext_row_word(word, win, tie, tot, tie_c, type, n_eq);
 }
 
-// Kind 0, one lane: completion `idx` alone -> its slot and sums (weight 0 or 1)
+// Kind 0, one lane: completion `idx` alone -> its slot; a (OUT: set, not added to), type and n_eq are its sums (weight 0 or 1)
 MCQ_HD uint32_t mcq_exact_runout_lone(const McqExactExtQuery &e, uint32_t idx, const uint8_t *r_id, const uint32_t *sel8,
                                       const uint32_t *tf, const uint32_t *tops, const uint32_t *sd, McqExactAcc &a,
                                       uint32_t &type, uint32_t &n_eq) {
     uint32_t pos[5];
-    mcq_exact_unrank(idx, e.b.L, e.b.k, pos);
-    type = mcq_exact_ext_lone_ways(e, idx, sel8, tf, tops, sd, a, n_eq);
+    McqExactBoard bd;
+    McqExactKnown kn;
+    const uint32_t w = mcq_exact_ext_lone_known(e, idx, sel8, tf, tops, sd, pos, bd, kn);
+    a = mcq_exact_ext_lone_acc(bd, kn, w);
+    type = mcq_key_type(bd.hero_key);
+    n_eq = kn.n_eq;
     return mcq_exact_runout_slot(e, r_id, pos);
 }
 

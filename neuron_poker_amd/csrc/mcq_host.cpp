@@ -1292,6 +1292,69 @@ int mcq_exact_batch(mcq_ctx *c, const mcq_query *q, size_t n, int law, mcq_resul
 
 }  // extern "C"
 
+/* Validation of a batch of extended records for exact enumeration, shared by exact_batch_ext_impl and
+ * mcq_exact_batch_ext_runouts; nothing is launched for a batch with one record that cannot be enumerated.  build(words,
+ * record, query) is the entry's query builder: it returns MCQ_XX_OK or why not -- below 5 one of the shared reasons, from 5
+ * on more[why - 5].  Then the dealability check, then refuse(i, query) with what only the entry refuses (its text, or
+ * nullptr).  -> xq[n] and the decks' card ids rid[64 n]. */
+template <class Build, class Refuse>
+static int exact_ext_validate(const mcq_query *q, const mcq_query_ext *ext, size_t n, const char *who, Build build,
+                              const char *const *more, Refuse refuse, std::vector<McqExactExtQuery> &xq, std::vector<uint8_t> &rid) {
+    static const char *const reason[] = {
+        "", "invalid extended query (as mcq_eval_batch_ext: distinct card ids < 52, at most 9 known hands, used ranges not empty)",
+        "a hero range is not enumerated (rotate a known hand into the hero's seat)",
+        "a known hand given as a range is not enumerated", "at most two random opponents"};
+    xq.resize(n);
+    rid.resize(n * 64u);
+    for (size_t i = 0; i < n; i++) {
+        const McqExtRec er = {reinterpret_cast<const uint32_t *>(&ext[i])};
+        const int why = build(mcq_query_words(q[i]), er, xq[i]);
+        const char *text = why == MCQ_XX_OK ? nullptr : why < 5 ? reason[why] : more[why - 5];
+        if (!text) {
+            mcq_exact_ext_r_ids(xq[i], &rid[64u * i]);
+            text = !mcq_exact_ext_dealable(xq[i], &rid[64u * i]) ? "the opponents' range cannot be dealt from the remaining cards"
+                                                                 : refuse(i, xq[i]);
+        }
+        if (text) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "query %zu: %s", i, text);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+    }
+    return MCQ_OK;
+}
+
+/* ... and their staging: jobs and extension records travel in pinned memory, the jobs grouped by kind = random opponents;
+ * launch(d_jobs, first, at, max_grid, kind, d_ext) starts jobs [first, at) of one kind.  h1_off (or null): where the
+ * per-first-hand sums of record i begin (kind 2). */
+template <class Launch>
+static int exact_ext_stage(mcq_ctx *c, const mcq_query *q, const mcq_query_ext *ext, size_t n,
+                           const std::vector<McqExactExtQuery> &xq, uint32_t n_kinds, uint64_t *h1_off, Launch launch) {
+    const size_t job_bytes = (n * sizeof(McqExactExtJob) + 255u) & ~(size_t)255u;
+    HIP_TRY(c->h_misc.reserve(job_bytes + n * sizeof(mcq_query_ext)));
+    McqExactExtJob *jobs = static_cast<McqExactExtJob *>(c->h_misc.p);
+    const McqExactExtJob *d_jobs = static_cast<const McqExactExtJob *>(c->h_misc.dev);
+    memcpy(static_cast<uint8_t *>(c->h_misc.p) + job_bytes, ext, n * sizeof(mcq_query_ext));
+    const uint32_t *d_ext = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(c->h_misc.dev) + job_bytes);
+    size_t at = 0;
+    uint64_t off = 0;
+    for (uint32_t kind = 0; kind < n_kinds; kind++) {
+        const size_t first = at;
+        uint32_t max_grid = 0;
+        for (size_t i = 0; i < n; i++) {
+            if (xq[i].b.n_opp != kind) continue;
+            if (h1_off) h1_off[i] = off;
+            const uint32_t g = mcq_exact_ext_plan(&q[i], (uint32_t)i, (uint32_t)i, kind, xq[i].b.L, (uint32_t)off,
+                                                  exact_cu(c), &jobs[at++]);
+            max_grid = g > max_grid ? g : max_grid;
+            if (kind == 2u) off += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
+        }
+        const int rc = launch(d_jobs, first, at, max_grid, kind, d_ext);
+        if (rc) return rc;
+    }
+    return MCQ_OK;
+}
+
 /* mcq_exact_batch_ext, mcq_exact_batch_ext_ways, mcq_exact_batch_seats and mcq_exact_batch_ext_seats: rw = 64-bit words of
  * a weight row; prob -> mcq_exact_prob or mcq_exact_prob_ways (none for the per-seat rows), weights -> rows of rw words;
  * seat_opp = the random opponents a per-seat record may have (0: the all-in entry, 1: the extended one) */
@@ -1304,42 +1367,23 @@ static int exact_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_
     if (!q || !ext || (seats ? !weights : !prob)) return mcq_fail(MCQ_EINVAL, who, "null buffer");
     if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return mcq_fail(MCQ_EINVAL, who, "bad law");
     if (n > 65535u) return mcq_fail(MCQ_EINVAL, who, "at most 65535 queries per call");
-    /* validation first: nothing is launched for a batch with one query that cannot be enumerated */
-    std::vector<McqExactExtQuery> xq(n);
-    std::vector<uint8_t> rid(n * 64u);
-    uint64_t h1_words = 0;
-    for (size_t i = 0; i < n; i++) {
-        const McqExtRec er = {reinterpret_cast<const uint32_t *>(&ext[i])};
-        const int why = mcq_exact_ext_query(mcq_query_words(q[i]), er, law, xq[i]);
-        char buf[200];
-        if (why != MCQ_XX_OK) {
-            static const char *const reason[] = {
-                "", "invalid extended query (as mcq_eval_batch_ext: distinct card ids < 52, at most 9 known hands, used ranges not empty)",
-                "a hero range is not enumerated (rotate a known hand into the hero's seat)",
-                "a known hand given as a range is not enumerated", "at most two random opponents"};
-            snprintf(buf, sizeof buf, "query %zu: %s", i, reason[why]);
-            return mcq_fail(MCQ_EINVAL, who, buf);
-        }
-        mcq_exact_ext_r_ids(xq[i], &rid[64u * i]);
-        if (!mcq_exact_ext_dealable(xq[i], &rid[64u * i])) {
-            snprintf(buf, sizeof buf, "query %zu: the opponents' range cannot be dealt from the remaining cards", i);
-            return mcq_fail(MCQ_EINVAL, who, buf);
-        }
-        if (seats && xq[i].b.n_opp > seat_opp) {
-            if (seat_opp == 0u)
-                snprintf(buf, sizeof buf, "query %zu: the per-seat enumeration takes known hands only (n_players == 1 + n_known)", i);
-            else
-                snprintf(buf, sizeof buf, "query %zu: two random opponents have no per-seat enumeration", i);
-            return mcq_fail(MCQ_EINVAL, who, buf);
-        }
-        if (xq[i].b.n_opp == 2u) {
-            if (ways) {
-                snprintf(buf, sizeof buf, "query %zu: two random opponents have no split-pot enumeration", i);
-                return mcq_fail(MCQ_EINVAL, who, buf);
-            }
-            h1_words += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
-        }
-    }
+    std::vector<McqExactExtQuery> xq;
+    std::vector<uint8_t> rid;
+    int rc = exact_ext_validate(
+        q, ext, n, who,
+        [law](const McqQueryWords &w, const McqExtRec &er, McqExactExtQuery &e) { return mcq_exact_ext_query(w, er, law, e); }, nullptr,
+        [=](size_t, const McqExactExtQuery &e) -> const char * {
+            if (seats && e.b.n_opp > seat_opp)
+                return seat_opp == 0u ? "the per-seat enumeration takes known hands only (n_players == 1 + n_known)"
+                                      : "two random opponents have no per-seat enumeration";
+            if (e.b.n_opp == 2u && ways) return "two random opponents have no split-pot enumeration";
+            return nullptr;
+        },
+        xq, rid);
+    if (rc) return rc;
+    uint64_t h1_words = 0; /* the per-first-hand sums of the two-opponent records */
+    for (size_t i = 0; i < n; i++)
+        if (xq[i].b.n_opp == 2u) h1_words += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
     MCQ_ENTER(c, who);
     McqDeviceScope dev_(c->device);
     HIP_TRY(dev_.err);
@@ -1352,30 +1396,14 @@ static int exact_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_
         HIP_TRY(c->d_draws.reserve(h1_words * 8u));
         HIP_TRY(hipMemsetAsync(c->d_draws.p, 0, h1_words * 8u, c->stream));
     }
-    /* jobs and extension records travel in pinned memory, the jobs grouped by kind */
-    const size_t job_bytes = (n * sizeof(McqExactExtJob) + 255u) & ~(size_t)255u;
-    HIP_TRY(c->h_misc.reserve(job_bytes + n * sizeof(mcq_query_ext)));
-    McqExactExtJob *jobs = static_cast<McqExactExtJob *>(c->h_misc.p);
-    const McqExactExtJob *d_jobs = static_cast<const McqExactExtJob *>(c->h_misc.dev);
-    memcpy(static_cast<uint8_t *>(c->h_misc.p) + job_bytes, ext, n * sizeof(mcq_query_ext));
-    const uint32_t *d_ext = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(c->h_misc.dev) + job_bytes);
     std::vector<uint64_t> h1_off(n, 0);
-    size_t at = 0;
-    uint64_t off = 0;
-    for (uint32_t kind = 0; kind < 3u; kind++) {
-        const size_t first = at;
-        uint32_t max_grid = 0;
-        for (size_t i = 0; i < n; i++) {
-            if (xq[i].b.n_opp != kind) continue;
-            h1_off[i] = off;
-            const uint32_t g = mcq_exact_ext_plan(&q[i], (uint32_t)i, (uint32_t)i, kind, xq[i].b.L, (uint32_t)off,
-                                                  exact_cu(c), &jobs[at++]);
-            max_grid = g > max_grid ? g : max_grid;
-            if (kind == 2u) off += (uint64_t)xq[i].n_rp * MCQ_XX_SUMS;
-        }
-        HIP_TRY(mcq_launch_exact_ext(d_jobs + first, (uint32_t)(at - first), max_grid, kind, d_ext, law, (mcq_result *)c->d_res.p,
-                                     (unsigned long long *)c->d_draws.p, c->d_luts, c->stream, ways, seats));
-    }
+    rc = exact_ext_stage(c, q, ext, n, xq, 3u, h1_off.data(),
+                         [&](const McqExactExtJob *d_jobs, size_t first, size_t at, uint32_t max_grid, uint32_t kind, const uint32_t *d_ext) {
+                             HIP_TRY(mcq_launch_exact_ext(d_jobs + first, (uint32_t)(at - first), max_grid, kind, d_ext, law, (mcq_result *)c->d_res.p,
+                                                          (unsigned long long *)c->d_draws.p, c->d_luts, c->stream, ways, seats));
+                             return (int)MCQ_OK;
+                         });
+    if (rc) return rc;
     uint8_t *hr = static_cast<uint8_t *>(c->h_res.p);
     HIP_TRY(hipMemcpyAsync(hr, c->d_res.p, n * row_bytes, hipMemcpyDeviceToHost, c->stream));
     if (h1_words)
@@ -1599,31 +1627,18 @@ int mcq_exact_batch_ext_runouts(mcq_ctx *c, const mcq_query *q, const mcq_query_
     if (!q || !ext || !cards) return mcq_fail(MCQ_EINVAL, who, "null buffer");
     if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return mcq_fail(MCQ_EINVAL, who, "bad law");
     if (n > MCQ_RUNOUT_MAX_BATCH) return mcq_fail(MCQ_EINVAL, who, "at most MCQ_RUNOUT_MAX_BATCH queries per call");
-    /* validation first, as mcq_exact_batch_ext_ways: nothing is launched for a batch with one record that is refused */
-    std::vector<McqExactExtQuery> xq(n);
-    char buf[200];
-    for (size_t i = 0; i < n; i++) {
-        const McqExtRec er = {reinterpret_cast<const uint32_t *>(&ext[i])};
-        const int why = mcq_exact_runout_query(mcq_query_words(q[i]), er, law, xq[i]);
-        if (why != MCQ_XX_OK) {
-            static const char *const reason[] = {
-                "", "invalid extended query (as mcq_eval_batch_ext: distinct card ids < 52, at most 9 known hands, used ranges not empty)",
-                "a hero range is not enumerated (rotate a known hand into the hero's seat)",
-                "a known hand given as a range is not enumerated", "at most two random opponents",
-                "two random opponents have no split-pot enumeration, so none per runout",
-                "runouts are enumerated on the flop and the turn only (3 or 4 table cards): preflop a record has C(50, 5) "
-                "completions",
-                "five table cards: no card to come"};
-            snprintf(buf, sizeof buf, "query %zu: %s", i, reason[why]);
-            return mcq_fail(MCQ_EINVAL, who, buf);
-        }
-        uint8_t rid[64];
-        mcq_exact_ext_r_ids(xq[i], rid);
-        if (!mcq_exact_ext_dealable(xq[i], rid)) {
-            snprintf(buf, sizeof buf, "query %zu: the opponents' range cannot be dealt from the remaining cards", i);
-            return mcq_fail(MCQ_EINVAL, who, buf);
-        }
-    }
+    static const char *const more[] = {
+        "two random opponents have no split-pot enumeration, so none per runout",
+        "runouts are enumerated on the flop and the turn only (3 or 4 table cards): preflop a record has C(50, 5) "
+        "completions",
+        "five table cards: no card to come"};
+    std::vector<McqExactExtQuery> xq;
+    std::vector<uint8_t> rid;
+    int rc = exact_ext_validate(
+        q, ext, n, who,
+        [law](const McqQueryWords &w, const McqExtRec &er, McqExactExtQuery &e) { return mcq_exact_runout_query(w, er, law, e); }, more,
+        [](size_t, const McqExactExtQuery &) -> const char * { return nullptr; }, xq, rid);
+    if (rc) return rc;
     MCQ_ENTER(c, who);
     McqDeviceScope dev_(c->device);
     HIP_TRY(dev_.err);
@@ -1635,25 +1650,14 @@ int mcq_exact_batch_ext_runouts(mcq_ctx *c, const mcq_query *q, const mcq_query_
     HIP_TRY(c->h_res.reserve(back_bytes));
     HIP_TRY(hipMemsetAsync(c->d_res.p, 0, card_bytes + pair_bytes, c->stream));
     mcq_result_ways *d_cards = static_cast<mcq_result_ways *>(c->d_res.p), *d_pairs = d_cards + n * MCQ_XR_CARD_ROWS;
-    /* jobs and extension records travel in pinned memory, the jobs grouped by kind */
-    const size_t job_bytes = (n * sizeof(McqExactExtJob) + 255u) & ~(size_t)255u;
-    HIP_TRY(c->h_misc.reserve(job_bytes + n * sizeof(mcq_query_ext)));
-    McqExactExtJob *jobs = static_cast<McqExactExtJob *>(c->h_misc.p);
+    rc = exact_ext_stage(c, q, ext, n, xq, 2u, nullptr,
+                         [&](const McqExactExtJob *d_jobs, size_t first, size_t at, uint32_t max_grid, uint32_t kind, const uint32_t *d_ext) {
+                             HIP_TRY(mcq_launch_exact_runouts(d_jobs + first, (uint32_t)(at - first), max_grid, kind, d_ext, law, d_cards, d_pairs,
+                                                              c->d_luts, c->stream));
+                             return (int)MCQ_OK;
+                         });
+    if (rc) return rc;
     const McqExactExtJob *d_jobs = static_cast<const McqExactExtJob *>(c->h_misc.dev);
-    memcpy(static_cast<uint8_t *>(c->h_misc.p) + job_bytes, ext, n * sizeof(mcq_query_ext));
-    const uint32_t *d_ext = reinterpret_cast<const uint32_t *>(static_cast<uint8_t *>(c->h_misc.dev) + job_bytes);
-    size_t at = 0;
-    for (uint32_t kind = 0; kind < 2u; kind++) {
-        const size_t first = at;
-        uint32_t max_grid = 0;
-        for (size_t i = 0; i < n; i++) {
-            if (xq[i].b.n_opp != kind) continue;
-            const uint32_t g = mcq_exact_ext_plan(&q[i], (uint32_t)i, (uint32_t)i, kind, xq[i].b.L, 0u, exact_cu(c), &jobs[at++]);
-            max_grid = g > max_grid ? g : max_grid;
-        }
-        HIP_TRY(mcq_launch_exact_runouts(d_jobs + first, (uint32_t)(at - first), max_grid, kind, d_ext, law, d_cards, d_pairs,
-                                         c->d_luts, c->stream));
-    }
     HIP_TRY(mcq_launch_exact_runout_cards(d_jobs, (uint32_t)n, d_cards, d_pairs, c->stream));
     HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, back_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "mcq_device.hpp"
 #include "mcq_exact.hpp"
 #include "mcq_exact_ext.hpp"
@@ -2011,285 +2013,25 @@ __global__ __launch_bounds__(TWO_OPP ? 384 : 1024) void mcq_exact_kernel(const M
 //      group * 1024 + t (an R-pair: fixed across completions) and walks every second hand; its sums stay in registers
 //      until the block's last completion and go to h1_sums[job.h1_off + 12 * hand] (integer atomics: deterministic).
 //      LDS: 97 KB of tables + 10 KB of keys and records, one block of 16 waves per CU.
-// Kinds 0 and 1 add into the zeroed row rows[job.row] by lane roles as mcq_exact_kernel does.
-// ROW = MCQ_ROW_WAYS (kinds 0 and 1): 22-word rows; lane 13 + (k - 2) adds the weight of the ties shared by k hands
-// (mcq_exact_ext.hpp).  ROW = MCQ_ROW_SEATS (kinds 0 and 1): 32-word rows of mcq_result_seats.  Kind 0 (the all-in case): a
-// lane ranks every hand of its completion, the level seats' weights are summed over the wave and lane l adds word l of
-// the row.  Kind 1, mcq_exact_ext_kernel<1, MCQ_ROW_SEATS>: the best key among hero and the known hands is wave-uniform,
-// so a lane keeps the candidates' weight above it, level with it and in all; after three wave sums lane l adds what the
-// completion gives word l (mcq_exact_ext_seats_word).  Two random opponents have no per-seat form.
-template <uint32_t KIND, int ROW>
-__global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
-                                                             int law, mcq_result *__restrict__ rows,
-                                                             unsigned long long *__restrict__ h1_sums,
-                                                             const McqTables *__restrict__ g_tab) {
-    const McqExactExtJob job = jobs[blockIdx.y];
-    if (blockIdx.x >= job.grid) return;
-    constexpr uint32_t kWaves = 16u, kRem = KIND == 1u ? kWaves : 1u;
-    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
-    __shared__ uint16_t pair_xy[MCQ_EXACT_PAIRS + 2];
-    __shared__ uint32_t xw[MCQ_EXT_WORDS];
-    __shared__ McqExactExtQuery xq;
-    __shared__ uint8_t r_id[64];
-    __shared__ uint8_t cb_tab[KIND != 0u ? MCQ_XX_MAX_RP : 1u];
-    __shared__ McqCard rem_card_all[kRem][64];
-    __shared__ uint32_t rem_pos_all[kRem][64];
-    __shared__ uint32_t keys[KIND == 2u ? MCQ_EXACT_PAIRS + 2 : 1u];
-    __shared__ uint32_t recs[KIND == 2u ? MCQ_EXACT_PAIRS + 2 : 1u];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
-    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
-    for (uint32_t i = tid; i < MCQ_EXACT_PAIRS; i += blockDim.x) {
-        uint32_t x, y;
-        mcq_exact_pair_xy(i, x, y);
-        pair_xy[i] = (uint16_t)(x | (y << 8));
-    }
-    load_tables(tab, g_tab); /* ends with a barrier */
-    if (tid == 0) {
-        const McqExtRec er = {xw};
-        (void)mcq_exact_ext_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, law, xq); /* validated by the host */
-        mcq_exact_ext_r_ids(xq, r_id);
-    }
-    __syncthreads();
-    const McqExactExtQuery &e = xq;
-    if (KIND != 0u) {
-        mcq_exact_ext_cb_table(e, r_id, tid, blockDim.x, cb_tab);
-        __syncthreads();
-    }
-    const uint32_t n_boards = job.n_boards;
-    constexpr bool WAYS = ROW == MCQ_ROW_WAYS;
-    static_assert(!WAYS || KIND != 2u, "two random opponents have no split-pot form");
-    static_assert(ROW != MCQ_ROW_SEATS || KIND <= 1u, "two random opponents have no per-seat form");
+// Kinds 0 and 1 add into the zeroed row rows[job.row]: lane l adds word l of the row, one atomic at the end.
+// ROW = MCQ_ROW_WAYS (kinds 0 and 1): 22-word rows; word 13 + (k - 2) is the weight of the ties shared by k hands
+// (mcq_exact_ext_row_word).  ROW = MCQ_ROW_SEATS (kinds 0 and 1): 32-word rows of mcq_result_seats
+// (mcq_exact_ext_seats_word).  Two random opponents have neither form.
+// Three bodies, one per kind; what differs by ROW is a small policy: McqExactLoneSums<ROW> (kind 0: a lane's counters over
+// its completions and their flush into lane roles) and McqExactRow<ROW> (kind 1: a lane's accumulator over the candidates of
+// one completion, the pass that fills it and the row word that the wave sums give).  mcq_exact_runout_kernel uses the same
+// loops with "store the completion's row" in place of "add to a running sum".
 
-    if constexpr (KIND == 0u && ROW == MCQ_ROW_SEATS) {
-        /* A lane sees at most C(48, 5) / 1024 + 1 = 1673 completions (one block), each of weight 0 or 1: a seat's share,
-         * in units of 2520 / k, stays below 2^23 per lane and 2^29 per wave; win and tie share one word as 16-bit halves. */
-        uint32_t tot = 0, share[MCQ_MAX_SEATS], wt[MCQ_MAX_SEATS];
-#pragma unroll
-        for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) share[s] = wt[s] = 0;
-        for (uint32_t idx = blockIdx.x * blockDim.x + tid; idx < n_boards; idx += job.grid * blockDim.x) {
-            uint32_t level, k;
-            const uint32_t w = mcq_exact_ext_lone_seats(e, idx, tab.sel8, g_tab->tf, tab.tops, tab.sd, level, k);
-            const uint32_t inc = w ? mcq_seat_increment(k) : 0u;
-            tot += w;
-#pragma unroll
-            for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) {
-                const bool on = ((level >> s) & 1u) != 0u;
-                share[s] += on ? inc & 0xFFFFu : 0u;
-                wt[s] += on ? ((inc >> MCQ_SEAT_WIN_SHIFT) & 1u) | (((inc >> MCQ_SEAT_TIE_SHIFT) & 1u) << 16) : 0u;
-            }
-        }
-        /* (64 lanes x 1673 does not fit a 16-bit half: win and tie are summed apart) */
-        unsigned long long mine = 0;
-        const uint32_t t = wave_sum(tot);
-        mine = lane == 0u ? t : 0ull;
-#pragma unroll
-        for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) {
-            const uint32_t win = wave_sum(wt[s] & 0xFFFFu), tie = wave_sum(wt[s] >> 16), sh = wave_sum(share[s]);
-            mine = lane == 2u + 3u * s ? win : lane == 3u + 3u * s ? tie : lane == 4u + 3u * s ? sh : mine;
-        }
-        if (lane < McqRowKind<MCQ_ROW_SEATS>::kWords && mine != 0ull)
-            atomicAdd(McqRowKind<MCQ_ROW_SEATS>::row(rows, job.row) + lane, mine);
-    } else if constexpr (KIND == 1u && ROW == MCQ_ROW_SEATS) {
-        McqCard *rem_card = rem_card_all[wib];
-        uint32_t *rem_pos = rem_pos_all[wib];
-        const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wib), n_waves = job.grid * kWaves;
-        unsigned long long sum = 0;
-        for (uint32_t board = wave; board < n_boards; board += n_waves) {
-            uint32_t pos[5];
-            mcq_exact_unrank(board, e.b.L, e.b.k, pos);
-            McqExactBoard bd;
-            mcq_exact_board(e.b, pos, tab.sel8, g_tab->tf, tab.tops, tab.sd, bd);
-            uint32_t level;
-            const uint32_t best = mcq_exact_ext_level_seats(e, bd, g_tab->tf, tab.tops, tab.sd, level);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* the previous completion's reads are done (same wave) */
-            if (lane < e.m) {
-                const uint32_t rp = mcq_exact_rem_pos(pos, lane);
-                rem_pos[lane] = rp;
-                rem_card[lane] = mcq_card(r_id[rp]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            McqExactAccSeats acc = {0, 0, 0};
-            mcq_exact_ext_pass_seats(e, bd, best, lane, 64u, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, acc);
-            const uint32_t gt = wave_sum(acc.gt), eq = wave_sum(acc.eq), tot = wave_sum(acc.tot);
-            /* lane l keeps word l of the row (lanes 32..63: seats nobody holds, nothing) */
-            sum += mcq_exact_ext_seats_word(lane, level, e.n_known, gt, eq, tot);
-        }
-        if (lane < McqRowKind<MCQ_ROW_SEATS>::kWords && sum != 0ull)
-            atomicAdd(McqRowKind<MCQ_ROW_SEATS>::row(rows, job.row) + lane, sum);
-    } else if constexpr (KIND == 0u && WAYS) {
-        McqExactAcc acc = {0, 0, 0};
-        uint32_t by_type[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ways[MCQ_N_WAYS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (uint32_t idx = blockIdx.x * blockDim.x + tid; idx < n_boards; idx += job.grid * blockDim.x) {
-            McqExactAcc a = {0, 0, 0};
-            uint32_t n_eq;
-            const uint32_t t = mcq_exact_ext_lone_ways(e, idx, tab.sel8, g_tab->tf, tab.tops, tab.sd, a, n_eq);
-            acc.win += a.win;
-            acc.tie += a.tie;
-            acc.tot += a.tot;
-#pragma unroll
-            for (uint32_t j = 0; j < 9; j++) by_type[j] += j == t ? a.win + a.tie : 0u;
-#pragma unroll
-            for (uint32_t j = 0; j < MCQ_N_WAYS; j++) ways[j] += j + 1u == n_eq ? a.tie : 0u; /* a tie: n_eq >= 1 */
-        }
-        uint32_t mine = 0;
-        const uint32_t tot = wave_sum(acc.tot), win = wave_sum(acc.win), tie = wave_sum(acc.tie);
-        mine = lane == 0u ? tot : lane == 2u ? win : lane == 3u ? tie : 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 9; j++) {
-            const uint32_t v = wave_sum(by_type[j]);
-            mine = lane == 4u + j ? v : mine;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < MCQ_N_WAYS; j++) {
-            const uint32_t v = wave_sum(ways[j]);
-            mine = lane == 13u + j ? v : mine;
-        }
-        if (lane < 13u + MCQ_N_WAYS && mine != 0u)
-            atomicAdd(McqRowKind<true>::row(rows, job.row) + lane, (unsigned long long)mine);
-    } else if constexpr (KIND == 1u && WAYS) {
-        McqCard *rem_card = rem_card_all[wib];
-        uint32_t *rem_pos = rem_pos_all[wib];
-        const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wib), n_waves = job.grid * kWaves;
-        unsigned long long sum = 0;
-        for (uint32_t board = wave; board < n_boards; board += n_waves) {
-            uint32_t pos[5];
-            mcq_exact_unrank(board, e.b.L, e.b.k, pos);
-            McqExactBoard bd;
-            mcq_exact_board(e.b, pos, tab.sel8, g_tab->tf, tab.tops, tab.sd, bd);
-            uint32_t n_eq;
-            const uint32_t kb = mcq_exact_ext_known_best_eq(e, bd, g_tab->tf, tab.tops, tab.sd, n_eq);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* the previous completion's reads are done (same wave) */
-            if (lane < e.m) {
-                const uint32_t rp = mcq_exact_rem_pos(pos, lane);
-                rem_pos[lane] = rp;
-                rem_card[lane] = mcq_card(r_id[rp]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            McqExactAccWays acc = {0, 0, 0, 0};
-            mcq_exact_ext_pass_a(e, bd, kb, lane, 64u, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, nullptr,
-                                 nullptr, acc);
-            const uint32_t win = wave_sum(acc.win), tie = wave_sum(acc.tie), tot = wave_sum(acc.tot), tie_c = wave_sum(acc.tie_c);
-            const uint32_t type = mcq_key_type(bd.hero_key);
-            if (lane == 0u) sum += tot;
-            if (lane == 2u) sum += win;
-            if (lane == 3u) sum += tie;
-            if (lane == 4u + type) sum += win + tie;
-            /* the candidate level with hero: 2 + n_eq hands share; else a known hand is (n_eq >= 1): 1 + n_eq hands.
-             * One random opponent leaves at most eight known hands: lane 13 + n_eq <= 21 */
-            if (lane == 13u + n_eq) sum += tie_c;
-            if (lane + 1u == 13u + n_eq) sum += tie - tie_c; /* (n_eq == 0: lane 12, and the difference is zero) */
-        }
-        if (lane < 13u + MCQ_N_WAYS && sum != 0ull) atomicAdd(McqRowKind<true>::row(rows, job.row) + lane, sum);
-    } else if (KIND == 0u) {
-        McqExactAcc acc = {0, 0, 0};
-        uint32_t by_type[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (uint32_t idx = blockIdx.x * blockDim.x + tid; idx < n_boards; idx += job.grid * blockDim.x) {
-            McqExactAcc a = {0, 0, 0};
-            const uint32_t t = mcq_exact_ext_lone(e, idx, tab.sel8, g_tab->tf, tab.tops, tab.sd, a);
-            acc.win += a.win;
-            acc.tie += a.tie;
-            acc.tot += a.tot;
-#pragma unroll
-            for (uint32_t j = 0; j < 9; j++) by_type[j] += j == t ? a.win + a.tie : 0u;
-        }
-        uint32_t mine = 0; /* lane roles as mcq_exact_kernel: 0 total, 2 wins, 3 ties, 4 + t type t */
-        const uint32_t tot = wave_sum(acc.tot), win = wave_sum(acc.win), tie = wave_sum(acc.tie);
-        mine = lane == 0u ? tot : lane == 2u ? win : lane == 3u ? tie : 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 9; j++) {
-            const uint32_t v = wave_sum(by_type[j]);
-            mine = lane == 4u + j ? v : mine;
-        }
-        if (lane < 13u && mine != 0u) atomicAdd(reinterpret_cast<unsigned long long *>(rows + job.row) + lane, (unsigned long long)mine);
-    } else if (KIND == 1u) {
-        McqCard *rem_card = rem_card_all[wib];
-        uint32_t *rem_pos = rem_pos_all[wib];
-        const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wib), n_waves = job.grid * kWaves;
-        unsigned long long sum = 0;
-        for (uint32_t board = wave; board < n_boards; board += n_waves) {
-            uint32_t pos[5];
-            mcq_exact_unrank(board, e.b.L, e.b.k, pos);
-            McqExactBoard bd;
-            mcq_exact_board(e.b, pos, tab.sel8, g_tab->tf, tab.tops, tab.sd, bd);
-            const uint32_t kb = mcq_exact_ext_known_best(e, bd, g_tab->tf, tab.tops, tab.sd);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* the previous completion's reads are done (same wave) */
-            if (lane < e.m) {
-                const uint32_t rp = mcq_exact_rem_pos(pos, lane);
-                rem_pos[lane] = rp;
-                rem_card[lane] = mcq_card(r_id[rp]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            McqExactAcc acc = {0, 0, 0};
-            mcq_exact_ext_pass_a(e, bd, kb, lane, 64u, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, nullptr,
-                                 nullptr, acc);
-            const uint32_t win = wave_sum(acc.win), tie = wave_sum(acc.tie), tot = wave_sum(acc.tot);
-            const uint32_t type = mcq_key_type(bd.hero_key);
-            if (lane == 0u) sum += tot;
-            if (lane == 2u) sum += win;
-            if (lane == 3u) sum += tie;
-            if (lane == 4u + type) sum += win + tie;
-        }
-        if (lane < 13u && sum != 0ull) atomicAdd(reinterpret_cast<unsigned long long *>(rows + job.row) + lane, sum);
-    } else {
-        McqCard *rem_card = rem_card_all[0];
-        uint32_t *rem_pos = rem_pos_all[0];
-        const uint32_t groups = job.groups, group = blockIdx.x % groups, h = group * blockDim.x + tid;
-        const bool own = h < e.n_rp;
-        uint32_t qa = 0, qb = 1;
-        if (own) mcq_exact_pair_xy(h, qa, qb);
-        McqExactExtSums s = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
-        for (uint32_t board = blockIdx.x / groups; board < n_boards; board += job.grid / groups) {
-            uint32_t pos[5];
-            mcq_exact_unrank(board, e.b.L, e.b.k, pos);
-            McqExactBoard bd;
-            mcq_exact_board(e.b, pos, tab.sel8, g_tab->tf, tab.tops, tab.sd, bd);
-            const uint32_t kb = mcq_exact_ext_known_best(e, bd, g_tab->tf, tab.tops, tab.sd);
-            __syncthreads(); /* the previous completion's pass B is done with keys and records */
-            if (tid < e.m) {
-                const uint32_t rp = mcq_exact_rem_pos(pos, tid);
-                rem_pos[tid] = rp;
-                rem_card[tid] = mcq_card(r_id[rp]);
-            }
-            __syncthreads();
-            McqExactAcc unused = {0, 0, 0};
-            mcq_exact_ext_pass_a(e, bd, kb, tid, blockDim.x, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, keys,
-                                 recs, unused);
-            __syncthreads();
-            const uint32_t mi = own ? mcq_exact_ext_m_index(e, pos, qa, qb) : e.n_pairs;
-            if (mi < e.n_pairs) {
-                McqExactAcc acc = {0, 0, 0};
-                mcq_exact_ext_pass_b(e, bd, qa, qb, mi, keys, recs, acc);
-                mcq_exact_ext_add(s, acc, mcq_key_type(bd.hero_key));
-            }
-        }
-        if (own) {
-            unsigned long long *dst = h1_sums + job.h1_off + (size_t)h * MCQ_XX_SUMS;
-            if (s.win) atomicAdd(dst + 0, s.win);
-            if (s.tie) atomicAdd(dst + 1, s.tie);
-            if (s.tot) atomicAdd(dst + 2, s.tot);
-#pragma unroll
-            for (uint32_t t = 0; t < 9; t++)
-                if (s.type[t]) atomicAdd(dst + 3 + t, s.type[t]);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------- exact enumeration, hero range
-// Four kernels -- postflop or preflop, class bits or a weight per hand (McqHeroKind<W>, mcq_exact_hero.hpp) -- made of two
-// bodies, one per street, and of the four helpers below, which both bodies share.  One job per query (blockIdx.y), a BLOCK
-// of 1024 threads per table completion, one block of 16 waves per CU.
-
-// Block prologue: the record's extension words, every D-pair as qa | qb << 8 (N_PAIRS entries), the evaluator's tables, the
-// query (built by thread 0; the host has validated it) and the deck's card ids.  Ends with a barrier.
-template <uint32_t N_PAIRS>
-__device__ __forceinline__ void hero_prologue(const McqExactExtJob &job, const uint32_t *__restrict__ ext, int law,
-                                              const McqTables *__restrict__ g_tab, LdsTablesEval &tab, uint16_t *pair_xy, uint32_t *xw,
-                                              McqExactHeroQuery &xq, uint8_t *r_id) {
+// Block prologue of the family (also of the hero bodies below): the record's extension words, the pair list (N_PAIRS entries
+// x | y << 8), the evaluator's tables, the query -- built by thread 0, the host has validated it; build(words, record)
+// returns its McqExactExtQuery -- and the deck's card ids by R-position (zero at and above L).  Ends with a barrier.
+template <uint32_t N_PAIRS, class Build>
+__device__ __forceinline__ void exact_prologue(const McqExactExtJob &job, const uint32_t *__restrict__ ext,
+                                               const McqTables *__restrict__ g_tab, LdsTablesEval &tab, uint16_t *pair_xy,
+                                               uint32_t *xw, uint8_t *r_id, Build build) {
     const uint32_t tid = threadIdx.x;
     if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
+    if (tid < 64u) r_id[tid] = 0;
     for (uint32_t i = tid; i < N_PAIRS; i += blockDim.x) {
         uint32_t x, y;
         mcq_exact_pair_xy(i, x, y);
@@ -2298,10 +2040,272 @@ __device__ __forceinline__ void hero_prologue(const McqExactExtJob &job, const u
     load_tables(tab, g_tab); /* ends with a barrier */
     if (tid == 0) {
         const McqExtRec er = {xw};
-        (void)mcq_exact_hero_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, law, false, xq);
-        mcq_exact_ext_r_ids(xq.x, r_id);
+        mcq_exact_ext_r_ids(build({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er), r_id);
     }
     __syncthreads();
+}
+
+/* A thread's view of its block's LDS beside the 97 KB of tables.  The arrays are declared by the kernel itself (a kernel
+ * pays only for those it reads: kind 0 keeps no pair list, no range bits and no rem lists); rem_card / rem_pos are the
+ * thread's own wave's (kind 1) or the block's (kind 2). */
+struct McqExactExtBlock {
+    static constexpr uint32_t kWaves = 16u;
+    LdsTablesEval &tab;
+    McqExactExtQuery &xq;
+    uint16_t *pair_xy;
+    uint8_t *r_id, *cb_tab;
+    McqCard *rem_card;
+    uint32_t *rem_pos;
+};
+
+/* ... and its filling: the prologue, then (kinds 1 and 2) the range bits of every R-pair */
+template <uint32_t KIND, class Build>
+__device__ __forceinline__ void exact_ext_setup(const McqExactExtJob &job, const uint32_t *__restrict__ ext,
+                                                const McqTables *__restrict__ g_tab, const McqExactExtBlock &s, uint32_t *xw,
+                                                Build build) {
+    exact_prologue<MCQ_EXACT_PAIRS>(job, ext, g_tab, s.tab, s.pair_xy, xw, s.r_id, build);
+    if (KIND != 0u) {
+        mcq_exact_ext_cb_table(s.xq, s.r_id, threadIdx.x, blockDim.x, s.cb_tab);
+        __syncthreads();
+    }
+}
+
+// One completion whose candidate hands its owner's threads share -- a wave (`who` = the lane) or, BLOCK, the block (`who`
+// = the thread): its R-positions, board and known hands, then the m cards left in rem_pos / rem_card, written between two
+// fences (the owner's reads of the previous completion are done; the new lists are visible) and ready after the barrier.
+template <bool BLOCK>
+__device__ __forceinline__ McqExactKnown exact_step(const McqExactExtBlock &s, uint32_t board, const McqTables *__restrict__ g_tab,
+                                                    uint32_t who, uint32_t pos[5], McqExactBoard &bd) {
+    const McqExactExtQuery &e = s.xq;
+    mcq_exact_unrank(board, e.b.L, e.b.k, pos);
+    mcq_exact_board(e.b, pos, s.tab.sel8, g_tab->tf, s.tab.tops, s.tab.sd, bd);
+    const McqExactKnown kn = mcq_exact_ext_known(e, bd, g_tab->tf, s.tab.tops, s.tab.sd);
+    if (BLOCK) __syncthreads();
+    else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    if (who < e.m) {
+        const uint32_t rp = mcq_exact_rem_pos(pos, who);
+        s.rem_pos[who] = rp;
+        s.rem_card[who] = mcq_card(s.r_id[rp]);
+    }
+    if (BLOCK) {
+        __syncthreads();
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    return kn;
+}
+
+// Kind 0: a lane per completion -- on(idx) for the completions this thread owns.
+template <class On>
+__device__ __forceinline__ void exact_lane_loop(const McqExactExtJob &job, On on) {
+    for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < job.n_boards; idx += job.grid * blockDim.x) on(idx);
+}
+
+/* ... and a lane's counters over them.  Plain and split-pot rows: weights of 0 or 1, at most C(48, 5) / 1024 + 1 = 1673 per
+ * lane; a tie without a random opponent is shared by 1 + n_eq hands (n_eq >= 1).  word(lane) = word `lane` of the row
+ * after the wave sums. */
+template <int ROW> struct McqExactLoneSums {
+    static constexpr bool kWays = ROW == MCQ_ROW_WAYS;
+    McqExactAcc acc;
+    uint32_t by_type[9], ways[kWays ? MCQ_N_WAYS : 1u];
+    __device__ __forceinline__ void add(const McqExactBoard &bd, const McqExactKnown &kn, uint32_t w) {
+        const McqExactAcc a = mcq_exact_ext_lone_acc(bd, kn, w);
+        const uint32_t t = mcq_key_type(bd.hero_key);
+        acc.win += a.win;
+        acc.tie += a.tie;
+        acc.tot += a.tot;
+#pragma unroll
+        for (uint32_t j = 0; j < 9; j++) by_type[j] += j == t ? a.win + a.tie : 0u;
+        if constexpr (kWays) {
+#pragma unroll
+            for (uint32_t j = 0; j < MCQ_N_WAYS; j++) ways[j] += j + 1u == kn.n_eq ? a.tie : 0u;
+        }
+    }
+    __device__ __forceinline__ unsigned long long word(uint32_t lane) const {
+        const uint32_t tot = wave_sum(acc.tot), win = wave_sum(acc.win), tie = wave_sum(acc.tie);
+        uint32_t mine = lane < 4u ? (uint32_t)mcq_exact_ext_row_word(lane, win, tie, tot, 0u, 0u, 0u) : 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 9; j++) {
+            const uint32_t v = wave_sum(by_type[j]);
+            mine = lane == 4u + j ? v : mine;
+        }
+        if constexpr (kWays) {
+#pragma unroll
+            for (uint32_t j = 0; j < MCQ_N_WAYS; j++) {
+                const uint32_t v = wave_sum(ways[j]);
+                mine = lane == 13u + j ? v : mine;
+            }
+        }
+        return mine;
+    }
+};
+/* Per seat (the all-in case): a lane ranks every hand of its completion and keeps the level seats' weights.  A seat's
+ * share, in units of 2520 / k, stays below 2^23 per lane and 2^29 per wave; win and tie share one word as 16-bit halves
+ * (64 lanes x 1673 does not fit a half: they are summed apart). */
+template <> struct McqExactLoneSums<MCQ_ROW_SEATS> {
+    uint32_t tot, share[MCQ_MAX_SEATS], wt[MCQ_MAX_SEATS];
+    __device__ __forceinline__ void add(const McqExactBoard &, const McqExactKnown &kn, uint32_t w) {
+        const uint32_t inc = w ? mcq_seat_increment(mcq_popc(kn.level)) : 0u;
+        tot += w;
+#pragma unroll
+        for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) {
+            const bool on = ((kn.level >> s) & 1u) != 0u;
+            share[s] += on ? inc & 0xFFFFu : 0u;
+            wt[s] += on ? ((inc >> MCQ_SEAT_WIN_SHIFT) & 1u) | (((inc >> MCQ_SEAT_TIE_SHIFT) & 1u) << 16) : 0u;
+        }
+    }
+    __device__ __forceinline__ unsigned long long word(uint32_t lane) const {
+        const uint32_t t = wave_sum(tot);
+        unsigned long long mine = lane == 0u ? t : 0ull;
+#pragma unroll
+        for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) {
+            const uint32_t win = wave_sum(wt[s] & 0xFFFFu), tie = wave_sum(wt[s] >> 16), sh = wave_sum(share[s]);
+            mine = lane == 2u + 3u * s ? win : lane == 3u + 3u * s ? tie : lane == 4u + 3u * s ? sh : mine;
+        }
+        return mine;
+    }
+};
+
+// Kind 1: what a row form does with one completion.  Plain and split-pot: the candidates' outcomes against the known hands'
+// best; the split-pot form keeps tie_c as well and names n_eq (one random opponent leaves at most eight known hands:
+// word 13 + n_eq <= 21).
+template <int ROW> struct McqExactRow {
+    typedef std::conditional_t<ROW == MCQ_ROW_WAYS, McqExactAccWays, McqExactAcc> Acc;
+    static __device__ __forceinline__ void pass(const McqExactExtBlock &s, const McqTables *__restrict__ g_tab,
+                                                const McqExactBoard &bd, const McqExactKnown &kn, uint32_t lane, Acc &acc) {
+        mcq_exact_ext_pass_a_tally(s.xq, bd, kn.best, lane, 64u, s.pair_xy, s.rem_card, s.rem_pos, s.cb_tab, g_tab->tf, s.tab.tops,
+                             s.tab.sd, acc);
+    }
+    static __device__ __forceinline__ unsigned long long word(uint32_t lane, const McqExactExtQuery &, const McqExactBoard &bd,
+                                                              const McqExactKnown &kn, const Acc &acc, uint32_t tot) {
+        const uint32_t win = wave_sum(acc.win), tie = wave_sum(acc.tie), type = mcq_key_type(bd.hero_key);
+        if constexpr (Acc::kWays) return mcq_exact_ext_row_word(lane, win, tie, tot, wave_sum(acc.tie_c), type, kn.n_eq);
+        else return mcq_exact_ext_row_word(lane, win, tie, tot, 0u, type, 0u);
+    }
+};
+/* Per seat: the best key among hero and the known hands is wave-uniform, so a lane keeps the candidates' weight above it,
+ * level with it and in all (lanes 32..63: seats nobody holds, nothing) */
+template <> struct McqExactRow<MCQ_ROW_SEATS> {
+    typedef McqExactAccSeats Acc;
+    static __device__ __forceinline__ void pass(const McqExactExtBlock &s, const McqTables *__restrict__ g_tab,
+                                                const McqExactBoard &bd, const McqExactKnown &kn, uint32_t lane, Acc &acc) {
+        mcq_exact_ext_pass_seats(s.xq, bd, kn.top, lane, 64u, s.pair_xy, s.rem_card, s.rem_pos, s.cb_tab, g_tab->tf, s.tab.tops,
+                                 s.tab.sd, acc);
+    }
+    static __device__ __forceinline__ unsigned long long word(uint32_t lane, const McqExactExtQuery &e, const McqExactBoard &,
+                                                              const McqExactKnown &kn, const Acc &acc, uint32_t tot) {
+        return mcq_exact_ext_seats_word(lane, kn.level, e.n_known, wave_sum(acc.gt), wave_sum(acc.eq), tot);
+    }
+};
+
+// Kind 1: a wave per completion, lanes over the candidate hands -- on(pos, tot, word) gets the completion's R-positions,
+// its total weight and, in lane l, word l of its row.
+template <int ROW, class On>
+__device__ __forceinline__ void exact_wave_loop(const McqExactExtJob &job, const McqExactExtBlock &s,
+                                                const McqTables *__restrict__ g_tab, On on) {
+    typedef McqExactRow<ROW> Row;
+    const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * s.kWaves + wib), n_waves = job.grid * s.kWaves;
+    for (uint32_t board = wave; board < job.n_boards; board += n_waves) {
+        uint32_t pos[5];
+        McqExactBoard bd;
+        const McqExactKnown kn = exact_step<false>(s, board, g_tab, lane, pos, bd);
+        typename Row::Acc acc = {};
+        Row::pass(s, g_tab, bd, kn, lane, acc);
+        const uint32_t tot = wave_sum(acc.tot);
+        on(pos, tot, Row::word(lane, s.xq, bd, kn, acc, tot));
+    }
+}
+
+template <uint32_t KIND, int ROW>
+__global__ __launch_bounds__(1024) void mcq_exact_ext_kernel(const McqExactExtJob *__restrict__ jobs, const uint32_t *__restrict__ ext,
+                                                             int law, mcq_result *__restrict__ rows,
+                                                             unsigned long long *__restrict__ h1_sums,
+                                                             const McqTables *__restrict__ g_tab) {
+    const McqExactExtJob job = jobs[blockIdx.y];
+    if (blockIdx.x >= job.grid) return;
+    static_assert(ROW == MCQ_ROW_PLAIN || KIND <= 1u, "two random opponents have no split-pot and no per-seat form");
+    constexpr uint32_t kRem = KIND == 1u ? McqExactExtBlock::kWaves : 1u;
+    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ uint16_t pair_xy[MCQ_EXACT_PAIRS + 2];
+    __shared__ uint32_t xw[MCQ_EXT_WORDS];
+    __shared__ McqExactExtQuery xq;
+    __shared__ uint8_t r_id[64];
+    __shared__ uint8_t cb_tab[KIND != 0u ? MCQ_XX_MAX_RP : 1u];
+    __shared__ McqCard rem_card[kRem][64];
+    __shared__ uint32_t rem_pos[kRem][64];
+    __shared__ uint32_t keys[KIND == 2u ? MCQ_EXACT_PAIRS + 2 : 1u];
+    __shared__ uint32_t recs[KIND == 2u ? MCQ_EXACT_PAIRS + 2 : 1u];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = KIND == 1u ? tid >> 6 : 0u;
+    const McqExactExtBlock s = {tab, xq, pair_xy, r_id, cb_tab, rem_card[wib], rem_pos[wib]};
+    exact_ext_setup<KIND>(job, ext, g_tab, s, xw, [&](const McqQueryWords &q, const McqExtRec &er) -> const McqExactExtQuery & {
+        (void)mcq_exact_ext_query(q, er, law, xq);
+        return xq;
+    });
+    const McqExactExtQuery &e = xq;
+    unsigned long long *row = reinterpret_cast<unsigned long long *>(McqRowKind<ROW>::row(rows, job.row));
+
+    if constexpr (KIND == 0u) {
+        McqExactLoneSums<ROW> c = {};
+        exact_lane_loop(job, [&](uint32_t idx) {
+            uint32_t pos[5];
+            McqExactBoard bd;
+            McqExactKnown kn;
+            const uint32_t w = mcq_exact_ext_lone_known(e, idx, tab.sel8, g_tab->tf, tab.tops, tab.sd, pos, bd, kn);
+            c.add(bd, kn, w);
+        });
+        const unsigned long long mine = c.word(lane);
+        if (lane < McqRowKind<ROW>::kWords && mine != 0ull) atomicAdd(row + lane, mine);
+    } else if constexpr (KIND == 1u) {
+        unsigned long long sum = 0;
+        exact_wave_loop<ROW>(job, s, g_tab, [&](const uint32_t *, uint32_t, unsigned long long word) { sum += word; });
+        if (lane < McqRowKind<ROW>::kWords && sum != 0ull) atomicAdd(row + lane, sum);
+    } else {
+        const uint32_t groups = job.groups, group = blockIdx.x % groups, h = group * blockDim.x + tid;
+        const bool own = h < e.n_rp;
+        uint32_t qa = 0, qb = 1;
+        if (own) mcq_exact_pair_xy(h, qa, qb);
+        McqExactExtSums sums = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0, 0}};
+        for (uint32_t board = blockIdx.x / groups; board < job.n_boards; board += job.grid / groups) {
+            uint32_t pos[5];
+            McqExactBoard bd;
+            /* (its first barrier: the previous completion's pass B is done with keys and records) */
+            const uint32_t kb = exact_step<true>(s, board, g_tab, tid, pos, bd).best;
+            mcq_exact_ext_pass_a_store(e, bd, kb, tid, blockDim.x, pair_xy, s.rem_card, s.rem_pos, cb_tab, g_tab->tf, tab.tops,
+                                       tab.sd, keys, recs);
+            __syncthreads();
+            const uint32_t mi = own ? mcq_exact_ext_m_index(e, pos, qa, qb) : e.n_pairs;
+            if (mi < e.n_pairs) {
+                McqExactAcc acc = {0, 0, 0};
+                mcq_exact_ext_pass_b(e, bd, qa, qb, mi, keys, recs, acc);
+                mcq_exact_ext_add(sums, acc, mcq_key_type(bd.hero_key));
+            }
+        }
+        if (own) {
+            unsigned long long *dst = h1_sums + job.h1_off + (size_t)h * MCQ_XX_SUMS;
+            if (sums.win) atomicAdd(dst + 0, sums.win);
+            if (sums.tie) atomicAdd(dst + 1, sums.tie);
+            if (sums.tot) atomicAdd(dst + 2, sums.tot);
+#pragma unroll
+            for (uint32_t t = 0; t < 9; t++)
+                if (sums.type[t]) atomicAdd(dst + 3 + t, sums.type[t]);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- exact enumeration, hero range
+// Four kernels -- postflop or preflop, class bits or a weight per hand (McqHeroKind<W>, mcq_exact_hero.hpp) -- made of two
+// bodies, one per street, of exact_prologue above (every D-pair as qa | qb << 8 in its pair list) and of the helpers below,
+// which both bodies share.  One job per query (blockIdx.y), a BLOCK of 1024 threads per table completion, one block of 16
+// waves per CU.
+
+// the prologue's query builder: thread 0 fills the block's McqExactHeroQuery
+__device__ __forceinline__ auto hero_query(int law, McqExactHeroQuery &xq) {
+    return [law, &xq](const McqQueryWords &q, const McqExtRec &er) -> const McqExactExtQuery & {
+        (void)mcq_exact_hero_query(q, er, law, false, xq);
+        return xq.x;
+    };
 }
 
 // W = true: the block's two weight tables per D-pair, folded from the query row's tables in wts -- the opponent's [1326]
@@ -2410,7 +2414,7 @@ __device__ __forceinline__ void hero_body(const McqExactExtJob *__restrict__ job
     __shared__ uint32_t recs[MCQ_XH_MAX_PAIRS + 3u];
     static_assert(MCQ_XH_MAX_PAIRS <= MCQ_XH_MAX_HANDS, "pair_xy covers the candidate hands");
     const uint32_t tid = threadIdx.x;
-    hero_prologue<MCQ_XH_MAX_HANDS>(job, ext, law, g_tab, tab, pair_xy, xw, xq, r_id);
+    exact_prologue<MCQ_XH_MAX_HANDS>(job, ext, g_tab, tab, pair_xy, xw, r_id, hero_query(law, xq));
     const McqExactHeroQuery &e = xq;
     const uint16_t *hw_tab = nullptr;
     if constexpr (W) {
@@ -2504,7 +2508,7 @@ __device__ __forceinline__ void hero_pre_body(const McqExactExtJob *__restrict__
     __shared__ uint32_t keys[MCQ_XP_MAX_PAIRS + 2u];
     __shared__ uint32_t recs[MCQ_XP_MAX_PAIRS + 2u];
     const uint32_t tid = threadIdx.x;
-    hero_prologue<MCQ_XP_MAX_PAIRS>(job, ext, law, g_tab, tab, pair_xy, xw, xq, r_id);
+    exact_prologue<MCQ_XP_MAX_PAIRS>(job, ext, g_tab, tab, pair_xy, xw, r_id, hero_query(law, xq));
     const McqExactHeroQuery &e = xq;
     if (tid < e.x.b.L) d_card[tid] = mcq_card(r_id[tid]);
     const uint16_t *hw_tab = nullptr;
@@ -2587,81 +2591,44 @@ __global__ __launch_bounds__(1024) void mcq_exact_runout_kernel(const McqExactEx
                                                                 const McqTables *__restrict__ g_tab) {
     const McqExactExtJob job = jobs[blockIdx.y];
     if (blockIdx.x >= job.grid) return;
-    constexpr uint32_t kWaves = 16u, kRem = KIND == 1u ? kWaves : 1u;
+    constexpr uint32_t kRem = KIND == 1u ? McqExactExtBlock::kWaves : 1u;
     __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
     __shared__ uint16_t pair_xy[MCQ_EXACT_PAIRS + 2];
     __shared__ uint32_t xw[MCQ_EXT_WORDS];
     __shared__ McqExactExtQuery xq;
     __shared__ uint8_t r_id[64];
     __shared__ uint8_t cb_tab[KIND != 0u ? MCQ_XX_MAX_RP : 1u];
-    __shared__ McqCard rem_card_all[kRem][64];
-    __shared__ uint32_t rem_pos_all[kRem][64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6;
-    if (tid < MCQ_EXT_WORDS) xw[tid] = ext[(size_t)job.ext * MCQ_EXT_WORDS + tid];
-    if (tid < 64u) r_id[tid] = 0; /* (positions at or above L are never owners; their ids stay defined) */
-    for (uint32_t i = tid; i < MCQ_EXACT_PAIRS; i += blockDim.x) {
-        uint32_t x, y;
-        mcq_exact_pair_xy(i, x, y);
-        pair_xy[i] = (uint16_t)(x | (y << 8));
-    }
-    load_tables(tab, g_tab); /* ends with a barrier */
-    if (tid == 0) {
-        const McqExtRec er = {xw};
-        (void)mcq_exact_runout_query({job.rec[0], job.rec[1], job.rec[2], job.rec[3]}, er, law, xq); /* validated by the host */
-        mcq_exact_ext_r_ids(xq, r_id);
-    }
-    __syncthreads();
+    __shared__ McqCard rem_card[kRem][64];
+    __shared__ uint32_t rem_pos[kRem][64];
+    const uint32_t lane = threadIdx.x & 63u, wib = KIND == 1u ? threadIdx.x >> 6 : 0u;
+    const McqExactExtBlock s = {tab, xq, pair_xy, r_id, cb_tab, rem_card[wib], rem_pos[wib]};
+    exact_ext_setup<KIND>(job, ext, g_tab, s, xw, [&](const McqQueryWords &q, const McqExtRec &er) -> const McqExactExtQuery & {
+        (void)mcq_exact_runout_query(q, er, law, xq);
+        return xq;
+    });
     const McqExactExtQuery &e = xq;
-    if (KIND != 0u) {
-        mcq_exact_ext_cb_table(e, r_id, tid, blockDim.x, cb_tab);
-        __syncthreads();
-    }
-    const uint32_t n_boards = job.n_boards;
     /* the record's rows: slots below MCQ_XR_CARD_ROWS among the card rows, the others among the pair rows */
     unsigned long long *rec_cards = card_rows + (size_t)job.row * (MCQ_XR_CARD_ROWS * MCQ_XR_WORDS);
     unsigned long long *rec_pairs = pair_rows + (size_t)job.row * (MCQ_XR_PAIR_ROWS * MCQ_XR_WORDS);
 
     if constexpr (KIND == 0u) {
-        for (uint32_t idx = blockIdx.x * blockDim.x + tid; idx < n_boards; idx += job.grid * blockDim.x) {
+        exact_lane_loop(job, [&](uint32_t idx) {
             McqExactAcc a = {0, 0, 0};
             uint32_t type, n_eq;
             const uint32_t slot = mcq_exact_runout_lone(e, idx, r_id, tab.sel8, g_tab->tf, tab.tops, tab.sd, a, type, n_eq);
-            if (a.tot == 0u || slot >= MCQ_XR_ROWS) continue; /* no weight: the row stays zero */
+            if (a.tot == 0u || slot >= MCQ_XR_ROWS) return; /* no weight: the row stays zero */
             ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(mcq_exact_runout_row(rec_cards, rec_pairs, slot)); /* 176-byte rows: 16-byte aligned */
 #pragma unroll
             for (uint32_t w = 0; w < MCQ_XR_WORDS; w += 2u)
-                dst[w / 2u] = make_ulonglong2(mcq_exact_runout_word(w, a.win, a.tie, a.tot, 0u, type, n_eq),
-                                              mcq_exact_runout_word(w + 1u, a.win, a.tie, a.tot, 0u, type, n_eq));
-        }
+                dst[w / 2u] = make_ulonglong2(mcq_exact_ext_row_word(w, a.win, a.tie, a.tot, 0u, type, n_eq),
+                                              mcq_exact_ext_row_word(w + 1u, a.win, a.tie, a.tot, 0u, type, n_eq));
+        });
     } else {
-        McqCard *rem_card = rem_card_all[wib];
-        uint32_t *rem_pos = rem_pos_all[wib];
-        const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + wib), n_waves = job.grid * kWaves;
-        for (uint32_t board = wave; board < n_boards; board += n_waves) {
-            uint32_t pos[5];
-            mcq_exact_unrank(board, e.b.L, e.b.k, pos);
-            McqExactBoard bd;
-            mcq_exact_board(e.b, pos, tab.sel8, g_tab->tf, tab.tops, tab.sd, bd);
-            uint32_t n_eq;
-            const uint32_t kb = mcq_exact_ext_known_best_eq(e, bd, g_tab->tf, tab.tops, tab.sd, n_eq);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* the previous completion's reads are done (same wave) */
-            if (lane < e.m) {
-                const uint32_t rp = mcq_exact_rem_pos(pos, lane);
-                rem_pos[lane] = rp;
-                rem_card[lane] = mcq_card(r_id[rp]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            McqExactAccWays acc = {0, 0, 0, 0};
-            mcq_exact_ext_pass_a(e, bd, kb, lane, 64u, pair_xy, rem_card, rem_pos, cb_tab, g_tab->tf, tab.tops, tab.sd, nullptr,
-                                 nullptr, acc);
-            const uint32_t win = wave_sum(acc.win), tie = wave_sum(acc.tie), tot = wave_sum(acc.tot), tie_c = wave_sum(acc.tie_c);
+        exact_wave_loop<MCQ_ROW_WAYS>(job, s, g_tab, [&](const uint32_t *pos, uint32_t tot, unsigned long long word) {
             const uint32_t slot = mcq_exact_runout_slot(e, r_id, pos);
-            /* lane l stores word l of the row; one random opponent leaves at most eight known hands: 13 + n_eq <= 21 */
-            if (tot != 0u && slot < MCQ_XR_ROWS && lane < MCQ_XR_WORDS)
-                mcq_exact_runout_row(rec_cards, rec_pairs, slot)[lane] =
-                    mcq_exact_runout_word(lane, win, tie, tot, tie_c, mcq_key_type(bd.hero_key), n_eq);
-        }
+            /* lane l stores word l of the row */
+            if (tot != 0u && slot < MCQ_XR_ROWS && lane < MCQ_XR_WORDS) mcq_exact_runout_row(rec_cards, rec_pairs, slot)[lane] = word;
+        });
     }
 }
 

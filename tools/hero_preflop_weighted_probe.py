@@ -128,63 +128,37 @@ AB_SHAPES = [("flop, any vs any", ["2D", "9H", "JS"], None, None, 10),
 AB_PASSES = 4
 
 
-def ab(parent_so, copy_so):
-    """All four entries of this build beside the parent commit's build and beside a second copy of the parent's build (the
-    same file under a second name, so that it loads separately): what a refactor of these entries must leave alone.  Per
-    entry and shape the three libraries are called in turn, in one order and then in the reverse one, after a warm-up call
-    whose rows and aggregates are checked to be equal byte for byte.  Per order: this / parent and copy / parent, the
-    ratios of the median call times (the two long preflop shapes get ONE timed call per order and pass, so their "median"
-    is that call: a call of seconds, whose rounds differ by under 0.2 %, profiles/hero_preflop_weighted_probe.txt).  An
-    unweighted entry is timed under the reference's law, its default, and under the uniform one: the walks are separate
-    copies of the loop per law, or read the law per candidate.  The same code differs by up to a percent and more between two CONTEXTS, steadily
-    for as long as they live (the copy against the parent shows it), so the whole is done AB_PASSES times, each with fresh
-    contexts of all three libraries.  The copy / parent ratios of all passes and orders span the interval that the same
-    code gives against itself; an entry and shape passes when every this / parent ratio lies in that interval widened on
-    each side by its own width.  "faster" (the ones outside lie below it) is printed for information and fails like
-    "OUTSIDE": the rule is inside, and a loop that got faster on one shape has changed and may be slower on another."""
+def ab_cases(ab_shapes):
+    """The cases of tools/ab_common.py's loop for the four hero-range entries on ab_shapes (entries as AB_SHAPES): an
+    unweighted entry is timed under the reference's law, its default, and under the uniform one -- the walks are separate
+    copies of the loop per law, or read the law per candidate."""
     import neuron_poker_amd as npa
     from neuron_poker_amd import _lib
     from neuron_poker_amd.montecarlo_hip import _opponent_range_bits
-    _lib.load_library()
     ones = np.ones((1, _lib.HAND_ROWS), np.uint16)
     out = [(np.zeros((1, _lib.HAND_ROWS), _lib.RESULT_DTYPE), np.zeros(1, _lib.EXACT_PROB_DTYPE)) for _ in range(3)]
     cases = []
-    for name, table, hero, opp, rounds in AB_SHAPES:
+    for name, table, hero, opp, rounds in ab_shapes:
         hb, ob = _opponent_range_bits(1 if hero is None else hero), _opponent_range_bits(1 if opp is None else opp)
         q = _lib.pack_query_one([0, 0], [npa.card_id(c) for c in table], 2, 1)
         x = _lib.pack_query_ext(1, hero_range=_lib.ALL_CLASSES if hb is None else hb, opp_range=ob)
         street = "hero_range" + ("" if table else "_preflop")
-        cases += [(street, name + ", reference law", q, x, rounds, 0), (street, name, q, x, rounds, 1),
-                  (street + "_weighted", name, q, x, rounds, 1)]
-    ratios = {c[:2]: [] for c in cases}                                  # (this / parent, copy / parent, parent ms) per pass and order
-    for _p in range(AB_PASSES):
-        libs = [("this", Baseline(_lib.library_path())), ("parent", Baseline(parent_so)), ("copy", Baseline(copy_so))]
-        for entry, name, q, x, rounds, law in cases:
-            w = ones if entry.endswith("_weighted") else None
-            first = [b.call(entry, q, x, r, a, w, law) for (_, b), (r, a) in zip(libs, out)]  # warm-up, and the check
-            assert all(r.tobytes() == first[0][0].tobytes() and a.tobytes() == first[0][1].tobytes() for r, a in first), (entry, name)
-            for order in (libs, libs[::-1]):
-                t = {k: [] for k, _ in libs}
-                for _ in range(rounds):
-                    for k, b in order:
-                        t0 = time.perf_counter()
-                        b.call(entry, q, x, out[0][0], out[0][1], w, law)
-                        t[k].append((time.perf_counter() - t0) * 1e3)
-                med = {k: float(np.median(v)) for k, v in t.items()}
-                ratios[(entry, name)].append((med["this"] / med["parent"], med["copy"] / med["parent"], med["parent"]))
-        for _, b in libs:
-            b.close()
-        print("pass done", flush=True)
-    ok = True
-    for (entry, name), r in ratios.items():
-        lo, hi = min(v[1] for v in r), max(v[1] for v in r)
-        lo, hi = lo - (hi - lo), hi + (hi - lo)
-        verdict = "inside" if all(lo <= v[0] <= hi for v in r) else "faster" if all(v[0] <= hi for v in r) else "OUTSIDE"
-        ok = ok and verdict == "inside"
-        print("%-28s %-46s parent %9.3f ms  widened [%.4f, %.4f]  %s\n    this/parent %s\n    copy/parent %s" %
-              (entry, name, float(np.median([v[2] for v in r])), lo, hi, verdict, " ".join("%.4f" % v[0] for v in r),
-               " ".join("%.4f" % v[1] for v in r)), flush=True)
-    return ok
+        for entry, label, w, law in ((street, name + ", reference law", None, 0), (street, name, None, 1),
+                                     (street + "_weighted", name, ones, 1)):
+            cases.append(((entry, label), rounds,
+                          lambda b, slot, entry=entry, q=q, x=x, w=w, law=law: b.call(entry, q, x, out[slot][0], out[slot][1], w, law)))
+    return cases
+
+
+def ab(parent_so, copy_so):
+    """All four entries of this build beside the parent commit's build and a second copy of it, by the loop and the rule of
+    tools/ab_common.py (the two long preflop shapes get ONE timed call per order and pass, so their "median" is that call:
+    a call of seconds, whose rounds differ by under 0.2 %, profiles/hero_preflop_weighted_probe.txt).  "faster" fails like
+    "OUTSIDE": the rule is inside, and a loop that got faster on one shape has changed and may be slower on another."""
+    import ab_common
+    from neuron_poker_amd import _lib
+    _lib.load_library()
+    return ab_common.ab(Baseline, (_lib.library_path(), parent_so, copy_so), ab_cases(AB_SHAPES), AB_PASSES, faster_fails=True)
 
 
 def trace():
