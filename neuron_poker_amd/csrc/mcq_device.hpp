@@ -1167,6 +1167,212 @@ MCQ_HD void mcq_deal_table(const McqQueryCtx &qc, Draws &dr, const Deck &deck, c
     if (n_deal > 0u) b.add(pend);
 }
 
+// ------------------------------------------------------------------------------------------ dealing in epochs
+// The two-level argument of mcq_draw_table does not depend on where the split is, and it nests.  Cut the N draws of an
+// iteration at CHECKPOINTS (a checkpoint c stands before draw c); the draws between two checkpoints are an EPOCH.
+//   * Holes of the current epoch move, as in mcq_draw_opp: draw j of its epoch behaves as opponent draw j does on the
+//     epoch's own registers, and that gives its position p in the list as it was at the epoch's opening checkpoint.
+//   * Holes of a closed epoch keep the coordinates they had in the list at their CLOSING checkpoint and are never written
+//     again.  p is mapped through the closed epochs, most recent first, each with p += #{t <= p} -- a count
+//     (mcq_hole_count), or one comparison for a hole left alone in its register (it is still the draw as it arrived).
+//   * The last draw of all leaves no hole: it only counts, in its own epoch too.
+// The base position equals list.pop's for any set of checkpoints (tests/test_epoch_dealing_host.py).  Where the
+// checkpoints stand only changes the number of instructions, and that is counted here, in the costs of the code above:
+//   moving scan 5 per register; splat 1 per draw and level; insert at slot >= 2: 1; mcq_hole_pair 4; count 3 per register
+//   (plus the level's splat); a lone hole compared directly 2.
+// The costs depend on the NUMBER of draws alone (an opponent's card and a table card are dealt alike), so a plan is a
+// function of n = 2 * NOPP + NDEAL and of the rule:
+//   rule 1..4: the cheapest set of at most that many checkpoints (dynamic programme over the last checkpoint);
+//   MCQ_DEAL_FULLREG: a checkpoint wherever a register is full ("a full register is never written again").
+// 6-max before the flop (15 draws): one checkpoint behind the opponents, the dealing before there were plans, 156;
+// {8} 148, {8, 12} 145, {8, 12, 13} 143, every full register {4, 8, 12} 146.
+#define MCQ_DEAL_FULLREG 9
+#define MCQ_PLAN_MAX_DRAWS (2 * MCQ_MAX_OPP + 5)
+#define MCQ_PLAN_MAX_EPOCHS 6
+#define MCQ_PLAN_REGS 6 /* hole registers of a plan: what H[5] and hb of the dealing without plans are */
+struct McqDealPlan {
+    int n_draws, n_epochs;
+    int first[MCQ_PLAN_MAX_EPOCHS + 1]; /* draws before epoch e; first[n_epochs] = n_draws */
+    int reg0[MCQ_PLAN_MAX_EPOCHS + 1];  /* the epoch's first register; reg0[n_epochs] = registers in all */
+    constexpr int epoch_of(int d) const {
+        int e = 0;
+        while (e + 1 < n_epochs && d >= first[e + 1]) e++;
+        return e;
+    }
+    constexpr int size(int e) const { return first[e + 1] - first[e]; }
+};
+// registers of `holes` holes that a count reads (two and more holes: sentinels fill the rest) / a hole left alone
+constexpr int mcq_plan_count_regs(int holes) { return holes / 4 + (holes % 4 >= 2 ? 1 : 0); }
+constexpr bool mcq_plan_lone(int holes) { return holes % 4 == 1; }
+// instructions with which a later draw passes a closed epoch of n holes
+constexpr int mcq_plan_cost_closed(int n) {
+    return (mcq_plan_count_regs(n) > 0 ? 1 + 3 * mcq_plan_count_regs(n) : 0) + (mcq_plan_lone(n) ? 2 : 0);
+}
+// instructions of draw j of its epoch among the epoch's own holes
+constexpr int mcq_plan_cost_own(int j, bool last) {
+    if (last) return mcq_plan_cost_closed(j);
+    int c = j % 4 == 1 ? 4 : 0;
+    if (j >= 2) c += 1 + 5 * (j % 4 < 2 ? j / 4 : j / 4 + 1) + (j % 4 >= 2 ? 1 : 0);
+    return c;
+}
+// an epoch of draws [a, b) of n: its own steps, and what the n - b later draws pay to pass it
+constexpr int mcq_plan_cost_epoch(int a, int b, int n) {
+    int c = 0;
+    for (int d = a; d < b; d++) c += mcq_plan_cost_own(d - a, d == n - 1);
+    return c + (n - b) * mcq_plan_cost_closed(b - a);
+}
+constexpr McqDealPlan mcq_deal_plan(int n, int rule) {
+    McqDealPlan pl = {};
+    pl.n_draws = n;
+    int cps[MCQ_PLAN_MAX_DRAWS + 1] = {}, n_cp = 0;
+    if (rule == MCQ_DEAL_FULLREG) {
+        for (int c = 4; c < n; c += 4) cps[n_cp++] = c;
+    } else {
+        /* f[m][b]: cheapest way to deal draws [0, b) in m epochs that are all closed at b (b == n: the last one open) */
+        constexpr int kInf = 1 << 28;
+        int f[MCQ_PLAN_MAX_EPOCHS + 1][MCQ_PLAN_MAX_DRAWS + 1] = {}, from[MCQ_PLAN_MAX_EPOCHS + 1][MCQ_PLAN_MAX_DRAWS + 1] = {};
+        for (int m = 0; m <= rule + 1; m++)
+            for (int b = 0; b <= n; b++) f[m][b] = m == 0 && b == 0 ? 0 : kInf;
+        for (int m = 1; m <= rule + 1; m++)
+            for (int b = 1; b <= n; b++)
+                for (int a = 0; a < b; a++) {
+                    if (f[m - 1][a] >= kInf) continue;
+                    const int c = f[m - 1][a] + mcq_plan_cost_epoch(a, b, n);
+                    if (c < f[m][b]) { f[m][b] = c; from[m][b] = a; }
+                }
+        int best = 1;
+        for (int m = 2; m <= rule + 1; m++)
+            if (f[m][n] < f[best][n]) best = m; /* fewer checkpoints where more do not pay */
+        int b = n;
+        for (int m = best; m >= 1; m--) {
+            b = from[m][b];
+            if (m > 1) cps[m - 2] = b;
+        }
+        n_cp = best - 1;
+    }
+    pl.n_epochs = n_cp + 1;
+    for (int e = 1; e <= n_cp; e++) pl.first[e] = cps[e - 1];
+    pl.first[pl.n_epochs] = n;
+    for (int e = 0; e < pl.n_epochs; e++) {
+        const int holes = pl.size(e) - (e == pl.n_epochs - 1 ? 1 : 0); /* the last draw leaves none */
+        pl.reg0[e + 1] = pl.reg0[e] + (holes + 3) / 4;
+    }
+    return pl;
+}
+constexpr int mcq_plan_cost(const McqDealPlan &pl) {
+    int c = 0;
+    for (int e = 0; e < pl.n_epochs; e++) c += mcq_plan_cost_epoch(pl.first[e], pl.first[e + 1], pl.n_draws);
+    return c;
+}
+constexpr bool mcq_plan_valid(const McqDealPlan &pl) {
+    if (pl.n_epochs < 1 || pl.n_epochs > MCQ_PLAN_MAX_EPOCHS || pl.first[0] != 0 || pl.first[pl.n_epochs] != pl.n_draws) return false;
+    for (int e = 0; e < pl.n_epochs; e++) {
+        if (pl.size(e) < 1) return false;
+        /* an epoch holds at most what its registers hold (the last draw of all needs no slot) */
+        if (pl.size(e) - (e == pl.n_epochs - 1 ? 1 : 0) > 4 * (pl.reg0[e + 1] - pl.reg0[e])) return false;
+    }
+    return pl.reg0[pl.n_epochs] <= MCQ_PLAN_REGS; /* no more hole registers live than without plans */
+}
+// the plan of (N, RULE), worked out once per pair
+template <int N, int RULE>
+struct McqPlanOf {
+    static constexpr McqDealPlan pl = mcq_deal_plan(N, RULE);
+    static_assert(mcq_plan_valid(pl), "dealing plan");
+};
+static_assert(mcq_plan_cost(mcq_deal_plan(15, 1)) == 148 && mcq_deal_plan(15, 1).first[1] == 8, "6-max before the flop, {8}");
+static_assert(mcq_plan_cost(mcq_deal_plan(15, 2)) == 145 && mcq_deal_plan(15, 2).first[2] == 12, "6-max before the flop, {8, 12}");
+static_assert(mcq_plan_cost(mcq_deal_plan(15, 3)) == 143 && mcq_deal_plan(15, 3).first[3] == 13, "6-max before the flop, {8, 12, 13}");
+static_assert(mcq_plan_cost(mcq_deal_plan(15, MCQ_DEAL_FULLREG)) == 146, "6-max before the flop, {4, 8, 12}");
+static_assert(mcq_plan_cost(mcq_deal_plan(23, 3)) == 308 && mcq_plan_cost(mcq_deal_plan(12, 3)) == 98, "ten players; 5 opponents, 2 to come");
+
+// Draw number D of the N an iteration deals by the plan (N, RULE).  E: the plan's hole registers, epoch by epoch.
+// Returned: base position + 128, as mcq_draw_opp / mcq_draw_table return it.
+template <int N, int RULE, int EE> /* through the closed epochs EE, EE - 1, .., 0 */
+MCQ_HD void mcq_epoch_pass(const uint32_t (&E)[MCQ_PLAN_REGS], uint32_t &k) {
+    if constexpr (EE >= 0) {
+        constexpr int n = McqPlanOf<N, RULE>::pl.size(EE), r0 = McqPlanOf<N, RULE>::pl.reg0[EE];
+        const uint32_t p = k; /* position in the list at the epoch's closing checkpoint, still | 0x80 */
+        if constexpr (mcq_plan_lone(n)) k += E[r0 + n / 4] <= p ? 1u : 0u;
+        if constexpr (mcq_plan_count_regs(n) > 0) {
+            const uint32_t pb = mcq_splat_byte(p);
+#pragma unroll
+            for (int i = 0; i < mcq_plan_count_regs(n); i++) mcq_hole_count(pb, E[r0 + i], k);
+        }
+        mcq_epoch_pass<N, RULE, EE - 1>(E, k);
+    }
+}
+#if defined(__GNUC__) && !defined(__clang__)
+/* (a host build with GCC folds the first draw of a plan into mcq_draw_opp<0>, whose code is the same, and then warns that
+ * the array of the one is not the size of the other's) */
+#define MCQ_NO_FOLD __attribute__((no_icf))
+#else
+#define MCQ_NO_FOLD
+#endif
+template <int N, int RULE, int D>
+MCQ_NO_FOLD MCQ_HD uint32_t mcq_draw_epoch(uint32_t rp, uint32_t (&E)[MCQ_PLAN_REGS]) {
+    if constexpr (D >= N) {
+        return rp; /* (the unrolled callers name draws their form never makes) */
+    } else {
+        constexpr int e = McqPlanOf<N, RULE>::pl.epoch_of(D), J = D - McqPlanOf<N, RULE>::pl.first[e],
+                      R0 = McqPlanOf<N, RULE>::pl.reg0[e];
+        uint32_t k = rp;
+        if constexpr (D == N - 1) { /* count only */
+            if constexpr (mcq_plan_lone(J)) k += E[R0 + J / 4] <= rp ? 1u : 0u;
+            if constexpr (mcq_plan_count_regs(J) > 0) {
+                const uint32_t rb = mcq_splat_byte(rp);
+#pragma unroll
+                for (int i = 0; i < mcq_plan_count_regs(J); i++) mcq_hole_count(rb, E[R0 + i], k);
+            }
+        } else { /* mcq_draw_opp<J> on the epoch's registers */
+            if constexpr (J % 4 == 1) mcq_hole_pair(rp, E[R0 + J / 4], k);
+            if constexpr (J % 4 == 0) E[R0 + J / 4] = rp;
+            if constexpr (J >= 2) {
+                const uint32_t rb = mcq_splat_byte(rp);
+#pragma unroll
+                for (int i = 0; i < (J % 4 < 2 ? J / 4 : J / 4 + 1); i++) mcq_hole_reg(rb, E[R0 + i], k);
+                if constexpr (J % 4 >= 2) mcq_hole_put<J>(E[R0 + J / 4], rp);
+            }
+        }
+        mcq_epoch_pass<N, RULE, e - 1>(E, k);
+        return mcq_opaque(k);
+    }
+}
+
+// The rule by which the straight forms of mcq_iteration_sum deal (0: without plans, mcq_draw_opp / mcq_draw_table).
+#ifndef MCQ_DEAL_RULE
+#define MCQ_DEAL_RULE 3 /* measured on the 6-max preflop shape against rules 1, 2 and MCQ_DEAL_FULLREG: DESIGN.md, section 7, r17 */
+#endif
+// the draws of a straight form's plan: where the table cards to come are counted at run time, the plan is that of five,
+// and an iteration with fewer stops early in it
+constexpr int mcq_plan_draws(int nopp, int ndeal) { return 2 * nopp + (ndeal >= 0 ? ndeal : 5); }
+
+#ifndef MCQ_L0_CONST
+#define MCQ_L0_CONST 1
+#endif
+// opponent draw number D: by the plan's rule, or (RULE 0) as before there were plans
+template <int N, int RULE, int D>
+MCQ_HD uint32_t mcq_draw_opp_by(uint32_t rp, uint32_t (&H)[5], uint32_t (&E)[MCQ_PLAN_REGS]) {
+    if constexpr (RULE != 0) return mcq_draw_epoch<N, RULE, D>(rp, E);
+    else return mcq_draw_opp<D>(rp, H);
+}
+// mcq_deal_table by a plan: the table's draws are the plan's draws D0, D0 + 1, ..
+template <int N, int RULE, int D0, class Draws, int NDEAL = -1, class Deck = McqDeckAoS>
+MCQ_HD void mcq_deal_table_plan(const McqQueryCtx &qc, Draws &dr, const Deck &deck, uint32_t (&E)[MCQ_PLAN_REGS], uint32_t L,
+                                McqSumBoard &b) {
+    const uint32_t n_deal = NDEAL >= 0 ? (uint32_t)NDEAL : mcq_opaque_uniform(qc.n_deal);
+    McqCard pend = {0u, 0u, 0u, 0u}; /* a card joins the table one draw late, see mcq_deal_table */
+#define MCQ_TABLE(K)                                                                                                  \
+    if (K < n_deal) {                                                                                                 \
+        const uint32_t at = mcq_draw_epoch<N, RULE, D0 + K>(dr.template table<K>(L - Draws::kTableShort), E); /* l.188 */ \
+        if (K > 0) b.add(pend);                                                                                       \
+        pend = deck.card(at);                                                                                         \
+        L -= 1;                                                                                                       \
+    }
+    MCQ_TABLE(0) MCQ_TABLE(1) MCQ_TABLE(2) MCQ_TABLE(3) MCQ_TABLE(4)
+#undef MCQ_TABLE
+    if (n_deal > 0u) b.add(pend);
+}
+
 // The late join of an opponent pair (mcq_iteration_sum): where the second card's suit masks may be used from.  Device: an
 // empty volatile asm on the two registers; a host build has no scheduler to hold.
 MCQ_HD void mcq_join_hold(McqCard &c) {
@@ -1186,12 +1392,21 @@ MCQ_HD void mcq_join_hold(McqCard &c) {
 // The hands are in the sum form (McqSumBoard / McqSumHole, ids instead of keys); mcq_iteration / mcq_iterations keep the
 // mask form's table arguments for the host builds of this file and find the sum-form tables behind them
 // (mcq_sum_tabs_of), the kernels call the _sum forms with their LDS image.
-template <class Draws, int NOPP = -1, int NDEAL = -1, class Acc = McqLaneAcc, class Deck = McqDeckAoS>
+// RULE: the straight forms (NOPP >= 1) deal by the plan of that rule (mcq_deal_plan), 0 and the general form as before
+// there were plans (mcq_draw_opp, mcq_deal_table): same draws, same positions, fewer instructions.
+template <class Draws, int NOPP = -1, int NDEAL = -1, class Acc = McqLaneAcc, class Deck = McqDeckAoS,
+          int RULE = (NOPP >= 1 ? MCQ_DEAL_RULE : 0)>
 // deck = the base deck table behind its accessor (McqDeckAoS / McqDeckSplit), its pointer biased by -128 entries: draw
 // indices carry a bias of 128 (r | 0x80).
 MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck, const McqSumTabs &tabs, Acc &acc) {
+    static_assert(RULE == 0 || NOPP >= 1, "a plan needs the number of opponents at compile time");
+    constexpr int kN = mcq_plan_draws(NOPP, NDEAL);
     uint32_t H[5] = {MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL};
-    uint32_t L = qc.L0;
+    uint32_t E[MCQ_PLAN_REGS] = {MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL,
+                                 MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL};
+    /* the deck's length is 50 - (5 - n_deal): a constant where the table cards to come are, and the pair decode's
+     * `dd + 128` a literal of its select instead of a move from a scalar register */
+    uint32_t L = MCQ_L0_CONST && NDEAL >= 0 ? (uint32_t)(45 + NDEAL) : qc.L0;
     McqSumHole opp[MCQ_MAX_OPP];
     const uint32_t n_opp_d = NOPP >= 0 ? (uint32_t)NOPP : mcq_opaque_uniform(qc.n_opp);
     /* Straight forms: a pair joins its hand one pair late, as a table card joins the table one draw late (mcq_deal_table).
@@ -1210,8 +1425,8 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
     if (P < n_opp_d) {                                                                                         \
         uint32_t r1, r2;                                                                                       \
         dr.template pair<P>(L, r1, r2); /* r1 in [0,L-1], r2 in [0,L-2], r1 != r2 (l.167-176), both | 0x80 */  \
-        const McqCard c1 = deck.hole_card(mcq_draw_opp<2 * P>(r1, H));     /* deck.pop(r1) (l.178) */          \
-        const McqCard c2 = deck.hole_card(mcq_draw_opp<2 * P + 1>(r2, H)); /* deck.pop(r2), shrunk list (l.179) */ \
+        const McqCard c1 = deck.hole_card(mcq_draw_opp_by<kN, RULE, 2 * P>(r1, H, E));     /* deck.pop(r1) (l.178) */ \
+        const McqCard c2 = deck.hole_card(mcq_draw_opp_by<kN, RULE, 2 * P + 1>(r2, H, E)); /* deck.pop(r2), shrunk list (l.179) */ \
         if constexpr (kLate) {                                                                                 \
             if (P > 0) {                                                                                       \
                 mcq_join_hold(j2);                                                                             \
@@ -1228,7 +1443,9 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
 #undef MCQ_OPP
     McqSumBoard b = qc.board_s;
     if (NDEAL == 5) b.clear(); /* all five to come: the known table is empty, nothing to add the cards to */
-    if (NOPP >= 0) {
+    if constexpr (RULE != 0) {
+        mcq_deal_table_plan<kN, RULE, 2 * NOPP, Draws, NDEAL>(qc, dr, deck, E, L, b);
+    } else if (NOPP >= 0) {
         mcq_deal_table<(NOPP >= 0 ? (2 * NOPP + 3) / 4 : 0), Draws, NDEAL>(qc, dr, deck, H, L, b);
     } else switch (mcq_opaque_uniform((2u * qc.n_opp + 3u) / 4u)) { /* registers holding the opponents' holes: wave-uniform */
         case 0: mcq_deal_table<0, Draws>(qc, dr, deck, H, L, b); break;

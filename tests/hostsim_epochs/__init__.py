@@ -1,0 +1,91 @@
+"""Test-only host build of the dealing in epochs and of the iterations that deal by it (see hs_epochs.cpp)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
+_SO = os.path.join(_HERE, "libhs_epochs.so")
+_SRCS = [os.path.join(_HERE, "hs_epochs.cpp"), os.path.join(_CSRC, "mcq_device.hpp"), os.path.join(_CSRC, "mcq_replay.hpp"),
+         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
+_lib = None
+
+FULLREG = 9                   # MCQ_DEAL_FULLREG
+RULES = (1, 2, 3, FULLREG)    # the plans built: at most one, two, three checkpoints; every full register
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
+            tmp = _SO + ".%d.tmp" % os.getpid()
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
+                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
+            os.replace(tmp, _SO)
+        L = C.CDLL(_SO)
+        L.hs_epochs_rule.restype = C.c_int
+        L.hs_epochs_plan.restype = C.c_int
+        L.hs_epochs_plan.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.hs_epochs_positions.restype = C.c_int
+        L.hs_epochs_positions.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.hs_epochs_run.restype = C.c_int
+        L.hs_epochs_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.hs_epochs_replay.restype = C.c_int
+        L.hs_epochs_replay.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        _lib = L
+    return _lib
+
+
+def shipped_rule():
+    return lib().hs_epochs_rule()
+
+
+def plan(n_plan, rule):
+    """-> dict(checkpoints, reg0 (first register of every epoch, then the total), cost, valid) of the plan of n_plan draws"""
+    out = np.zeros(17, np.int32)
+    rc = lib().hs_epochs_plan(n_plan, rule, out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise ValueError("hs_epochs_plan: %d (%d draws, rule %d)" % (rc, n_plan, rule))
+    ne = int(out[0])
+    return {"checkpoints": [int(v) for v in out[2:1 + ne]], "reg0": [int(v) for v in out[8:9 + ne]], "cost": int(out[15]),
+            "valid": bool(out[16])}
+
+
+def positions(n_plan, rule, draws):
+    """draws uint8 [rows, n], n <= n_plan: the first n draws of the plan -> base positions uint8 [rows, n]"""
+    d = np.ascontiguousarray(draws, np.uint8)
+    pos = np.full(d.shape, 255, np.uint8)
+    rc = lib().hs_epochs_positions(n_plan, rule, d.shape[1], d.ctypes.data_as(C.c_void_p), d.shape[0],
+                                   pos.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise ValueError("hs_epochs_positions: %d (%d draws of %d, rule %d)" % (rc, d.shape[1], n_plan, rule))
+    return pos
+
+
+def rows(queries, seed, first_qid, nopp, ndeal, uniform=False, ways=False, planned=True):
+    """Query i (16-byte records) with id first_qid + i through mcq_iteration_sum<.., nopp, ndeal, ..>: -> uint64 [n, 13 or 22]."""
+    L = lib()
+    q = np.ascontiguousarray(queries).view(np.uint8).reshape(-1, 16)
+    out = np.zeros((len(q), 22 if ways else 13), np.uint64)
+    for i in range(len(q)):
+        rec = q[i].copy()
+        rc = L.hs_epochs_run(rec.ctypes.data_as(C.c_void_p), seed, first_qid + i, nopp, ndeal, int(uniform), int(ways),
+                             int(planned), out[i].ctypes.data_as(C.c_void_p))
+        if rc:
+            raise ValueError("hs_epochs_run: %d (nopp %d, ndeal %d, query %s)" % (rc, nopp, ndeal, rec.tolist()))
+    return out
+
+
+def replay_rows(queries, seed32):
+    """Parity mode: query i from the start of the MT19937 stream of seed32 -> uint64 [n, 13]."""
+    L = lib()
+    q = np.ascontiguousarray(queries).view(np.uint8).reshape(-1, 16)
+    out = np.zeros((len(q), 13), np.uint64)
+    for i in range(len(q)):
+        rec = q[i].copy()
+        rc = L.hs_epochs_replay(rec.ctypes.data_as(C.c_void_p), seed32, out[i].ctypes.data_as(C.c_void_p))
+        if rc:
+            raise ValueError("hs_epochs_replay: %d (query %s)" % (rc, rec.tolist()))
+    return out
