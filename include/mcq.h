@@ -383,7 +383,7 @@ MCQ_API int mcq_exact_batch_hero_range(mcq_ctx *ctx, const mcq_query *q, const m
  * opp_weights == NULL, no allowed hero hand (eff_hero is 0 everywhere in D); and -- before anything is copied to the
  * caller -- an allowed hero hand whose row has no weight (eff_opp is 0 for every hand that shares no card with it).
  * MCQ_EBUSY as everywhere.
- * Not covered: the reference's law, weighted ranges in the Monte-Carlo entries, more than one opponent.  Before the flop:
+ * Not covered: the reference's law, more than one opponent (by Monte Carlo: mcq_eval_batch_ranges).  Before the flop:
  * mcq_exact_batch_hero_range_preflop_weighted below. */
 #define MCQ_COMBO_WEIGHT_MAX 65535u
 MCQ_API int mcq_exact_batch_hero_range_weighted(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n,
@@ -438,12 +438,54 @@ MCQ_API int mcq_exact_batch_hero_range_preflop(mcq_ctx *ctx, const mcq_query *q,
  * effective weight in D, and an allowed hero hand against which no opponent hand of positive effective weight is left.
  * The last is decided on the host before the enumeration: before the flop it is exact, because a hand g with eff_opp(g) > 0
  * that shares no card with h leaves |D| - 4 >= 5 cards for a completion that avoids both.  MCQ_EBUSY as everywhere.
- * Not covered: the reference's law, weighted ranges in the Monte-Carlo entries, more than one opponent. */
+ * Not covered: the reference's law, more than one opponent (by Monte Carlo: mcq_eval_batch_ranges). */
 MCQ_API int mcq_exact_batch_hero_range_preflop_weighted(mcq_ctx *ctx, const mcq_query *q, const mcq_query_ext *ext, size_t n,
                                                         const uint16_t *opp_weights /* [n][MCQ_HAND_ROWS] */,
                                                         const uint16_t *hero_weights /* [n][MCQ_HAND_ROWS], may be NULL: every allowed hand weighs 1 */,
                                                         mcq_result *rows /* [n][MCQ_HAND_ROWS] */,
                                                         mcq_exact_prob *agg /* [n], may be NULL */);
+
+/* Monte-Carlo MULTIWAY equity with a WEIGHTED RANGE PER SEAT: seat 0 opens this range, seat 1 three-bets that one, seat 2
+ * cold-calls a third -- what is each range worth on this board?  2..10 seats, a weight per two-card hand and seat.
+ * A record is q[i] (hole is ignored; n_board 0, 3, 4 or 5; n_players = p, 2..10; runs >= 1) and, for every seat s < p, the
+ * weight table w_s = tables[seat_table[i * 10 + s]]: MCQ_HAND_ROWS uint16 entries 0..MCQ_COMBO_WEIGHT_MAX indexed by
+ * MCQ_HAND_INDEX.  Entries of seat_table at s >= n_players are ignored.  Tables are shared by index: "every opponent holds
+ * the same range" over 4096 boards is one table, not 24 576.  A known hand is a table with one non-zero entry (such a seat
+ * holds its hand in every trial and takes no random word: the mapping below would select that hand for every word).
+ * The law.  B = the table cards, eff_s(h) = w_s[h] if h holds no card of B, else 0.  One iteration deals the p hands with
+ *     P(h_0, .., h_{p-1})  ~  prod_s eff_s(h_s) * [the hands are pairwise disjoint]
+ * and then the 5 - n_board missing table cards uniformly without replacement from the 52 - n_board - 2p cards left.  This
+ * is the JOINT law: symmetric in the seats, so permuting the seats permutes the rows in distribution.  It is NOT the
+ * sequential "hero first, then each opponent from what is left" law that agg of the hero-range entries describes (there the
+ * hero's hands are weighted by eff_hero alone; here every seat's hands are also weighted by how much room they leave the
+ * others).  The context's dealing-law switch does not matter: this entry is uniform by definition, and the reference's
+ * "never the highest card" does not apply to its table cards.
+ * It is realised by rejection, which is exact: (1) seat s draws a hand with probability w_s[h] / sum(w_s), one random word u
+ * per draw: t = mulhi32(u, total_s), the hand is the first index in ascending MCQ_HAND_INDEX order whose inclusive cumulative
+ * weight exceeds t (total_s < 2^27; a hand's probability is off by less than 2^-32); (2) that seat alone draws again while
+ * its hand holds a table card; (3) when two seats' hands share a card the WHOLE trial is abandoned, at the first collision,
+ * and every seat draws again.  Streams: those of mcq_eval_batch_ext (keyed by (seed, first_query_id + i, task * 64 + lane),
+ * sixteen iterations each), so a row depends on (record, tables, seed, query id) only -- not on the batch around it, on how
+ * the tables are numbered or shared, or on the launch shape -- and a batch split into calls with the matching first_query_id
+ * gives the same rows.
+ * Row: runs; passes = whole trials (passes >= runs, and == runs when the supports cannot collide); seat[s].win / tie / share
+ * exactly as mcq_eval_batch_ext_seats defines them: "best" by ranking key, share += MCQ_SHARE_UNIT / k, sum_s share ==
+ * MCQ_SHARE_UNIT * runs exactly, seats >= n_players zero.
+ * Refused with MCQ_EINVAL, nothing launched, out untouched: a null context or buffer (n == 0 returns MCQ_OK), n_tables == 0,
+ * an invalid record (a duplicate or out-of-range table card, non-zero reserved, n_board of 1 or 2, n_players outside 2..10,
+ * runs == 0), a seat_table entry >= n_tables, a seat whose table has no hand of positive weight clear of the table cards.
+ * A record whose seats block each other (two seats both holding only AsAh) is seen on the device: an iteration without an
+ * accepted trial within 65536 marks the row and the call returns MCQ_EINVAL with out untouched, as mcq_eval_batch_ext does
+ * for a range that cannot be dealt; the per-seat re-draw is bounded the same way.  MCQ_EBUSY as everywhere.
+ * Cost: whole-trial rejection is inherent to the law.  With every hand allowed to every seat, trials per iteration are about
+ * 1.1 at two seats, 1.3 at three, 3.6 at six and 55 at ten before the flop, and 75 at ten on a flop (a table hit is re-drawn
+ * by its seat alone and abandons nothing, but three cards fewer are left to be disjoint on).  Ten wide ranges are expensive,
+ * and narrow ranges crowded on the same cards can be worse (nine opponents on the top quarter of the classes: refused).  Device memory: 8 KB per distinct table.
+ * Not covered: dead or ghost cards, a per-hero-hand breakdown multiway, the one-launch path for small queries, a
+ * device-resident or torch entry, the parity mode (the reference has nothing to match), mcq_multi_*. */
+MCQ_API int mcq_eval_batch_ranges(mcq_ctx *ctx, const mcq_query *q, const uint32_t *seat_table /* [n][10] */,
+                                  const uint16_t *tables /* [n_tables][MCQ_HAND_ROWS] */, size_t n_tables, size_t n,
+                                  uint64_t seed, uint64_t first_query_id, mcq_result_seats *out);
 
 /* Exact equity PER RUNOUT, on the flop and the turn: which cards help and how much, from ONE enumeration per record.
  * Accepted: whatever mcq_exact_batch_ext_ways accepts -- hero given as two cards, 0..9 known hands each given as two cards,
@@ -479,7 +521,8 @@ MCQ_API int mcq_exact_batch_ext_runouts(mcq_ctx *ctx, const mcq_query *q, const 
                                         mcq_result_ways *pairs /* [n][MCQ_HAND_ROWS], may be NULL */);
 
 /* Select the dealing law used by MCQ_MODE_PHILOX on this context (MCQ_LAW_*).  Extended queries
- * (mcq_eval_batch_ext) are dealt by the reference's law only: under MCQ_LAW_UNIFORM that call gives MCQ_EINVAL. */
+ * (mcq_eval_batch_ext) are dealt by the reference's law only: under MCQ_LAW_UNIFORM that call gives MCQ_EINVAL.
+ * mcq_eval_batch_ranges does not look at the switch: its law is uniform by definition. */
 MCQ_API int mcq_set_dealing_law(mcq_ctx *ctx, int law);
 
 /* Kernel timing (off by default: a timestamped launch costs a small query about 6 us of its call time).  When on,

@@ -127,6 +127,8 @@ def load_library():
         L.mcq_exact_batch_seats.restype = C.c_int
         L.mcq_exact_batch_ext_seats.argtypes = [vp, vp, vp, sz, C.c_int, vp]
         L.mcq_exact_batch_ext_seats.restype = C.c_int
+        L.mcq_eval_batch_ranges.argtypes = [vp, vp, vp, vp, sz, sz, u64, u64, vp]
+        L.mcq_eval_batch_ranges.restype = C.c_int
         L.mcq_eval_batch_device_small.argtypes = [vp, vp, sz, u64, u64, vp, vp]
         L.mcq_eval_batch_device_small.restype = C.c_int
         L.mcq_showdown.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp]
@@ -576,6 +578,27 @@ class Engine:
         out = np.zeros(len(q), RESULT_SEATS_DTYPE)
         rc = self._lib.mcq_eval_batch_ext_seats(self._ctx, q.ctypes.data, e.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
                                                 int(first_query_id) & (2 ** 64 - 1), MODE_PHILOX, out.ctypes.data)
+        if rc:
+            _raise(rc)
+        return out
+
+    def eval_batch_ranges(self, queries, seat_table, tables, seed, first_query_id=0):
+        """Monte-Carlo multiway equity with a weighted range per SEAT (mcq_eval_batch_ranges): record i seats n_players
+        ranges, seat s holding tables[seat_table[i, s]] -- uint16 weights [n_tables, HAND_ROWS] indexed by hand_index(a, b),
+        shared by index; seat_table is uint32 [n, 10], its entries at or above n_players are ignored.  The hands are dealt
+        jointly, proportional to the product of the seats' weights over the disjoint deals clear of the table cards; `hole`
+        of the records is not read.  -> array of RESULT_SEATS_DTYPE (passes counts whole trials); seat_shares(rows) gives
+        the pot shares.  A wrong shape or dtype raises ValueError before the engine is touched."""
+        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        if not isinstance(tables, np.ndarray) or tables.dtype != np.uint16 or tables.ndim != 2 or tables.shape[1] != HAND_ROWS \
+                or tables.shape[0] == 0:
+            raise ValueError("tables is a uint16 array of shape [n_tables >= 1, HAND_ROWS = %d]" % HAND_ROWS)
+        if not isinstance(seat_table, np.ndarray) or seat_table.dtype != np.uint32 or seat_table.shape != (len(q), 10):
+            raise ValueError("seat_table is a uint32 array of shape [n, 10] = (%d, 10)" % len(q))
+        tb, st = np.ascontiguousarray(tables), np.ascontiguousarray(seat_table)
+        out = np.zeros(len(q), RESULT_SEATS_DTYPE)
+        rc = self._lib.mcq_eval_batch_ranges(self._ctx, q.ctypes.data, st.ctypes.data, tb.ctypes.data, len(tb), len(q),
+                                             int(seed) & (2 ** 64 - 1), int(first_query_id) & (2 ** 64 - 1), out.ctypes.data)
         if rc:
             _raise(rc)
         return out

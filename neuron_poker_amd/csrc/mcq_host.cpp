@@ -24,6 +24,7 @@
 #include "mcq_exact_runout.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt_blocks.hpp"
+#include "mcq_ranges.hpp"
 #include "mcq_replay.hpp"
 
 hipError_t mcq_eval_occupancy(int mode, int block, int *blocks_per_cu); /* mcq_kernels.hip */
@@ -1169,6 +1170,130 @@ int mcq_eval_batch_ext_seats(mcq_ctx *c, const mcq_query *q, const mcq_query_ext
     ABI_GUARD_BEGIN
     return eval_batch_ext_impl(c, q, ext, n, seed, first_query_id, mode, out, kSeatsWords);
     ABI_GUARD_END("mcq_eval_batch_ext_seats")
+}
+
+/* A weighted range per seat (mcq_ranges.hpp).  Everything that can be refused is refused here, before a launch; what is
+ * left for the device is the record whose seats block each other. */
+int mcq_eval_batch_ranges(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_table, const uint16_t *tables, size_t n_tables,
+                          size_t n, uint64_t seed, uint64_t first_query_id, mcq_result_seats *out) {
+    ABI_GUARD_BEGIN
+    if (n == 0) return MCQ_OK;
+    if (!c) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: null context");
+    if (!q || !seat_table || !tables || !out) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: null buffer");
+    if (n > 0x7fffffffu) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: n too large");
+    if (n_tables == 0 || n_tables > 0x7fffffffu / MCQ_RG_CUM_STRIDE)
+        return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: n_tables must be 1 .. 2^31 / 1328");
+    /* weight of the hands of table t that are clear of a set B of table cards, by inclusion and exclusion:
+     * total - sum_{c in B} (weight of the hands that hold c) + sum_{c < c' in B} w[{c, c'}] */
+    std::vector<uint32_t> with_card(n_tables * 53u); /* per table: [52] the total, [c] the weight of the hands holding c */
+    for (size_t t = 0; t < n_tables; t++) {
+        const uint16_t *w = tables + t * MCQ_HAND_ROWS;
+        uint32_t *wc = with_card.data() + t * 53u;
+        for (uint32_t b = 1; b < 52u; b++)
+            for (uint32_t a = 0; a < b; a++) {
+                const uint32_t v = w[MCQ_HAND_INDEX(a, b)];
+                wc[a] += v;
+                wc[b] += v;
+                wc[52] += v;
+            }
+    }
+    uint64_t total_tasks = 0;
+    char buf[200];
+    std::vector<uint32_t> price(n); /* estimated whole trials per iteration, for the cost axis only */
+    std::vector<double> held(10u * 52u); /* per seat: P(its hand holds card c), given that it is clear of the table */
+    for (size_t i = 0; i < n; i++) {
+        const McqQueryWords qw = mcq_query_words(q[i]);
+        if (!mcq_ranges_query_valid(qw)) {
+            snprintf(buf, sizeof buf, "mcq_eval_batch_ranges: record %zu invalid (0, 3, 4 or 5 distinct table cards < 52, "
+                     "n_players 2..10, reserved 0, runs >= 1)", i);
+            return mcq_fail(MCQ_EINVAL, buf);
+        }
+        for (uint32_t s = 0; s < qw.n_players(); s++) {
+            const uint32_t t = seat_table[i * 10u + s];
+            if (t >= n_tables) {
+                snprintf(buf, sizeof buf, "mcq_eval_batch_ranges: record %zu, seat %u names table %u of %zu", i, s, t, n_tables);
+                return mcq_fail(MCQ_EINVAL, buf);
+            }
+            const uint32_t *wc = with_card.data() + (size_t)t * 53u;
+            const uint16_t *w = tables + (size_t)t * MCQ_HAND_ROWS;
+            uint64_t blocked = 0; /* weight of the hands that hold a table card */
+            for (uint32_t k = 0; k < qw.n_board(); k++) {
+                const uint32_t ck = qw.card(2u + k);
+                blocked += wc[ck];
+                for (uint32_t j = 0; j < k; j++) {
+                    const uint32_t cj = qw.card(2u + j);
+                    blocked -= w[MCQ_HAND_INDEX((cj < ck ? cj : ck), (cj < ck ? ck : cj))];
+                }
+            }
+            if (blocked >= wc[52]) {
+                snprintf(buf, sizeof buf, "mcq_eval_batch_ranges: record %zu, seat %u: table %u has no hand of positive weight "
+                         "clear of the table cards", i, s, t);
+                return mcq_fail(MCQ_EINVAL, buf);
+            }
+            const double clear = (double)(wc[52] - blocked);
+            const uint64_t bm = mcq_ranges_board_mask(qw);
+            for (uint32_t c = 0; c < 52u; c++) {
+                uint64_t with_c = (bm >> c) & 1u ? 0u : wc[c];
+                if (with_c)
+                    for (uint32_t k = 0; k < qw.n_board(); k++) {
+                        const uint32_t ck = qw.card(2u + k);
+                        with_c -= w[MCQ_HAND_INDEX((c < ck ? c : ck), (c < ck ? ck : c))];
+                    }
+                held[s * 52u + c] = (double)with_c / clear;
+            }
+        }
+        /* P(no two seats share a card) as if the pairs of seats collided independently, and a pair with probability
+         * sum_c P(s holds c) P(s' holds c) (a shared hand counts twice: an overestimate, bounded below) */
+        double accept = 1.0;
+        for (uint32_t s = 1; s < qw.n_players(); s++)
+            for (uint32_t r = 0; r < s; r++) {
+                double hit = 0.0;
+                for (uint32_t c = 0; c < 52u; c++) hit += held[s * 52u + c] * held[r * 52u + c];
+                accept *= hit < 0.99 ? 1.0 - hit : 0.01;
+            }
+        const double est = accept > 1.0 / MCQ_RG_MAX_PRICE ? 1.0 / accept : (double)MCQ_RG_MAX_PRICE;
+        price[i] = (uint32_t)(est + 0.5);
+        total_tasks += mcq_ranges_task_count(qw);
+    }
+    if (total_tasks > 0xfffffff0ull) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: too many iterations in one call");
+    MCQ_ENTER(c, "mcq_eval_batch_ranges");
+    McqDeviceScope dev_(c->device);
+    HIP_TRY(dev_.err);
+    const size_t row_bytes = sizeof(mcq_result_seats);
+    HIP_TRY(c->h_res.reserve(n * row_bytes));
+    HIP_TRY(c->d_q.reserve(n * sizeof(mcq_query)));
+    HIP_TRY(c->d_res.reserve(n * row_bytes));
+    c->res_clean = 0;
+    HIP_TRY(c->scratch[0].prefix.reserve((n + 3) * sizeof(uint64_t)));
+    /* (buffers of the extended path, free while this call runs: the raw tables, the prepared tables, the seats' table numbers) */
+    HIP_TRY(c->d_lists.reserve(n_tables * MCQ_HAND_ROWS * sizeof(uint16_t)));
+    HIP_TRY(c->d_draws.reserve(n_tables * MCQ_RG_CUM_STRIDE * sizeof(uint32_t)));
+    HIP_TRY(c->d_cnts.reserve(n * 11u * sizeof(uint32_t))); /* ... and behind them the records' prices */
+    HIP_TRY(hipMemcpyAsync(c->d_q.p, q, n * sizeof(mcq_query), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_lists.p, tables, n_tables * MCQ_HAND_ROWS * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_cnts.p, seat_table, n * 10u * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((uint32_t *)c->d_cnts.p + n * 10u, price.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    c->last_ms = 0.f;
+    uint32_t grid, block;
+    pick_geometry(c, MCQ_MODE_PHILOX, total_tasks, &grid, &block);
+    const int slot = (int)(c->n_timed % mcq_ctx::kRing);
+    HIP_TRY(mcq_launch_eval_ranges((const mcq_query *)c->d_q.p, (const uint32_t *)c->d_cnts.p,
+                                   (const uint32_t *)c->d_cnts.p + n * 10u, (const uint16_t *)c->d_lists.p,
+                                   (uint32_t)n_tables, (uint32_t *)c->d_draws.p, (uint32_t)n, (uint64_t *)c->scratch[0].prefix.p,
+                                   (mcq_result *)c->d_res.p, seed, first_query_id, c->d_luts, grid, block, c->stream,
+                                   c->timing ? c->ev0[slot] : nullptr, c->timing ? c->ev1[slot] : nullptr));
+    if (c->timing) c->n_timed++;
+    HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * row_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!c->timing || kernel_times_impl(c, &c->last_ms, 1) != 1) c->last_ms = 0.f;
+    const uint64_t *hr = (const uint64_t *)c->h_res.p;
+    for (size_t i = 0; i < n; i++)
+        if (hr[(size_t)kSeatsWords * i] != q[i].runs)
+            return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: the seats' ranges block each other: an iteration found no "
+                                        "trial in which their hands are disjoint");
+    memcpy(out, hr, n * row_bytes);
+    return MCQ_OK;
+    ABI_GUARD_END("mcq_eval_batch_ranges")
 }
 
 int mcq_eval_batch_numpy_stream(mcq_ctx *c, const mcq_query *q, size_t n, uint32_t *mt_key, uint32_t *mt_pos,

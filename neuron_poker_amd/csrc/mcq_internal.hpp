@@ -99,6 +99,14 @@ hipError_t mcq_launch_eval_ext(int mode, const mcq_query *d_q, const mcq_query_e
                                uint32_t block, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
                                bool ways = false /* d_res holds mcq_result_ways rows (prepared with row_words = 22) */,
                                bool seats = false /* production mode: mcq_result_seats rows (row_words = 32) */);
+/* a weighted range per seat (mcq_ranges.hpp), three launches: the prepared tables (d_tables: n_tables x MCQ_HAND_ROWS
+ * uint16 -> d_cum: n_tables x MCQ_RG_CUM_STRIDE uint32), rows and cost prefix (d_prefix: n + 1 words), the evaluation
+ * (d_seat_table: n x 10 table numbers, all below n_tables for the seats of a record; mcq_result_seats rows).  d_trials: n
+ * words, the host's estimate of each record's whole trials per iteration (1 .. MCQ_RG_MAX_PRICE): scheduling only */
+hipError_t mcq_launch_eval_ranges(const mcq_query *d_q, const uint32_t *d_seat_table, const uint32_t *d_trials,
+                                  const uint16_t *d_tables, uint32_t n_tables, uint32_t *d_cum, uint32_t n, uint64_t *d_prefix, mcq_result *d_res, uint64_t seed,
+                                  uint64_t first_qid, const McqTables *d_luts, uint32_t grid, uint32_t block, hipStream_t s,
+                                  hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 /* host-buffer calls with few rows: d_rows[0..n_rows) -> pinned host memory (device address h_rows_dev), d_rows zeroed,
  * then *done_flag = ticket; n_rows even (buffers hold the odd row's neighbour), d_done a zeroed device word */
 hipError_t mcq_launch_publish(mcq_result *d_rows, mcq_result *h_rows_dev, uint64_t n_rows, uint32_t *d_done,

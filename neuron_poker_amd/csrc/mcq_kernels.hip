@@ -26,6 +26,7 @@
 #include "mcq_mt.hpp"
 #include "mcq_mt_ext.hpp"
 #include "mcq_mt_blocks.hpp"
+#include "mcq_ranges.hpp"
 
 namespace {
 
@@ -1704,6 +1705,253 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
     }
 }
 
+// ---------------------------------------------------------------------------------------------- a weighted range per seat
+// mcq_eval_batch_ranges: the law, the word -> hand mapping and the lane code are in mcq_ranges.hpp.
+// Preparation, one block per DISTINCT table: the 1326 inclusive prefix sums of its weights (six consecutive hands per
+// thread, a block scan of the threads' sums), the last of them the total, and behind them the number of non-zero entries
+// and the index of the last one (a table with one entry is a known hand, see mcq_ranges.hpp).  Nothing
+// here depends on a record -- the table cards are handled by the per-seat re-draw -- so device memory is 5.3 KB per
+// table, not per record and seat.
+constexpr int kRgTabBlock = 256;
+__global__ __launch_bounds__(kRgTabBlock) void mcq_ranges_tables_kernel(const uint16_t *__restrict__ tables,
+                                                                        uint32_t *__restrict__ cum) {
+    __shared__ uint32_t wave_tot[kRgTabBlock / 64];
+    __shared__ uint32_t s_nnz, s_last;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    constexpr uint32_t kPer = (MCQ_HAND_ROWS + kRgTabBlock - 1) / kRgTabBlock; /* 6 */
+    const uint16_t *src = tables + (size_t)blockIdx.x * MCQ_HAND_ROWS;
+    uint32_t v[kPer], mine = 0, nnz = 0, last = 0;
+    if (tid == 0) s_nnz = s_last = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kPer; k++) {
+        const uint32_t i = tid * kPer + k;
+        v[k] = i < MCQ_HAND_ROWS ? (uint32_t)src[i] : 0u;
+        mine += v[k];
+        nnz += v[k] != 0u ? 1u : 0u;
+        last = v[k] != 0u ? i : last;
+    }
+    __syncthreads();
+    if (nnz) { /* the known-hand form of a table: how many entries are not zero, and the last of them */
+        atomicAdd(&s_nnz, nnz);
+        atomicMax(&s_last, last);
+    }
+    uint32_t inc = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_up(inc, off, 64);
+        if (lane >= (uint32_t)off) inc += o;
+    }
+    if (lane == 63u) wave_tot[wv] = inc;
+    __syncthreads();
+    uint32_t at = inc - mine;
+    for (uint32_t k = 0; k < kRgTabBlock / 64; k++) at += k < wv ? wave_tot[k] : 0u;
+    uint32_t *dst = cum + (size_t)blockIdx.x * MCQ_RG_CUM_STRIDE;
+#pragma unroll
+    for (uint32_t k = 0; k < kPer; k++) {
+        const uint32_t i = tid * kPer + k;
+        at += v[k];
+        if (i < MCQ_HAND_ROWS) dst[i] = at;
+    }
+    if (tid == 0) { /* (behind the barrier above: every thread's atomics have landed) */
+        dst[MCQ_RG_NNZ_WORD] = s_nnz;
+        dst[MCQ_RG_LAST_WORD] = s_last;
+    }
+}
+
+/* rows zeroed behind `runs`, the cost prefix of the records (mcq_prep_ext_kernel's layout: prefix[n] = the total); a task
+ * costs its price by seats and street times trials[i], the host's estimate of the record's whole trials per iteration */
+__global__ __launch_bounds__(1024) void mcq_prep_ranges_kernel(const mcq_query *__restrict__ q, const uint32_t *__restrict__ trials,
+                                                               uint32_t n, mcq_result *__restrict__ res,
+                                                               uint64_t *__restrict__ prefix) {
+    __shared__ uint64_t wave_tot[16];
+    constexpr uint32_t kWords = McqRowKind<MCQ_ROW_SEATS>::kWords;
+    uint64_t carry = 0;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t base = 0; base < n; base += 1024) {
+        uint32_t i = base + tid;
+        uint64_t cost = 0;
+        if (i < n) {
+            const uint4 raw = reinterpret_cast<const uint4 *>(q)[i];
+            const McqQueryWords qq = {raw.x, raw.y, raw.z, raw.w};
+            const bool ok = mcq_ranges_query_valid(qq);
+            cost = ok ? (uint64_t)mcq_ranges_task_count(qq) * (mcq_ranges_task_weight(qq) * trials[i]) : 0ull;
+            uint64_t *r = reinterpret_cast<uint64_t *>(res) + (size_t)i * kWords;
+            r[0] = ok ? qq.runs() : 0ull;
+            r[1] = ok ? 0ull : ~0ull;
+#pragma unroll
+            for (int k = 2; k < (int)kWords; k++) r[k] = 0;
+        }
+        uint64_t chunk_total;
+        const uint64_t before = block_exclusive_scan_1024(cost, wave_tot, &chunk_total);
+        if (i < n) prefix[i] = carry + before;
+        carry += chunk_total;
+    }
+    if (tid == 0) prefix[n] = carry;
+}
+
+// The evaluation: the slicing of mcq_eval_ext_kernel -- cost prefix, waves over the cost axis, sixteen-iteration streams,
+// the per-seat wave tally and its flush -- around mcq_iteration_ranges.  A draw is one dependent chain, word -> t ->
+// eleven steps of a binary search in the seat's prepared table -> hand -> test, so where the table lies decides the
+// kernel: a block first brings the prepared tables that ITS records name (a block's waves cover a contiguous piece of
+// the cost axis, hence consecutive records) into LDS when there are at most MCQ_RG_STAGE_TABLES distinct ones among at
+// most MCQ_RG_STAGE_QUERIES records (32 KB beside the evaluator's tables and the hands' card ids: 152 KB in all, one
+// block per CU as for the other evaluation kernels), and the draws read them there with 32-bit LDS addresses; otherwise
+// they read them from HBM.  Lanes whose trial is accepted wait for the rest of the wave.  A record without an accepted
+// trial zeroes the row's `runs`.
+__global__ __launch_bounds__(kExtBlock) void mcq_eval_ranges_kernel(const mcq_query *__restrict__ queries,
+                                                                    const uint32_t *__restrict__ seat_table,
+                                                                    const uint32_t *__restrict__ cum,
+                                                                    const uint32_t *__restrict__ trials, uint32_t n,
+                                                                    const uint64_t *__restrict__ prefix,
+                                                                    mcq_result *__restrict__ res, uint64_t seed,
+                                                                    uint64_t first_qid, const McqTables *__restrict__ g_tab) {
+    typedef McqRowKind<MCQ_ROW_SEATS> Row;
+    typedef typename Row::Acc Acc;
+    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ McqCard cards[64];
+    __shared__ McqRangesWaveCtx wave_ctx[kExtBlock / 64];
+    __shared__ uint16_t ids[MCQ_MAX_SEATS * kExtBlock];
+    __shared__ __attribute__((aligned(16))) uint32_t s_cum[MCQ_RG_STAGE_TABLES * MCQ_RG_CUM_STRIDE];
+    __shared__ uint32_t s_tab_id[MCQ_RG_STAGE_TABLES];
+    __shared__ uint32_t s_stage[3]; /* first record, number of records, staged tables (0: nothing staged) */
+    if (threadIdx.x < 64) cards[threadIdx.x] = mcq_card(threadIdx.x < 52 ? threadIdx.x : 0u);
+    load_tables(tab, g_tab);
+
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * waves_per_block + (threadIdx.x >> 6));
+    const uint64_t n_waves = (uint64_t)gridDim.x * waves_per_block;
+    const uint64_t total = prefix[n];
+    const uint64_t lo = total * wave / n_waves, hi = total * (wave + 1ull) / n_waves;
+    if (threadIdx.x == 0) { /* the block's records: those whose cost interval meets the block's piece of the axis */
+        const uint64_t blo = total * ((uint64_t)blockIdx.x * waves_per_block) / n_waves;
+        const uint64_t bhi = total * ((uint64_t)(blockIdx.x + 1u) * waves_per_block) / n_waves;
+        uint32_t qa = 0, nq = 0, n_tab = 0;
+        if (blo < bhi) {
+            uint32_t a = 0, b = n;
+            while (b - a > 1) {
+                const uint32_t mid = (a + b) >> 1;
+                if (prefix[mid] <= blo) a = mid; else b = mid;
+            }
+            qa = a;
+            b = n;
+            while (b - a > 1) { /* last record that starts before the block's end */
+                const uint32_t mid = (a + b) >> 1;
+                if (prefix[mid] < bhi) a = mid; else b = mid;
+            }
+            nq = a - qa + 1u;
+            bool fits = nq <= MCQ_RG_STAGE_QUERIES;
+            for (uint32_t j = 0; j < nq && fits; j++) {
+                const uint32_t p = reinterpret_cast<const uint32_t *>(queries)[(size_t)(qa + j) * 4u + 2u] & 0xFFu;
+                for (uint32_t s = 0; s < p && s < MCQ_MAX_SEATS && fits; s++) {
+                    const uint32_t t = seat_table[(size_t)(qa + j) * MCQ_MAX_SEATS + s];
+                    if (cum[(size_t)t * MCQ_RG_CUM_STRIDE + MCQ_RG_NNZ_WORD] == 1u) continue; /* a known hand reads no table */
+                    uint32_t k = 0;
+                    while (k < n_tab && s_tab_id[k] != t) k++;
+                    if (k < n_tab) continue;
+                    if (n_tab == MCQ_RG_STAGE_TABLES) fits = false;
+                    else s_tab_id[n_tab++] = t;
+                }
+            }
+            if (!fits) n_tab = 0;
+        }
+        s_stage[0] = qa;
+        s_stage[1] = nq;
+        s_stage[2] = n_tab;
+    }
+    __syncthreads();
+    {
+        const uint32_t words = s_stage[2] * MCQ_RG_CUM_STRIDE; /* (at most MCQ_RG_STAGE_TABLES tables: inside s_cum) */
+        for (uint32_t w = threadIdx.x; w < words; w += blockDim.x) {
+            const uint32_t k = w / MCQ_RG_CUM_STRIDE;
+            s_cum[w] = cum[(size_t)s_tab_id[k] * MCQ_RG_CUM_STRIDE + (w - k * MCQ_RG_CUM_STRIDE)];
+        }
+    }
+    __syncthreads();
+    if (lo >= hi) return;
+    McqRangesWaveCtx &wc = wave_ctx[threadIdx.x >> 6];
+    uint16_t *my_ids = ids + threadIdx.x;
+
+    uint32_t a = 0, b = n;
+    while (b - a > 1) {
+        const uint32_t mid = (a + b) >> 1;
+        if (prefix[mid] <= lo) a = mid; else b = mid;
+    }
+    uint32_t qi = __builtin_amdgcn_readfirstlane(a);
+    uint32_t task = 0, n_tasks = 0, weight = 1;
+    uint64_t pfx = 0;
+    McqRangesCtx qc;
+    typename Row::Tally tally;
+    tally.clear();
+    bool failed = false, fresh = true, tab_in_lds = false;
+    for (;;) {
+        if (fresh) {
+            if (qi >= n) break;
+            const uint4 raw = reinterpret_cast<const uint4 *>(queries)[qi];
+            const McqQueryWords q = {raw.x, raw.y, raw.z, raw.w};
+            pfx = prefix[qi];
+            const bool ok = prefix[qi + 1] > pfx;
+            weight = mcq_ranges_task_weight(q) * trials[qi]; /* (as mcq_prep_ranges_kernel priced it) */
+            task = 0;
+            if (pfx < lo) task = (uint32_t)((lo - pfx + weight - 1) / weight);
+            fresh = false;
+            if (ok) {
+                mcq_ranges_ctx(q, qc);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                const uint32_t n_staged = s_stage[2];
+                tab_in_lds = __builtin_amdgcn_readfirstlane(n_staged != 0u && qi - s_stage[0] < s_stage[1] ? 1 : 0) != 0;
+                if (lane < MCQ_MAX_SEATS) { /* (entries at or above n_players are not read: they may name anything) */
+                    const uint32_t t = seat_table[(size_t)qi * MCQ_MAX_SEATS + (lane < qc.n_players ? lane : 0u)];
+                    const uint32_t *cp = cum + (size_t)t * MCQ_RG_CUM_STRIDE;
+                    const uint32_t tot = mcq_ranges_seat_total(cp);
+                    wc.total[lane] = tot;
+                    if (tab_in_lds && !(tot & MCQ_RG_KNOWN)) { /* every table of a staged record is among the staged ones */
+                        uint32_t k = 0;
+                        while (k + 1u < n_staged && s_tab_id[k] != t) k++;
+                        cp = s_cum + k * MCQ_RG_CUM_STRIDE;
+                    }
+                    wc.cum[lane] = cp;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+            n_tasks = ok ? mcq_ranges_task_count(q) : 0u;
+        }
+        if (task >= n_tasks) {
+            if (__any(failed)) {
+                if (lane == 0) atomicExch(reinterpret_cast<unsigned long long *>(Row::row(res, qi)), 0ull); /* runs := 0 */
+                failed = false;
+            }
+            tally.flush(Row::row(res, qi), lane);
+            qi++;
+            fresh = true;
+            continue;
+        }
+        if (pfx + (uint64_t)task * weight >= hi) break;
+
+        Acc acc = {};
+        const uint32_t stream = task * MCQ_WAVE + lane;
+        const uint64_t it0 = (uint64_t)stream * MCQ_STREAM_ITERS;
+        if (it0 < qc.runs) {
+            McqExtCtrDraws dr;
+            dr.start(seed, first_qid + qi, stream);
+            const uint32_t cnt = (uint32_t)min((uint64_t)MCQ_STREAM_ITERS, (uint64_t)qc.runs - it0);
+            if (tab_in_lds) /* (wave-uniform) */
+                for (uint32_t j = 0; j < cnt && !failed; j++)
+                    failed = !mcq_iteration_ranges<McqExtCtrDraws, true, Acc>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
+            else
+                for (uint32_t j = 0; j < cnt && !failed; j++)
+                    failed = !mcq_iteration_ranges<McqExtCtrDraws, false, Acc>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
+        }
+        tally.add(acc, lane);
+        task++;
+    }
+    if (qi < n) {
+        if (__any(failed) && lane == 0) atomicExch(reinterpret_cast<unsigned long long *>(Row::row(res, qi)), 0ull);
+        tally.flush(Row::row(res, qi), lane);
+    }
+}
+
 // A FEW extended queries in ONE launch (production mode; what a decision of the reference's agents asks for: ONE ranged
 // query of a thousand iterations, agent_*.py -> get_equity -> run_montecarlo).  The general path above is six stream
 // operations (two copies, prep, lists, evaluation, copy back: 140 us for such a query); here the queries travel in the
@@ -2839,6 +3087,18 @@ hipError_t mcq_launch_eval_ext(int mode, const mcq_query *d_q, const mcq_query_e
         else MCQ_LAUNCH_EXT(MCQ_MODE_REPLAY_MT19937, MCQ_ROW_PLAIN);
     }
 #undef MCQ_LAUNCH_EXT
+    return hipGetLastError();
+}
+
+hipError_t mcq_launch_eval_ranges(const mcq_query *d_q, const uint32_t *d_seat_table, const uint32_t *d_trials,
+                                  const uint16_t *d_tables, uint32_t n_tables, uint32_t *d_cum, uint32_t n, uint64_t *d_prefix, mcq_result *d_res, uint64_t seed,
+                                  uint64_t first_qid, const McqTables *d_luts, uint32_t grid, uint32_t block, hipStream_t s,
+                                  hipEvent_t t0, hipEvent_t t1) {
+    if (n == 0 || n_tables == 0 || block > (uint32_t)kExtBlock) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mcq_ranges_tables_kernel, dim3(n_tables), dim3(kRgTabBlock), 0, s, d_tables, d_cum);
+    hipLaunchKernelGGL(mcq_prep_ranges_kernel, dim3(1), dim3(1024), 0, s, d_q, d_trials, n, d_res, d_prefix);
+    MCQ_LAUNCH_TIMED(mcq_eval_ranges_kernel, grid, block, d_q, d_seat_table, (const uint32_t *)d_cum, d_trials, n,
+                     (const uint64_t *)d_prefix, d_res, seed, first_qid, d_luts);
     return hipGetLastError();
 }
 

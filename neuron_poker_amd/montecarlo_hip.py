@@ -34,7 +34,7 @@ import numpy as np
 from . import _lib
 from .cards import TYPES, card_id, card_str
 
-__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_range_equity_exact_weighted", "quantise_weight", "get_preflop_range_equity_exact", "get_preflop_range_equity_exact_weighted", "preflop_class_table", "get_runout_equities", "MonteCarlo", "seed",
+__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_range_equity_exact_weighted", "get_range_equities", "quantise_weight", "get_preflop_range_equity_exact", "get_preflop_range_equity_exact_weighted", "preflop_class_table", "get_runout_equities", "MonteCarlo", "seed",
            "configure"]
 
 _state = {"couple_numpy": False,
@@ -561,6 +561,67 @@ def _weighted_range(rng, what):
     for i, (a, b) in enumerate(_ROW_HANDS):
         table[0, i] = by_hand.get(i, by_class.get(_lib.class_bit(_hand_class(a, b)), 0))
     return _lib.ALL_CLASSES, table
+
+
+def _seat_table(entry, what):
+    """One seat of get_range_equities -> its weight table, uint16 [HAND_ROWS]: a two-card hand is one entry of
+    COMBO_WEIGHT_MAX, a dict is what _weighted_range makes of it, a plain range (a set of classes, a top fraction) is the
+    0/1 table of its class bits."""
+    if isinstance(entry, (list, tuple)) and len(entry) == 2 and all(isinstance(c, str) and len(c) == 2 for c in entry) \
+            and all(c[1] in "CDHS" for c in entry):
+        a, b = card_id(entry[0]), card_id(entry[1])
+        if a == b:
+            raise ValueError("%s: a hand is two different cards, not %r" % (what, entry))
+        table = np.zeros(_lib.HAND_ROWS, np.uint16)
+        table[_lib.hand_index(a, b)] = _lib.COMBO_WEIGHT_MAX
+        return table
+    bits, table = _weighted_range(entry, what)
+    if table is not None:
+        return table[0]
+    bits = np.asarray(bits, np.uint32)
+    return np.array([(int(bits[bit >> 5]) >> (bit & 31)) & 1 for bit in
+                     (_lib.class_bit(_hand_class(a, b)) for a, b in _ROW_HANDS)], np.uint16)
+
+
+def _range_tables(ranges):
+    """The seats of get_range_equities -> (tables uint16 [n_tables, HAND_ROWS], seat_table uint32 [1, 10]); seats whose
+    tables are equal share one."""
+    if not 2 <= len(ranges) <= 10:
+        raise ValueError("between two and ten seats")
+    tables, seen = [], {}
+    seat_table = np.zeros((1, 10), np.uint32)
+    for s, entry in enumerate(ranges):
+        t = _seat_table(entry, "seat %d" % s)
+        seat_table[0, s] = seen.setdefault(t.tobytes(), len(tables))
+        if seat_table[0, s] == len(tables):
+            tables.append(t)
+    return np.stack(tables), seat_table
+
+
+def get_range_equities(ranges, table_cards, runs=100000, *, engine=None):
+    """Range against range against range: what the range of EVERY seat is worth on this board, by Monte Carlo
+    (mcq_eval_batch_ranges).  `ranges` has one entry per seat, two to ten of them: a two-card hand (('AH', 'KH')), a range
+    as run_montecarlo takes it -- a set of class strings or a top fraction, every hand of it weighing 1 -- or a dict of
+    weights in [0, 1] by class ('AQO': 0.5) or by hand, as get_range_equity_exact_weighted takes it.  Seats with equal
+    ranges share one table.  The hands of all seats are dealt JOINTLY: every deal of pairwise disjoint hands clear of the
+    table cards is as likely as the product of its hands' weights -- symmetric in the seats, unlike a hero-first deal.
+    -> ([(win, tie, share)] per seat, as fractions of `runs`; trials per iteration).  share is the seat's part of the pot,
+    a tie among k hands counting 1 / k: the shares sum to 1.  One call takes one query id from the same seed() state as
+    get_equity.  Seats whose ranges cannot be dealt together, or a seat without a hand clear of the table, raise
+    ValueError."""
+    ranges = list(ranges)
+    tables, seat_table = _range_tables(ranges)
+    board = [card_id(c) for c in table_cards]
+    if len(board) > 5:
+        raise ValueError("table_cards holds more than five cards")
+    q = _lib.pack_query_one([0, 0], board, len(ranges), runs)
+    eng = engine or _lib.default_engine()
+    s, first = _take_ids(1)
+    rows = eng.eval_batch_ranges(q, seat_table, tables, s, first_query_id=first)
+    r, share = rows[0], _lib.seat_shares(rows)[0]
+    n = float(r["runs"])
+    return ([(float(r["seat"][k]["win"]) / n, float(r["seat"][k]["tie"]) / n, float(share[k])) for k in range(len(ranges))],
+            float(r["passes"]) / n)
 
 
 def get_range_equity_exact_weighted(hero, table_cards, opponent, ghost_cards='', engine=None, ties="credited"):
