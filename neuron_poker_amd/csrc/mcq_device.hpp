@@ -546,17 +546,24 @@ struct McqHole { /* two hole cards: B = r1 | r2, P = r1 & r2 (pocket pair) */
 // bytes 0-1 of los, diamonds 2-3, hearts bytes 0-1 of his, spades 2-3 -- in ONE instruction per hand; bfl4 is the
 // table's mask in it.  Without such a suit the field of clubs is taken: table + hole then hold fewer than five bits
 // and tf[] = 0.
+MCQ_HD uint32_t mcq_suit_psel(uint32_t s) { /* s = 0..3: clubs, diamonds, hearts, spades */
+    return mcq_mad24(s, 0x0202u, 0x0C0C0100u); /* + 0x0404: hearts or spades, his; + 0x0202: diamonds or spades, upper half-word */
+}
 struct McqFlushSel {
     uint32_t psel, bfl4;
+    /* the same, and the suit itself (0 without one): what an opponent's card is read by (hole_by_suit of the deck accessors) */
     template <class Board>
-    MCQ_HDM void from_board(const Board &b) {
+    MCQ_HDM uint32_t from_board_suit(const Board &b) {
         const uint32_t f = (b.cnt + 0x5555u) & 0x8888u; /* bit 4s+3 <=> suit s has >= 3 table cards: one bit at most */
         /* f * 0x0123 = 0x0123 << (4s + 3): its bits 15-16 are nibble 3 - s of the constant = s, and 0 for f = 0.  No compare,
          * no select (those went through VCC and its wait states): and, 24-bit multiply, bit-field extract, multiply-add */
         const uint32_t s = mcq_bfe(mcq_mul24(f, 0x0123u), 15u, 2u);
-        psel = mcq_mad24(s, 0x0202u, 0x0C0C0100u); /* + 0x0404: hearts or spades, his; + 0x0202: diamonds or spades, upper half-word */
+        psel = mcq_suit_psel(s);
         bfl4 = mcq_perm(b.his, b.los, psel);
+        return s;
     }
+    template <class Board>
+    MCQ_HDM void from_board(const Board &b) { (void)from_board_suit(b); }
 };
 
 // Table lookups by BYTE offset (x4-domain masks; never shifted left here).
@@ -938,10 +945,24 @@ MCQ_HD McqCard mcq_base_entry(const McqQueryCtx &qc, uint32_t l, const uint32_t 
 // How an iteration reads the base deck.  `at` = base position + 128, as mcq_draw_opp / mcq_draw_table return it (the bias
 // is folded into the pointer).  card(): a table card, all four fields; hole_card(): an opponent's card, whose suit counter
 // nobody reads.
+// hole_by_suit(): an opponent's card as the straight forms of mcq_iteration_sum read it, AFTER the table is dealt and by the
+// one suit s that can still make a flush (McqFlushSel::from_board_suit): {a = the rank's doubled weight (McqCard::rb of the
+// sum form), b = the card's tfid byte-offset bit if its suit is s, else 0} -- what McqSumHole::set and the v_perm of
+// mcq_sum_first extract from the card's four words, the three suits nobody asks for never loaded.  suit_key(s) is how the
+// accessor wants the suit named in the reads that follow (a table's byte offset, or s itself).
+struct __attribute__((aligned(8))) McqPair {
+    uint32_t a, b;
+};
+MCQ_HD McqPair mcq_hole_entry(const McqCard &c, uint32_t s) { /* from the card's fields: the definition */
+    const McqPair e = {c.rb, mcq_perm(c.his, c.los, mcq_suit_psel(s))};
+    return e;
+}
 struct McqDeckAoS { /* 64 entries of 16 bytes (host builds of the lane code) */
     const McqCard *base128;
     MCQ_HDM McqCard card(uint32_t at) const { return base128[at]; }
     MCQ_HDM McqCard hole_card(uint32_t at) const { return base128[at]; }
+    MCQ_HDM uint32_t suit_key(uint32_t s) const { return s; }
+    MCQ_HDM McqPair hole_by_suit(uint32_t at, uint32_t key) const { return mcq_hole_entry(base128[at], key); }
 };
 // The kernels' form: two arrays of 8-byte entries, X[e] = (rb, cnt) and Y[e] = (los, his) YOFF entries behind it.  A card
 // is two 8-byte reads from ONE address register (Y at an immediate offset).  8-byte reads bank by (address / 4) mod 64 in
@@ -951,9 +972,6 @@ struct McqDeckAoS { /* 64 entries of 16 bytes (host builds of the lane code) */
 // YOFF is the caller's layout.  Where 8 * YOFF is below 2048 or a multiple of 512, the compiler pairs the two reads of a
 // table card into ONE two-address instruction (ds_read2_b64 / ds_read2st64_b64), which banks by (address / 4) mod 32 in
 // groups of 16 lanes at twice the cycles: the kernels keep YOFF out of that set.
-struct __attribute__((aligned(8))) McqPair {
-    uint32_t a, b;
-};
 template <uint32_t YOFF>
 struct McqDeckSplit {
     const McqPair *x128; /* X - 128 entries */
@@ -970,11 +988,52 @@ struct McqDeckSplit {
         const McqCard c = {rb, 0u, y.a, y.b};
         return c;
     }
+    /* (without a table by suit: from the card's fields) */
+    MCQ_HDM uint32_t suit_key(uint32_t s) const { return s; }
+    MCQ_HDM McqPair hole_by_suit(uint32_t at, uint32_t key) const { return mcq_hole_entry(hole_card(at), key); }
     /* entry e of both arrays (device: lane e writes it) */
     static MCQ_HDM void put(McqPair *x, uint32_t e, const McqCard &c) {
         const McqPair px = {c.rb, c.cnt}, py = {c.los, c.his};
         x[e] = px;
         x[e + YOFF] = py;
+    }
+};
+// The bulk kernel's form: beside the two arrays a per-wave HOLE TABLE of 8-byte entries mcq_hole_entry(card at position p,
+// suit s), p = 0..49, s = 0..3, at byte (p << POS_SHIFT) + s * SUIT_STRIDE: 1600 bytes a wave.  hole_by_suit() is one
+// ds_read_b64 whose address is one shift-add of the position and the key; the key is formed once per iteration (a
+// multiply-add of the suit: the table's LDS address, the -128 entries of `at` included).
+//   position-major  POS_SHIFT 5, SUIT_STRIDE 8:   an entry's bank slot (8-byte reads: 32 slots) is 4 (p mod 8) + s
+//   suit-major      POS_SHIFT 3, SUIT_STRIDE 400: four sub-tables of 50 entries back to back, slot (p + 18 s) mod 32
+// About 63 % of the lanes read suit 0 (no flush possible, or clubs).  Position-major gives those lanes EIGHT slots for 50
+// positions; suit-major all 32, at most two positions on a slot, and the sub-table of the next suit starts on slot 18,
+// where the slots that suit 0 fills twice (0..17) end.  Measured: DESIGN.md, section 7, r19.
+#define MCQ_HOLE_POSITIONS 50u
+#define MCQ_HOLE_WAVE_BYTES (MCQ_HOLE_POSITIONS * 4u * 8u)
+template <uint32_t YOFF, uint32_t POS_SHIFT, uint32_t SUIT_STRIDE>
+struct McqDeckBySuit : McqDeckSplit<YOFF> {
+    static_assert((POS_SHIFT == 5u && SUIT_STRIDE == 8u) || (POS_SHIFT == 3u && SUIT_STRIDE == 8u * MCQ_HOLE_POSITIONS),
+                  "position-major or suit-major: either fills the wave's 1600 bytes exactly");
+    const char *h128; /* the wave's hole table - (128 << POS_SHIFT) bytes */
+    MCQ_HDM uint32_t suit_key(uint32_t s) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return mcq_mad24(s, SUIT_STRIDE, (uint32_t)(uintptr_t)h128); /* an LDS address: the low word of the generic one */
+#else
+        return s * SUIT_STRIDE;
+#endif
+    }
+    MCQ_HDM McqPair hole_by_suit(uint32_t at, uint32_t key) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef __attribute__((address_space(3))) const McqPair *LdsPair;
+        return *(LdsPair)(uintptr_t)((at << POS_SHIFT) + key);
+#else
+        return *reinterpret_cast<const McqPair *>(h128 + ((at << POS_SHIFT) + key));
+#endif
+    }
+    /* position e, all four suits (device: lane e < MCQ_HOLE_POSITIONS writes them); h = the wave's hole table */
+    static MCQ_HDM void put_holes(char *h, uint32_t e, const McqCard &c) {
+#pragma unroll
+        for (uint32_t s = 0; s < 4u; s++)
+            *reinterpret_cast<McqPair *>(h + (e << POS_SHIFT) + s * SUIT_STRIDE) = mcq_hole_entry(c, s);
     }
 };
 
@@ -1346,6 +1405,10 @@ MCQ_NO_FOLD MCQ_HD uint32_t mcq_draw_epoch(uint32_t rp, uint32_t (&E)[MCQ_PLAN_R
 // and an iteration with fewer stops early in it
 constexpr int mcq_plan_draws(int nopp, int ndeal) { return 2 * nopp + (ndeal >= 0 ? ndeal : 5); }
 
+// Whether the straight forms read the opponents' cards by the flush suit (0: where they are dealt, all four suits).
+#ifndef MCQ_HOLE_BY_SUIT
+#define MCQ_HOLE_BY_SUIT 1 /* measured on the 6-max preflop shape: DESIGN.md, section 7, r19 */
+#endif
 #ifndef MCQ_L0_CONST
 #define MCQ_L0_CONST 1
 #endif
@@ -1373,6 +1436,26 @@ MCQ_HD void mcq_deal_table_plan(const McqQueryCtx &qc, Draws &dr, const Deck &de
     if (n_deal > 0u) b.add(pend);
 }
 
+// mcq_sum_first / mcq_sum_ids of a hand whose two cards were read by the flush suit (hole_by_suit): the rank sum is one
+// three-input add, the flush mask one three-input or, and nothing of the other three suits was ever loaded.
+MCQ_HD void mcq_sum_first_by_suit(const McqSumBoard &b, const McqFlushSel &fs, const McqPair &c1, const McqPair &c2,
+                                  const McqSumTabs &t, uint32_t &s, uint32_t &d, uint32_t &flush_id) {
+    s = b.sum + c1.a + c2.a;
+    flush_id = mcq_ld_u32(t.tfid, fs.bfl4 | c1.b | c2.b);
+    d = mcq_ld_u16(t.hoff, s & (MCQ_SUM_MASK << 1));
+}
+MCQ_HD void mcq_sum_ids_by_suit(const McqSumBoard &b, const McqFlushSel &fs, const McqPair &c1, const McqPair &c2,
+                                const McqSumTabs &t, uint32_t &rank_id, uint32_t &flush_id) {
+#ifdef MCQ_ABLATE_EVAL /* diagnostic timing build: wrong results */
+    rank_id = ((b.sum ^ c1.a ^ c2.a ^ ((c1.b | c2.b) >> 3)) & 0xFFFu) | (1u << MCQ_ID_SHIFT);
+    flush_id = 0u;
+    return;
+#endif
+    uint32_t s, d;
+    mcq_sum_first_by_suit(b, fs, c1, c2, t, s, d, flush_id);
+    rank_id = mcq_sum_rank(t, s, d);
+}
+
 // The late join of an opponent pair (mcq_iteration_sum): where the second card's suit masks may be used from.  Device: an
 // empty volatile asm on the two registers; a host build has no scheduler to hold.
 MCQ_HD void mcq_join_hold(McqCard &c) {
@@ -1394,12 +1477,16 @@ MCQ_HD void mcq_join_hold(McqCard &c) {
 // (mcq_sum_tabs_of), the kernels call the _sum forms with their LDS image.
 // RULE: the straight forms (NOPP >= 1) deal by the plan of that rule (mcq_deal_plan), 0 and the general form as before
 // there were plans (mcq_draw_opp, mcq_deal_table): same draws, same positions, fewer instructions.
+// BYSUIT: the straight forms keep the POSITIONS of the opponents' cards while they deal and read the cards themselves behind
+// the table, by the flush suit (hole_by_suit: one 8-byte read a card, one add and one or a hand); false and the general
+// form: the cards are read where they are dealt, all four suits (hole_card), and joined as described below.
 template <class Draws, int NOPP = -1, int NDEAL = -1, class Acc = McqLaneAcc, class Deck = McqDeckAoS,
-          int RULE = (NOPP >= 1 ? MCQ_DEAL_RULE : 0)>
+          int RULE = (NOPP >= 1 ? MCQ_DEAL_RULE : 0), bool BYSUIT = (NOPP >= 1 && MCQ_HOLE_BY_SUIT != 0)>
 // deck = the base deck table behind its accessor (McqDeckAoS / McqDeckSplit), its pointer biased by -128 entries: draw
 // indices carry a bias of 128 (r | 0x80).
 MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck, const McqSumTabs &tabs, Acc &acc) {
     static_assert(RULE == 0 || NOPP >= 1, "a plan needs the number of opponents at compile time");
+    static_assert(!BYSUIT || NOPP >= 1, "only the straight forms read the opponents' cards by suit");
     constexpr int kN = mcq_plan_draws(NOPP, NDEAL);
     uint32_t H[5] = {MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL};
     uint32_t E[MCQ_PLAN_REGS] = {MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL, MCQ_HOLE_SENTINEL,
@@ -1409,7 +1496,10 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
     uint32_t L = MCQ_L0_CONST && NDEAL >= 0 ? (uint32_t)(45 + NDEAL) : qc.L0;
     McqSumHole opp[MCQ_MAX_OPP];
     const uint32_t n_opp_d = NOPP >= 0 ? (uint32_t)NOPP : mcq_opaque_uniform(qc.n_opp);
-    /* Straight forms: a pair joins its hand one pair late, as a table card joins the table one draw late (mcq_deal_table).
+    /* BYSUIT (every straight form the kernels run): of an opponent's card only its POSITION is kept while the iteration deals
+     * -- positions depend on the draws alone, the cards' contents are first used behind the table -- and the card is read
+     * there, by the flush suit.  No card of an opponent is waited for during the dealing, so there is no join to hold back.
+     * Without BYSUIT (host builds that name it: the form before there was a hole table): a pair joins its hand one pair late, as a table card joins the table one draw late (mcq_deal_table).
      * opp[P].set -- one add of the rank weights, two v_or of the suit masks -- is the first use of the pair's four LDS
      * reads, and where it follows them the wave waits there with lgkmcnt(0).  Held back behind the NEXT pair's reads (the
      * last pair's behind the table's draws) the wait becomes lgkmcnt(4) and the next pair's arithmetic covers it.  The
@@ -1419,23 +1509,29 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
      * the old order: its wave-uniform branches already separate the blocks -- and with it every caller of the general
      * form: the one-launch kernel (mcq_eval_direct_kernel, which has no straight dispatch), parity mode with split-pot
      * rows and parity mode with six or more opponents (mcq_iterations_replay4). */
-    constexpr bool kLate = NOPP >= 1; /* every straight form, both accumulators, every draw policy: none needs a register more */
+    constexpr bool kLate = NOPP >= 1 && !BYSUIT; /* every such form, both accumulators, every draw policy: none needs a register more */
     McqCard j1 = {0u, 0u, 0u, 0u}, j2 = {0u, 0u, 0u, 0u}; /* the pair that has not joined yet */
+    uint32_t at_h[2 * MCQ_MAX_OPP]; /* BYSUIT: where the opponents' cards lie (base position + 128) */
 #define MCQ_OPP(P)                                                                                             \
     if (P < n_opp_d) {                                                                                         \
         uint32_t r1, r2;                                                                                       \
         dr.template pair<P>(L, r1, r2); /* r1 in [0,L-1], r2 in [0,L-2], r1 != r2 (l.167-176), both | 0x80 */  \
-        const McqCard c1 = deck.hole_card(mcq_draw_opp_by<kN, RULE, 2 * P>(r1, H, E));     /* deck.pop(r1) (l.178) */ \
-        const McqCard c2 = deck.hole_card(mcq_draw_opp_by<kN, RULE, 2 * P + 1>(r2, H, E)); /* deck.pop(r2), shrunk list (l.179) */ \
-        if constexpr (kLate) {                                                                                 \
-            if (P > 0) {                                                                                       \
-                mcq_join_hold(j2);                                                                             \
-                opp[P > 0 ? P - 1 : 0].set(j1, j2);                                                            \
-            }                                                                                                  \
-            j1 = c1;                                                                                           \
-            j2 = c2;                                                                                           \
+        if constexpr (BYSUIT) {                                                                                \
+            at_h[2 * P] = mcq_draw_opp_by<kN, RULE, 2 * P>(r1, H, E);         /* deck.pop(r1) (l.178) */          \
+            at_h[2 * P + 1] = mcq_draw_opp_by<kN, RULE, 2 * P + 1>(r2, H, E); /* deck.pop(r2), shrunk list (l.179) */ \
         } else {                                                                                               \
-            opp[P].set(c1, c2);                                                                                \
+            const McqCard c1 = deck.hole_card(mcq_draw_opp_by<kN, RULE, 2 * P>(r1, H, E));     /* deck.pop(r1) */ \
+            const McqCard c2 = deck.hole_card(mcq_draw_opp_by<kN, RULE, 2 * P + 1>(r2, H, E)); /* deck.pop(r2) */ \
+            if constexpr (kLate) {                                                                             \
+                if (P > 0) {                                                                                   \
+                    mcq_join_hold(j2);                                                                         \
+                    opp[P > 0 ? P - 1 : 0].set(j1, j2);                                                        \
+                }                                                                                              \
+                j1 = c1;                                                                                       \
+                j2 = c2;                                                                                       \
+            } else {                                                                                           \
+                opp[P].set(c1, c2);                                                                            \
+            }                                                                                                  \
         }                                                                                                      \
         L -= 2;                                                                                                \
     }
@@ -1460,7 +1556,14 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
         opp[NOPP >= 1 ? NOPP - 1 : 0].set(j1, j2);
     }
     McqFlushSel fs;
-    fs.from_board(b);
+    McqPair hc[2 * MCQ_MAX_OPP]; /* BYSUIT: the opponents' cards, read here: every read sent before hero's hand is looked up */
+    if constexpr (BYSUIT) {
+        const uint32_t key = deck.suit_key(fs.from_board_suit(b));
+#pragma unroll
+        for (int i = 0; i < 2 * NOPP; i++) hc[i] = deck.hole_by_suit(at_h[i], key);
+    } else {
+        fs.from_board(b);
+    }
     const uint32_t hk = mcq_sum_key(b, fs, qc.hero_s, tabs);
     uint32_t best = 0;
     uint32_t n_equal = 0; /* (split-pot form only) opponents whose id equals hero's */
@@ -1468,7 +1571,8 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
 #define MCQ_EVAL(P) /* the opponents' best id straight from the two lookups: one v_max3_u32 per hand */ \
     if (P < n_opp_e) {                                                     \
         uint32_t rid, fid;                                                 \
-        mcq_sum_ids(b, fs, opp[P], tabs, rid, fid);                        \
+        if constexpr (BYSUIT) mcq_sum_ids_by_suit(b, fs, hc[2 * P], hc[2 * P + 1], tabs, rid, fid); \
+        else mcq_sum_ids(b, fs, opp[P], tabs, rid, fid);                   \
         if (Acc::kWays) { /* the hand's own id: max, compare, add with carry, max */ \
             const uint32_t k = rid > fid ? rid : fid;                      \
             n_equal += k == hk ? 1u : 0u;                                  \
@@ -1485,7 +1589,10 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
          * shows; hand by hand, that order waits for every read where it is sent: 3.67 ms against 3.53 in sweeps.) */
         uint32_t s[MCQ_MAX_OPP], d[MCQ_MAX_OPP], fid[MCQ_MAX_OPP], rid[MCQ_MAX_OPP];
 #pragma unroll
-        for (int P = 0; P < NOPP; P++) mcq_sum_first(b, fs, opp[P], tabs, s[P], d[P], fid[P]);
+        for (int P = 0; P < NOPP; P++) {
+            if constexpr (BYSUIT) mcq_sum_first_by_suit(b, fs, hc[2 * P], hc[2 * P + 1], tabs, s[P], d[P], fid[P]);
+            else mcq_sum_first(b, fs, opp[P], tabs, s[P], d[P], fid[P]);
+        }
 #pragma unroll
         for (int P = 0; P < NOPP; P++) rid[P] = mcq_sum_rank(tabs, s[P], d[P]);
 #pragma unroll

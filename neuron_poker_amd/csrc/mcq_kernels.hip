@@ -10,7 +10,9 @@
 // plus a few KB of table image per block.
 //
 // Memory: 16 B in / 104 B out per QUERY; per iteration nothing touches HBM in production mode (parity mode
-// reads <= 23 draw bytes).  LDS holds the lookup tables (97 KB per block; the flush table is read from global memory) and one 64-entry base deck per wave.
+// reads <= 23 draw bytes).  LDS holds the lookup tables (the bulk kernel: the 115 KB rank-sum image; the flush table is read
+// from global memory), one 64-entry base deck per wave (16 KB a block) and, in the bulk kernel, one hole table per wave: the
+// same cards by flush suit, as the opponents' hands read them (25 KB a block) -- 156 KB of the CU's 160.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -36,10 +38,17 @@ namespace {
  * deck holds 50 cards at most, the entries behind it are nobody's). */
 constexpr uint32_t kDeckY = 1024 + 1;
 typedef McqDeckSplit<kDeckY> McqDeckLds;
-constexpr int kMaxBlock = 1024; /* 16 waves = 4 per SIMD; one block per CU: tables 97 KB + 16 base decks 16 KB of the 160 KB LDS */
+constexpr int kMaxBlock = 1024; /* 16 waves = 4 per SIMD; one block per CU: tables 97-115 KB + 16 base decks 16 KB (+ 16 hole tables 25 KB) of the 160 KB LDS */
 static_assert(kDeckY == kMaxBlock + 1 && 8u * kDeckY >= 2048u && (8u * kDeckY) % 512u != 0u,
               "the Y arrays start one entry behind the block's X arrays: beyond a two-address read's offsets");
 static_assert((kMaxBlock - 64) + kDeckY + 62 < 2 * kMaxBlock, "entries 0..62 of the last wave's Y array lie inside base_tab");
+/* The bulk kernel's deck: beside them one hole table per wave, the opponents' cards by flush suit (McqDeckBySuit).  The
+ * layout is a measured choice: 1 suit-major, 0 position-major. */
+#ifndef MCQ_HOLE_LAYOUT
+#define MCQ_HOLE_LAYOUT 1
+#endif
+typedef McqDeckBySuit<kDeckY, MCQ_HOLE_LAYOUT ? 3u : 5u, MCQ_HOLE_LAYOUT ? 8u * MCQ_HOLE_POSITIONS : 8u> McqDeckBulk;
+constexpr uint32_t kHoleShift = MCQ_HOLE_LAYOUT ? 3u : 5u;
 constexpr int kExtBlock = 1024; /* extended queries: 40 KB of dealt card ids beside the tables */
 
 // A launch with or without the pair of timestamp events (mcq_set_kernel_timing): the timestamped form costs a
@@ -1007,6 +1016,10 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
      * skips ahead in its lane's stream), so the tallies do not depend on it. */
     __shared__ __attribute__((aligned(16))) McqSumImage tab; /* first: the hash is read at constant offsets from LDS address 0 */
     __shared__ McqPair base_tab[2 * kMaxBlock]; /* per wave: the query's ordered remaining deck, 2 x 64 entries x 8 B (kDeckY) */
+    __shared__ __attribute__((aligned(8))) char hole_tab[(kMaxBlock / 64) * MCQ_HOLE_WAVE_BYTES]; /* per wave: its cards by suit */
+    static_assert(sizeof(McqSumImage) + sizeof(base_tab) + sizeof(hole_tab) + 8u * McqRowKind<true>::kLanes + 8u <= 160u * 1024u &&
+                      sizeof(McqSumImage) == 117760u && sizeof(base_tab) == 16384u && sizeof(hole_tab) == 25600u,
+                  "image, base decks, hole tables, s_row, s_key and s_done in the 160 KB of a CU");
     /* SPLIT (small batches): the rows the work-group's waves END on are added up in LDS when they are one query's -- a
      * single long query is hundreds of waves, and twelve atomics per wave on ONE row serialise (a 100 000-run query: 392
      * waves, 18 us where the arithmetic takes 6) -- and the last wave sends the sum: s_key = that query (claimed by the
@@ -1039,7 +1052,8 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
     /* this wave's slice of the cost axis; a task belongs to the slice its start position falls into */
     const uint64_t lo = total * wave / n_waves, hi = total * (wave + 1ull) / n_waves;
     McqPair *base = base_tab + (threadIdx.x & ~63u);
-    const McqDeckLds deck = {base - 128};
+    char *holes = hole_tab + (threadIdx.x >> 6) * MCQ_HOLE_WAVE_BYTES;
+    const McqDeckBulk deck = {{base - 128}, holes - (128u << kHoleShift)};
 
     uint32_t a = 0, b = n; /* last query with prefix <= lo: it has a positive cost because lo < total */
     while (b - a > 1) {
@@ -1070,7 +1084,11 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
             if (ok) {
                 mcq_query_ctx(q, qc);
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); /* earlier lookups are done (same wave) */
-                if (lane < 63u) McqDeckLds::put(base, lane, mcq_base_entry(qc, lane, tab.sel8));
+                if (lane < 63u) {
+                    const McqCard c = mcq_base_entry(qc, lane, tab.sel8);
+                    McqDeckBulk::put(base, lane, c);
+                    if (lane < MCQ_HOLE_POSITIONS) McqDeckBulk::put_holes(holes, lane, c);
+                }
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 __builtin_amdgcn_wave_barrier();
             }

@@ -8,7 +8,8 @@ hardware (tools/ubench -> profiles/r01_ubench*.txt, profiles/r06_vcc_probe.txt, 
 What it does: unbundles the gfx950 code object (clang-offload-bundler), disassembles it (llvm-objdump -d), takes the
 kernel whose mangled name contains --kernel, finds its loops (backward branches) and picks the straight-line iteration
 of `nopp` opponents and `ndeal` table cards to come: the innermost loop WITHOUT any other branch inside whose signature
-fits -- 2 * nopp + ndeal reads of a card's second half (ds_read_b64 at McqDeckSplit's offset), 2 * (nopp + 1) 16-bit hash
+fits -- ndeal reads of a card's second half (ds_read_b64 at McqDeckSplit's offset; 2 * nopp + ndeal in a library from
+before the opponents' cards were read by flush suit, McqDeckBySuit), 2 * (nopp + 1) 16-bit hash
 reads and 3 * nopp + ndeal + ceil(ndeal / 2) 64-bit multiply-adds
 (one per random word, one per bounded draw; mcq_device.hpp: McqCtrDrawsT, McqMwc64x).  Every instruction of that loop
 is put into an issue class:
@@ -280,7 +281,10 @@ def pick_loop(ins, nopp, ndeal, rng_stub=False):
     words = nopp + (ndeal + 1) // 2
     mads = (0 if rng_stub else words) + 2 * nopp + ndeal
     want = (2 * nopp + ndeal, 2 * (nopp + 1), mads)
-    found = [(j, i) for j, i in loops_of(ins) if signature(ins[j:i + 1]) == want]
+    # the straight forms read the opponents' cards by flush suit, from the hole table (McqDeckBySuit): only the table's
+    # cards are read at the Y arrays' offset
+    by_suit = (ndeal,) + want[1:]
+    found = [(j, i) for j, i in loops_of(ins) if signature(ins[j:i + 1]) in (want, by_suit)]
     if not found:
         raise SystemExit("no straight-line loop with %d card reads, %d hash reads and %d multiply-adds (nopp %d, ndeal %d)"
                          % (want[0], want[1], want[2], nopp, ndeal))
@@ -343,7 +347,7 @@ def main():
                 best = None
                 for vj, vi in loops_of(vins):
                     vb = vins[vj:vi + 1]
-                    if card_reads(vb) == 2 * a.nopp + a.ndeal:
+                    if card_reads(vb) in (2 * a.nopp + a.ndeal, a.ndeal):
                         vh = histogram(vb, a.vcc_window)
                         if best is None or abs(vh["valu"] - full_valu) < abs(best["valu"] - full_valu):
                             best = vh
