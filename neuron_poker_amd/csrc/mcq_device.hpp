@@ -1090,15 +1090,38 @@ MCQ_HD uint32_t mcq_seat_increment(uint32_t k) { /* k = 1..10 hands share the po
 // Unused byte slots hold the sentinel 0x7F and are decremented along (23 draws at most: always > 49 >= r).
 // This is an exact restatement of montecarlo_python.py:178-179,188 (checked against list.pop in the tests).
 #define MCQ_HOLE_SENTINEL 0x7F7F7F7Fu
+// A BIASED register (the second one of a pair that mcq_hole_count2 counts with one popcount, see there) stores t + 0x40 in
+// every byte.  The three functions that write a register take the bias as a template argument, and it costs no
+// instruction in any of them: it is a different constant where there already is one.
+//   * Coordinates are at most 49, so a stored coordinate is at most 0x71.
+//   * A free slot stores the SAME sentinel, 0x7F: as a coordinate it now stands for 0x3F, and moved down by s scans for
+//     0x3F - s, which stays above 49 >= r while s <= 13 (MCQ_BIAS_MAX_SCANS).  The slots of a register fill in rising
+//     order, one a draw, so a free slot sees three scans at the most before it is filled or its epoch closes
+//     (mcq_plan_slot_scans); a closed register is never scanned again.
+//   * With rb = splat(r | 0x80) the byte of rb - h is 0x40 + r - t, in [15, 113] for a hole and in [1, 63] for a free
+//     slot: never a borrow into the next byte, bit 7 clear, and bit 6 says t <= r.
+#define MCQ_HOLE_BIAS 0x40404040u
+#define MCQ_BIAS_MAX_SCANS 13
+static_assert(0x40 + 49 <= 0x7F && 0x40 + 0x3F <= 0x7F, "a biased byte never exceeds 0x7F: bit 7 stays clear");
+static_assert(0x3F - MCQ_BIAS_MAX_SCANS > 49, "a free slot of a biased register stays above every draw");
 
+// MODE of a scan: MCQ_SCAN_PLAIN; MCQ_SCAN_BIASED; MCQ_SCAN_TO_BIASED, the first scan of a register that mcq_hole_pair wrote
+// plain a draw before: it reads the plain bytes and leaves them biased.  Only the two holes take the bias there -- slot 2 is
+// filled by this draw's mcq_hole_put, which brings its own, and slot 3 keeps its byte, 0x7D, which is a biased register's
+// free slot as it stands -- so the bias joins the constant of the scan's add and the pair's literal stays the one every
+// register shares (a second literal is a second move an iteration).
+#define MCQ_SCAN_PLAIN 0
+#define MCQ_SCAN_BIASED 1
+#define MCQ_SCAN_TO_BIASED 2
+template <int MODE = MCQ_SCAN_PLAIN>
 MCQ_HD void mcq_hole_reg(uint32_t rb, uint32_t &h, uint32_t &k) {
 #ifdef MCQ_ABLATE_HOLES /* diagnostic timing build: wrong results */
     k += (rb ^ h) & 1u;
     return;
 #endif
-    const uint32_t f = ((rb - h) >> 7) & 0x01010101u; /* byte i = 1 iff t_i <= r */
+    const uint32_t f = ((rb - h) >> (MODE == MCQ_SCAN_BIASED ? 6 : 7)) & 0x01010101u; /* byte i = 1 iff t_i <= r */
     k = mcq_sad_u8(f, k);                             /* k += number of such holes */
-    h = h + f - 0x01010101u;                          /* every other hole moves down by one */
+    h = h + f - 0x01010101u + (MODE == MCQ_SCAN_TO_BIASED ? MCQ_HOLE_BIAS & 0xFFFFu : 0u); /* every other hole moves down by one */
 }
 
 // Store t = r in byte SLOT of a register whose slots fill in rising order: the slot still holds the sentinel, moved down
@@ -1107,14 +1130,15 @@ MCQ_HD void mcq_hole_reg(uint32_t rb, uint32_t &h, uint32_t &k) {
 // the constant joins the scan's own (h + f - 0x01010101 + constant: one v_add3_u32) and the insert is one v_lshl_add_u32;
 // slot 0 of a fresh register is one add of a constant to rp.  (A bit-field insert with the mask as a literal is not
 // encodable in the three-operand form: the compiler splits it into an and and a three-operand logic instruction.)
-template <int SLOT>
+// BIASED: the slot is to hold r + 0x40, which lowers the constant by that much.
+template <int SLOT, bool BIASED = false>
 MCQ_HD void mcq_hole_put(uint32_t &h, uint32_t rp) {
     constexpr uint32_t sh = 8u * (SLOT & 3);
 #ifdef MCQ_ABLATE_HOLES /* diagnostic timing build (wrong results): its scans do not move the sentinel */
     h = mcq_bfi(0x7Fu << sh, rp << sh, h);
     return;
 #endif
-    h = h + (rp << sh) - ((0x80u + 0x7Fu - (uint32_t)(SLOT & 3)) << sh);
+    h = h + (rp << sh) - ((0x80u + 0x7Fu - (uint32_t)(SLOT & 3) - (BIASED ? 0x40u : 0u)) << sh);
 }
 
 // A hole that is ALONE in its register is one comparison, not a scan.  The first draw into a register leaves itself
@@ -1123,7 +1147,9 @@ MCQ_HD void mcq_hole_put(uint32_t &h, uint32_t rp) {
 // slot 1: bytes 3 and 2 the sentinel moved down once, byte 1 = r, byte 0 = t0 + f - 1.  Both draws carry the same
 // | 0x80, so they compare as they arrive, and their two biases and the -1 fold into the literal: v_cmp_le_u32,
 // v_addc_co_u32 (k), v_lshl_add_u32, v_addc_co_u32 (h) -- four instructions for the eight of the scan and the two
-// inserts, and the VCC of a vector compare is read at once.
+// inserts, and the VCC of a vector compare is read at once.  BIASED: bytes 1 and 0 take 0x40 each from the literal (only
+// where the register's epoch closes behind this draw: else its next scan biases it, MCQ_SCAN_TO_BIASED).
+template <bool BIASED = false>
 MCQ_HD void mcq_hole_pair(uint32_t rp, uint32_t &h, uint32_t &k) {
     const uint32_t rp0 = h;
 #ifdef MCQ_ABLATE_HOLES /* diagnostic timing build: wrong results */
@@ -1134,7 +1160,7 @@ MCQ_HD void mcq_hole_pair(uint32_t rp, uint32_t &h, uint32_t &k) {
     const uint32_t f = rp0 <= rp ? 1u : 0u;
     k = k + f;
     const uint32_t t = mcq_opaque((rp << 8) + rp0);
-    uint32_t c = MCQ_HOLE_SENTINEL - 0x01010101u - 0x7E7Eu - 0x8080u - 1u; /* 0x7E7D7F7F */
+    uint32_t c = MCQ_HOLE_SENTINEL - 0x01010101u - 0x7E7Eu - 0x8080u - 1u + (BIASED ? MCQ_HOLE_BIAS & 0xFFFFu : 0u); /* 0x7E7D7F7F */
 #if defined(__HIP_DEVICE_COMPILE__)
     /* t and the literal pinned in registers, the flag as a carry: left to itself the compiler selects between the literal
      * and the literal + 1 and adds (five instructions, two registers for the pair of constants).  Not volatile: the
@@ -1173,6 +1199,20 @@ MCQ_HD void mcq_hole_count(uint32_t rb, uint32_t h, uint32_t &k) {
 #endif
     k = mcq_opaque(mcq_popc((rb - h) & 0x80808080u) + k); /* v_sub, v_and, v_bcnt with its add (opaque: else the compiler
                                                             counts into zero and sums afterwards: one more add3) */
+}
+// Two registers of one level with ONE popcount: h0 as it is, h1b biased (MCQ_HOLE_BIAS, see there for why neither
+// subtraction borrows).  [t <= p] stands in bit 7 of every byte of pb - h0 and in bit 6 of every byte of pb - h1b, where
+// bit 7 is clear; the select takes bit 7 from the first and the rest from the second, and the mask keeps the eight
+// indicators: v_sub, v_sub, v_bfi (assembled as v_bitop3), v_and, v_bcnt with its add -- five for six, and one
+// instruction of the slow class fewer.  The select's mask is left to the compiler, which keeps it in an SGPR (the
+// three-operand form takes a scalar operand, not a literal); pinned in a VGPR it was set anew in every iteration.
+MCQ_HD void mcq_hole_count2(uint32_t pb, uint32_t h0, uint32_t h1b, uint32_t &k) {
+#ifdef MCQ_ABLATE_HOLES /* diagnostic timing build: wrong results */
+    k += (pb ^ h0 ^ h1b) & 1u;
+    return;
+#endif
+    const uint32_t m = mcq_bfi(0x80808080u, pb - h0, pb - h1b) & 0xC0C0C0C0u;
+    k = mcq_opaque(mcq_popc(m) + k);
 }
 
 // table draw number K (0..4).  Two levels, because the table is dealt after ALL opponents (l.215-217): the K earlier
@@ -1344,9 +1384,83 @@ static_assert(mcq_plan_cost(mcq_deal_plan(15, 3)) == 143 && mcq_deal_plan(15, 3)
 static_assert(mcq_plan_cost(mcq_deal_plan(15, MCQ_DEAL_FULLREG)) == 146, "6-max before the flop, {4, 8, 12}");
 static_assert(mcq_plan_cost(mcq_deal_plan(23, 3)) == 308 && mcq_plan_cost(mcq_deal_plan(12, 3)) == 98, "ten players; 5 opponents, 2 to come");
 
+// Counting in pairs (mcq_hole_count2).  Wherever a level counts two or more registers they are taken two at a time, the
+// epoch's registers 0 with 1, 2 with 3; the second of each pair lives BIASED (MCQ_HOLE_BIAS) from its pair draw or the scan behind it on
+// (mcq_plan_biased_by_pair), an odd register left over is counted singly.  Which registers are biased follows from the plan alone: the holes its epoch ends
+// with.  The plans themselves and mcq_plan_cost stay what they were (the checkpoints are chosen by the single counts);
+// mcq_plan_cost_paired is the cost of the same plan with the paired primitive: 5 a pair for 6.
+#ifndef MCQ_COUNT_PAIRED
+#define MCQ_COUNT_PAIRED 1 /* measured on the 6-max preflop shape: DESIGN.md, section 7, r20 */
+#endif
+// holes epoch e ends with (the last draw of all leaves none)
+constexpr int mcq_plan_holes(const McqDealPlan &pl, int e) { return pl.size(e) - (e == pl.n_epochs - 1 ? 1 : 0); }
+// scans that move a free slot of an epoch's register i down before the slot is filled or the epoch closes with `holes`
+// holes: the register is written whole by draw 4i + 1 of its epoch, as if scanned once, and scanned by every later draw
+constexpr int mcq_plan_slot_scans(int holes, int i) {
+    const int s = holes - 4 * i - 1;
+    return s < 0 ? 0 : s > 3 ? 3 : s;
+}
+// whether register i of an epoch that ends with `holes` holes is the biased half of a pair: a plan that broke the bound on
+// the free slots would count that register singly
+constexpr bool mcq_plan_biased(int holes, int i) {
+    return (i & 1) != 0 && i < mcq_plan_count_regs(holes) && mcq_plan_slot_scans(holes, i) <= MCQ_BIAS_MAX_SCANS;
+}
+constexpr int mcq_plan_pairs(int holes) {
+    int c = 0;
+    for (int i = 1; i < mcq_plan_count_regs(holes); i += 2) c += mcq_plan_biased(holes, i) ? 1 : 0;
+    return c;
+}
+constexpr int mcq_plan_cost_closed_paired(int n) { return mcq_plan_cost_closed(n) - mcq_plan_pairs(n); }
+constexpr int mcq_plan_cost_paired(const McqDealPlan &pl) {
+    int c = 0;
+    for (int e = 0; e < pl.n_epochs; e++) {
+        const int a = pl.first[e], b = pl.first[e + 1], n = pl.n_draws;
+        for (int d = a; d < b; d++) c += d == n - 1 ? mcq_plan_cost_closed_paired(d - a) : mcq_plan_cost_own(d - a, false);
+        c += (n - b) * mcq_plan_cost_closed_paired(b - a);
+    }
+    return c;
+}
+static_assert(mcq_plan_cost_paired(mcq_deal_plan(15, 3)) == 136, "6-max before the flop: draws 8..14 pass one pair each");
+static_assert(mcq_plan_cost_paired(mcq_deal_plan(23, 3)) == 286, "ten players, {8, 16, 20}: 15 + 7 passes over a full pair");
+static_assert(mcq_plan_cost_paired(mcq_deal_plan(15, 1)) == 140 && mcq_plan_cost_paired(mcq_deal_plan(15, 2)) == 138,
+              "6-max before the flop: {8}, whose last draw counts six holes of its own epoch in a pair, and {8, 12}");
+static_assert(mcq_plan_biased(8, 1) && mcq_plan_biased(6, 1) && !mcq_plan_biased(5, 1) && !mcq_plan_biased(8, 0) &&
+              mcq_plan_biased(16, 3) && !mcq_plan_biased(12, 2), "the second register of a pair, full or partly filled");
+
+// the epoch's registers that a level counts, from register I on: in pairs where the plan has them, else one by one
+template <int N, int RULE, int EE, int PAIRED, int I = 0>
+MCQ_HD void mcq_epoch_count(uint32_t pb, const uint32_t (&E)[MCQ_PLAN_REGS], uint32_t &k) {
+    constexpr int holes = mcq_plan_holes(McqPlanOf<N, RULE>::pl, EE), r0 = McqPlanOf<N, RULE>::pl.reg0[EE];
+    if constexpr (I < mcq_plan_count_regs(holes)) {
+        if constexpr (PAIRED != 0 && mcq_plan_biased(holes, I + 1)) {
+            mcq_hole_count2(pb, E[r0 + I], E[r0 + I + 1], k);
+            mcq_epoch_count<N, RULE, EE, PAIRED, I + 2>(pb, E, k);
+        } else {
+            mcq_hole_count(pb, E[r0 + I], k);
+            mcq_epoch_count<N, RULE, EE, PAIRED, I + 1>(pb, E, k);
+        }
+    }
+}
+// A biased register's first write is its pair draw (draw 4i + 1 of the epoch, mcq_hole_pair) only where the epoch closes
+// right behind it; else the pair is written plain and the scan of the next draw, 4i + 2, biases it (MCQ_SCAN_TO_BIASED).
+constexpr bool mcq_plan_biased_by_pair(int holes, int i) { return mcq_plan_biased(holes, i) && holes == 4 * i + 2; }
+constexpr int mcq_plan_scan_mode(int holes, int i, int j) { /* draw j of the epoch scans its register i */
+    return !mcq_plan_biased(holes, i) ? MCQ_SCAN_PLAIN
+           : (j == 4 * i + 2 && !mcq_plan_biased_by_pair(holes, i)) ? MCQ_SCAN_TO_BIASED : MCQ_SCAN_BIASED;
+}
+// the moving scan of draw J of the epoch over its registers I .. CNT - 1, each by the bit its indicator stands in
+template <int N, int RULE, int EE, int PAIRED, int J, int CNT, int I = 0>
+MCQ_HD void mcq_epoch_scan(uint32_t rb, uint32_t (&E)[MCQ_PLAN_REGS], uint32_t &k) {
+    if constexpr (I < CNT) {
+        constexpr int holes = mcq_plan_holes(McqPlanOf<N, RULE>::pl, EE), r0 = McqPlanOf<N, RULE>::pl.reg0[EE];
+        mcq_hole_reg<(PAIRED != 0 ? mcq_plan_scan_mode(holes, I, J) : MCQ_SCAN_PLAIN)>(rb, E[r0 + I], k);
+        mcq_epoch_scan<N, RULE, EE, PAIRED, J, CNT, I + 1>(rb, E, k);
+    }
+}
+
 // Draw number D of the N an iteration deals by the plan (N, RULE).  E: the plan's hole registers, epoch by epoch.
 // Returned: base position + 128, as mcq_draw_opp / mcq_draw_table return it.
-template <int N, int RULE, int EE> /* through the closed epochs EE, EE - 1, .., 0 */
+template <int N, int RULE, int EE, int PAIRED = MCQ_COUNT_PAIRED> /* through the closed epochs EE, EE - 1, .., 0 */
 MCQ_HD void mcq_epoch_pass(const uint32_t (&E)[MCQ_PLAN_REGS], uint32_t &k) {
     if constexpr (EE >= 0) {
         constexpr int n = McqPlanOf<N, RULE>::pl.size(EE), r0 = McqPlanOf<N, RULE>::pl.reg0[EE];
@@ -1354,10 +1468,9 @@ MCQ_HD void mcq_epoch_pass(const uint32_t (&E)[MCQ_PLAN_REGS], uint32_t &k) {
         if constexpr (mcq_plan_lone(n)) k += E[r0 + n / 4] <= p ? 1u : 0u;
         if constexpr (mcq_plan_count_regs(n) > 0) {
             const uint32_t pb = mcq_splat_byte(p);
-#pragma unroll
-            for (int i = 0; i < mcq_plan_count_regs(n); i++) mcq_hole_count(pb, E[r0 + i], k);
+            mcq_epoch_count<N, RULE, EE, PAIRED>(pb, E, k);
         }
-        mcq_epoch_pass<N, RULE, EE - 1>(E, k);
+        mcq_epoch_pass<N, RULE, EE - 1, PAIRED>(E, k);
     }
 }
 #if defined(__GNUC__) && !defined(__clang__)
@@ -1367,32 +1480,32 @@ MCQ_HD void mcq_epoch_pass(const uint32_t (&E)[MCQ_PLAN_REGS], uint32_t &k) {
 #else
 #define MCQ_NO_FOLD
 #endif
-template <int N, int RULE, int D>
+template <int N, int RULE, int D, int PAIRED = MCQ_COUNT_PAIRED>
 MCQ_NO_FOLD MCQ_HD uint32_t mcq_draw_epoch(uint32_t rp, uint32_t (&E)[MCQ_PLAN_REGS]) {
     if constexpr (D >= N) {
         return rp; /* (the unrolled callers name draws their form never makes) */
     } else {
         constexpr int e = McqPlanOf<N, RULE>::pl.epoch_of(D), J = D - McqPlanOf<N, RULE>::pl.first[e],
                       R0 = McqPlanOf<N, RULE>::pl.reg0[e];
+        constexpr int kHoles = mcq_plan_holes(McqPlanOf<N, RULE>::pl, e);
+        constexpr bool kBiased = PAIRED != 0 && mcq_plan_biased(kHoles, J / 4); /* the register this draw's hole goes to */
         uint32_t k = rp;
         if constexpr (D == N - 1) { /* count only */
             if constexpr (mcq_plan_lone(J)) k += E[R0 + J / 4] <= rp ? 1u : 0u;
             if constexpr (mcq_plan_count_regs(J) > 0) {
                 const uint32_t rb = mcq_splat_byte(rp);
-#pragma unroll
-                for (int i = 0; i < mcq_plan_count_regs(J); i++) mcq_hole_count(rb, E[R0 + i], k);
+                mcq_epoch_count<N, RULE, e, PAIRED>(rb, E, k); /* the J holes are all the last epoch ends with */
             }
         } else { /* mcq_draw_opp<J> on the epoch's registers */
-            if constexpr (J % 4 == 1) mcq_hole_pair(rp, E[R0 + J / 4], k);
+            if constexpr (J % 4 == 1) mcq_hole_pair<(PAIRED != 0 && mcq_plan_biased_by_pair(kHoles, J / 4))>(rp, E[R0 + J / 4], k);
             if constexpr (J % 4 == 0) E[R0 + J / 4] = rp;
             if constexpr (J >= 2) {
                 const uint32_t rb = mcq_splat_byte(rp);
-#pragma unroll
-                for (int i = 0; i < (J % 4 < 2 ? J / 4 : J / 4 + 1); i++) mcq_hole_reg(rb, E[R0 + i], k);
-                if constexpr (J % 4 >= 2) mcq_hole_put<J>(E[R0 + J / 4], rp);
+                mcq_epoch_scan<N, RULE, e, PAIRED, J, (J % 4 < 2 ? J / 4 : J / 4 + 1)>(rb, E, k);
+                if constexpr (J % 4 >= 2) mcq_hole_put<J, kBiased>(E[R0 + J / 4], rp);
             }
         }
-        mcq_epoch_pass<N, RULE, e - 1>(E, k);
+        mcq_epoch_pass<N, RULE, e - 1, PAIRED>(E, k);
         return mcq_opaque(k);
     }
 }
@@ -1413,20 +1526,20 @@ constexpr int mcq_plan_draws(int nopp, int ndeal) { return 2 * nopp + (ndeal >= 
 #define MCQ_L0_CONST 1
 #endif
 // opponent draw number D: by the plan's rule, or (RULE 0) as before there were plans
-template <int N, int RULE, int D>
+template <int N, int RULE, int D, int PAIRED = MCQ_COUNT_PAIRED>
 MCQ_HD uint32_t mcq_draw_opp_by(uint32_t rp, uint32_t (&H)[5], uint32_t (&E)[MCQ_PLAN_REGS]) {
-    if constexpr (RULE != 0) return mcq_draw_epoch<N, RULE, D>(rp, E);
+    if constexpr (RULE != 0) return mcq_draw_epoch<N, RULE, D, PAIRED>(rp, E);
     else return mcq_draw_opp<D>(rp, H);
 }
 // mcq_deal_table by a plan: the table's draws are the plan's draws D0, D0 + 1, ..
-template <int N, int RULE, int D0, class Draws, int NDEAL = -1, class Deck = McqDeckAoS>
+template <int N, int RULE, int D0, class Draws, int NDEAL = -1, class Deck = McqDeckAoS, int PAIRED = MCQ_COUNT_PAIRED>
 MCQ_HD void mcq_deal_table_plan(const McqQueryCtx &qc, Draws &dr, const Deck &deck, uint32_t (&E)[MCQ_PLAN_REGS], uint32_t L,
                                 McqSumBoard &b) {
     const uint32_t n_deal = NDEAL >= 0 ? (uint32_t)NDEAL : mcq_opaque_uniform(qc.n_deal);
     McqCard pend = {0u, 0u, 0u, 0u}; /* a card joins the table one draw late, see mcq_deal_table */
 #define MCQ_TABLE(K)                                                                                                  \
     if (K < n_deal) {                                                                                                 \
-        const uint32_t at = mcq_draw_epoch<N, RULE, D0 + K>(dr.template table<K>(L - Draws::kTableShort), E); /* l.188 */ \
+        const uint32_t at = mcq_draw_epoch<N, RULE, D0 + K, PAIRED>(dr.template table<K>(L - Draws::kTableShort), E); /* l.188 */ \
         if (K > 0) b.add(pend);                                                                                       \
         pend = deck.card(at);                                                                                         \
         L -= 1;                                                                                                       \
@@ -1480,8 +1593,10 @@ MCQ_HD void mcq_join_hold(McqCard &c) {
 // BYSUIT: the straight forms keep the POSITIONS of the opponents' cards while they deal and read the cards themselves behind
 // the table, by the flush suit (hole_by_suit: one 8-byte read a card, one add and one or a hand); false and the general
 // form: the cards are read where they are dealt, all four suits (hole_card), and joined as described below.
+// PAIRED: the dealing by a plan counts a closed epoch's registers two per popcount (mcq_hole_count2); 0: one by one.
 template <class Draws, int NOPP = -1, int NDEAL = -1, class Acc = McqLaneAcc, class Deck = McqDeckAoS,
-          int RULE = (NOPP >= 1 ? MCQ_DEAL_RULE : 0), bool BYSUIT = (NOPP >= 1 && MCQ_HOLE_BY_SUIT != 0)>
+          int RULE = (NOPP >= 1 ? MCQ_DEAL_RULE : 0), bool BYSUIT = (NOPP >= 1 && MCQ_HOLE_BY_SUIT != 0),
+          int PAIRED = MCQ_COUNT_PAIRED>
 // deck = the base deck table behind its accessor (McqDeckAoS / McqDeckSplit), its pointer biased by -128 entries: draw
 // indices carry a bias of 128 (r | 0x80).
 MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck, const McqSumTabs &tabs, Acc &acc) {
@@ -1517,11 +1632,11 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
         uint32_t r1, r2;                                                                                       \
         dr.template pair<P>(L, r1, r2); /* r1 in [0,L-1], r2 in [0,L-2], r1 != r2 (l.167-176), both | 0x80 */  \
         if constexpr (BYSUIT) {                                                                                \
-            at_h[2 * P] = mcq_draw_opp_by<kN, RULE, 2 * P>(r1, H, E);         /* deck.pop(r1) (l.178) */          \
-            at_h[2 * P + 1] = mcq_draw_opp_by<kN, RULE, 2 * P + 1>(r2, H, E); /* deck.pop(r2), shrunk list (l.179) */ \
+            at_h[2 * P] = mcq_draw_opp_by<kN, RULE, 2 * P, PAIRED>(r1, H, E);         /* deck.pop(r1) (l.178) */          \
+            at_h[2 * P + 1] = mcq_draw_opp_by<kN, RULE, 2 * P + 1, PAIRED>(r2, H, E); /* deck.pop(r2), shrunk list (l.179) */ \
         } else {                                                                                               \
-            const McqCard c1 = deck.hole_card(mcq_draw_opp_by<kN, RULE, 2 * P>(r1, H, E));     /* deck.pop(r1) */ \
-            const McqCard c2 = deck.hole_card(mcq_draw_opp_by<kN, RULE, 2 * P + 1>(r2, H, E)); /* deck.pop(r2) */ \
+            const McqCard c1 = deck.hole_card(mcq_draw_opp_by<kN, RULE, 2 * P, PAIRED>(r1, H, E));     /* deck.pop(r1) */ \
+            const McqCard c2 = deck.hole_card(mcq_draw_opp_by<kN, RULE, 2 * P + 1, PAIRED>(r2, H, E)); /* deck.pop(r2) */ \
             if constexpr (kLate) {                                                                             \
                 if (P > 0) {                                                                                   \
                     mcq_join_hold(j2);                                                                         \
@@ -1540,7 +1655,7 @@ MCQ_HD void mcq_iteration_sum(const McqQueryCtx &qc, Draws &dr, const Deck &deck
     McqSumBoard b = qc.board_s;
     if (NDEAL == 5) b.clear(); /* all five to come: the known table is empty, nothing to add the cards to */
     if constexpr (RULE != 0) {
-        mcq_deal_table_plan<kN, RULE, 2 * NOPP, Draws, NDEAL>(qc, dr, deck, E, L, b);
+        mcq_deal_table_plan<kN, RULE, 2 * NOPP, Draws, NDEAL, Deck, PAIRED>(qc, dr, deck, E, L, b);
     } else if (NOPP >= 0) {
         mcq_deal_table<(NOPP >= 0 ? (2 * NOPP + 3) / 4 : 0), Draws, NDEAL>(qc, dr, deck, H, L, b);
     } else switch (mcq_opaque_uniform((2u * qc.n_opp + 3u) / 4u)) { /* registers holding the opponents' holes: wave-uniform */

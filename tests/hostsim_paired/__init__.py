@@ -1,0 +1,103 @@
+"""Test-only host build of the paired count of the dealing in epochs, both settings of its switch (see hs_paired.cpp)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
+_SO = os.path.join(_HERE, "libhs_paired.so")
+_SRCS = [os.path.join(_HERE, "hs_paired.cpp"), os.path.join(_CSRC, "mcq_device.hpp"), os.path.join(_CSRC, "mcq_replay.hpp"),
+         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
+_lib = None
+
+FULLREG = 9                   # MCQ_DEAL_FULLREG
+RULES = (1, 2, 3, FULLREG)
+BIAS = 0x40404040             # MCQ_HOLE_BIAS
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
+            tmp = _SO + ".%d.tmp" % os.getpid()
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
+                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
+            os.replace(tmp, _SO)
+        L = C.CDLL(_SO)
+        L.hs_paired_default.restype = C.c_int
+        L.hs_paired_count2.restype = None
+        L.hs_paired_count2.argtypes = [C.c_uint64] + [C.c_void_p] * 5
+        L.hs_paired_plan.restype = C.c_int
+        L.hs_paired_plan.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.hs_paired_positions.restype = C.c_int
+        L.hs_paired_positions.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.hs_paired_run.restype = C.c_int
+        L.hs_paired_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.hs_paired_replay.restype = C.c_int
+        L.hs_paired_replay.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        _lib = L
+    return _lib
+
+
+def shipped_switch():
+    return lib().hs_paired_default()
+
+
+def count2(pb, h0, h1b):
+    """uint32 arrays -> (what mcq_hole_count2 adds, what two mcq_hole_count add with the bias taken off the second)"""
+    pb, h0, h1b = (np.ascontiguousarray(a, np.uint32) for a in (pb, h0, h1b))
+    assert pb.shape == h0.shape == h1b.shape and pb.ndim == 1
+    out, single = np.zeros_like(pb), np.zeros_like(pb)
+    lib().hs_paired_count2(len(pb), *(a.ctypes.data_as(C.c_void_p) for a in (pb, h0, h1b, out, single)))
+    return out, single
+
+
+def plan(n_plan, rule):
+    """-> dict(cost, cost_paired, regs: per register 0 plain / 1 biased by its pair draw / 2 biased by its first scan,
+    holes: per epoch) of the plan of n_plan draws"""
+    out = np.zeros(15, np.int32)
+    rc = lib().hs_paired_plan(n_plan, rule, out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise ValueError("hs_paired_plan: %d (%d draws, rule %d)" % (rc, n_plan, rule))
+    return {"cost": int(out[1]), "cost_paired": int(out[2]), "regs": [int(v) for v in out[3:9]],
+            "holes": [int(v) for v in out[9:9 + int(out[0])]]}
+
+
+def positions(n_plan, rule, draws, paired=True):
+    """draws uint8 [rows, n], n <= n_plan: the first n draws of the plan -> base positions uint8 [rows, n]"""
+    d = np.ascontiguousarray(draws, np.uint8)
+    pos = np.full(d.shape, 255, np.uint8)
+    rc = lib().hs_paired_positions(n_plan, rule, int(paired), d.shape[1], d.ctypes.data_as(C.c_void_p), d.shape[0],
+                                   pos.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise ValueError("hs_paired_positions: %d (%d draws of %d, rule %d)" % (rc, d.shape[1], n_plan, rule))
+    return pos
+
+
+def rows(queries, seed, first_qid, nopp, ndeal, uniform=False, ways=False, paired=True):
+    """Query i (16-byte records) with id first_qid + i through mcq_iteration_sum<.., nopp, ndeal, ..>: -> uint64 [n, 13 or 22]."""
+    L = lib()
+    q = np.ascontiguousarray(queries).view(np.uint8).reshape(-1, 16)
+    out = np.zeros((len(q), 22 if ways else 13), np.uint64)
+    for i in range(len(q)):
+        rec = q[i].copy()
+        rc = L.hs_paired_run(rec.ctypes.data_as(C.c_void_p), seed, first_qid + i, nopp, ndeal, int(uniform), int(ways),
+                             int(paired), out[i].ctypes.data_as(C.c_void_p))
+        if rc:
+            raise ValueError("hs_paired_run: %d (nopp %d, ndeal %d, query %s)" % (rc, nopp, ndeal, rec.tolist()))
+    return out
+
+
+def replay_rows(queries, seed32):
+    """Parity mode: query i from the start of the MT19937 stream of seed32 -> uint64 [n, 13]."""
+    L = lib()
+    q = np.ascontiguousarray(queries).view(np.uint8).reshape(-1, 16)
+    out = np.zeros((len(q), 13), np.uint64)
+    for i in range(len(q)):
+        rec = q[i].copy()
+        rc = L.hs_paired_replay(rec.ctypes.data_as(C.c_void_p), seed32, out[i].ctypes.data_as(C.c_void_p))
+        if rc:
+            raise ValueError("hs_paired_replay: %d (query %s)" % (rc, rec.tolist()))
+    return out
