@@ -520,6 +520,42 @@ MCQ_API int mcq_exact_batch_ext_runouts(mcq_ctx *ctx, const mcq_query *q, const 
                                         mcq_result_ways *cards /* [n][52] */,
                                         mcq_result_ways *pairs /* [n][MCQ_HAND_ROWS], may be NULL */);
 
+/* The exact hand-against-hand matrix of a board: every two-card hand against every other one, heads-up, from ONE enumeration
+ * per record -- the linear map whose weighted row sums mcq_exact_batch_hero_range_weighted returns.  The law is always
+ * MCQ_LAW_UNIFORM (no law argument: under the reference's law the weight of a completion depends on both hands, so a pair's
+ * total would not be a constant).  3 to 5 table cards; a batch may mix the streets.
+ * Definitions.  D = the 52 cards minus the table cards and the dead cards, L = |D|, k = 5 - n_board, total[i] = C(L - 4, k).
+ * For two-card hands h, g of D that share no card, with T running over the k-subsets of D minus h minus g:
+ *   win[i][MCQ_HAND_INDEX(h)][MCQ_HAND_INDEX(g)] = the number of T on which h ranks strictly above g,
+ *   tie[i][MCQ_HAND_INDEX(h)][MCQ_HAND_INDEX(g)] = the number of T on which they are level,
+ * so win[h][g] + win[g][h] + tie[h][g] == total and tie is symmetric.  Every other entry is written as 0: the diagonal, pairs
+ * that share a card, hands that hold a table or a dead card.  The ranking is the evaluator's, as in every other entry.
+ * Refused with MCQ_EINVAL, nothing launched, the outputs untouched for the whole batch: n_board outside 3..5 (preflop is
+ * C(48, 5) completions with 32-bit counts: not this entry), a card id >= 52, a table card twice, a table card that is also
+ * dead, reserved bytes or mask bits 52..63 not 0, L - 4 < k (no pair of hands leaves a completion), n == 0,
+ * n > MCQ_MATRIX_MAX_BATCH, win == NULL.  Deterministic: integer counts, every entry has one owner that stores it once; a
+ * batch gives what the single calls give, however the library cuts it into launches.  Each record costs
+ * MCQ_HAND_ROWS * MCQ_HAND_ROWS * 2 = 3.5 MB per matrix. */
+typedef struct mcq_matrix_query { /* 16 bytes */
+    uint8_t board[5];             /* n_board of them used, distinct card ids < 52; the others are not read */
+    uint8_t n_board;              /* 3, 4 or 5 */
+    uint8_t reserved[2];          /* 0 */
+    uint64_t dead;                /* bit c set: card c is out of the deck (bits 52..63 must be 0) */
+} mcq_matrix_query;
+#define MCQ_MATRIX_MAX_BATCH 256u
+MCQ_API int mcq_exact_matrix(mcq_ctx *ctx, const mcq_matrix_query *q, size_t n,
+                             uint16_t *win /* [n][MCQ_HAND_ROWS][MCQ_HAND_ROWS] */,
+                             uint16_t *tie /* [n][MCQ_HAND_ROWS][MCQ_HAND_ROWS], may be NULL */,
+                             uint32_t *total /* [n], may be NULL */);
+/* The same with the matrices written to DEVICE memory on hip_stream (NULL = the null stream).  The records are host memory
+ * and are validated on the host before anything is launched (unlike mcq_eval_batch_device, which cannot refuse a record);
+ * total is host memory and is filled before the call returns.  Asynchronous once the context's scratch for this stream is
+ * large enough (it grows on the first call of a size); not to be captured into a graph. */
+MCQ_API int mcq_exact_matrix_device(mcq_ctx *ctx, const mcq_matrix_query *q /* host */, size_t n,
+                                    void *d_win /* uint16 [n][MCQ_HAND_ROWS][MCQ_HAND_ROWS] */,
+                                    void *d_tie /* likewise, may be NULL */, uint32_t *total /* host [n], may be NULL */,
+                                    void *hip_stream);
+
 /* Select the dealing law used by MCQ_MODE_PHILOX on this context (MCQ_LAW_*).  Extended queries
  * (mcq_eval_batch_ext) are dealt by the reference's law only: under MCQ_LAW_UNIFORM that call gives MCQ_EINVAL.
  * mcq_eval_batch_ranges does not look at the switch: its law is uniform by definition. */

@@ -147,6 +147,10 @@ def load_library():
         L.mcq_exact_batch_hero_range_preflop_weighted.restype = C.c_int
         L.mcq_exact_batch_ext_runouts.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
         L.mcq_exact_batch_ext_runouts.restype = C.c_int
+        L.mcq_exact_matrix.argtypes = [vp, vp, sz, vp, vp, vp]
+        L.mcq_exact_matrix.restype = C.c_int
+        L.mcq_exact_matrix_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+        L.mcq_exact_matrix_device.restype = C.c_int
         L.mcq_set_dealing_law.argtypes = [vp, C.c_int]
         L.mcq_set_dealing_law.restype = C.c_int
         L.mcq_set_kernel_timing.argtypes = [vp, C.c_int]
@@ -278,6 +282,27 @@ HERO_PREFLOP_MAX_BATCH = 64   # MCQ_HERO_PREFLOP_MAX_BATCH
 COMBO_WEIGHT_MAX = 65535      # MCQ_COMBO_WEIGHT_MAX
 RUNOUT_CARD_ROWS = 52     # MCQ_RUNOUT_CARD_ROWS
 RUNOUT_MAX_BATCH = 1024   # MCQ_RUNOUT_MAX_BATCH
+MATRIX_MAX_BATCH = 256    # MCQ_MATRIX_MAX_BATCH
+# mcq_matrix_query: a board of 3 to 5 table cards and a mask of dead cards (bit c: card id c is out of the deck)
+MATRIX_QUERY_DTYPE = np.dtype([("board", "u1", (5,)), ("n_board", "u1"), ("reserved", "u1", (2,)), ("dead", "<u8")])
+assert MATRIX_QUERY_DTYPE.itemsize == 16
+
+
+def pack_matrix_query(board, dead=()):
+    """One MATRIX_QUERY_DTYPE record from card ids: `board` the 3 to 5 table cards, `dead` the cards out of the deck."""
+    board = [int(c) for c in board]
+    if not 0 <= len(board) <= 5 or any(not 0 <= c < 256 for c in board):
+        raise ValueError("a board is at most five card ids")
+    q = np.zeros(1, MATRIX_QUERY_DTYPE)
+    q["board"][0, :len(board)] = board
+    q["n_board"] = len(board)
+    mask = 0
+    for c in dead:
+        if not 0 <= int(c) < 64:
+            raise ValueError("a dead card is a card id")
+        mask |= 1 << int(c)
+    q["dead"] = mask
+    return q
 
 
 def hand_index(a, b):
@@ -637,6 +662,37 @@ class Engine:
         if rc:
             _raise(rc)
         return out
+
+    def exact_matrix(self, queries, want_tie=True):
+        """The exact hand-against-hand matrices of MATRIX_QUERY_DTYPE records (mcq_exact_matrix): heads-up, uniform law,
+        3 to 5 table cards.  -> (win, tie, total): win[i, hand_index(h), hand_index(g)] = the table completions on which
+        hand h beats hand g, tie likewise (None without want_tie), both uint16 [n, HAND_ROWS, HAND_ROWS] and zero where the
+        two hands cannot meet; total[i] = the completions of a pair of hands, win[h][g] + win[g][h] + tie[h][g]."""
+        q = np.ascontiguousarray(queries, dtype=MATRIX_QUERY_DTYPE).reshape(-1)
+        if not 1 <= len(q) <= MATRIX_MAX_BATCH:
+            raise ValueError("1 to MATRIX_MAX_BATCH = %d records per call" % MATRIX_MAX_BATCH)
+        win = np.zeros((len(q), HAND_ROWS, HAND_ROWS), np.uint16)
+        tie = np.zeros((len(q), HAND_ROWS, HAND_ROWS), np.uint16) if want_tie else None
+        total = np.zeros(len(q), np.uint32)
+        rc = self._lib.mcq_exact_matrix(self._ctx, q.ctypes.data, len(q), win.ctypes.data,
+                                        tie.ctypes.data if want_tie else None, total.ctypes.data)
+        if rc:
+            _raise(rc)
+        return win, tie, total
+
+    def exact_matrix_device(self, queries, d_win, d_tie, stream=0):
+        """exact_matrix with the matrices written to device memory (mcq_exact_matrix_device): d_win / d_tie are raw device
+        pointers (ints) to n x HAND_ROWS x HAND_ROWS uint16 each, d_tie 0 or None for win alone, stream a hipStream_t handle
+        (int) or 0.  The records are host memory and are validated before anything is launched.  Asynchronous.
+        -> total (uint32 [n])."""
+        q = np.ascontiguousarray(queries, dtype=MATRIX_QUERY_DTYPE).reshape(-1)
+        total = np.zeros(len(q), np.uint32)
+        rc = self._lib.mcq_exact_matrix_device(self._ctx, q.ctypes.data, len(q), int(d_win) if d_win else None,
+                                               int(d_tie) if d_tie else None, total.ctypes.data,
+                                               int(stream) if stream else None)
+        if rc:
+            _raise(rc)
+        return total
 
     def eval_batch_ext(self, queries, ext, seed, first_query_id=0, mode=MODE_PHILOX):
         """queries with one QUERY_EXT_DTYPE record each (ranges, hero range, ghost cards, second known hand)."""

@@ -119,6 +119,7 @@ struct mcq_ctx {
     uint32_t grid_cap = 0; /* sliced launches (mcq_eval_kernel, mcq_eval_ext_kernel) get at most this many blocks; 0: no cap (MCQ_GRID_CAP, tests) */
     uint32_t exact_cu = 0; /* the exact plans (mcq_exact_plan, mcq_exact_ext_plan) see at most this many CUs; 0: n_cu (MCQ_EXACT_CU, tests) */
     uint32_t hero_pre_slice = 0; /* mcq_exact_batch_hero_range_preflop: table completions per launch; 0: MCQ_XP_DEFAULT_SLICE (MCQ_HERO_PRE_SLICE, tests) */
+    uint32_t matrix_chunk = 16; /* mcq_exact_matrix: records per launch, 8.7 MB of scratch each on a flop (MCQ_MATRIX_CHUNK, tests) */
     uint32_t split_max = 4; /* finest cut of a task for small batches: 16 >> split_max iterations per lane */
     hipStream_t stream = nullptr;
     static constexpr int kRing = 64; /* event pairs around the most recent evaluation-kernel launches */

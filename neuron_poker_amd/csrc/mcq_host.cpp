@@ -21,6 +21,7 @@
 #include "mcq_exact_ext.hpp"
 #include "mcq_exact_hero.hpp"
 #include "mcq_exact_hero_pre.hpp"
+#include "mcq_exact_matrix.hpp"
 #include "mcq_exact_runout.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt_blocks.hpp"
@@ -578,6 +579,10 @@ mcq_ctx *mcq_create(int device, int flags) {
     if (const char *e = getenv("MCQ_HERO_PRE_SLICE")) { /* table completions per launch of the preflop hero-range enumeration (tests) */
         const long long v = atoll(e);
         if (v >= 1) c->hero_pre_slice = mcq_exact_hero_pre_slice((uint64_t)v);
+    }
+    if (const char *e = getenv("MCQ_MATRIX_CHUNK")) { /* records per launch of mcq_exact_matrix (tests): the output does not depend on it */
+        const long v = atol(e);
+        if (v >= 1) c->matrix_chunk = (uint32_t)(v > (long)MCQ_MATRIX_MAX_BATCH ? (long)MCQ_MATRIX_MAX_BATCH : v);
     }
     if (const char *e = getenv("MCQ_REPLAY_DEVICE_BYTES")) { /* chunking of the parity mode's draw buffer (tests) */
         const long long v = atoll(e);
@@ -1790,6 +1795,138 @@ int mcq_exact_batch_ext_runouts(mcq_ctx *c, const mcq_query *q, const mcq_query_
     if (pairs) memcpy(pairs, static_cast<const uint8_t *>(c->h_res.p) + card_bytes, pair_bytes);
     return MCQ_OK;
     ABI_GUARD_END("mcq_exact_batch_ext_runouts")
+}
+
+}  // extern "C"
+
+/* mcq_exact_matrix and mcq_exact_matrix_device (mcq_exact_matrix.hpp): one implementation.  The batch goes out in chunks of at
+ * most c->matrix_chunk records, three launches each on stream s; a record's scratch -- key table and counts by D-pair -- is
+ * one of the chunk's slots in the stream's scratch buffer, all slots sized for the largest record of the batch (the sizes
+ * change nothing in the output: every word a kernel reads was written for that record by the launch before).  d_win / d_tie:
+ * the caller's device matrices, or null: the host entry, whose chunks land in c->d_res and travel back through pinned memory. */
+static int exact_matrix_impl(mcq_ctx *c, const mcq_matrix_query *q, size_t n, uint16_t *h_win, uint16_t *h_tie, uint16_t *d_win,
+                             uint16_t *d_tie, uint32_t *total, hipStream_t user_stream, const char *who) {
+    const bool host = d_win == nullptr;
+    if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
+    if (n == 0) return mcq_fail(MCQ_EINVAL, who, "no record (n == 0)");
+    if (n > MCQ_MATRIX_MAX_BATCH) return mcq_fail(MCQ_EINVAL, who, "at most MCQ_MATRIX_MAX_BATCH records per call");
+    if (!q) return mcq_fail(MCQ_EINVAL, who, "null records");
+    if (host && !h_win) return mcq_fail(MCQ_EINVAL, who, "null win");
+    /* validation first: nothing is launched for a batch with one record that is refused */
+    std::vector<McqMatrixJob> jobs(n);
+    std::vector<uint32_t> tot(n);
+    uint32_t max_stride = 0, max_stages = 0;
+    for (size_t i = 0; i < n; i++) {
+        static const char *const reason[] = {
+            "",
+            "the matrix is enumerated on the flop, the turn and the river (n_board 3 to 5): preflop it is C(48, 5) completions "
+            "per pair with 32-bit counts",
+            "reserved bytes must be 0",
+            "bits 52..63 of the dead mask must be 0",
+            "a table card id is not below 52",
+            "a table card is given twice",
+            "a table card is also dead",
+            "too few cards left: no two hands leave a table completion (L - 4 < k)"};
+        McqMatrixQuery e;
+        const int why = mcq_matrix_query_build(q[i], e);
+        if (why != MCQ_XM_OK) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "record %zu: %s", i, reason[why]);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+        jobs[i].q = q[i];
+        jobs[i].stride = mcq_matrix_stride(e.n_rp);
+        jobs[i].stages = mcq_matrix_stages(e.n_boards);
+        tot[i] = e.total;
+        max_stride = jobs[i].stride > max_stride ? jobs[i].stride : max_stride;
+        max_stages = jobs[i].stages > max_stages ? jobs[i].stages : max_stages;
+    }
+    MCQ_ENTER(c, who);
+    McqDeviceScope dev_(c->device);
+    HIP_TRY(dev_.err);
+    hipStream_t s = host ? c->stream : user_stream;
+    if (!host && stream_capturing(s)) return mcq_fail(MCQ_EINVAL, who, "the stream is being captured: this entry is not captured into a graph");
+    uint32_t chunk = c->matrix_chunk < MCQ_XM_MAX_CHUNK ? c->matrix_chunk : MCQ_XM_MAX_CHUNK;
+    chunk = chunk < 1u ? 1u : chunk > n ? (uint32_t)n : chunk;
+    const size_t key_words = (size_t)max_stages * MCQ_XM_STAGE * max_stride, cnt_words = (size_t)max_stride * max_stride;
+    const size_t key_bytes = chunk * key_words * sizeof(uint32_t), mat = (size_t)MCQ_XH_ROWS * MCQ_XH_ROWS, mat_bytes = mat * sizeof(uint16_t);
+    mcq_ctx::Scratch *sc = nullptr;
+    const int rc = scratch_for(c, s, key_bytes + chunk * cnt_words * sizeof(uint16_t), false, &sc);
+    if (rc) return rc;
+    uint32_t *d_keys = static_cast<uint32_t *>(sc->prefix.p);
+    uint16_t *d_cnt = reinterpret_cast<uint16_t *>(static_cast<uint8_t *>(sc->prefix.p) + key_bytes);
+    const size_t mats = h_tie || d_tie ? 2u : 1u;
+    if (host) {
+        HIP_TRY(c->d_res.reserve(chunk * mats * mat_bytes));
+        c->res_clean = 0;
+        HIP_TRY(c->h_res.reserve(chunk * mats * mat_bytes));
+        d_win = static_cast<uint16_t *>(c->d_res.p);
+        d_tie = h_tie ? d_win + chunk * mat : nullptr;
+    }
+    if (total) memcpy(total, tot.data(), n * sizeof(uint32_t));
+    const bool timed = c->timing;
+    const uint64_t timed0 = c->n_timed;
+    c->last_ms = 0.f;
+    for (size_t a = 0; a < n; a += chunk) {
+        const uint32_t m = (uint32_t)(n - a < chunk ? n - a : chunk);
+        uint32_t stride = 0, stages = 0;
+        for (uint32_t i = 0; i < m; i++) {
+            jobs[a + i].slot = i;
+            jobs[a + i].out = host ? i : (uint32_t)(a + i);
+            stride = jobs[a + i].stride > stride ? jobs[a + i].stride : stride;
+            stages = jobs[a + i].stages > stages ? jobs[a + i].stages : stages;
+        }
+        /* the grids by the CUs the plans may see, shared among the chunk's records: one block walks everything under MCQ_EXACT_CU=1 */
+        const uint32_t cu = exact_cu(c), per = cu / m < 1u ? 1u : cu / m, rows = stages * MCQ_XM_STAGE;
+        const uint32_t rank_grid = per < rows ? per : rows, finish_grid = 4u * per < MCQ_XH_ROWS ? 4u * per : MCQ_XH_ROWS;
+        hipEvent_t ev[6];
+        for (int k = 0; k < 3; k++) {
+            const int slot = (int)((c->n_timed + (uint64_t)k) % mcq_ctx::kRing);
+            ev[2 * k] = c->ev0[slot];
+            ev[2 * k + 1] = c->ev1[slot];
+        }
+        HIP_TRY(mcq_launch_exact_matrix(&jobs[a], m, rank_grid, finish_grid, stride, d_keys, key_words, d_cnt, cnt_words, d_win, d_tie,
+                                        c->d_luts, s, timed ? ev : nullptr));
+        if (timed) c->n_timed += 3u;
+        if (host) {
+            uint8_t *back = static_cast<uint8_t *>(c->h_res.p);
+            HIP_TRY(hipMemcpyAsync(back, d_win, m * mat_bytes, hipMemcpyDeviceToHost, s));
+            if (h_tie) HIP_TRY(hipMemcpyAsync(back + chunk * mat_bytes, d_tie, m * mat_bytes, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            memcpy(h_win + a * mat, back, m * mat_bytes);
+            if (h_tie) memcpy(h_tie + a * mat, back + chunk * mat_bytes, m * mat_bytes);
+        }
+    }
+    /* a caller's stream may run on while another stream's call takes over the scratch: mark its last reader */
+    if (sc != &c->scratch[0]) {
+        HIP_TRY(hipEventRecord(sc->done, s));
+        sc->done_recorded = true;
+    }
+    if (host && timed) { /* the kernels of this call, as far as the ring of events still holds them */
+        float ms[mcq_ctx::kRing];
+        const uint64_t launched = c->n_timed - timed0;
+        const int want = (int)(launched < (uint64_t)mcq_ctx::kRing ? launched : (uint64_t)mcq_ctx::kRing);
+        const int got = kernel_times_impl(c, ms, want);
+        for (int k = 0; k < got; k++) c->last_ms += ms[k];
+    }
+    return MCQ_OK;
+}
+
+extern "C" {
+
+int mcq_exact_matrix(mcq_ctx *c, const mcq_matrix_query *q, size_t n, uint16_t *win, uint16_t *tie, uint32_t *total) {
+    ABI_GUARD_BEGIN
+    return exact_matrix_impl(c, q, n, win, tie, nullptr, nullptr, total, nullptr, "mcq_exact_matrix");
+    ABI_GUARD_END("mcq_exact_matrix")
+}
+
+int mcq_exact_matrix_device(mcq_ctx *c, const mcq_matrix_query *q, size_t n, void *d_win, void *d_tie, uint32_t *total,
+                            void *hip_stream) {
+    ABI_GUARD_BEGIN
+    if (!d_win) return mcq_fail(MCQ_EINVAL, "mcq_exact_matrix_device", "null win");
+    return exact_matrix_impl(c, q, n, nullptr, nullptr, static_cast<uint16_t *>(d_win), static_cast<uint16_t *>(d_tie), total,
+                             (hipStream_t)hip_stream, "mcq_exact_matrix_device");
+    ABI_GUARD_END("mcq_exact_matrix_device")
 }
 
 }  // extern "C"

@@ -54,6 +54,24 @@ uint32_t mcq_exact_hero_plan(bool preflop, const mcq_query *q, uint32_t ext, uin
 hipError_t mcq_launch_exact_hero(bool preflop, bool weighted, const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid,
                                  const uint32_t *d_ext, int law, const uint16_t *d_wts, bool hero_w, uint32_t lo, uint32_t hi,
                                  mcq_result *d_rows, const McqTables *d_luts, hipStream_t s);
+/* the hand-against-hand matrix (mcq_exact_matrix.hpp): one job per record, validated by the host, at most MCQ_XM_MAX_CHUNK
+ * of them per call: they travel in the kernel arguments (512 B), so a call leaves nothing behind that a later call on
+ * another stream could overwrite.  Three launches.  A job's
+ * scratch is slot `slot` of d_keys (key_words 32-bit words per slot: at least stages * MCQ_XM_STAGE rows of `stride` words)
+ * and of d_cnt (cnt_words 16-bit words per slot: at least stride * stride); its matrices are number `out` of d_win / d_tie
+ * ([MCQ_HAND_ROWS][MCQ_HAND_ROWS] uint16 each; d_tie may be null).  rank_grid blocks rank a job's completions and
+ * finish_grid blocks write its rows; ev (or null): six events, a pair of timestamps per kernel in launch order. */
+struct McqMatrixJob {
+    mcq_matrix_query q;                   /* the 16-byte record */
+    uint32_t out, slot, stride, stages;   /* mcq_matrix_stride, mcq_matrix_stages of the record */
+};
+#define MCQ_XM_MAX_CHUNK 16u
+struct McqMatrixJobs {
+    McqMatrixJob job[MCQ_XM_MAX_CHUNK];
+};
+hipError_t mcq_launch_exact_matrix(const McqMatrixJob *jobs /* host */, uint32_t n_jobs, uint32_t rank_grid, uint32_t finish_grid,
+                                   uint32_t max_stride, uint32_t *d_keys, size_t key_words, uint16_t *d_cnt, size_t cnt_words,
+                                   uint16_t *d_win, uint16_t *d_tie, const McqTables *d_luts, hipStream_t s, hipEvent_t *ev);
 /* per-runout enumeration (mcq_exact_runout.hpp): flop and turn records with at most one random opponent, jobs planned by
  * mcq_exact_ext_plan (kind 0 or 1, job->row = the record's index); d_cards holds 52 and d_pairs MCQ_HAND_ROWS zeroed
  * mcq_result_ways rows per record.  The second launch takes the jobs of both kinds and fills the card rows of the flop

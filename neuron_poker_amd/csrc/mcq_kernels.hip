@@ -23,6 +23,7 @@
 #include "mcq_exact_ext.hpp"
 #include "mcq_exact_hero.hpp"
 #include "mcq_exact_hero_pre.hpp"
+#include "mcq_exact_matrix.hpp"
 #include "mcq_exact_runout.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt.hpp"
@@ -3282,4 +3283,179 @@ hipError_t mcq_eval_occupancy(int mode, int block, int *blocks_per_cu) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, mcq_eval_kernel<MCQ_INTERNAL_MODE_UNIFORM, false, false>,
                                                             block, 0);
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, mcq_eval_kernel<MCQ_MODE_REPLAY_MT19937, false, false>, block, 0);
+}
+
+// ---------------------------------------------------------------------------------------------- exact enumeration, the matrix
+// mcq_exact_matrix (mcq_exact_matrix.hpp): three kernels per launch group, one job per record (blockIdx.y);
+// the jobs of a group travel in the kernel arguments.
+namespace {
+
+// (a) Ranking.  A block of 1024 threads per table completion at a time (blockIdx.x, then + gridDim.x): the word of every
+// D-pair on it -- 0 = dead, else key + 1 -- into row `board` of the record's key table, `stride` words a row.  The padding
+// (D-pairs from n_rp to stride, rows from n_boards to stages * MCQ_XM_STAGE) is written as dead, so the count kernel reads
+// whole tiles and whole stages and tests no bound.  LDS: 97 KB of tables, one block of 16 waves per CU.
+__global__ __launch_bounds__(1024) void mcq_exact_matrix_rank_kernel(const McqMatrixJobs jobs, uint32_t *__restrict__ keys,
+                                                                      size_t key_words, const McqTables *__restrict__ g_tab) {
+    const McqMatrixJob &job = jobs.job[blockIdx.y]; /* (the kernel arguments: scalar loads) */
+    const uint32_t rows = job.stages * MCQ_XM_STAGE, stride = job.stride, tid = threadIdx.x;
+    if (blockIdx.x >= rows) return;
+    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ uint16_t pair_xy[MCQ_XH_MAX_HANDS];
+    __shared__ McqMatrixQuery xq;
+    __shared__ uint8_t r_id[64];
+    for (uint32_t i = tid; i < MCQ_XH_MAX_HANDS; i += blockDim.x) {
+        uint32_t x, y;
+        mcq_exact_pair_xy(i, x, y);
+        pair_xy[i] = (uint16_t)(x | (y << 8));
+    }
+    load_tables(tab, g_tab); /* ends with a barrier */
+    if (tid == 0) {
+        (void)mcq_matrix_query_build(job.q, xq); /* the host has validated it */
+        mcq_matrix_r_ids(xq, r_id);
+    }
+    __syncthreads();
+    const McqMatrixQuery &e = xq;
+    uint32_t *dst = keys + (size_t)job.slot * key_words;
+    for (uint32_t board = blockIdx.x; board < rows; board += gridDim.x) {
+        uint32_t *row = dst + (size_t)board * stride;
+        if (board >= e.n_boards) {
+            for (uint32_t rp = tid; rp < stride; rp += blockDim.x) row[rp] = 0u;
+            continue;
+        }
+        uint32_t pos[5];
+        mcq_exact_unrank(board, e.b.L, e.b.k, pos);
+        McqExactBoard bd;
+        mcq_exact_hero_board(e.b, pos, r_id, bd);
+        for (uint32_t rp = tid; rp < stride; rp += blockDim.x)
+            row[rp] = rp < e.n_rp ? mcq_matrix_rank(bd, pos, r_id, pair_xy[rp], g_tab->tf, tab.tops, tab.sd) : 0u;
+    }
+}
+
+// (b) Counting.  A block of 256 threads owns a tile of MCQ_XM_TILE x MCQ_XM_TILE D-pairs (row tile blockIdx.x / tiles, column
+// tile blockIdx.x % tiles) and walks every completion; thread (ty, tx) of 16 x 16 holds the TH x TG = 4 x 4 counters of row
+// hands ty * 4 .. + 3 and column hands tx * 4 .. + 3 in registers for the whole loop and stores them once, as uint16.
+// The words travel global -> registers -> LDS in stages of MCQ_XM_STAGE completions, two LDS buffers: while a stage is
+// counted the next one's two 16-byte loads per thread are in flight, they are written to the other buffer behind the
+// counting, one barrier per stage.  A stage in LDS is [completion][64 row words | 64 column words], the column words with
+// the dead mark already turned (mcq_matrix_col): per completion a thread reads its 4 row words and its 4 column words with
+// one 16-byte LDS read each -- within a wave the row reads are 4 addresses (broadcast) and the column reads 16 consecutive
+// 16-byte slots, one bank row -- and does 16 compare-and-adds.
+// The tile: a flop has 19 x 19 = 361 tiles of 4 waves, 1444 waves on 1024 SIMDs; 16 counters a thread keep the kernel small
+// enough in registers for every wave of a CU's share to be resident at once.  LDS: 16 KB.
+constexpr uint32_t kMatrixCountBlock = (MCQ_XM_TILE / MCQ_XM_TH) * (MCQ_XM_TILE / MCQ_XM_TG);
+constexpr uint32_t kMatrixStageVecs = MCQ_XM_STAGE * 2u * MCQ_XM_TILE / 4u / kMatrixCountBlock; /* 16-byte loads per thread and stage */
+static_assert(MCQ_XM_TH == 4u && MCQ_XM_TG == 4u && kMatrixCountBlock == 256u, "a thread's row and column words are one uint4 each");
+static_assert(kMatrixStageVecs * kMatrixCountBlock * 4u == MCQ_XM_STAGE * 2u * MCQ_XM_TILE && kMatrixCountBlock % (2u * MCQ_XM_TILE / 4u) == 0u,
+              "a stage is whole loads, and a thread's loads of a stage lie in the same part of their rows");
+
+__global__ __launch_bounds__(kMatrixCountBlock) void mcq_exact_matrix_count_kernel(const McqMatrixJobs jobs,
+                                                                                  const uint32_t *__restrict__ keys, size_t key_words,
+                                                                                  uint16_t *__restrict__ cnt, size_t cnt_words) {
+    const McqMatrixJob &job = jobs.job[blockIdx.y]; /* (the kernel arguments: scalar loads) */
+    const uint32_t stride = job.stride, tiles = stride / MCQ_XM_TILE, stages = job.stages;
+    if (blockIdx.x >= tiles * tiles) return;
+    __shared__ __attribute__((aligned(16))) uint32_t buf[2][MCQ_XM_STAGE][2u * MCQ_XM_TILE];
+    const uint32_t tid = threadIdx.x, tx = tid % (MCQ_XM_TILE / MCQ_XM_TG), ty = tid / (MCQ_XM_TILE / MCQ_XM_TG);
+    const uint32_t row0 = blockIdx.x / tiles * MCQ_XM_TILE, col0 = blockIdx.x % tiles * MCQ_XM_TILE;
+    /* staging: load v of a stage covers completion (tid + v * 256) / 32 of it, part tid % 32 of its 32 16-byte pieces: the
+     * first 16 are the tile's row words, the others its column words */
+    constexpr uint32_t kParts = 2u * MCQ_XM_TILE / 4u;
+    const uint32_t part = tid % kParts, comp0 = tid / kParts;
+    const bool is_col = part >= kParts / 2u;
+    const uint32_t *src = keys + (size_t)job.slot * key_words + (is_col ? col0 + (part - kParts / 2u) * 4u : row0 + part * 4u);
+    uint4 v[kMatrixStageVecs];
+    auto fetch = [&](uint32_t stage) {
+#pragma unroll
+        for (uint32_t i = 0; i < kMatrixStageVecs; i++) {
+            const uint32_t comp = stage * MCQ_XM_STAGE + comp0 + i * (kMatrixCountBlock / kParts);
+            v[i] = *reinterpret_cast<const uint4 *>(src + (size_t)comp * stride);
+        }
+    };
+    auto put = [&](uint32_t b) {
+#pragma unroll
+        for (uint32_t i = 0; i < kMatrixStageVecs; i++) {
+            uint4 w = v[i];
+            if (is_col) w = make_uint4(mcq_matrix_col(w.x), mcq_matrix_col(w.y), mcq_matrix_col(w.z), mcq_matrix_col(w.w));
+            *reinterpret_cast<uint4 *>(&buf[b][comp0 + i * (kMatrixCountBlock / kParts)][part * 4u]) = w;
+        }
+    };
+    uint32_t acc[MCQ_XM_TH][MCQ_XM_TG];
+#pragma unroll
+    for (uint32_t a = 0; a < MCQ_XM_TH; a++)
+#pragma unroll
+        for (uint32_t b = 0; b < MCQ_XM_TG; b++) acc[a][b] = 0u;
+    fetch(0u);
+    put(0u);
+    __syncthreads();
+    for (uint32_t s = 0; s < stages; s++) {
+        const bool more = s + 1u < stages; /* block-uniform */
+        if (more) fetch(s + 1u);
+        const uint32_t(*cur)[2u * MCQ_XM_TILE] = buf[s & 1u];
+#pragma unroll
+        for (uint32_t c = 0; c < MCQ_XM_STAGE; c++) {
+            const uint4 rv = *reinterpret_cast<const uint4 *>(&cur[c][ty * MCQ_XM_TH]);
+            const uint4 cv = *reinterpret_cast<const uint4 *>(&cur[c][MCQ_XM_TILE + tx * MCQ_XM_TG]);
+            const uint32_t row[MCQ_XM_TH] = {rv.x, rv.y, rv.z, rv.w}, col[MCQ_XM_TG] = {cv.x, cv.y, cv.z, cv.w};
+            mcq_matrix_count<MCQ_XM_TH, MCQ_XM_TG>(acc, row, col);
+        }
+        if (more) put((s + 1u) & 1u); /* the buffer stage s - 1 was counted from: every thread has passed the barrier behind it */
+        __syncthreads();
+    }
+    uint16_t *dst = cnt + (size_t)job.slot * cnt_words + (size_t)(row0 + ty * MCQ_XM_TH) * stride + col0 + tx * MCQ_XM_TG;
+#pragma unroll
+    for (uint32_t a = 0; a < MCQ_XM_TH; a++) /* (padding rows and columns lie inside the slot: no edge test) */
+        *reinterpret_cast<uint2 *>(dst + (size_t)a * stride) = make_uint2(acc[a][0] | (acc[a][1] << 16), acc[a][2] | (acc[a][3] << 16));
+}
+
+// (c) Finish: rows blockIdx.x, + gridDim.x, ... of the record's [1326][1326] matrices from its counts by D-pair
+// (mcq_matrix_entry) -- every entry is written, the zeros too; tie == null: win alone.
+__global__ __launch_bounds__(256) void mcq_exact_matrix_finish_kernel(const McqMatrixJobs jobs, const uint16_t *__restrict__ cnt,
+                                                                      size_t cnt_words, uint16_t *__restrict__ win,
+                                                                      uint16_t *__restrict__ tie) {
+    const McqMatrixJob &job = jobs.job[blockIdx.y]; /* (the kernel arguments: scalar loads) */
+    __shared__ McqMatrixQuery xq;
+    __shared__ uint8_t r_id[64], pos_of[52];
+    __shared__ uint16_t cards[MCQ_XH_ROWS], dpair[MCQ_XH_ROWS];
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        (void)mcq_matrix_query_build(job.q, xq);
+        mcq_matrix_r_ids(xq, r_id);
+        mcq_matrix_pos_of(xq, r_id, pos_of);
+    }
+    __syncthreads();
+    mcq_matrix_hands(pos_of, tid, blockDim.x, cards, dpair);
+    __syncthreads();
+    const uint16_t *src = cnt + (size_t)job.slot * cnt_words;
+    const size_t base = (size_t)job.out * MCQ_XH_ROWS * MCQ_XH_ROWS;
+    for (uint32_t r = blockIdx.x; r < MCQ_XH_ROWS; r += gridDim.x)
+        for (uint32_t c = tid; c < MCQ_XH_ROWS; c += blockDim.x) {
+            uint32_t w, t;
+            mcq_matrix_entry(xq, src, job.stride, cards, dpair, r, c, w, t);
+            const size_t at = base + (size_t)r * MCQ_XH_ROWS + c;
+            win[at] = (uint16_t)w;
+            if (tie) tie[at] = (uint16_t)t;
+        }
+}
+
+}  // namespace
+
+hipError_t mcq_launch_exact_matrix(const McqMatrixJob *jobs, uint32_t n_jobs, uint32_t rank_grid, uint32_t finish_grid,
+                                   uint32_t max_stride, uint32_t *d_keys, size_t key_words, uint16_t *d_cnt, size_t cnt_words,
+                                   uint16_t *d_win, uint16_t *d_tie, const McqTables *d_luts, hipStream_t s, hipEvent_t *ev) {
+    if (n_jobs == 0) return hipSuccess;
+    const uint32_t tiles = max_stride / MCQ_XM_TILE;
+    if (n_jobs > MCQ_XM_MAX_CHUNK || rank_grid == 0 || finish_grid == 0 || tiles == 0 || max_stride % MCQ_XM_TILE != 0u ||
+        max_stride > MCQ_XM_MAX_STRIDE || cnt_words < (size_t)max_stride * max_stride || !d_win)
+        return hipErrorInvalidValue;
+    McqMatrixJobs d_jobs;
+    __builtin_memset(&d_jobs, 0, sizeof d_jobs);
+    __builtin_memcpy(d_jobs.job, jobs, n_jobs * sizeof(McqMatrixJob));
+    hipEvent_t t0 = ev ? ev[0] : nullptr, t1 = ev ? ev[1] : nullptr;
+    MCQ_LAUNCH_TIMED(mcq_exact_matrix_rank_kernel, dim3(rank_grid, n_jobs), 1024, d_jobs, d_keys, key_words, d_luts);
+    t0 = ev ? ev[2] : nullptr, t1 = ev ? ev[3] : nullptr;
+    MCQ_LAUNCH_TIMED(mcq_exact_matrix_count_kernel, dim3(tiles * tiles, n_jobs), kMatrixCountBlock, d_jobs, d_keys, key_words, d_cnt,
+                     cnt_words);
+    t0 = ev ? ev[4] : nullptr, t1 = ev ? ev[5] : nullptr;
+    MCQ_LAUNCH_TIMED(mcq_exact_matrix_finish_kernel, dim3(finish_grid, n_jobs), 256, d_jobs, d_cnt, cnt_words, d_win, d_tie);
+    return hipGetLastError();
 }

@@ -35,7 +35,7 @@ from . import _lib
 from .cards import TYPES, card_id, card_str
 
 __all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_range_equity_exact_weighted", "get_range_equities", "quantise_weight", "get_preflop_range_equity_exact", "get_preflop_range_equity_exact_weighted", "preflop_class_table", "get_runout_equities", "MonteCarlo", "seed",
-           "configure"]
+           "configure", "get_equity_matrix", "matrix_equity"]
 
 _state = {"couple_numpy": False,
           "mode": _lib.MODE_REPLAY_MT19937 if os.environ.get("MCQ_MODE", "philox").lower() == "replay"
@@ -653,6 +653,35 @@ def get_range_equity_exact_weighted(hero, table_cards, opponent, ghost_cards='',
     eng = engine or _lib.default_engine()
     rows, _ = eng.exact_hero_range_weighted(q, ext, opp_w, hero_w)
     return _weighted_rows_to_hands(rows[0], hero_w, ties)
+
+
+def get_equity_matrix(table_cards, dead_cards='', engine=None):
+    """The exact hand-against-hand matrix of a board with 3, 4 or 5 table cards (mcq_exact_matrix; heads-up, the uniform
+    law): the table that the weighted range entries fold away.  table_cards and dead_cards are lists of card strings;
+    dead_cards (any number, '' or None: none) leave the deck like ghost cards.
+    -> (win, tie, total): uint16 arrays [1326, 1326] indexed by hand_index(card id, card id) on both axes -- win[h, g] = the
+    table completions on which hand h beats hand g, tie[h, g] = those on which they are level -- and the completions of a
+    pair of hands, total = win[h, g] + win[g, h] + tie[h, g] wherever h and g can both be dealt (they share no card and hold
+    no table or dead card); every other entry is 0.  matrix_equity turns them into equities.  Preflop raises ValueError."""
+    board = [card_id(c) for c in table_cards]
+    if len(board) > 5:
+        raise ValueError("table_cards holds more than five cards")
+    dead = [card_id(c) for c in (dead_cards or [])]
+    eng = engine or _lib.default_engine()
+    win, tie, total = eng.exact_matrix(_lib.pack_matrix_query(board, dead))
+    return win[0], tie[0], int(total[0])
+
+
+def matrix_equity(win, tie, total, ties="split"):
+    """get_equity_matrix's counts as a float64 matrix of the row hand's equity against the column hand: ties="split" the
+    heads-up pot share (win + tie / 2) / total, ties="credited" (win + tie) / total as the reference credits a tie; NaN where
+    the two hands cannot both be dealt."""
+    if ties not in ("credited", "split"):
+        raise ValueError("ties must be 'credited' or 'split'")
+    w, t = np.asarray(win, np.float64), np.asarray(tie, np.float64)
+    dealt = (w + w.T + t) == float(total)
+    eq = (w + (t / 2.0 if ties == "split" else t)) / float(total)
+    return np.where(dealt, eq, np.nan)
 
 
 def _weighted_rows_to_hands(r, hero_w, ties):

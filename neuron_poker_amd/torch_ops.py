@@ -15,6 +15,7 @@ the numbers equal Engine.eval_batch / get_equity_batch on the same inputs, bit f
 ties="split": equity is hero's expected share of the pot (a tie among k hands counts 1/k), tallies int64 [B,22] with
 nine more columns tie_ways[k - 2], k = 2..10 (mcq_result_ways) -- both computed on the device.
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -71,3 +72,35 @@ def get_equity_batch_torch(hole, board, n_players, runs, seed=0, first_query_id=
     q.record_stream(torch.cuda.current_stream(q.device))
     equity = (out[:, 2] + out[:, 3]).to(torch.float64) / out[:, 0].clamp(min=1).to(torch.float64)
     return equity, out
+
+
+def get_equity_matrix_torch(boards, dead=None, engine=None, want_tie=True):
+    """The exact hand-against-hand matrices of a batch of boards as device tensors (mcq_exact_matrix_device; heads-up, the
+    uniform law, 3 to 5 table cards per board).
+
+    boards [n,5] uint8 card ids, 255 = empty slot (any position); dead (optional) [n] int64 masks, bit c = card id c is out
+    of the deck.  The records are 16 bytes each and are validated on the host -- they are read back from the device if they
+    live there --; the matrices never leave it: the kernels write them on the current stream of the boards' device (the
+    current device for host tensors) and nothing waits for them.
+    -> (win, tie, total): win, tie int16 [n,1326,1326] on the device, indexed by hand_index on both axes (tie None without
+    want_tie), total int64 [n] on the host: win[i,h,g] + win[i,g,h] + tie[i,h,g] wherever h and g can both be dealt."""
+    index = boards.device.index if boards.is_cuda and boards.device.index is not None else torch.cuda.current_device()
+    device = torch.device("cuda", index)
+    b = boards.detach().to("cpu", torch.uint8).reshape(-1, 5).numpy()
+    n = b.shape[0]
+    q = np.zeros(n, _lib.MATRIX_QUERY_DTYPE)
+    for i in range(n):                                   # the table cards left-packed
+        cards = b[i][b[i] != 255]
+        q["board"][i, :len(cards)] = cards
+        q["n_board"][i] = len(cards)
+    if dead is not None:
+        d = dead.detach().to("cpu", torch.int64).reshape(-1).numpy()
+        if d.shape[0] != n:
+            raise ValueError("one dead mask per board")
+        q["dead"] = d.astype(np.uint64)
+    eng = engine or _engine(index)
+    win = torch.empty((n, _lib.HAND_ROWS, _lib.HAND_ROWS), dtype=torch.int16, device=device)
+    tie = torch.empty_like(win) if want_tie else None
+    total = eng.exact_matrix_device(q, win.data_ptr(), tie.data_ptr() if want_tie else 0,
+                                    stream=torch.cuda.current_stream(device).cuda_stream)
+    return win, tie, torch.from_numpy(total.astype(np.int64))
