@@ -1,58 +1,22 @@
 """The weighted-range-per-seat Monte-Carlo entry on the host: the lane code of mcq_ranges.hpp (tests/hostsim_ranges)
 against literal Python enumerations of its law,  P(h_0, .., h_{p-1}) ~ prod_s eff_s(h_s) * [pairwise disjoint],  then the
 missing table cards uniformly.  Fixed seeds, 5.5 sigma (tests/lawstats.py): a failure is a finding about the law."""
-import itertools
 from collections import Counter
 
 import numpy as np
 import pytest
 
 from neuron_poker_amd import _lib
-from oracle import oracle as O
 from tests import hostsim_ranges as H
 from tests import lawstats as LS
 from tests import seats_expect as SE
+from tests.ranges_law import cid, hand, hidx, joint_law, literal_rows, table
 
 UNIT = 2520
 
 
-def cid(s):
-    return 4 * "23456789TJQKA".index(s[0]) + "CDHS".index(s[1])
-
-
-def hand(s):
-    """'AsKh' style is not used here: 'ASKH' -> (a, b), a < b."""
-    a, b = cid(s[:2]), cid(s[2:])
-    return (min(a, b), max(a, b))
-
-
-def hidx(h):
-    return h[1] * (h[1] - 1) // 2 + h[0]
-
-
-def table(support):
-    """{hand string: weight} -> uint16 [1326]"""
-    t = np.zeros(1326, np.uint16)
-    for s, w in support.items():
-        t[hidx(hand(s))] = w
-    return t
-
-
 def query(board, p, runs):
     return _lib.pack_query_one([0, 0], [cid(c) for c in board], p, runs)
-
-
-def joint_law(supports, board):
-    """The specification, literally: {(h_0, .., h_{p-1}): probability} over the deals of positive weight."""
-    B = {cid(c) for c in board}
-    eff = [[(hand(s), w) for s, w in sup.items() if w and not (set(hand(s)) & B)] for sup in supports]
-    law = {}
-    for combo in itertools.product(*eff):
-        cards = [c for h, _ in combo for c in h]
-        if len(set(cards)) == len(cards):
-            law[tuple(h for h, _ in combo)] = float(np.prod([w for _, w in combo]))
-    z = sum(law.values())
-    return {k: v / z for k, v in law.items()}
 
 
 def dealt(hands, p):
@@ -106,37 +70,6 @@ def test_whole_trial_rejection_not_sequential_redraw():
     k = sum(v for key, v in seen.items() if key[0] == hand("ASAH"))
     LS.check("P(seat 0 holds ASAH)", [("joint", k / n, p_joint, z_of(k, n, p_joint))])
     LS.check("every outcome", [(key, seen.get(key, 0) / n, pr, z_of(seen.get(key, 0), n, pr)) for key, pr in law.items()])
-
-
-def literal_rows(supports, board):
-    """Per seat (P(win), P(tie), E[share / UNIT], Var[share / UNIT] per iteration) from the literal enumeration of the joint
-    law and of every completion of the table, scored with the oracle's scorer."""
-    p = len(supports)
-    B = [cid(c) for c in board]
-    law = joint_law(supports, board)
-    keys, seven, wts = list(law), [], []
-    for k in keys:
-        used = set(B) | {c for h in k for c in h}
-        rest = [c for c in range(52) if c not in used]
-        comps = list(itertools.combinations(rest, 5 - len(B)))
-        for comp in comps:
-            for h in k:
-                seven.append(list(h) + B + list(comp))
-            wts.append(law[k] / len(comps))
-    sc = O.score_batch(np.array(seven, np.uint8), 4).reshape(-1, p)
-    wts = np.array(wts)
-    best = sc.max(1, keepdims=True)
-    level = sc == best
-    kk = level.sum(1, keepdims=True)
-    win = (level & (kk == 1)).astype(float)
-    tie = (level & (kk > 1)).astype(float)
-    share = level / kk
-    out = []
-    for s in range(p):
-        m = float((wts * share[:, s]).sum())
-        out.append((float((wts * win[:, s]).sum()), float((wts * tie[:, s]).sum()), m,
-                    float((wts * share[:, s] ** 2).sum()) - m * m))
-    return out
 
 
 @pytest.mark.parametrize("board", [RIVER, RIVER[:4]], ids=["river", "turn"])
