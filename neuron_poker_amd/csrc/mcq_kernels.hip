@@ -18,6 +18,7 @@
 
 #include <type_traits>
 
+#include "mcq_axis.hpp"
 #include "mcq_device.hpp"
 #include "mcq_exact.hpp"
 #include "mcq_exact_ext.hpp"
@@ -145,9 +146,42 @@ __device__ __forceinline__ uint64_t block_exclusive_scan_1024(uint64_t v, uint64
 }
 
 // ---------------------------------------------------------------------------------------------- prep
-// One block.  Validates every query, zeroes its result row and builds the exclusive prefix of the queries'
-// scheduling cost (tasks x weight; prefix[n] = total).  Invalid queries cost nothing and get runs = 0,
-// passes = UINT64_MAX.
+// The preparation of a batch on the extended and the ranges path, one block of 1024 threads: price(i) says whether record
+// i is valid, what it costs on the cost axis (mcq_axis.hpp; nothing when it is invalid) and the `runs` its row starts with.
+// Writes the rows -- runs, passes = 0 (UINT64_MAX marks an invalid record), zeros behind them -- and the exclusive
+// prefix of the costs, 1024 records at a time with the running total carried over; prefix[n] = the total.
+struct McqPrepRecord {
+    bool ok;
+    uint64_t cost, runs;
+};
+template <uint32_t ROW_WORDS, class Price>
+__device__ __forceinline__ void mcq_prep_rows(uint32_t n, mcq_result *__restrict__ res, uint64_t *__restrict__ prefix, Price price) {
+    __shared__ uint64_t wave_tot[16];
+    uint64_t carry = 0; /* every thread keeps the running total */
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t base = 0; base < n; base += 1024) {
+        uint32_t i = base + tid;
+        uint64_t cost = 0;
+        if (i < n) {
+            const McqPrepRecord rec = price(i);
+            cost = rec.ok ? rec.cost : 0ull;
+            uint64_t *r = reinterpret_cast<uint64_t *>(res) + (size_t)i * ROW_WORDS;
+            r[0] = rec.ok ? rec.runs : 0ull;
+            r[1] = rec.ok ? 0ull : ~0ull;
+#pragma unroll
+            for (int k = 2; k < (int)ROW_WORDS; k++) r[k] = 0;
+        }
+        uint64_t chunk_total;
+        const uint64_t before = block_exclusive_scan_1024(cost, wave_tot, &chunk_total);
+        if (i < n) prefix[i] = carry + before;
+        carry += chunk_total;
+    }
+    if (tid == 0) prefix[n] = carry;
+}
+
+// The plain path's preparation, one block: the same rows, markers and prefix (its own chunk loop), and what only this
+// path has -- the share of a query that belongs to this launch, the invalid marker from ONE share only, and the task sums
+// that pick the small batches' cut.
 // ROW_WORDS: 64-bit words of a result row, 13 (mcq_result) or 22 (mcq_result_ways).
 template <uint32_t ROW_WORDS>
 __global__ __launch_bounds__(1024) void mcq_prep_kernel(const mcq_query *__restrict__ q, uint32_t n,
@@ -746,6 +780,26 @@ __global__ __launch_bounds__(256) void mcq_add_u64_kernel(uint64_t *__restrict__
     if ((n & 1ull) && blockIdx.x == 0 && threadIdx.x == 0) dst[n - 1] += src[n - 1];
 }
 
+// ---------------------------------------------------------------------------------------------- completion
+// The end of a kernel whose results the host picks up by polling a flag (every thread of every block calls it, behind
+// its last store): ONE system-scope release per block, behind the barrier that orders the other waves' stores before it
+// -- a fence in every wave would write the L2 back once per wave -- then the count of finished blocks (`done`: device
+// memory, zero before the launch, reset for the next launch on the stream).  Each block counts itself in behind its own
+// release, so the one that completes the count has seen every block's results leave: it raises *done_flag (pinned host
+// memory) to `ticket`.
+__device__ __forceinline__ void mcq_block_done(uint32_t *__restrict__ done, volatile uint32_t *done_flag, uint32_t ticket) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence_system(); /* this block's results have reached the host's memory */
+        bool last = true;
+        if (gridDim.x > 1u) {
+            last = atomicAdd(done, 1u) + 1u == gridDim.x;
+            if (last) *done = 0;
+        }
+        if (last) *done_flag = ticket;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- publish
 // Behind the evaluation kernel of a host-buffer call with few rows: moves the finished rows from HBM into pinned
 // host memory, leaves the HBM rows zero for the next call and raises a flag the host is polling -- instead of a
@@ -760,16 +814,7 @@ __global__ __launch_bounds__(256) void mcq_publish_kernel(ulonglong2 *__restrict
         h_rows[i] = d_rows[i];
         d_rows[i] = zero;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence_system(); /* this block's rows have reached the host's memory */
-        bool last = true;
-        if (gridDim.x > 1u) {
-            last = atomicAdd(done, 1u) + 1u == gridDim.x;
-            if (last) *done = 0;
-        }
-        if (last) *done_flag = ticket;
-    }
+    mcq_block_done(done, done_flag, ticket);
 }
 
 // ---------------------------------------------------------------------------------------------- eval
@@ -997,7 +1042,7 @@ template <> struct McqRowKind<MCQ_ROW_SEATS> {
         return reinterpret_cast<unsigned long long *>(res) + (size_t)i * kWords;
     }
 };
-static_assert(McqRowKind<true>::kWords * 8u == sizeof(mcq_result_ways), "row of mcq_result_ways");
+static_assert(McqRowKind<MCQ_ROW_WAYS>::kWords * 8u == sizeof(mcq_result_ways), "row of mcq_result_ways");
 static_assert(McqRowKind<MCQ_ROW_SEATS>::kWords * 8u == sizeof(mcq_result_seats) && sizeof(mcq_seat) == 24u, "row of mcq_result_seats");
 
 template <int MODE, bool SPLIT, bool WAYS>
@@ -1018,14 +1063,14 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__
     __shared__ __attribute__((aligned(16))) McqSumImage tab; /* first: the hash is read at constant offsets from LDS address 0 */
     __shared__ McqPair base_tab[2 * kMaxBlock]; /* per wave: the query's ordered remaining deck, 2 x 64 entries x 8 B (kDeckY) */
     __shared__ __attribute__((aligned(8))) char hole_tab[(kMaxBlock / 64) * MCQ_HOLE_WAVE_BYTES]; /* per wave: its cards by suit */
-    static_assert(sizeof(McqSumImage) + sizeof(base_tab) + sizeof(hole_tab) + 8u * McqRowKind<true>::kLanes + 8u <= 160u * 1024u &&
+    static_assert(sizeof(McqSumImage) + sizeof(base_tab) + sizeof(hole_tab) + 8u * McqRowKind<MCQ_ROW_WAYS>::kLanes + 8u <= 160u * 1024u &&
                       sizeof(McqSumImage) == 117760u && sizeof(base_tab) == 16384u && sizeof(hole_tab) == 25600u,
                   "image, base decks, hole tables, s_row, s_key and s_done in the 160 KB of a CU");
     /* SPLIT (small batches): the rows the work-group's waves END on are added up in LDS when they are one query's -- a
      * single long query is hundreds of waves, and twelve atomics per wave on ONE row serialise (a 100 000-run query: 392
      * waves, 18 us where the arithmetic takes 6) -- and the last wave sends the sum: s_key = that query (claimed by the
      * first wave to finish), s_done = waves that have finished */
-    typedef McqRowKind<WAYS> Row; /* WAYS: 22-word rows with the ties split by the hands that share the pot */
+    typedef McqRowKind<WAYS ? MCQ_ROW_WAYS : MCQ_ROW_PLAIN> Row; /* WAYS: 22-word rows with the ties split by the hands that share the pot */
     constexpr uint32_t kLanes = Row::kLanes;
     __shared__ unsigned long long s_row[kLanes];
     __shared__ uint32_t s_key, s_done;
@@ -1239,7 +1284,7 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
     constexpr uint32_t kWaves = kMaxBlock / 64, kStage = MCQ_DIRECT_STAGE_ROUNDS * kWaves;
     __shared__ __attribute__((aligned(16))) McqSumImage tab; /* first: the hash is read at constant offsets from LDS address 0 */
     __shared__ McqPair base_tab[2 * kMaxBlock]; /* as in mcq_eval_kernel */
-    typedef McqRowKind<WAYS> Row; /* WAYS: 22-word rows, tie_ways[9] behind by_type[9] */
+    typedef McqRowKind<WAYS ? MCQ_ROW_WAYS : MCQ_ROW_PLAIN> Row; /* WAYS: 22-word rows, tie_ways[9] behind by_type[9] */
     constexpr uint32_t kLanes = Row::kLanes;
     __shared__ unsigned long long partial[2][kWaves][kLanes]; /* [round parity][wave][passes, win, tie, by_type[9](, tie_ways[9])] */
     __shared__ uint4 s_rec[kStage];
@@ -1429,8 +1474,8 @@ __global__ __launch_bounds__(kMaxBlock) void mcq_eval_direct_kernel(const uint4 
 }
 
 // ---------------------------------------------------------------------------------------------- extended queries
-// SURVEY 8f-2 (ranges, ghost cards, any number of known hands, each two cards or a range): same slicing and tallying
-// as above, the mask-based iteration of mcq_iteration_ext.  Production mode draws from candidate lists that
+// SURVEY 8f-2 (ranges, ghost cards, any number of known hands, each two cards or a range): the slicing and tallying
+// of the plain path (the cost axis: mcq_axis.hpp), the mask-based iteration of mcq_iteration_ext.  Production mode draws from candidate lists that
 // mcq_ext_lists_kernel lays out once per query (mcq_device.hpp).  A range that could not be dealt zeroes the row's
 // `runs`.  ROW_WORDS / WAYS: 22-word rows (mcq_result_ways) with the ties split as in the plain kernels; the failed-range
 // marker (runs := 0) and the invalid marker (passes = UINT64_MAX) leave zeros in the nine further words.
@@ -1438,32 +1483,17 @@ template <uint32_t ROW_WORDS>
 __global__ __launch_bounds__(1024) void mcq_prep_ext_kernel(const mcq_query *__restrict__ q,
                                                             const mcq_query_ext *__restrict__ ext, uint32_t n, int mode,
                                                             mcq_result *__restrict__ res, uint64_t *__restrict__ prefix) {
-    __shared__ uint64_t wave_tot[16];
-    uint64_t carry = 0;
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t base = 0; base < n; base += 1024) {
-        uint32_t i = base + tid;
-        uint64_t cost = 0;
-        if (i < n) {
-            const uint4 raw = reinterpret_cast<const uint4 *>(q)[i];
-            const McqQueryWords qq = {raw.x, raw.y, raw.z, raw.w};
-            const McqExtRec er = {reinterpret_cast<const uint32_t *>(ext + i)};
-            bool ok = mcq_query_ext_valid(qq, er);
-            const uint32_t s_iters = ok && mode == MCQ_MODE_PHILOX ? mcq_ext_stream_iters(qq, er) : MCQ_STREAM_ITERS;
-            cost = ok ? (uint64_t)mcq_ext_task_count(qq, s_iters) * mcq_ext_task_weight(qq, s_iters) : 0ull;
-            uint64_t *r = reinterpret_cast<uint64_t *>(res) + (size_t)i * ROW_WORDS;
-            r[0] = ok ? qq.runs() : 0ull;
-            r[1] = ok ? 0ull : ~0ull;
-#pragma unroll
-            for (int k = 2; k < (int)ROW_WORDS; k++) r[k] = 0;
-        }
-        uint64_t chunk_total;
-        const uint64_t before = block_exclusive_scan_1024(cost, wave_tot, &chunk_total);
-        if (i < n) prefix[i] = carry + before;
-        carry += chunk_total;
-    }
-    if (tid == 0) {
-        prefix[n] = carry;
+    mcq_prep_rows<ROW_WORDS>(n, res, prefix, [&](uint32_t i) -> McqPrepRecord {
+        const uint4 raw = reinterpret_cast<const uint4 *>(q)[i];
+        const McqQueryWords qq = {raw.x, raw.y, raw.z, raw.w};
+        const McqExtRec er = {reinterpret_cast<const uint32_t *>(ext + i)};
+        const bool ok = mcq_query_ext_valid(qq, er);
+        const uint32_t s_iters = ok && mode == MCQ_MODE_PHILOX ? mcq_ext_stream_iters(qq, er) : MCQ_STREAM_ITERS;
+        /* (an invalid record is priced as well -- on MCQ_STREAM_ITERS, nothing is read outside the record -- and
+         * mcq_prep_rows drops the price: with the guard here the kernel takes two more registers than it did) */
+        return {ok, (uint64_t)mcq_ext_task_count(qq, s_iters) * mcq_ext_task_weight(qq, s_iters), qq.runs()};
+    });
+    if (threadIdx.x == 0) {
         prefix[n + 1] = 0;
         prefix[n + 2] = 0; /* work counter of mcq_mt_parse_ext_kernel */
     }
@@ -1557,36 +1587,22 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * waves_per_block + (threadIdx.x >> 6));
     const uint64_t n_waves = (uint64_t)gridDim.x * waves_per_block;
     const uint64_t total = prefix[n];
-    const uint64_t lo = total * wave / n_waves, hi = total * (wave + 1ull) / n_waves;
+    const McqAxisSlice slice = mcq_axis_slice(total, wave, n_waves);
+    const uint64_t lo = slice.lo, hi = slice.hi;
     if (MODE == MCQ_MODE_PHILOX) {
         if (threadIdx.x == 0) { /* the block's queries: those whose cost interval meets the block's piece of the axis */
-            const uint64_t blo = total * ((uint64_t)blockIdx.x * waves_per_block) / n_waves;
-            const uint64_t bhi = total * ((uint64_t)(blockIdx.x + 1u) * waves_per_block) / n_waves;
-            uint32_t qa = 0, qb = 0, nq = 0, staged = 0;
-            if (blo < bhi) {
-                uint32_t a = 0, b = n;
-                while (b - a > 1) {
-                    const uint32_t mid = (a + b) >> 1;
-                    if (prefix[mid] <= blo) a = mid; else b = mid;
+            const McqAxisRecords mine = mcq_axis_block_records(prefix, n, blockIdx.x, waves_per_block, gridDim.x);
+            const uint32_t qa = mine.first, nq = mine.count;
+            uint32_t staged = 0;
+            if (nq != 0u && (uint64_t)nq * lists_stride <= kStageLists) {
+                uint32_t at = 0;
+                for (uint32_t k = 0; k < nq * lists_stride; k++) {
+                    s_list_off[k] = at;
+                    at += (cnts[(size_t)qa * lists_stride + k] + 1u) & ~1u; /* whole 32-bit words */
+                    if (at > kStageEntries) break;
                 }
-                qa = a;
-                a = qa, b = n;
-                while (b - a > 1) { /* last query that starts before the block's end */
-                    const uint32_t mid = (a + b) >> 1;
-                    if (prefix[mid] < bhi) a = mid; else b = mid;
-                }
-                qb = a;
-                nq = qb - qa + 1u;
-                if ((uint64_t)nq * lists_stride <= kStageLists) {
-                    uint32_t at = 0;
-                    for (uint32_t k = 0; k < nq * lists_stride; k++) {
-                        s_list_off[k] = at;
-                        at += (cnts[(size_t)qa * lists_stride + k] + 1u) & ~1u; /* whole 32-bit words */
-                        if (at > kStageEntries) break;
-                    }
-                    s_list_off[nq * lists_stride] = at;
-                    staged = at <= kStageEntries ? 1u : 0u;
-                }
+                s_list_off[nq * lists_stride] = at;
+                staged = at <= kStageEntries ? 1u : 0u;
             }
             s_stage[0] = qa;
             s_stage[1] = nq;
@@ -1608,12 +1624,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
     McqExtWaveCtx &wc = wave_ctx[threadIdx.x >> 6];
     uint16_t *my_ids = ids + threadIdx.x;
 
-    uint32_t a = 0, b = n;
-    while (b - a > 1) {
-        const uint32_t mid = (a + b) >> 1;
-        if (prefix[mid] <= lo) a = mid; else b = mid;
-    }
-    uint32_t qi = __builtin_amdgcn_readfirstlane(a);
+    uint32_t qi = __builtin_amdgcn_readfirstlane(mcq_axis_last_le(prefix, n, lo)); /* it has a cost: lo < total */
     uint32_t task = 0, n_tasks = 0, weight = 1, s_iters = MCQ_STREAM_ITERS;
     uint64_t pfx = 0;
     McqExtCtx qc;
@@ -1630,8 +1641,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
             const McqExtRec er = {reinterpret_cast<const uint32_t *>(ext + qi)};
             s_iters = ok && MODE == MCQ_MODE_PHILOX ? mcq_ext_stream_iters(q, er) : MCQ_STREAM_ITERS;
             weight = mcq_ext_task_weight(q, s_iters);
-            task = 0;
-            if (pfx < lo) task = (uint32_t)((lo - pfx + weight - 1) / weight);
+            task = mcq_axis_first_task(pfx, lo, weight); /* (not 0 only for the wave's first record) */
             fresh = false;
             if (ok) {
                 mcq_ext_ctx(q, er, qc);
@@ -1669,7 +1679,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
             fresh = true;
             continue;
         }
-        if (pfx + (uint64_t)task * weight >= hi) break;
+        if (!mcq_axis_owns(pfx, task, weight, hi)) break; /* the task belongs to a later slice */
 
         Acc acc = {};
         if (MODE == MCQ_MODE_PHILOX) {
@@ -1777,39 +1787,22 @@ __global__ __launch_bounds__(kRgTabBlock) void mcq_ranges_tables_kernel(const ui
     }
 }
 
-/* rows zeroed behind `runs`, the cost prefix of the records (mcq_prep_ext_kernel's layout: prefix[n] = the total); a task
- * costs its price by seats and street times trials[i], the host's estimate of the record's whole trials per iteration */
+/* rows and cost prefix of the records (mcq_prep_rows; nothing is written behind prefix[n]); a task costs its price by
+ * seats and street times trials[i], the host's estimate of the record's whole trials per iteration */
 __global__ __launch_bounds__(1024) void mcq_prep_ranges_kernel(const mcq_query *__restrict__ q, const uint32_t *__restrict__ trials,
                                                                uint32_t n, mcq_result *__restrict__ res,
                                                                uint64_t *__restrict__ prefix) {
-    __shared__ uint64_t wave_tot[16];
-    constexpr uint32_t kWords = McqRowKind<MCQ_ROW_SEATS>::kWords;
-    uint64_t carry = 0;
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t base = 0; base < n; base += 1024) {
-        uint32_t i = base + tid;
-        uint64_t cost = 0;
-        if (i < n) {
-            const uint4 raw = reinterpret_cast<const uint4 *>(q)[i];
-            const McqQueryWords qq = {raw.x, raw.y, raw.z, raw.w};
-            const bool ok = mcq_ranges_query_valid(qq);
-            cost = ok ? (uint64_t)mcq_ranges_task_count(qq) * (mcq_ranges_task_weight(qq) * trials[i]) : 0ull;
-            uint64_t *r = reinterpret_cast<uint64_t *>(res) + (size_t)i * kWords;
-            r[0] = ok ? qq.runs() : 0ull;
-            r[1] = ok ? 0ull : ~0ull;
-#pragma unroll
-            for (int k = 2; k < (int)kWords; k++) r[k] = 0;
-        }
-        uint64_t chunk_total;
-        const uint64_t before = block_exclusive_scan_1024(cost, wave_tot, &chunk_total);
-        if (i < n) prefix[i] = carry + before;
-        carry += chunk_total;
-    }
-    if (tid == 0) prefix[n] = carry;
+    mcq_prep_rows<McqRowKind<MCQ_ROW_SEATS>::kWords>(n, res, prefix, [&](uint32_t i) -> McqPrepRecord {
+        const uint4 raw = reinterpret_cast<const uint4 *>(q)[i];
+        const McqQueryWords qq = {raw.x, raw.y, raw.z, raw.w};
+        const bool ok = mcq_ranges_query_valid(qq);
+        return {ok, ok ? (uint64_t)mcq_ranges_task_count(qq) * (mcq_ranges_task_weight(qq) * trials[i]) : 0ull, qq.runs()};
+    });
 }
 
-// The evaluation: the slicing of mcq_eval_ext_kernel -- cost prefix, waves over the cost axis, sixteen-iteration streams,
-// the per-seat wave tally and its flush -- around mcq_iteration_ranges.  A draw is one dependent chain, word -> t ->
+// The evaluation: waves over the cost axis (the rule and the arithmetic of mcq_axis.hpp, written out here as
+// mcq_eval_ext_kernel had it: through the header's calls this kernel came out 0.65 % slower, profiles/axis_walk_ab.txt),
+// sixteen-iteration streams of mcq_iteration_ranges, the per-seat wave tally and its flush.  A draw is one dependent chain, word -> t ->
 // eleven steps of a binary search in the seat's prepared table -> hand -> test, so where the table lies decides the
 // kernel: a block first brings the prepared tables that ITS records name (a block's waves cover a contiguous piece of
 // the cost axis, hence consecutive records) into LDS when there are at most MCQ_RG_STAGE_TABLES distinct ones among at
@@ -1987,7 +1980,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_small_kernel(McqExtSma
                                                                        const McqTables *__restrict__ g_tab,
                                                                        uint32_t *__restrict__ done, volatile uint32_t *done_flag,
                                                                        uint32_t ticket) {
-    typedef McqRowKind<WAYS> Row; /* WAYS: one 22-word row per block */
+    typedef McqRowKind<WAYS ? MCQ_ROW_WAYS : MCQ_ROW_PLAIN> Row; /* WAYS: one 22-word row per block */
     typedef typename Row::Acc Acc;
     constexpr uint32_t kWaves = kExtBlock / 64;
     constexpr uint32_t kStageEntries = MCQ_EXT_SMALL_LISTS * MCQ_EXT_LIST_STRIDE;
@@ -2103,16 +2096,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_small_kernel(McqExtSma
         else if (bad) v = tid == 1u && !valid ? ~0ull : 0ull; /* invalid: passes = UINT64_MAX, as mcq_prep_ext_kernel marks it */
         reinterpret_cast<unsigned long long *>(Row::row(res, blockIdx.x))[tid] = v;
     }
-    __syncthreads();
-    if (tid == 0) {
-        __threadfence_system(); /* this block's row has reached the host's memory */
-        bool last = true;
-        if (gridDim.x > 1u) {
-            last = atomicAdd(done, 1u) + 1u == gridDim.x;
-            if (last) *done = 0; /* ready for the next launch on this stream */
-        }
-        if (last) *done_flag = ticket;
-    }
+    mcq_block_done(done, done_flag, ticket);
 }
 
 // ---------------------------------------------------------------------------------------------- showdown
@@ -2185,16 +2169,7 @@ __global__ __launch_bounds__(kShowBlock) void mcq_showdown_kernel(const uint8_t 
         }
     }
     if (ticket == 0u) return; /* not the last launch of the call */
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence_system(); /* this block's results (and `bad`) have reached the host's memory */
-        bool last = true;
-        if (gridDim.x > 1u) {
-            last = atomicAdd(done, 1u) + 1u == gridDim.x;
-            if (last) *done = 0;
-        }
-        if (last) *done_flag = ticket;
-    }
+    mcq_block_done(done, done_flag, ticket); /* (the results and `bad`) */
 }
 
 // ---------------------------------------------------------------------------------------------- exact enumeration

@@ -262,6 +262,32 @@ def geometry(total_tasks, n_cu, occ):
     return grid, max(wpb, 4)
 
 
+def block_records(prefix, n, blk, wpb, grid):
+    """The records of block `blk` of `grid` blocks of `wpb` waves on the cost axis prefix[0..n] (Python integers): (first
+    record, number of records), or None for a block without a piece of the axis.  The mirror of mcq_axis_block_records
+    (csrc/mcq_axis.hpp); tests/test_axis_host.py holds the two together."""
+    total, n_waves = int(prefix[n]), grid * wpb
+    blo, bhi = total * (blk * wpb) // n_waves, total * ((blk + 1) * wpb) // n_waves
+    if blo >= bhi:
+        return None
+    a, b = 0, n
+    while b - a > 1:
+        mid = (a + b) >> 1
+        if prefix[mid] <= blo:
+            a = mid
+        else:
+            b = mid
+    qa = a
+    b = n
+    while b - a > 1:
+        mid = (a + b) >> 1
+        if prefix[mid] < bhi:
+            a = mid
+        else:
+            b = mid
+    return qa, a - qa + 1
+
+
 def staging(recs, n_cu, occ):
     """What every block of mcq_eval_ext_kernel decides about its queries' candidate lists, for a batch on the general
     path: a list, one entry per block with work, of ("staged" | "count" | "entries", first query, queries).  "count": more
@@ -269,9 +295,7 @@ def staging(recs, n_cu, occ):
     n = len(recs)
     stride = max(max(r.lists for r in recs), 1)
     prefix = np.concatenate([[0], np.cumsum([r.tasks * r.weight for r in recs], dtype=np.uint64)]).astype(object)
-    total = int(prefix[n])
     grid, wpb = geometry(sum(r.tasks for r in recs), n_cu, occ)
-    n_waves = grid * wpb
     cnts = {}
 
     def cnt(k):   # cnts[query * stride + li]
@@ -281,25 +305,10 @@ def staging(recs, n_cu, occ):
         return cnts[k]
     out = []
     for blk in range(grid):
-        blo, bhi = total * (blk * wpb) // n_waves, total * ((blk + 1) * wpb) // n_waves
-        if blo >= bhi:
+        mine = block_records(prefix, n, blk, wpb, grid)
+        if mine is None:
             continue
-        a, b = 0, n
-        while b - a > 1:
-            mid = (a + b) >> 1
-            if prefix[mid] <= blo:
-                a = mid
-            else:
-                b = mid
-        qa = a
-        b = n
-        while b - a > 1:
-            mid = (a + b) >> 1
-            if prefix[mid] < bhi:
-                a = mid
-            else:
-                b = mid
-        nq = a - qa + 1
+        qa, nq = mine
         if nq * stride > STAGE_LISTS:
             out.append(("count", qa, nq))
             continue
