@@ -1,33 +1,17 @@
 """Test-only host build of the product's lane arithmetic (see hostsim.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.environ.get("MCQ_HOSTSIM_SO", os.path.join(_HERE, "libmcq_hostsim.so"))   # override: tests/sanitize_cpu.sh
-_SRCS = [os.path.join(_HERE, "hostsim.cpp"),
-         os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc", "mcq_device.hpp"),
-         os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc", "mcq_replay.hpp"),
-         os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc", "mcq_exact.hpp"),
-         os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc", "mcq_mt.hpp"),
-         os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc", "mcq_mt_ext.hpp"),
-         os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc", "mcq_mt_blocks.hpp"),
-         os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc", "mcq_layout.hpp"),
-         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if "MCQ_HOSTSIM_SO" not in os.environ and (not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS)):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized", "-shared", "-fPIC", "-pthread", "-o", _SO, _SRCS[0]])
-        L = C.CDLL(_SO)
-        L.hs_select_pop.restype = C.c_uint32
-        _lib = L
-    return _lib
+    L = hostbuild.load("hostsim/hostsim.cpp", "hostsim/libmcq_hostsim.so", env="MCQ_HOSTSIM_SO")   # (tests/sanitize_cpu.sh)
+    L.hs_select_pop.restype = C.c_uint32
+    return L
 
 
 def _p(a, t):

@@ -1,44 +1,32 @@
 """Test-only host build of the cost-axis arithmetic of the Monte-Carlo kernels (see hs_axis.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_axis.so")
-_SRCS = [os.path.join(_HERE, "hs_axis.cpp"), os.path.join(_CSRC, "mcq_axis.hpp"), os.path.join(_CSRC, "mcq_device.hpp"),
-         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
+
 _U64P, _U32P = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_axis_slice.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, _U64P]
-        L.hs_axis_slice.restype = None
-        L.hs_axis_last_le.argtypes = [_U64P, C.c_uint32, C.c_uint64]
-        L.hs_axis_last_le.restype = C.c_uint32
-        L.hs_axis_last_lt.argtypes = [_U64P, C.c_uint32, C.c_uint32, C.c_uint64]
-        L.hs_axis_last_lt.restype = C.c_uint32
-        L.hs_axis_first_task.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
-        L.hs_axis_first_task.restype = C.c_uint32
-        L.hs_axis_owns.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]
-        L.hs_axis_owns.restype = C.c_int
-        L.hs_axis_block_records.argtypes = [_U64P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _U32P]
-        L.hs_axis_block_records.restype = None
-        L.hs_axis_walk.argtypes = [_U64P, _U32P, _U32P, C.c_uint32, C.c_uint32, C.c_uint32, _U32P, C.c_uint64]
-        L.hs_axis_walk.restype = C.c_uint64
-        L.hs_axis_partition_exhaustive.argtypes = [C.c_uint32, C.c_uint32, _U32P, C.c_uint32, C.c_uint32, _U64P, _U32P]
-        L.hs_axis_partition_exhaustive.restype = C.c_uint64
-        _lib = L
-    return _lib
+    L = hostbuild.load("hostsim_axis/hs_axis.cpp")
+    L.hs_axis_slice.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, _U64P]
+    L.hs_axis_slice.restype = None
+    L.hs_axis_last_le.argtypes = [_U64P, C.c_uint32, C.c_uint64]
+    L.hs_axis_last_le.restype = C.c_uint32
+    L.hs_axis_last_lt.argtypes = [_U64P, C.c_uint32, C.c_uint32, C.c_uint64]
+    L.hs_axis_last_lt.restype = C.c_uint32
+    L.hs_axis_first_task.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
+    L.hs_axis_first_task.restype = C.c_uint32
+    L.hs_axis_owns.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]
+    L.hs_axis_owns.restype = C.c_int
+    L.hs_axis_block_records.argtypes = [_U64P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _U32P]
+    L.hs_axis_block_records.restype = None
+    L.hs_axis_walk.argtypes = [_U64P, _U32P, _U32P, C.c_uint32, C.c_uint32, C.c_uint32, _U32P, C.c_uint64]
+    L.hs_axis_walk.restype = C.c_uint64
+    L.hs_axis_partition_exhaustive.argtypes = [C.c_uint32, C.c_uint32, _U32P, C.c_uint32, C.c_uint32, _U64P, _U32P]
+    L.hs_axis_partition_exhaustive.restype = C.c_uint64
+    return L
 
 
 def _u64(v):

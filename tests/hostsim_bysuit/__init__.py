@@ -1,16 +1,10 @@
 """Test-only host build of the opponents' cards read by flush suit (see hs_bysuit.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_bysuit.so")
-_SRCS = [os.path.join(_HERE, "hs_bysuit.cpp"), os.path.join(_CSRC, "mcq_device.hpp"),
-         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 POSITIONS = 50
 # accessors of hs_bysuit_run
@@ -19,25 +13,18 @@ DEALT, BY_SUIT_CARDS, BY_SUIT_POSITION_MAJOR, BY_SUIT_SUIT_MAJOR = 0, 1, 2, 3
 ENTRY_SOURCES = ("set + perm", "array of cards", "arrays of halves", "position-major table", "suit-major table")
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_bysuit_default.restype = C.c_int
-        L.hs_bysuit_rank_weight2.restype = C.c_uint32
-        L.hs_bysuit_rank_weight2.argtypes = [C.c_uint32]
-        L.hs_bysuit_wave_bytes.restype = C.c_uint32
-        L.hs_bysuit_entries.restype = C.c_int
-        L.hs_bysuit_entries.argtypes = [C.c_void_p, C.c_void_p]
-        L.hs_bysuit_run.restype = C.c_int
-        L.hs_bysuit_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        _lib = L
-    return _lib
+    L = hostbuild.load("hostsim_bysuit/hs_bysuit.cpp")
+    L.hs_bysuit_default.restype = C.c_int
+    L.hs_bysuit_rank_weight2.restype = C.c_uint32
+    L.hs_bysuit_rank_weight2.argtypes = [C.c_uint32]
+    L.hs_bysuit_wave_bytes.restype = C.c_uint32
+    L.hs_bysuit_entries.restype = C.c_int
+    L.hs_bysuit_entries.argtypes = [C.c_void_p, C.c_void_p]
+    L.hs_bysuit_run.restype = C.c_int
+    L.hs_bysuit_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    return L
 
 
 def shipped():

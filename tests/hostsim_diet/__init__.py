@@ -1,30 +1,17 @@
 """Test-only host build of the plain path's iteration, folded into result rows (see hs_diet.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_diet.so")
-_SRCS = [os.path.join(_HERE, "hs_diet.cpp"), os.path.join(_CSRC, "mcq_device.hpp"),
-         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_diet_run.restype = C.c_int
-        L.hs_diet_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
-        L.hs_diet_card_sum.restype = C.c_uint32
-        L.hs_diet_card_sum.argtypes = [C.c_uint32]
-        L.hs_diet_psel.restype = C.c_uint32
-        L.hs_diet_psel.argtypes = [C.c_void_p, C.c_uint32]
-        _lib = L
-    return _lib
+    L = hostbuild.load("hostsim_diet/hs_diet.cpp")
+    L.hs_diet_run.restype = C.c_int
+    L.hs_diet_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
+    L.hs_diet_card_sum.restype = C.c_uint32
+    L.hs_diet_card_sum.argtypes = [C.c_uint32]
+    L.hs_diet_psel.restype = C.c_uint32
+    L.hs_diet_psel.argtypes = [C.c_void_p, C.c_uint32]
+    return L

@@ -1,41 +1,28 @@
 """Test-only host build of the dealing in epochs and of the iterations that deal by it (see hs_epochs.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_epochs.so")
-_SRCS = [os.path.join(_HERE, "hs_epochs.cpp"), os.path.join(_CSRC, "mcq_device.hpp"), os.path.join(_CSRC, "mcq_replay.hpp"),
-         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 FULLREG = 9                   # MCQ_DEAL_FULLREG
 RULES = (1, 2, 3, FULLREG)    # the plans built: at most one, two, three checkpoints; every full register
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_epochs_rule.restype = C.c_int
-        L.hs_epochs_plan.restype = C.c_int
-        L.hs_epochs_plan.argtypes = [C.c_int, C.c_int, C.c_void_p]
-        L.hs_epochs_positions.restype = C.c_int
-        L.hs_epochs_positions.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
-        L.hs_epochs_run.restype = C.c_int
-        L.hs_epochs_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.hs_epochs_replay.restype = C.c_int
-        L.hs_epochs_replay.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-        _lib = L
-    return _lib
+    L = hostbuild.load("hostsim_epochs/hs_epochs.cpp")
+    L.hs_epochs_rule.restype = C.c_int
+    L.hs_epochs_plan.restype = C.c_int
+    L.hs_epochs_plan.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.hs_epochs_positions.restype = C.c_int
+    L.hs_epochs_positions.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.hs_epochs_run.restype = C.c_int
+    L.hs_epochs_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.hs_epochs_replay.restype = C.c_int
+    L.hs_epochs_replay.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    return L
 
 
 def shipped_rule():

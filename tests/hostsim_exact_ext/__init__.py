@@ -1,39 +1,25 @@
 """Test-only host build of the extended exact enumeration's lane code (see hs_exact_ext.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_exact_ext.so")
-_SRCS = [os.path.join(_HERE, "hs_exact_ext.cpp"), os.path.join(_CSRC, "mcq_device.hpp"), os.path.join(_CSRC, "mcq_exact.hpp"),
-         os.path.join(_CSRC, "mcq_exact_ext.hpp"), os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 REFUSALS = {1: "invalid", 2: "hero range", 3: "known range", 4: "too many random opponents", 5: "range cannot be dealt"}
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_exact_ext.restype = C.c_int
-        L.hs_exact_ext_r.restype = C.c_int
-        _lib = L
-    return _lib
+    L = hostbuild.load("hostsim_exact_ext/hs_exact_ext.cpp")
+    L.hs_exact_ext.restype = C.c_int
+    L.hs_exact_ext_r.restype = C.c_int
+    return L
 
 
 def exact_ext(query16, ext, uniform=False):
     """-> (prob[11] float64: win, tie, by_type[9]; weights[13] uint64 like a result row).  A refusal raises ValueError."""
-    q = np.ascontiguousarray(query16).view(np.uint8).reshape(-1)[:16].copy()
-    e = np.ascontiguousarray(ext).view(np.uint8).reshape(-1)[:304].copy()
+    q, e = hostbuild.record(query16, ext)
     prob = np.zeros(11, np.float64)
     w = np.zeros(13, np.uint64)
     rc = lib().hs_exact_ext(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), C.c_int(1 if uniform else 0),

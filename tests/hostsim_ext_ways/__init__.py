@@ -1,43 +1,26 @@
 """Test-only host build of the extended lane code with the split-pot switch on (see hs_ext_ways.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_ext_ways.so")
-_SRCS = [os.path.join(_HERE, "hs_ext_ways.cpp")] + [os.path.join(_CSRC, f) for f in (
-    "mcq_device.hpp", "mcq_replay.hpp", "mcq_exact.hpp", "mcq_exact_ext.hpp")] + [os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_ext_ways_run.restype = C.c_int
-        L.hs_ext_ways_is_fast.restype = C.c_int
-        L.hs_exact_ext_ways.restype = C.c_int
-        _lib = L
-    return _lib
-
-
-def _bytes(a, n):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)[:n].copy()
+    L = hostbuild.load("hostsim_ext_ways/hs_ext_ways.cpp")
+    L.hs_ext_ways_run.restype = C.c_int
+    L.hs_ext_ways_is_fast.restype = C.c_int
+    L.hs_exact_ext_ways.restype = C.c_int
+    return L
 
 
 def run(replay, query16, ext304, seed, qid=0, general=False, hands=False):
     """One extended query through the lane code -> the 22 words of its mcq_result_ways row (and, with hands=True, every
     iteration's dealt hands: [runs, 2 * n_players + 5] card ids, the five table cards last).  replay: the caller passes
     seed = (seed + qid) mod 2^32, as the library's parity mode seeds a query."""
-    q, e = _bytes(query16, 16), _bytes(ext304, 304)
+    q, e = hostbuild.record(query16, ext304)
     out = np.zeros(22, np.uint64)
     runs, n_players = int(q[12:16].view("<u4")[0]), int(q[8])
     tr = np.full((max(runs, 1), 2 * n_players + 5), 255, np.uint8) if hands else None
@@ -50,12 +33,12 @@ def run(replay, query16, ext304, seed, qid=0, general=False, hands=False):
 
 
 def is_fast(query16, ext304):
-    q, e = _bytes(query16, 16), _bytes(ext304, 304)
+    q, e = hostbuild.record(query16, ext304)
     return bool(lib().hs_ext_ways_is_fast(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p)))
 
 
 def _u32(name, query16, ext304, *more):
-    q, e = _bytes(query16, 16), _bytes(ext304, 304)
+    q, e = hostbuild.record(query16, ext304)
     f = getattr(lib(), name)
     f.restype = C.c_uint32
     return int(f(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), *[C.c_uint32(m) for m in more]))
@@ -88,7 +71,7 @@ def list_len(query16, ext304, li):
 
 def exact(query16, ext304, law):
     """The exact split-pot lane code (kinds 0 and 1) -> 22 words of integer weights; ValueError(code) on a refusal."""
-    q, e = _bytes(query16, 16), _bytes(ext304, 304)
+    q, e = hostbuild.record(query16, ext304)
     out = np.zeros(22, np.uint64)
     rc = lib().hs_exact_ext_ways(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), C.c_int(law),
                                  out.ctypes.data_as(C.c_void_p))

@@ -1,18 +1,11 @@
 """Test-only host build of the preflop hero-range exact enumeration's lane code and its slow reference (see
 hs_hero_preflop.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_hero_preflop.so")
-_SRCS = [os.path.join(_HERE, "hs_hero_preflop.cpp")] + [os.path.join(_CSRC, h) for h in (
-    "mcq_device.hpp", "mcq_exact.hpp", "mcq_exact_ext.hpp", "mcq_exact_hero.hpp", "mcq_exact_hero_pre.hpp")] + [
-    os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 ROWS = 1326
 SENTINEL = 0xA5A5A5A5A5A5A5A5
@@ -20,41 +13,28 @@ REFUSALS = {-2: "empty completion range", -1: "bad law", 1: "invalid", 2: "hero 
             4: "not heads-up", 6: "no allowed hero hand", 7: "range cannot be dealt"}
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-pthread", "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_hero_pre.restype = C.c_int
-        L.hs_hero_pre_allowed.restype = C.c_int
-        L.hs_slow_ref.restype = C.c_int
-        L.hs_unrank.restype = None
-        L.hs_next.restype = None
-        for name in ("hs_binom", "hs_pre_slice", "hs_pre_owned", "hs_pre_max_owned", "hs_pre_share"):
-            getattr(L, name).restype = C.c_uint32
-        L.hs_pre_slice.argtypes = [C.c_uint64]
-        L.hs_pre_owned.argtypes = [C.c_uint32, C.c_uint32]
-        L.hs_binom.argtypes = [C.c_uint32, C.c_uint32]
-        L.hs_pre_share.argtypes = [C.c_uint32]
-        _lib = L
-    return _lib
-
-
-def _rec(query16, ext):
-    q = np.ascontiguousarray(query16).view(np.uint8).reshape(-1)[:16].copy()
-    e = np.ascontiguousarray(ext).view(np.uint8).reshape(-1)[:304].copy()
-    return q, e
+    L = hostbuild.load("hostsim_hero_preflop/hs_hero_preflop.cpp")
+    L.hs_hero_pre.restype = C.c_int
+    L.hs_hero_pre_allowed.restype = C.c_int
+    L.hs_slow_ref.restype = C.c_int
+    L.hs_unrank.restype = None
+    L.hs_next.restype = None
+    for name in ("hs_binom", "hs_pre_slice", "hs_pre_owned", "hs_pre_max_owned", "hs_pre_share"):
+        getattr(L, name).restype = C.c_uint32
+    L.hs_pre_slice.argtypes = [C.c_uint64]
+    L.hs_pre_owned.argtypes = [C.c_uint32, C.c_uint32]
+    L.hs_binom.argtypes = [C.c_uint32, C.c_uint32]
+    L.hs_pre_share.argtypes = [C.c_uint32]
+    return L
 
 
 def hero_pre(query16, ext, law=0, lo=0, hi=0xFFFFFFFF):
     """-> (rows[1326, 13] uint64: the partial rows of the completions [lo, hi), agg[11] float64 or None when the range does
     not cover every completion, counts: allowed, live, ranked, completions).  A refusal raises ValueError after checking that
     it left the outputs untouched."""
-    q, e = _rec(query16, ext)
+    q, e = hostbuild.record(query16, ext)
     rows = np.full((ROWS, 13), SENTINEL, np.uint64)
     agg = np.full(11, -7.0, np.float64)
     counts = np.full(4, 0xFFFFFFFF, np.uint32)
@@ -71,7 +51,7 @@ def hero_pre(query16, ext, law=0, lo=0, hi=0xFFFFFFFF):
 
 def allowed_rows(query16, ext):
     """The rows of the allowed hero hands in the order of the kernel's `allowed` list."""
-    q, e = _rec(query16, ext)
+    q, e = hostbuild.record(query16, ext)
     out = np.zeros(ROWS, np.uint32)
     n = lib().hs_hero_pre_allowed(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
     if n < 0:

@@ -1,17 +1,10 @@
 """Test-only host build of the weighted preflop hero-range exact enumeration's lane code (see hs_hero_preflop_weighted.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_hero_preflop_weighted.so")
-_SRCS = [os.path.join(_HERE, "hs_hero_preflop_weighted.cpp")] + [os.path.join(_CSRC, h) for h in (
-    "mcq_device.hpp", "mcq_exact.hpp", "mcq_exact_ext.hpp", "mcq_exact_hero.hpp", "mcq_exact_hero_pre.hpp")] + [
-    os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 ROWS = 1326
 SENTINEL = 0xA5A5A5A5A5A5A5A5
@@ -19,29 +12,16 @@ REFUSALS = {-3: "no opponent weights", -2: "empty completion range", 1: "invalid
             4: "not heads-up", 6: "no allowed hero hand", 7: "range cannot be dealt"}
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-pthread", "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_hero_pre_w.restype = C.c_int
-        L.hs_hero_pre_w.argtypes = [C.c_void_p] * 4 + [C.c_uint32] * 2 + [C.c_void_p] * 3
-        L.hs_hero_pre_w_allowed.restype = C.c_int
-        L.hs_hero_pre_w_allowed.argtypes = [C.c_void_p] * 5
-        L.hs_hero_pre_w_walked.restype = C.c_uint64
-        L.hs_hero_pre_w_walked.argtypes = []
-        _lib = L
-    return _lib
-
-
-def _rec(query16, ext):
-    q = np.ascontiguousarray(query16).view(np.uint8).reshape(-1)[:16].copy()
-    e = np.ascontiguousarray(ext).view(np.uint8).reshape(-1)[:304].copy()
-    return q, e
+    L = hostbuild.load("hostsim_hero_preflop_weighted/hs_hero_preflop_weighted.cpp")
+    L.hs_hero_pre_w.restype = C.c_int
+    L.hs_hero_pre_w.argtypes = [C.c_void_p] * 4 + [C.c_uint32] * 2 + [C.c_void_p] * 3
+    L.hs_hero_pre_w_allowed.restype = C.c_int
+    L.hs_hero_pre_w_allowed.argtypes = [C.c_void_p] * 5
+    L.hs_hero_pre_w_walked.restype = C.c_uint64
+    L.hs_hero_pre_w_walked.argtypes = []
+    return L
 
 
 def _table(w, name):
@@ -62,7 +42,7 @@ def hero_pre_w(query16, ext, opp_w, hero_w=None, lo=0, hi=0xFFFFFFFF):
     """-> (rows[1326, 13] uint64: the partial rows of the completions [lo, hi), agg[11] float64 or None when the range does
     not cover every completion, counts: allowed, live, ranked, completions).  A refusal raises ValueError after checking that
     it left the outputs untouched."""
-    q, e = _rec(query16, ext)
+    q, e = hostbuild.record(query16, ext)
     ow, hw = _table(opp_w, "opp_w"), _table(hero_w, "hero_w")
     rows = np.full((ROWS, 13), SENTINEL, np.uint64)
     agg = np.full(11, -7.0, np.float64)
@@ -79,7 +59,7 @@ def hero_pre_w(query16, ext, opp_w, hero_w=None, lo=0, hi=0xFFFFFFFF):
 
 def allowed_rows(query16, ext, opp_w, hero_w=None):
     """The rows of the allowed hero hands in the order of the kernel's `allowed` list."""
-    q, e = _rec(query16, ext)
+    q, e = hostbuild.record(query16, ext)
     ow, hw = _table(opp_w, "opp_w"), _table(hero_w, "hero_w")
     out = np.zeros(ROWS, np.uint32)
     n = lib().hs_hero_pre_w_allowed(q.ctypes.data, e.ctypes.data, ow.ctypes.data, None if hw is None else hw.ctypes.data,

@@ -1,48 +1,28 @@
 """Test-only host build of the hero-range exact enumeration's lane code (see hs_hero_range.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_hero_range.so")
-_SRCS = [os.path.join(_HERE, "hs_hero_range.cpp"), os.path.join(_CSRC, "mcq_device.hpp"), os.path.join(_CSRC, "mcq_exact.hpp"),
-         os.path.join(_CSRC, "mcq_exact_ext.hpp"), os.path.join(_CSRC, "mcq_exact_hero.hpp"),
-         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 ROWS = 1326
 REFUSALS = {-1: "bad law", 1: "invalid", 2: "hero is not a range", 3: "known hands", 4: "not heads-up", 5: "preflop",
             6: "no allowed hero hand", 7: "range cannot be dealt"}
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-pthread", "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_hero_range.restype = C.c_int
-        L.hs_hero_weights.restype = C.c_int
-        _lib = L
-    return _lib
-
-
-def _rec(query16, ext):
-    q = np.ascontiguousarray(query16).view(np.uint8).reshape(-1)[:16].copy()
-    e = np.ascontiguousarray(ext).view(np.uint8).reshape(-1)[:304].copy()
-    return q, e
+    L = hostbuild.load("hostsim_hero_range/hs_hero_range.cpp")
+    L.hs_hero_range.restype = C.c_int
+    L.hs_hero_weights.restype = C.c_int
+    return L
 
 
 def hero_range(query16, ext, law=0):
     """-> (rows[1326, 13] uint64 like result rows, agg[11] float64: win, tie, by_type[9]).  A refusal raises ValueError
     after checking that it left both outputs untouched."""
-    q, e = _rec(query16, ext)
+    q, e = hostbuild.record(query16, ext)
     rows = np.full((ROWS, 13), 0xA5A5A5A5A5A5A5A5, np.uint64)
     agg = np.full(11, -7.0, np.float64)
     rc = lib().hs_hero_range(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), C.c_int(int(law)),
@@ -55,7 +35,7 @@ def hero_range(query16, ext, law=0):
 
 def hero_weights(query16, ext, law=0):
     """-> w[1326] uint32: how often the law deals hero each hand, in proportion (0 = not an allowed hand of the deck)."""
-    q, e = _rec(query16, ext)
+    q, e = hostbuild.record(query16, ext)
     w = np.zeros(ROWS, np.uint32)
     rc = lib().hs_hero_weights(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), C.c_int(int(law)),
                                w.ctypes.data_as(C.c_void_p))

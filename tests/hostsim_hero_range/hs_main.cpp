@@ -1,5 +1,6 @@
 // hs_main.cpp -- TEST HARNESS ONLY: a stand-alone program around the host build of the hero-range lane code
-// (hs_hero_range.cpp), for a run under the host compiler's sanitizers:
+// (hs_hero_range.cpp), built and run under the host compiler's sanitizers by
+// tests/test_hero_range_host.py::test_stand_alone_program_under_the_host_sanitizers:
 //   g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined hs_main.cpp -o hs_main && ./hs_main
 // One river and one turn case, both laws; prints the aggregates and returns 0 when every call was accepted.
 #include <stdio.h>

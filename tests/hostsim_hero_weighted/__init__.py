@@ -1,17 +1,10 @@
 """Test-only host build of the weighted hero-range exact enumeration's lane code (see hs_hero_weighted.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_hero_weighted.so")
-_SRCS = [os.path.join(_HERE, "hs_hero_weighted.cpp"), os.path.join(_CSRC, "mcq_device.hpp"), os.path.join(_CSRC, "mcq_exact.hpp"),
-         os.path.join(_CSRC, "mcq_exact_ext.hpp"), os.path.join(_CSRC, "mcq_exact_hero.hpp"),
-         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 ROWS = 1326
 SENTINEL = 0xA5A5A5A5A5A5A5A5
@@ -19,19 +12,12 @@ REFUSALS = {-2: "no opponent weights", 1: "invalid", 2: "hero is not a range", 3
             6: "no allowed hero hand", 7: "range cannot be dealt"}
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-pthread", "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_hero_weighted.restype = C.c_int
-        L.hs_hero_weighted.argtypes = [C.c_void_p] * 6
-        _lib = L
-    return _lib
+    L = hostbuild.load("hostsim_hero_weighted/hs_hero_weighted.cpp")
+    L.hs_hero_weighted.restype = C.c_int
+    L.hs_hero_weighted.argtypes = [C.c_void_p] * 6
+    return L
 
 
 def _table(w, name):
@@ -46,8 +32,7 @@ def _table(w, name):
 def hero_weighted(query16, ext, opp_w, hero_w=None):
     """-> (rows[1326, 13] uint64 like result rows, agg[11] float64: win, tie, by_type[9]).  A refusal raises ValueError
     after checking that it left both outputs untouched."""
-    q = np.ascontiguousarray(query16).view(np.uint8).reshape(-1)[:16].copy()
-    e = np.ascontiguousarray(ext).view(np.uint8).reshape(-1)[:304].copy()
+    q, e = hostbuild.record(query16, ext)
     ow, hw = _table(opp_w, "opp_w"), _table(hero_w, "hero_w")
     rows = np.full((ROWS, 13), SENTINEL, np.uint64)
     agg = np.full(11, -7.0, np.float64)

@@ -1,5 +1,5 @@
-// hs_main.cpp -- TEST HARNESS ONLY: a stand-alone program around the host build of the matrix lane code (hs_matrix.cpp), for
-// a run by hand under the host compiler's sanitizers:
+// hs_main.cpp -- TEST HARNESS ONLY: a stand-alone program around the host build of the matrix lane code (hs_matrix.cpp), built
+// and run under the host compiler's sanitizers by tests/test_matrix_host.py::test_stand_alone_program_under_the_host_sanitizers:
 //   g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined hs_main.cpp -o hs_main && ./hs_main
 // A river, a turn with two dead cards, a flop with 43 dead cards (six cards left: one partial tile) and a refused record;
 // prints per case the return code, total and the sums of both matrices, and returns 0 when the three were accepted and the

@@ -1,44 +1,31 @@
 """Test-only host build of the paired count of the dealing in epochs, both settings of its switch (see hs_paired.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_paired.so")
-_SRCS = [os.path.join(_HERE, "hs_paired.cpp"), os.path.join(_CSRC, "mcq_device.hpp"), os.path.join(_CSRC, "mcq_replay.hpp"),
-         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 FULLREG = 9                   # MCQ_DEAL_FULLREG
 RULES = (1, 2, 3, FULLREG)
 BIAS = 0x40404040             # MCQ_HOLE_BIAS
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_paired_default.restype = C.c_int
-        L.hs_paired_count2.restype = None
-        L.hs_paired_count2.argtypes = [C.c_uint64] + [C.c_void_p] * 5
-        L.hs_paired_plan.restype = C.c_int
-        L.hs_paired_plan.argtypes = [C.c_int, C.c_int, C.c_void_p]
-        L.hs_paired_positions.restype = C.c_int
-        L.hs_paired_positions.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
-        L.hs_paired_run.restype = C.c_int
-        L.hs_paired_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.hs_paired_replay.restype = C.c_int
-        L.hs_paired_replay.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-        _lib = L
-    return _lib
+    L = hostbuild.load("hostsim_paired/hs_paired.cpp")
+    L.hs_paired_default.restype = C.c_int
+    L.hs_paired_count2.restype = None
+    L.hs_paired_count2.argtypes = [C.c_uint64] + [C.c_void_p] * 5
+    L.hs_paired_plan.restype = C.c_int
+    L.hs_paired_plan.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.hs_paired_positions.restype = C.c_int
+    L.hs_paired_positions.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.hs_paired_run.restype = C.c_int
+    L.hs_paired_run.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.hs_paired_replay.restype = C.c_int
+    L.hs_paired_replay.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    return L
 
 
 def shipped_switch():

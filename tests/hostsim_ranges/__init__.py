@@ -1,32 +1,20 @@
 """Test-only host build of the lane code of the weighted-range-per-seat Monte-Carlo entry (see hs_ranges.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_ranges.so")
-_SRCS = [os.path.join(_HERE, "hs_ranges.cpp")] + [os.path.join(_CSRC, f) for f in ("mcq_device.hpp", "mcq_ranges.hpp")] + [
-    os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
+
 FAILED = 2   # hs_ranges_run: the failure marker (an iteration without an accepted trial)
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_ranges_run.restype = C.c_int
-        L.hs_ranges_pick.restype = C.c_uint32
-        _lib = L
-    return _lib
+    L = hostbuild.load("hostsim_ranges/hs_ranges.cpp")
+    L.hs_ranges_run.restype = C.c_int
+    L.hs_ranges_pick.restype = C.c_uint32
+    return L
 
 
 def run(query16, seat_table, tables, seed, qid, hands=False):
@@ -34,7 +22,7 @@ def run(query16, seat_table, tables, seed, qid, hands=False):
     its mcq_result_seats row (and, with hands=True, every iteration's deal: [runs, 2 * n_players + 5] card ids, the five
     table cards last).  seat_table: ten table numbers, tables: uint16 [n_tables, 1326].
     ValueError(-1) for what the library refuses before a launch, ValueError(FAILED) for the failure marker."""
-    q = np.ascontiguousarray(query16).view(np.uint8).reshape(-1)[:16].copy()
+    q = hostbuild.first_bytes(query16, 16)
     st = np.zeros(10, np.uint32)
     seat_table = np.asarray(seat_table, np.uint32).reshape(-1)
     st[:len(seat_table)] = seat_table

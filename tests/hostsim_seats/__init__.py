@@ -1,42 +1,25 @@
 """Test-only host build of the extended lane code with the per-seat switch on (see hs_seats.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_seats.so")
-_SRCS = [os.path.join(_HERE, "hs_seats.cpp")] + [os.path.join(_CSRC, f) for f in (
-    "mcq_device.hpp", "mcq_exact.hpp", "mcq_exact_ext.hpp")] + [os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-shared", "-fPIC", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_seats_run.restype = C.c_int
-        L.hs_seats_exact.restype = C.c_int
-        _lib = L
-    return _lib
-
-
-def _bytes(a, n):
-    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)[:n].copy()
+    L = hostbuild.load("hostsim_seats/hs_seats.cpp")
+    L.hs_seats_run.restype = C.c_int
+    L.hs_seats_exact.restype = C.c_int
+    return L
 
 
 def run(query16, ext304, seed, qid, hands=False):
     """One extended query through the per-seat lane code (MCQ-CTR v5x streams of (seed, qid)) -> the 32 words of its
     mcq_result_seats row (and, with hands=True, every iteration's dealt hands: [runs, 2 * n_players + 5] card ids, the five
     table cards last).  ValueError(code) for what the library refuses (an invalid record, an undealable range)."""
-    q, e = _bytes(query16, 16), _bytes(ext304, 304)
+    q, e = hostbuild.record(query16, ext304)
     out = np.zeros(32, np.uint64)
     runs, n_players = int(q[12:16].view("<u4")[0]), int(q[8])
     tr = np.full((max(runs, 1), 2 * n_players + 5), 255, np.uint8) if hands else None
@@ -50,7 +33,7 @@ def run(query16, ext304, seed, qid, hands=False):
 def exact_refusal(query16, ext304, law):
     """Why the all-in enumeration refuses a record: 0 = it does not, 1..4 = MCQ_XX_* (invalid, hero range, ranged known
     hand, too many random opponents), 5 = cannot be dealt, 7 = a random opponent."""
-    q, e = _bytes(query16, 16), _bytes(ext304, 304)
+    q, e = hostbuild.record(query16, ext304)
     out = np.zeros(32, np.uint64)
     return int(lib().hs_seats_exact(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), C.c_int(law),
                                     out.ctypes.data_as(C.c_void_p)))
@@ -58,7 +41,7 @@ def exact_refusal(query16, ext304, law):
 
 def exact(query16, ext304, law):
     """The all-in enumeration's per-seat lane code -> 32 words of integer weights; ValueError(code) on a refusal."""
-    q, e = _bytes(query16, 16), _bytes(ext304, 304)
+    q, e = hostbuild.record(query16, ext304)
     out = np.zeros(32, np.uint64)
     rc = lib().hs_seats_exact(q.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), C.c_int(law),
                               out.ctypes.data_as(C.c_void_p))

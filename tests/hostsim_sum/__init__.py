@@ -1,32 +1,20 @@
 """Test-only host build of the sum-form evaluator (see hs_sum.cpp)."""
 import ctypes as C
-import os
-import subprocess
+import functools
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "..", "neuron_poker_amd", "csrc")
-_SO = os.path.join(_HERE, "libhs_sum.so")
-_SRCS = [os.path.join(_HERE, "hs_sum.cpp"), os.path.join(_CSRC, "mcq_device.hpp"),
-         os.path.join(_HERE, "..", "..", "include", "mcq.h")]
-_lib = None
+from tests import hostbuild
+
 N_CODES = 10
 
 
+@functools.cache
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in _SRCS):
-            tmp = _SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                                   "-shared", "-fPIC", "-pthread", "-o", tmp, _SRCS[0]])
-            os.replace(tmp, _SO)
-        L = C.CDLL(_SO)
-        L.hs_sum_multisets.restype = C.c_uint32
-        L.hs_sum_sweep.restype = C.c_uint64
-        _lib = L
-    return _lib
+    L = hostbuild.load("hostsim_sum/hs_sum.cpp")
+    L.hs_sum_multisets.restype = C.c_uint32
+    L.hs_sum_sweep.restype = C.c_uint64
+    return L
 
 
 def _p(a):

@@ -16,17 +16,14 @@ tests/hostsim_epochs builds the lane code for the host with the instantiation na
   oracle's MT19937 mode.
 * The same lane code in a stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer.
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import hostbuild
 from tests import hostsim_epochs as E
 from tests import hostsim_join
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SHAPES = [(nopp, ndeal) for nopp in range(1, 10) for ndeal in range(0, 6)]
 N_RANDOM = 100000
 
@@ -236,11 +233,5 @@ def test_parity_forms_equal_the_mt_walk():
 def test_stand_alone_program_under_the_host_sanitizers(tmp_path):
     """hs_main.cpp -- plans of every rule on boundary rows, iterations of a few forms, parity mode -- built with
     AddressSanitizer and UndefinedBehaviorSanitizer and run as a program of its own."""
-    exe = str(tmp_path / "hs_main")
-    subprocess.check_call(["g++", "-O0", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           os.path.join(HERE, "hostsim_epochs", "hs_main.cpp"), "-o", exe])
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    lines = res.stdout.strip().splitlines()
-    assert lines[-1].startswith("ok:"), res.stdout
+    lines = hostbuild.run_sanitized("hostsim_epochs/hs_main.cpp", "-O0", tmp_path)
+    assert lines[-1].startswith("ok:"), lines

@@ -11,6 +11,7 @@ from neuron_poker_amd import _lib
 from neuron_poker_amd import montecarlo_hip as mh
 from tests import hero_preflop_cases as PC
 from tests import hero_range_cases as HC
+from tests import hostbuild
 from tests import hostsim_hero_preflop as HP
 from tests import hostsim_hero_range as HS
 
@@ -226,17 +227,8 @@ def _lib_card(c):
 def test_stand_alone_program_under_the_host_sanitizers(tmp_path):
     """hs_main.cpp -- slices at 52 and 50 cards and a whole flop, both laws -- built with AddressSanitizer and
     UndefinedBehaviorSanitizer and run as a program of its own."""
-    import os
-    import subprocess
-    here = os.path.dirname(os.path.abspath(__file__))
-    exe = str(tmp_path / "hs_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           os.path.join(here, "hostsim_hero_preflop", "hs_main.cpp"), "-o", exe])
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    lines = res.stdout.strip().splitlines()
-    assert len(lines) == 6 and all(" rc 0," in ln for ln in lines), res.stdout
+    lines = hostbuild.run_sanitized("hostsim_hero_preflop/hs_main.cpp", "-O1", tmp_path)
+    assert len(lines) == 6 and all(" rc 0," in ln for ln in lines), lines
     assert "lists 1326 1326 1326 of 2598960 completions" in lines[0] and "of 2118760 completions" in lines[2]
     # the program's flop is the host build's of the postflop lane code
     q = _lib.pack_query_one([0, 0], [51, 29, 10], 2, 1)

@@ -5,6 +5,7 @@ import pytest
 
 from neuron_poker_amd import _lib
 from tests import hero_range_cases as HC
+from tests import hostbuild
 from tests import hostsim_exact_ext as XS
 from tests import hostsim_hero_range as HS
 
@@ -139,3 +140,18 @@ def test_refusals():
     # the opponent's range cannot be dealt against AH AS
     for law in (0, 1):
         assert _refused(*HC.records(HC.UNDEALABLE), law=law) == "range cannot be dealt"
+
+
+def test_stand_alone_program_under_the_host_sanitizers(tmp_path):
+    """hs_main.cpp -- a river and a ghost turn, both laws -- built with AddressSanitizer and UndefinedBehaviorSanitizer and
+    run as a program of its own; its aggregates are the host build's."""
+    lines = hostbuild.run_sanitized("hostsim_hero_range/hs_main.cpp", "-O1", tmp_path)
+    assert len(lines) == 4 and all(" rc 0," in ln for ln in lines), lines
+    pairs_and_suited_aces = ["%s%s" % (r, r) for r in "23456789TJQKA"] + ["A%sS" % r for r in "23456789TJQK"]
+    river = (_lib.pack_query_one([0, 0], [4, 17, 22, 35, 44], 2, 1), _lib.pack_query_ext(1, hero_range=_lib.ALL_CLASSES))
+    turn = (_lib.pack_query_one([0, 0], [51, 29, 10, 40], 2, 1),
+            _lib.pack_query_ext(1, ghost=[0, 45], hero_range=_lib.ALL_CLASSES, opp_range=_lib.range_bits(pairs_and_suited_aces)))
+    for ln, (name, rec, law) in zip(lines, [("river", river, 0), ("river", river, 1), ("turn", turn, 0), ("turn", turn, 1)]):
+        rows, agg = HS.hero_range(rec[0], rec[1], law)
+        assert ln.startswith("%s law %d:" % (name, law)), ln
+        assert "%d hero hands, win %.9f tie %.9f" % (int((rows[:, 0] != 0).sum()), agg[0], agg[1]) in ln, (ln, agg[:2])

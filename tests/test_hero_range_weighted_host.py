@@ -1,8 +1,6 @@
 """The weighted hero-range enumeration's lane code (csrc/mcq_exact_hero.hpp, "weighted hands") on the host, no GPU: its
 rows and aggregate against an independent walk of the definition, against the unweighted lane code when every weight is
 1, linearity in the opponent's weights, the 64-bit sums on the full flop, and the refusals."""
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -10,11 +8,11 @@ import pytest
 
 from neuron_poker_amd import _lib
 from tests import hero_range_cases as HC
+from tests import hostbuild
 from tests import hostsim_hero_range as HS
 from tests import hostsim_hero_weighted as HW
 from tests import weighted_range_cases as WC
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 _rows = {}
 
 
@@ -140,14 +138,8 @@ def test_refusals():
 def test_stand_alone_program_under_the_host_sanitizers(tmp_path):
     """hs_main.cpp -- a river and a ghost turn with hero weights -- built with AddressSanitizer and
     UndefinedBehaviorSanitizer and run as a program of its own; its sums are the host build's."""
-    exe = str(tmp_path / "hs_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                           "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           os.path.join(HERE, "hostsim_hero_weighted", "hs_main.cpp"), "-o", exe])
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    lines = res.stdout.strip().splitlines()
-    assert len(lines) == 2 and all(" rc 0," in ln for ln in lines), res.stdout
+    lines = hostbuild.run_sanitized("hostsim_hero_weighted/hs_main.cpp", "-O1", tmp_path)
+    assert len(lines) == 2 and all(" rc 0," in ln for ln in lines), lines
     i = np.arange(WC.ROWS, dtype=np.uint64)
     opp = np.where(i % 3 != 0, (i * 40503) & 0xFFFF, 0).astype(np.uint16)
     hero = np.where(i % 5 != 0, 1 + i % 7, 0).astype(np.uint16)

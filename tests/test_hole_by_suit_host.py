@@ -13,17 +13,14 @@ mcq_iteration_sum read them behind the table), without a GPU.  tests/hostsim_bys
 * The same lane code in a stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer (hole tables of exactly
   1600 bytes at the end of their heap blocks).
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from oracle import oracle as O
 from tests import bysuit_cases
+from tests import hostbuild
 from tests import hostsim_bysuit as B
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SEED, FQ = (1 << 44) | 0xB5017, 41
 RUNS = 1041
 LAWS = [(O.MODE_CTR, False), (O.MODE_CTR_UNIFORM, True)]
@@ -105,11 +102,5 @@ def test_cards_read_by_suit_give_the_same_rows(dealt_rows, accessor, ways):
 def test_stand_alone_program_under_the_host_sanitizers(tmp_path):
     """hs_main.cpp -- the table fill and every entry of a few decks, iterations of a few forms through every accessor --
     built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a program of its own."""
-    exe = str(tmp_path / "hs_main")
-    subprocess.check_call(["g++", "-O0", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           os.path.join(HERE, "hostsim_bysuit", "hs_main.cpp"), "-o", exe])
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    lines = res.stdout.strip().splitlines()
-    assert lines[-1].startswith("ok:"), res.stdout
+    lines = hostbuild.run_sanitized("hostsim_bysuit/hs_main.cpp", "-O0", tmp_path)
+    assert lines[-1].startswith("ok:"), lines

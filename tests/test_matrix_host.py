@@ -8,6 +8,7 @@ import pytest
 
 from neuron_poker_amd import _lib
 from oracle import oracle as O
+from tests import hostbuild
 from tests import hostsim_matrix as HM
 from tests import matrix_cases as MC
 
@@ -119,3 +120,18 @@ def test_refusals():
     # L - 4 == k is the smallest deck that is enumerated: one completion per pair of hands
     edge = _lib.pack_matrix_query(MC.CASES["flop_tiny"][0], MC.CASES["flop_tiny"][1])
     assert HM.matrix(edge)[2] == 1
+
+
+def test_stand_alone_program_under_the_host_sanitizers(tmp_path):
+    """hs_main.cpp -- a river, a turn with two dead cards, a flop with six cards left and a refused record -- built with
+    AddressSanitizer and UndefinedBehaviorSanitizer and run as a program of its own; its sums are the host build's."""
+    lines = hostbuild.run_sanitized("hostsim_matrix/hs_main.cpp", "-O1", tmp_path)
+    assert len(lines) == 4, lines
+    flop = [50, 46, 21]
+    lowest = [c for c in range(52) if c not in flop]
+    for i, (board, dead) in enumerate([([4, 17, 22, 35, 44], []), ([51, 29, 10, 40], [0, 45]), (flop, lowest[:43])]):
+        win, tie, total = HM.matrix(_lib.pack_matrix_query(board, dead))
+        assert lines[i] == "case %d: rc 0, total %d, win %d, tie %d" % (i, total, int(win.sum(dtype=np.uint64)),
+                                                                        int(tie.sum(dtype=np.uint64))), lines[i]
+    assert lines[3].startswith("case 3: rc 7,"), lines[3]                       # MCQ_XM_SHORT
+    assert _refused(_lib.pack_matrix_query(flop, lowest[:45])) == "too few cards"

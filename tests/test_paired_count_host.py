@@ -13,18 +13,15 @@ by the caller, so paired and unpaired text run side by side.
 * Parity mode's straight forms against the oracle's MT19937 mode.
 * The same lane code in a stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer.
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import hostbuild
 from tests import hostsim_join
 from tests import hostsim_paired as P
 from tests import test_epoch_dealing_host as T   # its rows, shapes and queries; nothing of it is collected from here
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 N_RANDOM = 100000
 
 
@@ -216,11 +213,5 @@ def test_stand_alone_program_under_the_host_sanitizers(tmp_path):
     """hs_main.cpp -- the primitive on every byte pair, plans of every rule on boundary rows with the switch on and off,
     iterations of a few forms, parity mode -- built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a
     program of its own."""
-    exe = str(tmp_path / "hs_main")
-    subprocess.check_call(["g++", "-O0", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           os.path.join(HERE, "hostsim_paired", "hs_main.cpp"), "-o", exe])
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    lines = res.stdout.strip().splitlines()
-    assert lines[-1].startswith("ok:"), res.stdout
+    lines = hostbuild.run_sanitized("hostsim_paired/hs_main.cpp", "-O0", tmp_path)
+    assert lines[-1].startswith("ok:"), lines

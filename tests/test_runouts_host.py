@@ -2,20 +2,18 @@
 against an independent literal walk of the reference, the probability of the next card against that walk's ORDERED table
 draws, the rows' sums against the host build of the existing split-pot enumeration, and the identities between card rows,
 pair rows and hand types.  Both laws."""
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from neuron_poker_amd import _lib
+from tests import hostbuild
 from tests import hostsim_ext_ways as WS
 from tests import hostsim_runouts as HS
 from tests import runout_literal as RL
 
 LAWS = [0, 1]   # MCQ_LAW_REFERENCE, MCQ_LAW_UNIFORM
-HERE = os.path.dirname(os.path.abspath(__file__))
 _rows, _lit = {}, {}
 
 
@@ -173,14 +171,8 @@ def test_refusals():
 def test_stand_alone_program_under_the_host_sanitizers(tmp_path):
     """hs_main.cpp -- cases (b) and (c), both laws -- built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a
     program of its own."""
-    exe = str(tmp_path / "hs_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           os.path.join(HERE, "hostsim_runouts", "hs_main.cpp"), "-o", exe])
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    lines = res.stdout.strip().splitlines()
-    assert len(lines) == 4 and all(" rc 0," in ln for ln in lines), res.stdout
+    lines = hostbuild.run_sanitized("hostsim_runouts/hs_main.cpp", "-O1", tmp_path)
+    assert len(lines) == 4 and all(" rc 0," in ln for ln in lines), lines
     # the program's sums are the host build's
     for ln, (name, law) in zip(lines, [("turn_known_ghost", 0), ("turn_known_ghost", 1), ("flop_allin", 0), ("flop_allin", 1)]):
         cards, pairs = rows_of(name, law)
