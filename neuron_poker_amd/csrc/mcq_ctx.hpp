@@ -110,17 +110,13 @@ struct PinBuf {
 struct mcq_ctx {
     McqBusyFlag busy; /* one call in flight per context: see MCQ_ENTER */
     int device = 0;
-    int n_cu = 0;
-    int occ[3] = {1, 1, 1}; /* resident kBlock-thread blocks per CU of the eval kernels (by internal mode) */
+    McqPlanKnobs knobs; /* what the launch plans read (mcq_plan.hpp): the device's CUs, the eval kernels' occupancy, MCQ_LOAD_WAVES, MCQ_GRID_CAP, MCQ_SPLIT_MAX */
     int law = MCQ_LAW_REFERENCE;
     uint64_t replay_device_bytes = 4ull << 30; /* parity mode: draw bytes per launch (MCQ_REPLAY_DEVICE_BYTES) */
     uint32_t direct_max_tasks = 8; /* queries of at most this many 1024-iteration tasks take the one-launch path (MCQ_DIRECT_MAX_TASKS, 0 = never) */
-    uint32_t load_waves = 16; /* waves per block that load the table image when fewer take work (MCQ_LOAD_WAVES) */
-    uint32_t grid_cap = 0; /* sliced launches (mcq_eval_kernel, mcq_eval_ext_kernel) get at most this many blocks; 0: no cap (MCQ_GRID_CAP, tests) */
     uint32_t exact_cu = 0; /* the exact plans (mcq_exact_plan, mcq_exact_ext_plan) see at most this many CUs; 0: n_cu (MCQ_EXACT_CU, tests) */
     uint32_t hero_pre_slice = 0; /* mcq_exact_batch_hero_range_preflop: table completions per launch; 0: MCQ_XP_DEFAULT_SLICE (MCQ_HERO_PRE_SLICE, tests) */
     uint32_t matrix_chunk = 16; /* mcq_exact_matrix: records per launch, 8.7 MB of scratch each on a flop (MCQ_MATRIX_CHUNK, tests) */
-    uint32_t split_max = 4; /* finest cut of a task for small batches: 16 >> split_max iterations per lane */
     hipStream_t stream = nullptr;
     static constexpr int kRing = 64; /* event pairs around the most recent evaluation-kernel launches */
     hipEvent_t ev0[kRing] = {}, ev1[kRing] = {};

@@ -28,14 +28,11 @@
 #include "mcq_ranges.hpp"
 #include "mcq_replay.hpp"
 
-hipError_t mcq_eval_occupancy(int mode, int block, int *blocks_per_cu); /* mcq_kernels.hip */
-
 namespace {
 
 thread_local std::string g_err;
 
 constexpr size_t kReplayChunkBytes = 256u << 20;  /* draw bytes staged per launch by the host walk (numpy-stream entry) */
-constexpr uint32_t kBlock = 1024;                /* threads per block of the evaluation kernels */
 /* 64-bit words of a result row: mcq_result, or mcq_result_ways (the *_ways entries).  The staging code below handles rows
  * as `rw` words; row i of a buffer starts rw * 8 * i bytes in. */
 constexpr uint32_t kPlainWords = sizeof(mcq_result) / 8u, kWaysWords = sizeof(mcq_result_ways) / 8u;
@@ -58,39 +55,6 @@ int mcq_fail(int code, const char *what, const char *detail) {
 }
 
 namespace {
-
-/* grid/block for a launch whose total task count is known (host entry) or unknown (0) */
-void pick_geometry(const mcq_ctx *c, int mode, uint64_t total_tasks, uint32_t *grid, uint32_t *block,
-                   uint32_t *split = nullptr, uint64_t max_tasks = 0, uint32_t *work_wpb = nullptr) {
-    const uint32_t full = (uint32_t)c->n_cu * (uint32_t)c->occ[mode];
-    if (split) *split = 0;
-    if (work_wpb) *work_wpb = 0;
-    if (total_tasks == 0) {
-        *block = kBlock;
-        *grid = c->grid_cap && full > c->grid_cap ? c->grid_cap : full;
-        return;
-    }
-    if (split) { /* small batches are cut finer, see mcq_pick_split */
-        *split = mcq_pick_split(total_tasks, max_tasks ? max_tasks : total_tasks, (uint32_t)c->n_cu, c->split_max);
-        total_tasks <<= *split;
-    }
-    /* one block per CU (the LDS tables allow no more); few tasks are spread over all CUs with fewer waves per
-     * block: 98 tasks of a single 100k query -> 98 one-wave blocks, 1024 tasks -> 256 four-wave blocks */
-    uint64_t wpb = (total_tasks + (uint64_t)c->n_cu - 1) / (uint64_t)c->n_cu;
-    if (wpb < 1) wpb = 1;
-    if (wpb > kBlock / 64) wpb = kBlock / 64;
-    const uint64_t blocks = (total_tasks + wpb - 1) / wpb;
-    *grid = (uint32_t)(blocks < (uint64_t)c->n_cu ? blocks : (wpb == kBlock / 64 ? full : (uint64_t)c->n_cu));
-    /* the block brings 97 KB of tables into LDS before anything else happens: more waves than take work shorten
-     * that (six 16-byte loads per lane with 16 waves, one round trip, instead of 24 with four) */
-    uint64_t launch = wpb < c->load_waves ? c->load_waves : wpb;
-    if (work_wpb && launch != wpb) *work_wpb = (uint32_t)wpb;
-    else launch = wpb < 4 ? 4 : wpb, wpb = launch;
-    *block = (uint32_t)(64 * launch);
-    /* tests: fewer blocks than the work asks for, so that a wave's slice is many tasks of one query (streams are keyed by
-     * query id and iteration: the tallies do not depend on the number of blocks) */
-    if (c->grid_cap && *grid > c->grid_cap) *grid = c->grid_cap;
-}
 
 /* is stream s being captured into a graph? (a failing query counts as "no") */
 bool stream_capturing(hipStream_t s) {
@@ -161,11 +125,11 @@ int mcq_run_slice(mcq_ctx *c, int mode, const mcq_query *d_q, uint32_t n, mcq_re
         int rc = scratch_for(c, s, ((size_t)n + 3) * sizeof(uint64_t), capturing, &sc);
         if (rc) return rc;
         d_prefix = (const uint64_t *)sc->prefix.p;
-        HIP_TRY(mcq_launch_prep(d_q, n, d_res, (uint64_t *)sc->prefix.p, part, n_parts, (uint32_t)c->n_cu, c->split_max, s,
+        HIP_TRY(mcq_launch_prep(d_q, n, d_res, (uint64_t *)sc->prefix.p, part, n_parts, c->knobs.n_cu, c->knobs.split_max, s,
                                 row_words));
     }
-    uint32_t grid, block, split, work_wpb;
-    pick_geometry(c, mode, total_tasks, &grid, &block, &split, max_tasks, &work_wpb);
+    const McqGeometry geo = mcq_plan_geometry(c->knobs, mode, total_tasks, true, max_tasks);
+    uint32_t split = geo.split;
     if (mode == MCQ_MODE_REPLAY_MT19937 && split > 2) split = 2; /* the parity kernel's lanes take four iterations at a time */
     /* queries in HBM (the host has not seen them): up to 1024 of them may be a small batch -- the prep kernel
      * decides the cut and the evaluation kernel reads it; more queries are at least as many tasks: never cut */
@@ -184,10 +148,10 @@ int mcq_run_slice(mcq_ctx *c, int mode, const mcq_query *d_q, uint32_t n, mcq_re
         else
             HIP_TRY(mcq_launch_mt_parse(d_q, n, *mt_seed32, const_cast<uint8_t *>(d_draws), d_off, d_res,
                                         const_cast<uint32_t *>(reinterpret_cast<const uint32_t *>(d_prefix + n + 2)),
-                                        (uint32_t)c->n_cu, s, row_words));
+                                        c->knobs.n_cu, s, row_words));
     }
-    HIP_TRY(mcq_launch_eval(mode, d_q, n, d_prefix, d_res, seed, first_qid, c->d_luts, d_draws, d_off, grid, block, split,
-                            part, n_parts, s, t0, t1, work_wpb, ways));
+    HIP_TRY(mcq_launch_eval(mode, d_q, n, d_prefix, d_res, seed, first_qid, c->d_luts, d_draws, d_off, geo.grid, geo.block, split,
+                            part, n_parts, s, t0, t1, geo.work_wpb, ways));
     if (timed) c->n_timed++;
     /* a caller's stream may run on while another stream's call takes over the scratch: mark its last reader.  The
      * context's own stream (slot 0) is synchronised by every host entry before it returns. */
@@ -450,9 +414,7 @@ mcq_ctx *mcq_ctx_clone(const mcq_ctx *c) {
     mcq_ctx *d = mcq_create(c->device, 0);
     if (d) {
         d->law = c->law;
-        d->split_max = c->split_max;
-        d->load_waves = c->load_waves;
-        d->grid_cap = c->grid_cap;
+        d->knobs = c->knobs; /* (the same device: the same CUs and occupancy) */
         d->direct_max_tasks = c->direct_max_tasks;
         d->direct_poll = c->direct_poll;
         d->direct_sleep = c->direct_sleep;
@@ -538,10 +500,10 @@ mcq_ctx *mcq_create(int device, int flags) {
     if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
     CREATE_TRY(hipSetDevice(device));
     CREATE_TRY(hipGetDeviceProperties(&prop, device));
-    c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (const char *e = getenv("MCQ_SPLIT_MAX")) { /* tuning knob, see pick_geometry */
+    c->knobs.n_cu = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256u;
+    if (const char *e = getenv("MCQ_SPLIT_MAX")) { /* tuning knob, see mcq_plan_geometry */
         int v = atoi(e);
-        c->split_max = (uint32_t)(v < 0 ? 0 : (v > 4 ? 4 : v));
+        c->knobs.split_max = (uint32_t)(v < 0 ? 0 : (v > 4 ? 4 : v));
     }
     if (const char *e = getenv("MCQ_DIRECT_MAX_TASKS")) { /* tuning knob, see eval_host_philox */
         const int v = atoi(e);
@@ -564,13 +526,13 @@ mcq_ctx *mcq_create(int device, int flags) {
         const long v = atol(e);
         c->publish_max_rows = (size_t)(v < 0 ? 0 : v);
     }
-    if (const char *e = getenv("MCQ_LOAD_WAVES")) { /* tuning knob, see pick_geometry */
+    if (const char *e = getenv("MCQ_LOAD_WAVES")) { /* tuning knob, see mcq_plan_geometry */
         const int v = atoi(e);
-        c->load_waves = (uint32_t)(v < 1 ? 1 : (v > 16 ? 16 : v));
+        c->knobs.load_waves = (uint32_t)(v < 1 ? 1 : (v > 16 ? 16 : v));
     }
-    if (const char *e = getenv("MCQ_GRID_CAP")) { /* at most this many blocks in a sliced launch (tests), see pick_geometry */
+    if (const char *e = getenv("MCQ_GRID_CAP")) { /* at most this many blocks in a sliced launch (tests), see mcq_plan_geometry */
         const long v = atol(e);
-        if (v >= 1) c->grid_cap = (uint32_t)(v > 0x7fffffffL ? 0x7fffffffL : v);
+        if (v >= 1) c->knobs.grid_cap = (uint32_t)(v > 0x7fffffffL ? 0x7fffffffL : v);
     }
     if (const char *e = getenv("MCQ_EXACT_CU")) { /* the CU count the exact plans size their grids by, capped (tests), see exact_cu */
         const long v = atol(e);
@@ -600,8 +562,8 @@ mcq_ctx *mcq_create(int device, int flags) {
     CREATE_TRY(hipMemcpy(c->d_luts, tabs, sizeof(McqTables), hipMemcpyHostToDevice));
     for (int mode = 0; mode < 3; mode++) {
         int occ = 0;
-        CREATE_TRY(mcq_eval_occupancy(mode, (int)kBlock, &occ));
-        c->occ[mode] = occ < 1 ? 1 : (occ > 8 ? 8 : occ);
+        CREATE_TRY(mcq_eval_occupancy(mode, (int)MCQ_PLAN_BLOCK, &occ));
+        c->knobs.occ[mode] = (uint32_t)(occ < 1 ? 1 : (occ > 8 ? 8 : occ));
     }
 #undef CREATE_TRY
     delete tabs;
@@ -721,20 +683,14 @@ int mcq_eval_batch_device_small(mcq_ctx *c, const void *d_queries, size_t n, uin
     int rc = scratch_for(c, s, 0, capturing, &sc);
     if (rc) return rc;
     uint32_t *d_done = reinterpret_cast<uint32_t *>(static_cast<char *>(c->d_done_dev.p) + 64 * (sc - c->scratch));
-    /* about 16 waves per CU in all, at most eight per query (a sixteenth wave steps over fifteen iterations' words) */
-    uint32_t lg = 0;
-    while (lg < 3u && ((uint64_t)n << (lg + 1u)) <= 16ull * (uint64_t)c->n_cu) lg++;
-    if (c->split_max < lg) lg = c->split_max;
-    const uint64_t waves = (uint64_t)n << lg, blocks = (waves + 15u) / 16u;
-    const uint32_t grid = (uint32_t)(blocks < (uint64_t)c->n_cu ? blocks : (uint64_t)c->n_cu);
-    const uint32_t rounds = (uint32_t)((blocks + grid - 1u) / grid);
+    const McqSmallCut cut = mcq_plan_small_cut(n, c->knobs.n_cu, c->knobs.split_max);
     const uint32_t mode = c->law == MCQ_LAW_UNIFORM ? MCQ_INTERNAL_MODE_UNIFORM : MCQ_MODE_PHILOX;
     const bool timed = c->timing && !capturing;
     const int slot = (int)(c->n_timed % mcq_ctx::kRing);
     c->last_ms = 0.f;
-    HIP_TRY(mcq_launch_eval_direct((int)mode, d_queries, nullptr, rounds, lg ? 1u : 0u, (mcq_result *)d_results, seed, first_query_id,
-                                   c->d_luts, grid, d_done, d_done + 8 /* nobody polls: the stream orders the call */, 1u, s,
-                                   timed ? c->ev0[slot] : nullptr, timed ? c->ev1[slot] : nullptr, nullptr, (uint32_t)n, lg));
+    HIP_TRY(mcq_launch_eval_direct((int)mode, d_queries, nullptr, cut.rounds, cut.lg ? 1u : 0u, (mcq_result *)d_results, seed, first_query_id,
+                                   c->d_luts, cut.grid, d_done, d_done + 8 /* nobody polls: the stream orders the call */, 1u, s,
+                                   timed ? c->ev0[slot] : nullptr, timed ? c->ev1[slot] : nullptr, nullptr, (uint32_t)n, cut.lg));
     if (timed) c->n_timed++;
     if (!capturing && sc != &c->scratch[0]) {
         HIP_TRY(hipEventRecord(sc->done, s));
@@ -788,7 +744,7 @@ static int wait_ticket(mcq_ctx *c, uint32_t ticket, bool *by_flag, double est_us
     return MCQ_OK;
 }
 /* expected kernel time of work of scheduling cost `cost` (mcq_task_weight units, about 0.0066 ns each on a whole MI355X) */
-static double cost_to_us(const mcq_ctx *c, uint64_t cost) { return (double)cost * 6.6e-6 * 256.0 / (double)(c->n_cu > 0 ? c->n_cu : 256); }
+static double cost_to_us(const mcq_ctx *c, uint64_t cost) { return (double)cost * 6.6e-6 * 256.0 / (double)(c->knobs.n_cu > 0 ? c->knobs.n_cu : 256); }
 
 /* Production mode from host buffers.  The host has the queries in its hands, so it prices them itself: the cost
  * prefix travels with the queries in ONE copy, the result rows are zero already (every call leaves them so), and
@@ -806,7 +762,7 @@ static int eval_host_philox(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t s
     const size_t r_pad = (n + (n & 1u)) * rw * 8u; /* whole 16-byte words (mcq_publish_kernel) */
     /* behind the records: the cost prefix, then (one-launch path) the wave layout: at most n + 2 * 16 * n_cu waves, dealt
      * to the blocks in whole rounds */
-    const size_t a_off = (q_bytes + p_bytes + 15u) & ~(size_t)15u, a_cap = n + 96u * (size_t)c->n_cu + 64u; /* waves */
+    const size_t a_off = (q_bytes + p_bytes + 15u) & ~(size_t)15u, a_cap = n + 96u * (size_t)c->knobs.n_cu + 64u; /* waves */
     HIP_TRY(c->h_q.reserve(a_off + a_cap * (sizeof(mcq_query) + sizeof(uint32_t))));
     HIP_TRY(c->d_q.reserve(q_bytes + p_bytes));
     HIP_TRY(c->h_res.reserve(r_pad));
@@ -837,21 +793,16 @@ static int eval_host_philox(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t s
              * 2^lg waves per query from the query count alone) and reads the caller's records -- copied into this pinned
              * buffer, nothing else -- across PCIe: the host neither prices nor places a thousand queries (12 us), and a
              * uniform cut turned out no slower on the GPU than the cost-proportional one. */
-            uint32_t lg = 0;
-            while (lg < 3u && ((uint64_t)n << (lg + 1u)) <= 16ull * (uint64_t)c->n_cu) lg++;
-            if (c->split_max < lg) lg = c->split_max;
-            const uint64_t blocks = (((uint64_t)n << lg) + 15u) / 16u;
-            const uint32_t grid = (uint32_t)(blocks < (uint64_t)c->n_cu ? blocks : (uint64_t)c->n_cu);
-            const uint32_t rounds = (uint32_t)((blocks + grid - 1u) / grid);
+            const McqSmallCut cut = mcq_plan_small_cut(n, c->knobs.n_cu, c->knobs.split_max);
             rc = flag_ready(c);
             if (rc) return rc;
             const uint32_t ticket = next_ticket(c);
             const int slot = (int)(c->n_timed % mcq_ctx::kRing);
             c->last_ms = 0.f;
-            HIP_TRY(mcq_launch_eval_direct((int)mode, c->h_q.dev, nullptr, rounds, lg ? 1u : 0u, (mcq_result *)c->h_res.dev, seed,
-                                           first_query_id, c->d_luts, grid, (uint32_t *)c->d_done.p, (uint32_t *)c->h_flag.dev,
+            HIP_TRY(mcq_launch_eval_direct((int)mode, c->h_q.dev, nullptr, cut.rounds, cut.lg ? 1u : 0u, (mcq_result *)c->h_res.dev, seed,
+                                           first_query_id, c->d_luts, cut.grid, (uint32_t *)c->d_done.p, (uint32_t *)c->h_flag.dev,
                                            ticket, c->stream, c->timing ? c->ev0[slot] : nullptr,
-                                           c->timing ? c->ev1[slot] : nullptr, nullptr, (uint32_t)n, lg, ways));
+                                           c->timing ? c->ev1[slot] : nullptr, nullptr, (uint32_t)n, cut.lg, ways));
             if (c->timing) c->n_timed++;
             rc = wait_ticket(c, ticket, nullptr);
             if (rc) return rc;
@@ -864,7 +815,7 @@ static int eval_host_philox(mcq_ctx *c, const mcq_query *q, size_t n, uint64_t s
         McqDirectLayout &lay = c->direct_layout;
         /* at most eight waves per query here: a sixteenth wave steps over fifteen iterations' words to run one
          * (tools/single_probe.py: one 1000-run query 1 us slower with sixteen, whatever the players and the table) */
-        mcq_direct_layout(qcost.data(), n, (uint32_t)c->n_cu, c->split_max < 3u ? c->split_max : 3u, lay);
+        mcq_direct_layout(qcost.data(), n, c->knobs.n_cu, c->knobs.split_max < 3u ? c->knobs.split_max : 3u, lay);
         const uint32_t grid = lay.grid, rounds = lay.rounds;
         const size_t a_words = lay.slots;
         if (a_words > a_cap) return mcq_fail(MCQ_EDEVICE, who, "internal: wave layout larger than its bound");
@@ -1034,14 +985,14 @@ static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_e
     McqDeviceScope dev_(c->device);
     HIP_TRY(dev_.err);
     HIP_TRY(c->h_res.reserve(n * row_bytes));
-    if (!seats && mode == MCQ_MODE_PHILOX && c->ext_small && n <= MCQ_EXT_SMALL_Q && lists_stride <= MCQ_EXT_SMALL_LISTS &&
-        most_tasks <= MCQ_EXT_SMALL_TASKS && !stream_capturing(c->stream)) {
+    if (!seats && mode == MCQ_MODE_PHILOX && c->ext_small && mcq_ext_small_fits(n, lists_stride, most_tasks) &&
+        !stream_capturing(c->stream)) {
         /* what a decision of the reference's agents asks for -- one ranged query of a thousand iterations -- in ONE
          * launch: the records in the kernel arguments, a block per query (lists laid out in its LDS), the rows into
          * pinned memory, the flag: 140 -> ~25 us per call */
         static_assert(sizeof(mcq_query_ext) == sizeof(((McqExtSmallKarg *)0)->ext[0]), "extension record in the kernel arguments");
         McqExtSmallKarg karg;
-        uint32_t n_blocks = 0, first_block[MCQ_EXT_SMALL_Q + 1], tasks[MCQ_EXT_SMALL_Q];
+        uint32_t tasks[MCQ_EXT_SMALL_Q];
         for (size_t i = 0; i < n; i++) {
             memcpy(karg.q[i], &q[i], sizeof(mcq_query));
             memcpy(karg.ext[i], &ext[i], sizeof(mcq_query_ext));
@@ -1049,18 +1000,7 @@ static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_e
             const McqQueryWords qw = mcq_query_words(q[i]);
             tasks[i] = mcq_ext_task_count(qw, mcq_ext_stream_iters(qw, er));
         }
-        uint32_t wpb = 4; /* working waves per block: the fewest with which the launch's blocks suffice */
-        for (; wpb < 16u; wpb <<= 1) {
-            uint32_t need = 0;
-            for (size_t i = 0; i < n; i++) need += tasks[i] > wpb ? (tasks[i] + wpb - 1u) / wpb : 1u;
-            if (need <= MCQ_EXT_SMALL_BLOCKS) break;
-        }
-        for (size_t i = 0; i < n; i++) {
-            const uint32_t parts = tasks[i] > wpb ? (tasks[i] + wpb - 1u) / wpb : 1u;
-            first_block[i] = n_blocks;
-            for (uint32_t p = 0; p < parts; p++) karg.blk[n_blocks++] = (uint32_t)i | (p << 8) | (parts << 16) | (wpb << 24);
-        }
-        first_block[n] = n_blocks;
+        const McqExtSmallPlan plan = mcq_ext_small_plan(tasks, (uint32_t)n, karg.blk);
         HIP_TRY(c->h_res.reserve(MCQ_EXT_SMALL_BLOCKS * row_bytes));
         int rc = flag_ready(c);
         if (rc) return rc;
@@ -1068,7 +1008,7 @@ static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_e
         const int slot = (int)(c->n_timed % mcq_ctx::kRing);
         const bool timed = c->timing;
         c->last_ms = 0.f;
-        HIP_TRY(mcq_launch_eval_ext_small(&karg, n_blocks, (mcq_result *)c->h_res.dev, seed, first_query_id, c->d_luts,
+        HIP_TRY(mcq_launch_eval_ext_small(&karg, plan.n_blocks, (mcq_result *)c->h_res.dev, seed, first_query_id, c->d_luts,
                                           (uint32_t *)c->d_done.p, (uint32_t *)c->h_flag.dev, ticket, c->stream,
                                           timed ? c->ev0[slot] : nullptr, timed ? c->ev1[slot] : nullptr, ways));
         if (timed) c->n_timed++;
@@ -1078,12 +1018,12 @@ static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_e
         const uint64_t *hr = (const uint64_t *)c->h_res.p; /* one row (13 or 22 words) per block */
         static_assert(sizeof(mcq_result) == 13 * sizeof(uint64_t), "result row");
         for (size_t i = 0; i < n; i++) /* all rows first: an undealable range leaves `out` untouched */
-            for (uint32_t b = first_block[i]; b < first_block[i + 1]; b++)
+            for (uint32_t b = plan.first_block[i]; b < plan.first_block[i + 1]; b++)
                 if (hr[(size_t)rw * b] != q[i].runs)
                     return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ext: a range cannot be dealt from the remaining cards");
         for (size_t i = 0; i < n; i++) {
             uint64_t row[kWaysWords] = {q[i].runs};
-            for (uint32_t b = first_block[i]; b < first_block[i + 1]; b++)
+            for (uint32_t b = plan.first_block[i]; b < plan.first_block[i + 1]; b++)
                 for (uint32_t k = 1; k < rw; k++) row[k] += hr[(size_t)rw * b + k];
             memcpy(static_cast<uint8_t *>(out) + i * row_bytes, row, row_bytes);
         }
@@ -1102,8 +1042,7 @@ static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_e
     HIP_TRY(hipMemcpyAsync(c->d_ext.p, hq + n * sizeof(mcq_query), n * sizeof(mcq_query_ext), hipMemcpyHostToDevice,
                            c->stream));
     c->last_ms = 0.f;
-    uint32_t grid, block;
-    pick_geometry(c, mode, total_tasks, &grid, &block);
+    const McqGeometry geo = mcq_plan_geometry(c->knobs, mode, total_tasks);
     if (mode == MCQ_MODE_REPLAY_MT19937) {
         /* the draw buffer the stream walk fills and the evaluation kernel reads (one chunk: the extended path is a
          * feature path, not a bulk path); the walk itself runs on the device: mcq_mt_parse_ext_kernel, one wave per query */
@@ -1128,7 +1067,7 @@ static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_e
         HIP_TRY(mcq_launch_mt_parse_ext((const mcq_query *)c->d_q.p, (const mcq_query_ext *)c->d_ext.p, (uint32_t)n,
                                         (uint32_t)(seed + first_query_id), (uint8_t *)c->d_draws.p, (const uint64_t *)c->d_off.p,
                                         (mcq_result *)c->d_res.p,
-                                        reinterpret_cast<uint32_t *>((uint64_t *)c->scratch[0].prefix.p + n + 2), (uint32_t)c->n_cu,
+                                        reinterpret_cast<uint32_t *>((uint64_t *)c->scratch[0].prefix.p + n + 2), c->knobs.n_cu,
                                         c->stream, rw));
     }
     if (mode == MCQ_MODE_PHILOX) { /* the candidate lists of the ranges, once per query */
@@ -1140,7 +1079,7 @@ static int eval_batch_ext_impl(mcq_ctx *c, const mcq_query *q, const mcq_query_e
     HIP_TRY(mcq_launch_eval_ext(mode, (const mcq_query *)c->d_q.p, (const mcq_query_ext *)c->d_ext.p, (uint32_t)n,
                                 (const uint64_t *)c->scratch[0].prefix.p, (mcq_result *)c->d_res.p, seed, first_query_id, c->d_luts,
                                 (const uint8_t *)c->d_draws.p, (const uint64_t *)c->d_off.p, (const uint16_t *)c->d_lists.p,
-                                (const uint32_t *)c->d_cnts.p, lists_stride, grid, block, c->stream,
+                                (const uint32_t *)c->d_cnts.p, lists_stride, geo.grid, geo.block, c->stream,
                                 t0, c->timing ? c->ev1[slot] : nullptr, ways, seats));
     if (c->timing) c->n_timed++;
     HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * row_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1188,24 +1127,11 @@ int mcq_eval_batch_ranges(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_t
     if (n > 0x7fffffffu) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: n too large");
     if (n_tables == 0 || n_tables > 0x7fffffffu / MCQ_RG_CUM_STRIDE)
         return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: n_tables must be 1 .. 2^31 / 1328");
-    /* weight of the hands of table t that are clear of a set B of table cards, by inclusion and exclusion:
-     * total - sum_{c in B} (weight of the hands that hold c) + sum_{c < c' in B} w[{c, c'}] */
-    std::vector<uint32_t> with_card(n_tables * 53u); /* per table: [52] the total, [c] the weight of the hands holding c */
-    for (size_t t = 0; t < n_tables; t++) {
-        const uint16_t *w = tables + t * MCQ_HAND_ROWS;
-        uint32_t *wc = with_card.data() + t * 53u;
-        for (uint32_t b = 1; b < 52u; b++)
-            for (uint32_t a = 0; a < b; a++) {
-                const uint32_t v = w[MCQ_HAND_INDEX(a, b)];
-                wc[a] += v;
-                wc[b] += v;
-                wc[52] += v;
-            }
-    }
+    std::vector<uint32_t> with_card(n_tables * MCQ_RG_WITH_CARD_STRIDE);
+    for (size_t t = 0; t < n_tables; t++) mcq_ranges_with_card(tables + t * MCQ_HAND_ROWS, with_card.data() + t * MCQ_RG_WITH_CARD_STRIDE);
     uint64_t total_tasks = 0;
     char buf[200];
     std::vector<uint32_t> price(n); /* estimated whole trials per iteration, for the cost axis only */
-    std::vector<double> held(10u * 52u); /* per seat: P(its hand holds card c), given that it is clear of the table */
     for (size_t i = 0; i < n; i++) {
         const McqQueryWords qw = mcq_query_words(q[i]);
         if (!mcq_ranges_query_valid(qw)) {
@@ -1213,51 +1139,17 @@ int mcq_eval_batch_ranges(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_t
                      "n_players 2..10, reserved 0, runs >= 1)", i);
             return mcq_fail(MCQ_EINVAL, buf);
         }
-        for (uint32_t s = 0; s < qw.n_players(); s++) {
-            const uint32_t t = seat_table[i * 10u + s];
-            if (t >= n_tables) {
-                snprintf(buf, sizeof buf, "mcq_eval_batch_ranges: record %zu, seat %u names table %u of %zu", i, s, t, n_tables);
-                return mcq_fail(MCQ_EINVAL, buf);
-            }
-            const uint32_t *wc = with_card.data() + (size_t)t * 53u;
-            const uint16_t *w = tables + (size_t)t * MCQ_HAND_ROWS;
-            uint64_t blocked = 0; /* weight of the hands that hold a table card */
-            for (uint32_t k = 0; k < qw.n_board(); k++) {
-                const uint32_t ck = qw.card(2u + k);
-                blocked += wc[ck];
-                for (uint32_t j = 0; j < k; j++) {
-                    const uint32_t cj = qw.card(2u + j);
-                    blocked -= w[MCQ_HAND_INDEX((cj < ck ? cj : ck), (cj < ck ? ck : cj))];
-                }
-            }
-            if (blocked >= wc[52]) {
-                snprintf(buf, sizeof buf, "mcq_eval_batch_ranges: record %zu, seat %u: table %u has no hand of positive weight "
-                         "clear of the table cards", i, s, t);
-                return mcq_fail(MCQ_EINVAL, buf);
-            }
-            const double clear = (double)(wc[52] - blocked);
-            const uint64_t bm = mcq_ranges_board_mask(qw);
-            for (uint32_t c = 0; c < 52u; c++) {
-                uint64_t with_c = (bm >> c) & 1u ? 0u : wc[c];
-                if (with_c)
-                    for (uint32_t k = 0; k < qw.n_board(); k++) {
-                        const uint32_t ck = qw.card(2u + k);
-                        with_c -= w[MCQ_HAND_INDEX((c < ck ? c : ck), (c < ck ? ck : c))];
-                    }
-                held[s * 52u + c] = (double)with_c / clear;
-            }
+        const McqRangesPrice pr = mcq_ranges_price(tables, n_tables, with_card.data(), qw, seat_table + i * 10u);
+        if (pr.refused == MCQ_RG_REFUSED_TABLE) {
+            snprintf(buf, sizeof buf, "mcq_eval_batch_ranges: record %zu, seat %u names table %u of %zu", i, pr.seat, pr.table, n_tables);
+            return mcq_fail(MCQ_EINVAL, buf);
         }
-        /* P(no two seats share a card) as if the pairs of seats collided independently, and a pair with probability
-         * sum_c P(s holds c) P(s' holds c) (a shared hand counts twice: an overestimate, bounded below) */
-        double accept = 1.0;
-        for (uint32_t s = 1; s < qw.n_players(); s++)
-            for (uint32_t r = 0; r < s; r++) {
-                double hit = 0.0;
-                for (uint32_t c = 0; c < 52u; c++) hit += held[s * 52u + c] * held[r * 52u + c];
-                accept *= hit < 0.99 ? 1.0 - hit : 0.01;
-            }
-        const double est = accept > 1.0 / MCQ_RG_MAX_PRICE ? 1.0 / accept : (double)MCQ_RG_MAX_PRICE;
-        price[i] = (uint32_t)(est + 0.5);
+        if (pr.refused) {
+            snprintf(buf, sizeof buf, "mcq_eval_batch_ranges: record %zu, seat %u: table %u has no hand of positive weight "
+                     "clear of the table cards", i, pr.seat, pr.table);
+            return mcq_fail(MCQ_EINVAL, buf);
+        }
+        price[i] = pr.price;
         total_tasks += mcq_ranges_task_count(qw);
     }
     if (total_tasks > 0xfffffff0ull) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: too many iterations in one call");
@@ -1279,13 +1171,12 @@ int mcq_eval_batch_ranges(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_t
     HIP_TRY(hipMemcpyAsync(c->d_cnts.p, seat_table, n * 10u * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync((uint32_t *)c->d_cnts.p + n * 10u, price.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     c->last_ms = 0.f;
-    uint32_t grid, block;
-    pick_geometry(c, MCQ_MODE_PHILOX, total_tasks, &grid, &block);
+    const McqGeometry geo = mcq_plan_geometry(c->knobs, MCQ_MODE_PHILOX, total_tasks);
     const int slot = (int)(c->n_timed % mcq_ctx::kRing);
     HIP_TRY(mcq_launch_eval_ranges((const mcq_query *)c->d_q.p, (const uint32_t *)c->d_cnts.p,
                                    (const uint32_t *)c->d_cnts.p + n * 10u, (const uint16_t *)c->d_lists.p,
                                    (uint32_t)n_tables, (uint32_t *)c->d_draws.p, (uint32_t)n, (uint64_t *)c->scratch[0].prefix.p,
-                                   (mcq_result *)c->d_res.p, seed, first_query_id, c->d_luts, grid, block, c->stream,
+                                   (mcq_result *)c->d_res.p, seed, first_query_id, c->d_luts, geo.grid, geo.block, c->stream,
                                    c->timing ? c->ev0[slot] : nullptr, c->timing ? c->ev1[slot] : nullptr));
     if (c->timing) c->n_timed++;
     HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * row_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1357,7 +1248,7 @@ int mcq_showdown(mcq_ctx *c, const uint8_t *hands, size_t n_tables, int n_player
         HIP_TRY(mcq_launch_showdown(dp + a * per_table, (uint32_t)(b - a), (uint32_t)n_players, c->d_luts, dp + off_w + a,
                                     dp + off_t + a, keys ? reinterpret_cast<uint32_t *>(dp + off_k) + a * n_players : nullptr,
                                     static_cast<uint32_t *>(c->h_flag.dev) + 1, (uint32_t *)c->d_done.p,
-                                    (uint32_t *)c->h_flag.dev, b == n_tables ? ticket : 0u, (uint32_t)c->n_cu, c->stream));
+                                    (uint32_t *)c->h_flag.dev, b == n_tables ? ticket : 0u, c->knobs.n_cu, c->stream));
     }
     rc = wait_ticket(c, ticket, nullptr);
     if (rc) return rc;
@@ -1372,8 +1263,7 @@ int mcq_showdown(mcq_ctx *c, const uint8_t *hands, size_t n_tables, int n_player
 
 /* the CU count mcq_exact_plan and mcq_exact_ext_plan size a grid by: the device's, or MCQ_EXACT_CU where that is smaller */
 static uint32_t exact_cu(const mcq_ctx *c) {
-    const uint32_t n_cu = (uint32_t)c->n_cu;
-    return c->exact_cu && c->exact_cu < n_cu ? c->exact_cu : n_cu;
+    return c->exact_cu && c->exact_cu < c->knobs.n_cu ? c->exact_cu : c->knobs.n_cu;
 }
 
 int mcq_exact_batch(mcq_ctx *c, const mcq_query *q, size_t n, int law, mcq_result *out) {

@@ -4,10 +4,14 @@
 #include <stdint.h>
 
 #include "../../include/mcq.h"
+#include "mcq_plan.hpp"
 
 struct McqTables;
 
 #define MCQ_INTERNAL_MODE_UNIFORM 2 /* MCQ_MODE_PHILOX with the context's dealing law set to MCQ_LAW_UNIFORM */
+
+/* resident blocks per CU of the bulk evaluation kernel of a mode at `block` threads (McqPlanKnobs::occ) */
+hipError_t mcq_eval_occupancy(int mode, int block, int *blocks_per_cu);
 
 hipError_t mcq_launch_prep(const mcq_query *d_q, uint32_t n, mcq_result *d_res, uint64_t *d_prefix, uint32_t part,
                            uint32_t n_parts, uint32_t n_cu, uint32_t split_max, hipStream_t s,
@@ -17,37 +21,13 @@ hipError_t mcq_launch_eval(int mode, const mcq_query *d_q, uint32_t n, const uin
                            const uint64_t *d_draw_off, uint32_t grid, uint32_t block, uint32_t split, uint32_t part,
                            uint32_t n_parts, hipStream_t s, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr, uint32_t work_wpb = 0,
                            bool ways = false /* d_res holds mcq_result_ways rows: the instantiation that splits the ties */);
-/* exact enumeration (n_players <= 3), any number of queries per launch: one job per query (blockIdx.y), all of the same
- * kind -- two opponents or fewer; every job adds into its zeroed row d_rows[job.row] */
-struct McqExactJob {
-    uint32_t rec[4];                        /* the 16-byte query record */
-    uint32_t n_boards, slices, row, grid;   /* table completions, cuts of the first-opponent loop, result row, blocks that work */
-};
-void mcq_exact_plan(const mcq_query *q, uint32_t row, uint32_t n_cu, McqExactJob *job);
-/* exact enumeration of extended queries (mcq_exact_ext.hpp): one job per query, one launch per kind = random opponents
- * (0, 1, 2); the extension records lie in device-visible memory, 76 words each.  Kinds 0 and 1 add into the zeroed row
- * d_rows[job.row], kind 2 into the zeroed per-first-hand sums d_h1[h1_off + 12 * hand] (hand < C(L, 2)). */
-struct McqExactExtJob {
-    uint32_t rec[4];                      /* the 16-byte query record */
-    uint32_t ext, n_boards, row, grid;    /* its extension record, table completions, result row, blocks that work */
-    uint32_t groups, h1_off, pad_[2];     /* kind 2: blocks per completion (1024 first hands each), offset of its sums */
-};
-/* plan of one job (L = |R|, the cards the opponents are dealt from) -> its grid */
-uint32_t mcq_exact_ext_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t kind, uint32_t L, uint32_t h1_off,
-                            uint32_t n_cu, McqExactExtJob *job);
+/* exact enumeration: the jobs are planned by mcq_exact_plan, mcq_exact_ext_plan (one launch per kind) and mcq_exact_hero_plan
+ * (mcq_plan.hpp) */
 hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, uint32_t kind,
                                 const uint32_t *d_ext, int law, mcq_result *d_rows, unsigned long long *d_h1,
                                 const McqTables *d_luts, hipStream_t s,
                                 bool ways = false /* kinds 0 and 1: d_rows holds zeroed mcq_result_ways rows */,
                                 bool seats = false /* kind 0: d_rows holds zeroed mcq_result_seats rows */);
-/* hero-range enumeration (mcq_exact_hero.hpp, preflop: mcq_exact_hero_pre.hpp): one job per query, L = |D|, n_allowed = its
- * allowed hero hands (> 0); d_rows holds zeroed [MCQ_HAND_ROWS] mcq_result rows per query, job->row = the query's index.
- * preflop: the completions go out in launches of `slice`, each over [lo, hi) with hi - lo <= slice, all adding into the same
- * rows; the plan returns 0 when a block would own more completions per launch than a thread's 32-bit sums allow
- * (MCQ_XP_MAX_OWNED; the 64-bit sums of the weighted kernel need no bound, the plan is the same).  Postflop: one launch,
- * slice, lo and hi are not read. */
-uint32_t mcq_exact_hero_plan(bool preflop, const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed,
-                             uint32_t n_cu, uint32_t slice, McqExactExtJob *job);
 /* weighted: a weight per hand, uniform law (law is not read); d_wts holds 2 * MCQ_HAND_ROWS uint16 per query -- the opponent's
  * table, then the hero's, which is read only with hero_w (else every hand of his classes weighs 1).  n_allowed is then
  * counted from the hero's folded table. */
@@ -89,17 +69,7 @@ hipError_t mcq_launch_exact(const McqExactJob *d_jobs, uint32_t n_jobs, uint32_t
 hipError_t mcq_launch_showdown(const uint8_t *hands, uint32_t n_tables, uint32_t n_players, const McqTables *d_luts,
                                uint8_t *winner, uint8_t *wtype, uint32_t *keys, uint32_t *bad, uint32_t *d_done,
                                uint32_t *done_flag, uint32_t ticket, uint32_t n_cu, hipStream_t s);
-/* a few extended queries in one launch (mcq_eval_ext_small_kernel): the queries and their extension records travel in
- * the kernel arguments */
-#define MCQ_EXT_SMALL_Q 8u      /* queries per launch (8 x 320 B of kernel arguments) */
-#define MCQ_EXT_SMALL_LISTS 6u  /* candidate lists per query that fit the block's LDS (6 x 2704 x 2 B) */
-#define MCQ_EXT_SMALL_TASKS 64u /* wave tasks per query */
-#define MCQ_EXT_SMALL_BLOCKS 32u /* blocks per launch: a query is cut into parts of 4, 8 or 16 wave tasks, whatever fits */
-struct McqExtSmallKarg {
-    uint32_t q[MCQ_EXT_SMALL_Q][4];
-    uint32_t ext[MCQ_EXT_SMALL_Q][76];
-    uint32_t blk[MCQ_EXT_SMALL_BLOCKS]; /* block b: query | part << 8 | parts << 16 | waves that take tasks << 24; its row goes to row b of the result buffer */
-};
+/* a few extended queries in one launch (mcq_eval_ext_small_kernel, planned by mcq_ext_small_plan): n_blocks rows come back */
 hipError_t mcq_launch_eval_ext_small(const McqExtSmallKarg *karg, uint32_t n_blocks, mcq_result *h_res_dev, uint64_t seed,
                                      uint64_t first_qid, const McqTables *d_luts, uint32_t *d_done, uint32_t *done_flag,
                                      uint32_t ticket, hipStream_t s, hipEvent_t t0, hipEvent_t t1,

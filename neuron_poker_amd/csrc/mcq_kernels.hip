@@ -257,6 +257,7 @@ __global__ __launch_bounds__(1024) void mcq_prep_kernel(const mcq_query *__restr
 // producer fills block b + 1 while block b is parsed).  The parser tells the producer at which barrier to stop.
 // Queries are handed out through an atomic counter (their lengths differ).  7.7 KB of LDS per pair: 16 pairs per CU.
 constexpr int kMtBlock = 128;
+constexpr uint32_t kMtBlocksPerCu = 16u; /* grid cap of the launch: what a CU holds at once, 16 work-groups */
 struct McqMtPairWave { /* what mcq_mt_batch touches: the position tables and the ring as in McqMtWave, the words as bytes */
     uint32_t ptab[MCQ_MT_POSITIONS];
     uint8_t ring[(MCQ_MT_MAX_DRAWS + 1u) * MCQ_MT_ROW];
@@ -335,6 +336,7 @@ __global__ __launch_bounds__(kMtBlock) void mcq_mt_parse_kernel(const mcq_query 
 // stage by stage).  6.5 KB of LDS per wave.  A query whose range cannot be dealt gets passes = UINT64_MAX.
 // ROW_WORDS: as mcq_prep_kernel (the walk itself, and what it stores, are the same for either row).
 constexpr int kMtExtBlock = 256;
+constexpr uint32_t kMtExtBlocksPerCu = 5u; /* grid cap of the launch: what fits a CU at once, 27 KB of LDS per block */
 template <uint32_t ROW_WORDS>
 __global__ __launch_bounds__(kMtExtBlock) void mcq_mt_parse_ext_kernel(const mcq_query *__restrict__ queries,
                                                                     const mcq_query_ext *__restrict__ ext, uint32_t n, uint32_t seed32,
@@ -764,6 +766,7 @@ __global__ __launch_bounds__(kMtbParseBlock) void mcq_mtb_parse_kernel(const mcq
 // ---------------------------------------------------------------------------------------------- multi-GPU helper
 // dst[i] += src[i]: adds the tally matrix of a second shard on the same device (mcq_multi.cpp) -- HBM-bound
 // streaming, two 16-byte loads and one store per lane.
+constexpr uint64_t kAddMaxBlocks = 2048; /* grid cap of the launch: the lanes stride over what is left */
 __global__ __launch_bounds__(256) void mcq_add_u64_kernel(uint64_t *__restrict__ dst, const uint64_t *__restrict__ src,
                                                           uint64_t n) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -805,6 +808,7 @@ __device__ __forceinline__ void mcq_block_done(uint32_t *__restrict__ done, vola
 // host memory, leaves the HBM rows zero for the next call and raises a flag the host is polling -- instead of a
 // D2H copy, a stream synchronisation (24 us on this pool against 7.5 us for a flag, tools/launch_floor.hip) and a
 // memset.  16-byte words; the last block to finish (device counter, reset for the next launch) writes the flag.
+constexpr uint64_t kPublishMaxBlocks = 64; /* grid cap of the launch (few rows: every block counts itself in at `done`) */
 __global__ __launch_bounds__(256) void mcq_publish_kernel(ulonglong2 *__restrict__ d_rows, ulonglong2 *__restrict__ h_rows,
                                                           uint64_t n_words16, uint32_t *__restrict__ done,
                                                           volatile uint32_t *done_flag, uint32_t ticket) {
@@ -1993,7 +1997,8 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_small_kernel(McqExtSma
     __shared__ uint32_t wave_tot[kWaves];
     __shared__ unsigned long long partial[kWaves][Row::kLanes];
     __shared__ uint32_t s_failed;
-    const uint32_t blk = karg.blk[blockIdx.x], qi = blk & 0xFFu, part = (blk >> 8) & 0xFFu, parts = (blk >> 16) & 0xFFu, wpb = blk >> 24;
+    const McqExtSmallBlock me = mcq_ext_small_unpack(karg.blk[blockIdx.x]);
+    const uint32_t qi = me.query, part = me.part, parts = me.parts, wpb = me.wpb;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
     if (tid < 64) cards[tid] = mcq_card(tid < 52 ? tid : 0u);
     if (tid >= 4u && tid < 4u + MCQ_EXT_WORDS) s_rec[tid] = karg.ext[qi][tid - 4u];
@@ -2109,6 +2114,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_small_kernel(McqExtSma
 // validation on the device, as mcq_prep_kernel does for queries.  With ticket != 0 the last block to finish raises the
 // host's completion flag behind a system-scope release, as mcq_publish_kernel does.
 constexpr int kShowBlock = 256;
+constexpr uint32_t kShowBlocksPerCu = 5u; /* grid cap of the launch: 30 KB of LDS per block, five blocks per CU */
 __global__ __launch_bounds__(kShowBlock) void mcq_showdown_kernel(const uint8_t *__restrict__ hands, uint32_t n_tables,
                                                                   uint32_t n_players, const McqTables *__restrict__ g_tab,
                                                                   uint8_t *__restrict__ winner, uint8_t *__restrict__ wtype,
@@ -2963,7 +2969,7 @@ hipError_t mcq_launch_mt_parse(const mcq_query *d_q, uint32_t n, uint32_t seed32
                                mcq_result *d_res, uint32_t *d_counter, uint32_t n_cu, hipStream_t s, uint32_t row_words) {
     if (n == 0) return hipSuccess;
     uint32_t blocks = n; /* one pair of waves per query */
-    if (blocks > 16u * n_cu) blocks = 16u * n_cu; /* what a CU holds at once: 16 work-groups */
+    if (blocks > kMtBlocksPerCu * n_cu) blocks = kMtBlocksPerCu * n_cu;
     hipLaunchKernelGGL(mcq_mt_parse_kernel, dim3(blocks), dim3(kMtBlock), 0, s, d_q, n, seed32, d_draws, d_draw_off, d_res,
                        d_counter, row_words);
     return hipGetLastError();
@@ -3013,7 +3019,7 @@ hipError_t mcq_launch_mt_parse_ext(const mcq_query *d_q, const mcq_query_ext *d_
     if (n == 0) return hipSuccess;
     if (row_words != 13u && row_words != 22u) return hipErrorInvalidValue;
     uint32_t blocks = (n + kMtExtBlock / 64 - 1) / (kMtExtBlock / 64);
-    if (blocks > 5u * n_cu) blocks = 5u * n_cu; /* what fits a CU at once: 27 KB of LDS per block */
+    if (blocks > kMtExtBlocksPerCu * n_cu) blocks = kMtExtBlocksPerCu * n_cu;
     if (row_words == 13u)
         hipLaunchKernelGGL(mcq_mt_parse_ext_kernel<13u>, dim3(blocks), dim3(kMtExtBlock), 0, s, d_q, d_ext, n, seed32, d_draws,
                            d_draw_off, d_res, d_counter);
@@ -3029,7 +3035,7 @@ hipError_t mcq_launch_publish(mcq_result *d_rows, mcq_result *h_rows_dev, uint64
     if (n_rows == 0 || (n_rows & 1ull)) return hipErrorInvalidValue; /* whole 16-byte words: the caller rounds the rows up */
     const uint64_t words = n_rows * row_bytes / 16u;
     uint64_t blocks = (words + 1023u) / 1024u; /* four words per thread */
-    if (blocks > 64u) blocks = 64u;
+    if (blocks > kPublishMaxBlocks) blocks = kPublishMaxBlocks;
     hipLaunchKernelGGL(mcq_publish_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, reinterpret_cast<ulonglong2 *>(d_rows),
                        reinterpret_cast<ulonglong2 *>(h_rows_dev), words, d_done, done_flag, ticket);
     return hipGetLastError();
@@ -3039,7 +3045,7 @@ hipError_t mcq_launch_add_u64(uint64_t *d_dst, const uint64_t *d_src, uint64_t n
     if (n == 0) return hipSuccess;
     uint64_t blocks = (n / 2 + 255) / 256;
     if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
+    if (blocks > kAddMaxBlocks) blocks = kAddMaxBlocks;
     hipLaunchKernelGGL(mcq_add_u64_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, d_dst, d_src, n);
     return hipGetLastError();
 }
@@ -3112,28 +3118,10 @@ hipError_t mcq_launch_showdown(const uint8_t *hands, uint32_t n_tables, uint32_t
                                uint32_t *done_flag, uint32_t ticket, uint32_t n_cu, hipStream_t s) {
     if (n_tables == 0 || n_players < 1 || n_players > 10) return hipErrorInvalidValue;
     uint32_t grid = (n_tables + kShowBlock - 1) / kShowBlock;
-    if (grid > 5u * n_cu) grid = 5u * n_cu; /* 30 KB of LDS per block: five blocks per CU */
+    if (grid > kShowBlocksPerCu * n_cu) grid = kShowBlocksPerCu * n_cu;
     hipLaunchKernelGGL(mcq_showdown_kernel, dim3(grid), dim3(kShowBlock), 0, s, hands, n_tables, n_players, d_luts, winner,
                        wtype, keys, bad, d_done, done_flag, ticket);
     return hipGetLastError();
-}
-
-void mcq_exact_plan(const mcq_query *q, uint32_t row, uint32_t n_cu, McqExactJob *job) {
-    __builtin_memcpy(job->rec, q, 16);
-    const uint32_t L = 50u - q->n_board, k = 5u - q->n_board;
-    job->n_boards = mcq_exact_binom(L, k);
-    job->row = row;
-    if (q->n_players == 3) {
-        /* few completions (turn, river): cut the first-opponent loop so that every wave has work */
-        uint32_t slices = 1;
-        while (slices < 64u && (uint64_t)job->n_boards * slices < 6ull * n_cu * 4ull) slices *= 2u;
-        const uint64_t units = (uint64_t)job->n_boards * slices;
-        job->slices = slices;
-        job->grid = (uint32_t)((units + 5u) / 6u < n_cu ? (units + 5u) / 6u : n_cu);
-    } else {
-        job->slices = 1u;
-        job->grid = (job->n_boards + 15u) / 16u < n_cu ? (job->n_boards + 15u) / 16u : n_cu;
-    }
 }
 
 hipError_t mcq_launch_exact(const McqExactJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, bool two_opp, int law,
@@ -3145,31 +3133,6 @@ hipError_t mcq_launch_exact(const McqExactJob *d_jobs, uint32_t n_jobs, uint32_t
     else
         hipLaunchKernelGGL(mcq_exact_kernel<false>, dim3(max_grid, n_jobs), dim3(1024), 0, s, d_jobs, law, d_rows, d_luts);
     return hipGetLastError();
-}
-
-uint32_t mcq_exact_ext_plan(const mcq_query *q, uint32_t ext, uint32_t row, uint32_t kind, uint32_t L, uint32_t h1_off,
-                            uint32_t n_cu, McqExactExtJob *job) {
-    __builtin_memcpy(job->rec, q, 16);
-    const uint32_t k = 5u - q->n_board, n_rp = L * (L - 1u) / 2u;
-    job->ext = ext;
-    job->n_boards = mcq_exact_binom(L, k);
-    job->row = row;
-    job->h1_off = h1_off;
-    job->groups = 1u;
-    if (kind == 0u) {
-        const uint32_t blocks = (job->n_boards + 1023u) / 1024u;
-        job->grid = blocks < n_cu ? blocks : n_cu;
-    } else if (kind == 1u) {
-        const uint32_t blocks = (job->n_boards + 15u) / 16u;
-        job->grid = blocks < n_cu ? blocks : n_cu;
-    } else {
-        job->groups = (n_rp + 1023u) / 1024u;
-        uint32_t per = n_cu / job->groups;
-        if (per < 1u) per = 1u;
-        if (per > job->n_boards) per = job->n_boards;
-        job->grid = per * job->groups;
-    }
-    return job->grid;
 }
 
 hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid, uint32_t kind,
@@ -3193,24 +3156,6 @@ hipError_t mcq_launch_exact_ext(const McqExactExtJob *d_jobs, uint32_t n_jobs, u
     }
 #undef MCQ_LAUNCH_XX
     return hipGetLastError();
-}
-
-uint32_t mcq_exact_hero_plan(bool preflop, const mcq_query *q, uint32_t ext, uint32_t row, uint32_t L, uint32_t n_allowed,
-                             uint32_t n_cu, uint32_t slice, McqExactExtJob *job) {
-    __builtin_memcpy(job->rec, q, 16);
-    job->ext = ext;
-    job->n_boards = mcq_exact_binom(L, 5u - q->n_board);
-    job->row = row;
-    job->h1_off = 0u;
-    job->groups = (n_allowed + 1023u) / 1024u;
-    uint32_t per = n_cu / job->groups;
-    if (per < 1u) per = 1u;
-    if (preflop && per > slice) per = slice;
-    if (per > job->n_boards) per = job->n_boards;
-    job->grid = per * job->groups;
-    /* preflop, a thread's 32-bit sums: the completions one block owns in a launch */
-    if (preflop && (slice == 0u || mcq_exact_hero_pre_owned(slice, per) > MCQ_XP_MAX_OWNED)) return 0u;
-    return job->grid;
 }
 
 hipError_t mcq_launch_exact_hero(bool preflop, bool weighted, const McqExactExtJob *d_jobs, uint32_t n_jobs, uint32_t max_grid,

@@ -375,7 +375,8 @@ def enumerate_all_in(rec, law, threads=16):
     return _enum[key]
 
 
-# ---- mirrors of mcq_exact_plan / mcq_exact_ext_plan (csrc/mcq_kernels.hip) and of how the kernels walk a job
+# ---- mirrors of mcq_exact_plan / mcq_exact_ext_plan (csrc/mcq_plan.hpp; tests/test_plan_host.py holds them to the header)
+#      and of how the kernels walk a job
 def binom(n, k):
     from math import comb
     return comb(n, k)

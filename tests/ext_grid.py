@@ -236,14 +236,15 @@ def expect(recs, fq, seed=SEED, seats=True):
 
 
 # ---- mirrors of the host layer's and the kernels' choices
-SMALL_Q, SMALL_LISTS, SMALL_TASKS, SMALL_BLOCKS = 8, 6, 64, 32   # MCQ_EXT_SMALL_* (csrc/mcq_internal.hpp)
+SMALL_Q, SMALL_LISTS, SMALL_TASKS, SMALL_BLOCKS = 8, 6, 64, 32   # MCQ_EXT_SMALL_* (csrc/mcq_plan.hpp)
 STAGE_ENTRIES, STAGE_LISTS = 18 * 1024, 96                        # kStageEntries, kStageLists of mcq_eval_ext_kernel
 BLOCK_WAVES = 16                                                   # kBlock / 64
 
 
 def small_plan(recs):
     """eval_batch_ext_impl's choice for the hero and ways rows under the default knobs: None = the general path, else
-    (wpb, parts per query, blocks) of the one-launch kernel."""
+    (wpb, parts per query, blocks) of the one-launch kernel.  The mirror of mcq_ext_small_fits and mcq_ext_small_plan
+    (csrc/mcq_plan.hpp); tests/test_plan_host.py holds the two together."""
     if len(recs) > SMALL_Q or max(max(r.lists for r in recs), 1) > SMALL_LISTS or max(r.tasks for r in recs) > SMALL_TASKS:
         return None
     parts = lambda r, wpb: -(-r.tasks // wpb) if r.tasks > wpb else 1   # noqa: E731
@@ -255,7 +256,8 @@ def small_plan(recs):
 
 
 def geometry(total_tasks, n_cu, occ):
-    """pick_geometry for the extended evaluation kernel -> (grid, waves per block)."""
+    """mcq_plan_geometry (csrc/mcq_plan.hpp) for the extended evaluation kernel -> (grid, waves per block);
+    tests/test_plan_host.py holds the two together."""
     wpb = min(max(-(-total_tasks // n_cu), 1), BLOCK_WAVES)
     blocks = -(-total_tasks // wpb)
     grid = blocks if blocks < n_cu else (n_cu * occ if wpb == BLOCK_WAVES else n_cu)

@@ -75,7 +75,7 @@ def tasks(q):
 
 def pick_split(q, n_cu, split_max):
     """the host's cut for a batch (mcq_pick_split): as fine as split_max allows while 2^split times the tasks stay
-    within eight per CU and 512 per query"""
+    within eight per CU and 512 per query.  tests/test_plan_host.py holds this mirror to the header."""
     total, most = int(tasks(q).sum()), int(tasks(q).max())
     s = 0
     while s < split_max and total << (s + 1) <= 8 * n_cu and most << (s + 1) <= 512:

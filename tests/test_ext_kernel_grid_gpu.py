@@ -8,8 +8,9 @@ tests/ext_grid.py (whose expected rows tests/test_ext_kernel_grid_host.py pins t
     per query, exactly 32 blocks, streams of 2 and of 16;
   * the fences between the two (6 / 7 lists, 64 / 65 tasks, 8 / 9 queries).
 Which path, which cut and which list placement a batch gets is not observable from outside: the choices of
-eval_batch_ext_impl (csrc/mcq_host.cpp) and of the kernel's staging step are mirrored in tests/ext_grid.py and the
-intended value is asserted for every batch."""
+eval_batch_ext_impl (through csrc/mcq_plan.hpp) and of the kernel's staging step are mirrored in tests/ext_grid.py
+(held to the headers on the host by tests/test_plan_host.py and tests/test_axis_host.py) and the intended value is
+asserted for every batch."""
 import numpy as np
 import pytest
 

@@ -105,6 +105,19 @@ def test_one_launch_mirror_gives_the_intended_cuts():
         assert (G.small_plan(recs) is not None) == small, name
 
 
+def test_one_launch_header_gives_the_intended_cuts():
+    """The same expectations against the host layer's own plan (csrc/mcq_plan.hpp through tests/hostsim_plan)."""
+    from tests import hostsim_plan as P
+    fits = lambda recs: P.ext_small_fits(len(recs), max(max(r.lists for r in recs), 1), max(r.tasks for r in recs))   # noqa: E731
+    for name, (recs, _, want) in G.small_batches().items():
+        assert fits(recs), name
+        wpb, blocks, first = P.ext_small_plan([r.tasks for r in recs])
+        assert (wpb, len(blocks)) == want, (name, wpb, len(blocks))
+        assert [first[i + 1] - first[i] for i in range(len(recs))] == G.small_plan(recs)[1], name
+    for name, (recs, _, small) in G.fence_batches().items():
+        assert fits(recs) == small, name
+
+
 def test_list_placement_mirror_gives_the_intended_branches():
     """At 256 compute units, one or two resident blocks per CU (the GPU file asserts the same at the device's count)."""
     verdicts = {name: G.placement_verdicts(recs, 256)[0] for name, (recs, _) in G.placement_batches().items()}

@@ -645,7 +645,7 @@ def test_native_table_driver_on_gpu_equals_stepwise_batches(eng):
 
 
 def test_small_batch_task_split_does_not_change_tallies():
-    """Small batches cut each 1024-iteration task into 2^split sub-tasks (pick_geometry in csrc/mcq_host.cpp);
+    """Small batches cut each 1024-iteration task into 2^split sub-tasks (mcq_plan_geometry in csrc/mcq_plan.hpp);
     every setting of the cut must give the oracle's tallies, in both modes, for ragged run counts."""
     rng = np.random.default_rng(99)
     runs = [1000, 1, 17, 5000, 1024, 1025, 100000, 63, 64, 65, 2048, 999]

@@ -12,8 +12,9 @@ highest cards of the deck, a table that holds the deck's top card, ten players o
 registers full) and two players on a full table (no scan of a full register at all).
 
 * 16 384 + 17 runs each and one further query of 100 000 runs: above the one-launch path's eight tasks, with a ragged last
-  task.  That batch is 778 tasks, which the host cuts into sub-tasks (mcq_pick_split: up to 8 x 256 CUs / 2) -- the
-  small-batch cut of the bulk kernel; the batch twice over is 1 556 tasks and runs uncut -- the bulk instance proper.
+  task.  That batch is 778 tasks, which the host cuts into sub-tasks (mcq_pick_split through mcq_plan_geometry,
+  csrc/mcq_plan.hpp, held to its mirror by tests/test_plan_host.py: up to 8 x 256 CUs / 2) -- the small-batch cut of the
+  bulk kernel; the batch twice over is 1 556 tasks and runs uncut -- the bulk instance proper.
 * the same cells at 1 000 runs: the one-launch kernel (general form, see above).
 * under both dealing laws: Engine.eval_batch == the oracle's CTR mode bit for bit; Engine.eval_batch_ways: its plain row ==
   eval_batch byte for byte, its tie_ways == the host build of the lane code; the device-pointer entries == the host entries.

@@ -4,8 +4,8 @@ Part B -- many tasks per wave.  WaveTallyWays keeps the nine tie_ways counters a
 MCQ_WAYS_TALLY_TASKS = 63 tasks of one query; at the full grid a wave sees 63 tasks of one query only from about 2.6e8
 iterations on, which no CPU reference reaches bit for bit.  MCQ_GRID_CAP=1 launches the shipped kernels
 with ONE block, so a query of a million iterations is some 250 tasks per wave, and the oracle still follows.  The one
-block has as many working waves as pick_geometry gives the launch: 4 for 1008 tasks, 5 for 1124, 8 for 2016 (host
-entry, one query), 16 for the batch of twelve and for the device entry.  So 1 032 192 and 2 064 384 iterations are 252 =
+block has as many working waves as mcq_plan_geometry gives the launch: 4 for 1008 tasks, 5 for 1124, 8 for 2016 (host
+entry, one query; csrc/mcq_plan.hpp, pinned without a GPU by tests/test_plan_host.py), 16 for the batch of twelve and for the device entry.  So 1 032 192 and 2 064 384 iterations are 252 =
 4 x 63 tasks for every wave -- the flush falls on the wave's last task and the end-of-query flush finds a clean tally --
 and 1 150 000 iterations are 224 or 225 tasks per wave: three flushes, then a tail of 35 or 36 tasks.
 
@@ -41,9 +41,9 @@ BASE = (1 << 33) + 4001                  # query ids: above 2^32, so the parity 
 LAST_TASK, MID, TWICE = 63 * 16 * 1024, 1150000, 2 * 63 * 16 * 1024
 CAP_RUNS = (LAST_TASK, MID, TWICE)
 # "The flush falls on the wave's last task" needs the wave's share of the query to be a whole multiple of 63 tasks.  How
-# many waves of the one block take work is pick_geometry's choice (csrc/mcq_host.cpp: 4 and 8 today); 63 x 16 tasks and
+# many waves of the one block take work is mcq_plan_geometry's choice (csrc/mcq_plan.hpp: 4 and 8 today); 63 x 16 tasks and
 # twice that split into whole multiples of 63 for every power of two up to the block's 16 waves, and for no other
-# count: if pick_geometry ever picks one, these two run counts must follow it.
+# count: if mcq_plan_geometry ever picks one, these two run counts must follow it.
 assert all((r // 1024) % (63 * w) == 0 and r % 1024 == 0 for r in (LAST_TASK, TWICE) for w in (1, 2, 4, 8, 16))
 SAT_HERO, SAT_BOARD = ("2C", "3D"), ("KC", "KD", "KH", "KS", "AS")
 # B2: the cases in which k varies, then quads on the table with hero above them and a wheel on the table, at 6 players
