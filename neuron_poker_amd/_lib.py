@@ -82,6 +82,61 @@ def _share_hip_runtime_with_torch():
         C.CDLL(cand, mode=C.RTLD_GLOBAL)
 
 
+# The prototypes of include/mcq.h, in the header's order: (name, return type, argument types...).  Every pointer is a
+# c_void_p (None = NULL), mcq_version's excepted.  tests/test_binding.py holds the table to the header type by type.
+_I, _U32, _U64, _SZ, _P = C.c_int, C.c_uint32, C.c_uint64, C.c_size_t, C.c_void_p
+_PROTOTYPES = (
+    ("mcq_device_count", _I),
+    ("mcq_create", _P, _I, _I),
+    ("mcq_destroy", None, _P),
+    ("mcq_eval_batch", _I, _P, _P, _SZ, _U64, _U64, _I, _P),
+    ("mcq_eval_one", _I, _P, _P, _U64, _I, _P),
+    ("mcq_eval_batch_ext", _I, _P, _P, _P, _SZ, _U64, _U64, _I, _P),
+    ("mcq_eval_batch_ext_ways", _I, _P, _P, _P, _SZ, _U64, _U64, _I, _P),
+    ("mcq_eval_batch_ext_seats", _I, _P, _P, _P, _SZ, _U64, _U64, _I, _P),
+    ("mcq_eval_batch_numpy_stream", _I, _P, _P, _SZ, _P, _P, _P),
+    ("mcq_eval_batch_device", _I, _P, _P, _SZ, _U64, _U64, _P, _P),
+    ("mcq_eval_batch_device_small", _I, _P, _P, _SZ, _U64, _U64, _P, _P),
+    ("mcq_eval_batch_ways", _I, _P, _P, _SZ, _U64, _U64, _I, _P),
+    ("mcq_eval_batch_device_ways", _I, _P, _P, _SZ, _U64, _U64, _P, _P),
+    ("mcq_showdown", _I, _P, _P, _SZ, _I, _P, _P, _P),
+    ("mcq_eval_batch_part", _I, _P, _P, _SZ, _U64, _U64, _U32, _U32, _P),
+    ("mcq_exact_batch", _I, _P, _P, _SZ, _I, _P),
+    ("mcq_exact_batch_ext", _I, _P, _P, _P, _SZ, _I, _P, _P),
+    ("mcq_exact_batch_ext_ways", _I, _P, _P, _P, _SZ, _I, _P, _P),
+    ("mcq_exact_batch_seats", _I, _P, _P, _P, _SZ, _I, _P),
+    ("mcq_exact_batch_ext_seats", _I, _P, _P, _P, _SZ, _I, _P),
+    ("mcq_exact_batch_hero_range", _I, _P, _P, _P, _SZ, _I, _P, _P),
+    ("mcq_exact_batch_hero_range_weighted", _I, _P, _P, _P, _SZ, _P, _P, _P, _P),
+    ("mcq_exact_batch_hero_range_preflop", _I, _P, _P, _P, _SZ, _I, _P, _P),
+    ("mcq_exact_batch_hero_range_preflop_weighted", _I, _P, _P, _P, _SZ, _P, _P, _P, _P),
+    ("mcq_eval_batch_ranges", _I, _P, _P, _P, _P, _SZ, _SZ, _U64, _U64, _P),
+    ("mcq_exact_batch_ext_runouts", _I, _P, _P, _P, _SZ, _I, _P, _P),
+    ("mcq_exact_matrix", _I, _P, _P, _SZ, _P, _P, _P),
+    ("mcq_exact_matrix_device", _I, _P, _P, _SZ, _P, _P, _P, _P),
+    ("mcq_set_dealing_law", _I, _P, _I),
+    ("mcq_set_kernel_timing", _I, _P, _I),
+    ("mcq_kernel_times", _I, _P, _P, _I),
+    ("mcq_last_kernel_ms", C.c_float, _P),
+    ("mcq_tables_create", _P, _P, _P),
+    ("mcq_tables_destroy", None, _P),
+    ("mcq_tables_begin", _SZ, _P, _P),
+    ("mcq_tables_resume", _I, _P, _P),
+    ("mcq_tables_run", _I, _P, _U32, _P),
+    ("mcq_tables_stats", None, _P, _P),
+    ("mcq_tables_state", _I, _P, _U32, _P, _P),
+    ("mcq_multi_create", _P, _P, _I, _I),
+    ("mcq_multi_destroy", None, _P),
+    ("mcq_multi_eval_batch", _I, _P, _P, _SZ, _U64, _U64, _I, _P),
+    ("mcq_multi_eval_batch_device", _I, _P, _P, _SZ, _U64, _U64, _I, _P),
+    ("mcq_multi_set_dealing_law", _I, _P, _I),
+    ("mcq_multi_info", _I, _P, _P),
+    ("mcq_multi_times", _I, _P, _P),
+    ("mcq_last_error", C.c_char_p),
+    ("mcq_version", None, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)),
+)
+
+
 def load_library():
     """Load libmcq_hip.so and declare the prototypes of include/mcq.h.  Loud failure if it is not built."""
     global _lib
@@ -94,114 +149,71 @@ def load_library():
                               "neuron_poker_amd has no CPU fallback." % path)
         _share_hip_runtime_with_torch()
         L = C.CDLL(path)
-        vp, u64, sz = C.c_void_p, C.c_uint64, C.c_size_t
-        L.mcq_device_count.argtypes = []
-        L.mcq_device_count.restype = C.c_int
-        L.mcq_create.argtypes = [C.c_int, C.c_int]
-        L.mcq_create.restype = vp
-        L.mcq_destroy.argtypes = [vp]
-        L.mcq_destroy.restype = None
-        L.mcq_eval_batch.argtypes = [vp, vp, sz, u64, u64, C.c_int, vp]
-        L.mcq_eval_batch.restype = C.c_int
-        L.mcq_eval_batch_part.argtypes = [vp, vp, sz, u64, u64, C.c_uint32, C.c_uint32, vp]
-        L.mcq_eval_batch_part.restype = C.c_int
-        L.mcq_eval_one.argtypes = [vp, vp, u64, C.c_int, vp]
-        L.mcq_eval_one.restype = C.c_int
-        L.mcq_eval_batch_ext.argtypes = [vp, vp, vp, sz, u64, u64, C.c_int, vp]
-        L.mcq_eval_batch_ext.restype = C.c_int
-        L.mcq_eval_batch_numpy_stream.argtypes = [vp, vp, sz, vp, vp, vp]
-        L.mcq_eval_batch_numpy_stream.restype = C.c_int
-        L.mcq_eval_batch_device.argtypes = [vp, vp, sz, u64, u64, vp, vp]
-        L.mcq_eval_batch_device.restype = C.c_int
-        L.mcq_eval_batch_ways.argtypes = [vp, vp, sz, u64, u64, C.c_int, vp]
-        L.mcq_eval_batch_ways.restype = C.c_int
-        L.mcq_eval_batch_device_ways.argtypes = [vp, vp, sz, u64, u64, vp, vp]
-        L.mcq_eval_batch_device_ways.restype = C.c_int
-        L.mcq_eval_batch_ext_ways.argtypes = [vp, vp, vp, sz, u64, u64, C.c_int, vp]
-        L.mcq_eval_batch_ext_ways.restype = C.c_int
-        L.mcq_exact_batch_ext_ways.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
-        L.mcq_exact_batch_ext_ways.restype = C.c_int
-        L.mcq_eval_batch_ext_seats.argtypes = [vp, vp, vp, sz, u64, u64, C.c_int, vp]
-        L.mcq_eval_batch_ext_seats.restype = C.c_int
-        L.mcq_exact_batch_seats.argtypes = [vp, vp, vp, sz, C.c_int, vp]
-        L.mcq_exact_batch_seats.restype = C.c_int
-        L.mcq_exact_batch_ext_seats.argtypes = [vp, vp, vp, sz, C.c_int, vp]
-        L.mcq_exact_batch_ext_seats.restype = C.c_int
-        L.mcq_eval_batch_ranges.argtypes = [vp, vp, vp, vp, sz, sz, u64, u64, vp]
-        L.mcq_eval_batch_ranges.restype = C.c_int
-        L.mcq_eval_batch_device_small.argtypes = [vp, vp, sz, u64, u64, vp, vp]
-        L.mcq_eval_batch_device_small.restype = C.c_int
-        L.mcq_showdown.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp]
-        L.mcq_showdown.restype = C.c_int
-        L.mcq_exact_batch.argtypes = [vp, vp, sz, C.c_int, vp]
-        L.mcq_exact_batch.restype = C.c_int
-        L.mcq_exact_batch_ext.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
-        L.mcq_exact_batch_ext.restype = C.c_int
-        L.mcq_exact_batch_hero_range.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
-        L.mcq_exact_batch_hero_range.restype = C.c_int
-        L.mcq_exact_batch_hero_range_weighted.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
-        L.mcq_exact_batch_hero_range_weighted.restype = C.c_int
-        L.mcq_exact_batch_hero_range_preflop.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
-        L.mcq_exact_batch_hero_range_preflop.restype = C.c_int
-        L.mcq_exact_batch_hero_range_preflop_weighted.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
-        L.mcq_exact_batch_hero_range_preflop_weighted.restype = C.c_int
-        L.mcq_exact_batch_ext_runouts.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp]
-        L.mcq_exact_batch_ext_runouts.restype = C.c_int
-        L.mcq_exact_matrix.argtypes = [vp, vp, sz, vp, vp, vp]
-        L.mcq_exact_matrix.restype = C.c_int
-        L.mcq_exact_matrix_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
-        L.mcq_exact_matrix_device.restype = C.c_int
-        L.mcq_set_dealing_law.argtypes = [vp, C.c_int]
-        L.mcq_set_dealing_law.restype = C.c_int
-        L.mcq_set_kernel_timing.argtypes = [vp, C.c_int]
-        L.mcq_set_kernel_timing.restype = C.c_int
-        L.mcq_kernel_times.argtypes = [vp, vp, C.c_int]
-        L.mcq_kernel_times.restype = C.c_int
-        L.mcq_last_kernel_ms.argtypes = [vp]
-        L.mcq_last_kernel_ms.restype = C.c_float
-        L.mcq_tables_create.argtypes = [vp, vp]
-        L.mcq_tables_create.restype = vp
-        L.mcq_tables_destroy.argtypes = [vp]
-        L.mcq_tables_destroy.restype = None
-        L.mcq_tables_begin.argtypes = [vp, vp]
-        L.mcq_tables_begin.restype = sz
-        L.mcq_tables_resume.argtypes = [vp, vp]
-        L.mcq_tables_resume.restype = C.c_int
-        L.mcq_tables_run.argtypes = [vp, C.c_uint32, vp]
-        L.mcq_tables_run.restype = C.c_int
-        L.mcq_tables_stats.argtypes = [vp, vp]
-        L.mcq_tables_stats.restype = None
-        L.mcq_tables_state.argtypes = [vp, C.c_uint32, vp, vp]
-        L.mcq_tables_state.restype = C.c_int
-        L.mcq_multi_create.argtypes = [vp, C.c_int, C.c_int]
-        L.mcq_multi_create.restype = vp
-        L.mcq_multi_destroy.argtypes = [vp]
-        L.mcq_multi_destroy.restype = None
-        L.mcq_multi_eval_batch.argtypes = [vp, vp, sz, u64, u64, C.c_int, vp]
-        L.mcq_multi_eval_batch.restype = C.c_int
-        L.mcq_multi_eval_batch_device.argtypes = [vp, vp, sz, u64, u64, C.c_int, vp]
-        L.mcq_multi_eval_batch_device.restype = C.c_int
-        L.mcq_multi_set_dealing_law.argtypes = [vp, C.c_int]
-        L.mcq_multi_set_dealing_law.restype = C.c_int
-        L.mcq_multi_info.argtypes = [vp, vp]
-        L.mcq_multi_info.restype = C.c_int
-        L.mcq_multi_times.argtypes = [vp, vp]
-        L.mcq_multi_times.restype = C.c_int
-        L.mcq_last_error.argtypes = []
-        L.mcq_last_error.restype = C.c_char_p
-        L.mcq_version.argtypes = [C.POINTER(C.c_int)] * 3
-        L.mcq_version.restype = None
+        for name, restype, *argtypes in _PROTOTYPES:
+            fn = getattr(L, name)   # AttributeError names a symbol the library lacks
+            fn.argtypes, fn.restype = argtypes, restype
         _lib = L
         return _lib
 
 
+def _last_error():
+    """mcq_last_error() of the calling thread as text ('' when there is none).  The loaded library is read without _lock:
+    set_default_dealing_law and default_engine report an engine's error while they hold it."""
+    return ((_lib or load_library()).mcq_last_error() or b"").decode("utf-8", "replace")
+
+
 def _raise(rc):
-    msg = (load_library().mcq_last_error() or b"").decode("utf-8", "replace")
+    msg = _last_error()
     if rc == MCQ_EINVAL:
         raise ValueError(msg)
     if rc == MCQ_EBUSY:
         raise McqBusyError(msg)
     raise McqError("libmcq_hip error %d: %s" % (rc, msg))
+
+
+# What every method of Engine, MultiEngine and Tables marshals its arguments with.  The checks raise before the engine is
+# touched; a method checks the law first, then the records, then its tables.
+
+def _call(fn, *args):
+    """Call an entry point that returns MCQ_OK or an MCQ_E* code; the code is raised as _raise maps it."""
+    rc = fn(*args)
+    if rc:
+        _raise(rc)
+
+
+def _law_code(law):
+    code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
+    if code is None:
+        raise ValueError("law must be 'reference' or 'uniform'")
+    return code
+
+
+def _queries(queries, dtype=QUERY_DTYPE):
+    """-> the records as one contiguous row of `dtype`"""
+    return np.ascontiguousarray(queries, dtype=dtype).reshape(-1)
+
+
+def _records(queries, ext):
+    """-> (mcq_query[n], mcq_query_ext[n]), one extension record per query"""
+    q, e = _queries(queries), _queries(ext, QUERY_EXT_DTYPE)
+    if len(e) != len(q):
+        raise ValueError("one mcq_query_ext per query")
+    return q, e
+
+
+def _u64(x):
+    """a seed or a query id as the uint64_t the library takes"""
+    return int(x) & 0xFFFFFFFFFFFFFFFF
+
+
+def _opt(x):
+    """an optional device pointer or stream handle: None (NULL) for None or 0"""
+    return int(x) if x else None
+
+
+def _addr(a):
+    """the address of an optional array: None (NULL) for None"""
+    return None if a is None else a.ctypes.data
 
 
 def pack_queries(hole, board, n_players, runs):
@@ -378,52 +390,29 @@ def _hero_range(eng, entry, queries, ext, law=None, weights=None):
     tables, the records, the output arrays, the call of the library's `entry`.  Every ValueError is raised before the
     engine is touched.  -> (rows, agg)"""
     if weights is None:
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-    q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-    e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-    if len(e) != len(q):
-        raise ValueError("one mcq_query_ext per query")
+        code = _law_code(law)
+    q, e = _records(queries, ext)
     if weights is None:
         mid = (code,)
     else:
         opp = _hero_weight_table("opp_weights", weights[0], len(q))
         hero = None if weights[1] is None else _hero_weight_table("hero_weights", weights[1], len(q))
-        mid = (opp.ctypes.data, None if hero is None else hero.ctypes.data)
+        mid = (opp.ctypes.data, _addr(hero))
     rows = np.zeros((len(q), HAND_ROWS), RESULT_DTYPE)
     agg = np.zeros(len(q), EXACT_PROB_DTYPE)
-    rc = getattr(eng._lib, entry)(eng._ctx, q.ctypes.data, e.ctypes.data, len(q), *mid, rows.ctypes.data, agg.ctypes.data)
-    if rc:
-        _raise(rc)
+    _call(getattr(eng._lib, entry), eng._ctx, q.ctypes.data, e.ctypes.data, len(q), *mid, rows.ctypes.data, agg.ctypes.data)
     return rows, agg
 
 
-class Engine:
-    """One mcq_ctx: an equity engine bound to one GPU.  Not re-entrant: one call in flight per engine -- a second thread
-    calling into the same Engine meanwhile gets McqBusyError (the library checks).  One Engine per thread."""
-
-    def __init__(self, device=0, kernel_times=False):
-        self._lib = load_library()
-        self._ctx = self._lib.mcq_create(int(device), 0)
-        if not self._ctx:
-            msg = (self._lib.mcq_last_error() or b"").decode("utf-8", "replace")
-            raise McqError("mcq_create(device=%d) failed: %s" % (device, msg))
-        self.device = int(device)
-        if kernel_times:
-            self.set_kernel_timing(True)
-
-    def set_kernel_timing(self, on):
-        """Timestamp every evaluation-kernel launch (kernel_times / last_kernel_ms); off by default: it costs a small
-        query about 6 us of its call time."""
-        rc = self._lib.mcq_set_kernel_timing(self._ctx, 1 if on else 0)
-        if rc:
-            _raise(rc)
+class _Handle:
+    """What Engine, MultiEngine and Tables share: the library in `_lib` and one native object, held in the attribute that
+    `_handle` names and freed by the entry point that `_destroy` names, at close() or when the object is collected."""
+    _handle = _destroy = None
 
     def close(self):
-        if getattr(self, "_ctx", None):
-            self._lib.mcq_destroy(self._ctx)
-            self._ctx = None
+        if getattr(self, self._handle, None):
+            getattr(self._lib, self._destroy)(getattr(self, self._handle))
+            setattr(self, self._handle, None)
 
     def __del__(self):
         try:
@@ -431,76 +420,76 @@ class Engine:
         except Exception:
             pass
 
+
+class Engine(_Handle):
+    """One mcq_ctx: an equity engine bound to one GPU.  Not re-entrant: one call in flight per engine -- a second thread
+    calling into the same Engine meanwhile gets McqBusyError (the library checks).  One Engine per thread."""
+    _handle, _destroy = "_ctx", "mcq_destroy"
+
+    def __init__(self, device=0, kernel_times=False):
+        self._lib = load_library()
+        self._ctx = self._lib.mcq_create(int(device), 0)
+        if not self._ctx:
+            raise McqError("mcq_create(device=%d) failed: %s" % (device, _last_error()))
+        self.device = int(device)
+        if kernel_times:
+            self.set_kernel_timing(True)
+
+    def set_kernel_timing(self, on):
+        """Timestamp every evaluation-kernel launch (kernel_times / last_kernel_ms); off by default: it costs a small
+        query about 6 us of its call time."""
+        _call(self._lib.mcq_set_kernel_timing, self._ctx, 1 if on else 0)
+
     def set_dealing_law(self, law):
         """'reference' (default: the Python reference's law incl. its index bias) or 'uniform' (unbiased)."""
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-        rc = self._lib.mcq_set_dealing_law(self._ctx, code)
-        if rc:
-            _raise(rc)
+        code = _law_code(law)
+        _call(self._lib.mcq_set_dealing_law, self._ctx, code)
 
     def eval_batch(self, queries, seed, first_query_id=0, mode=MODE_PHILOX, part=None):
         """queries: array of QUERY_DTYPE (host).  -> array of RESULT_DTYPE.
         part=(p, n): only share p of n of every query's iterations (mcq_eval_batch_part; the rows of all shares
         add up to the unsplit result)."""
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        q = _queries(queries)
         out = np.empty(len(q), RESULT_DTYPE)   # every row is written by the library on success; on failure we raise
         if part is not None:
             if mode != MODE_PHILOX:
                 raise ValueError("only the production mode can split the iterations of a query")
-            rc = self._lib.mcq_eval_batch_part(self._ctx, q.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
-                                               int(first_query_id) & (2 ** 64 - 1), int(part[0]), int(part[1]),
-                                               out.ctypes.data)
+            _call(self._lib.mcq_eval_batch_part, self._ctx, q.ctypes.data, len(q), _u64(seed), _u64(first_query_id),
+                  int(part[0]), int(part[1]), out.ctypes.data)
         else:
-            rc = self._lib.mcq_eval_batch(self._ctx, q.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
-                                          int(first_query_id) & (2 ** 64 - 1), int(mode), out.ctypes.data)
-        if rc:
-            _raise(rc)
+            _call(self._lib.mcq_eval_batch, self._ctx, q.ctypes.data, len(q), _u64(seed), _u64(first_query_id), int(mode),
+                  out.ctypes.data)
         return out
 
     def eval_batch_ways(self, queries, seed, first_query_id=0, mode=MODE_PHILOX):
         """eval_batch with the ties split by the number of hands that share the pot (mcq_eval_batch_ways).
         -> array of RESULT_WAYS_DTYPE: the fields of RESULT_DTYPE exactly as eval_batch returns them, then tie_ways[9];
         pot_share(rows) is hero's expected share of the pot."""
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        q = _queries(queries)
         out = np.empty(len(q), RESULT_WAYS_DTYPE)   # every row is written by the library on success; on failure we raise
-        rc = self._lib.mcq_eval_batch_ways(self._ctx, q.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
-                                           int(first_query_id) & (2 ** 64 - 1), int(mode), out.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_eval_batch_ways, self._ctx, q.ctypes.data, len(q), _u64(seed), _u64(first_query_id), int(mode),
+              out.ctypes.data)
         return out
 
     def exact(self, queries, law="reference"):
         """Exact enumeration (1..3 players; `runs` of the queries is ignored).  -> RESULT_DTYPE rows of integer
         weights: runs = total weight, equity = (win + tie) / runs exactly."""
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        code = _law_code(law)
+        q = _queries(queries)
         out = np.zeros(len(q), RESULT_DTYPE)
-        rc = self._lib.mcq_exact_batch(self._ctx, q.ctypes.data, len(q), code, out.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_exact_batch, self._ctx, q.ctypes.data, len(q), code, out.ctypes.data)
         return out
 
     def exact_ext(self, queries, ext, law="reference"):
         """Exact enumeration of extended queries (mcq_exact_batch_ext: further known hands, ghost cards, an opponent range;
         at most two random opponents).  -> (prob, weights): EXACT_PROB_DTYPE rows (win, tie, by_type) and RESULT_DTYPE
         rows of integer weights -- zeroed for a query with a range and two random opponents (no common total)."""
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
+        code = _law_code(law)
+        q, e = _records(queries, ext)
         prob = np.zeros(len(q), EXACT_PROB_DTYPE)
         weights = np.zeros(len(q), RESULT_DTYPE)
-        rc = self._lib.mcq_exact_batch_ext(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, prob.ctypes.data,
-                                           weights.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_exact_batch_ext, self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, prob.ctypes.data,
+              weights.ctypes.data)
         return prob, weights
 
     def exact_hero_range(self, queries, ext, law="reference"):
@@ -542,19 +531,12 @@ class Engine:
         """exact_ext with the ties split by the hands that share the pot (mcq_exact_batch_ext_ways; at most ONE random
         opponent).  -> (prob, weights): EXACT_PROB_WAYS_DTYPE rows (p as exact_ext's prob, tie_ways[9]) and
         RESULT_WAYS_DTYPE rows of integer weights, always defined; pot_share(weights, exact=True) is the exact share."""
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
+        code = _law_code(law)
+        q, e = _records(queries, ext)
         prob = np.zeros(len(q), EXACT_PROB_WAYS_DTYPE)
         weights = np.zeros(len(q), RESULT_WAYS_DTYPE)
-        rc = self._lib.mcq_exact_batch_ext_ways(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, prob.ctypes.data,
-                                                weights.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_exact_batch_ext_ways, self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, prob.ctypes.data,
+              weights.ctypes.data)
         return prob, weights
 
     def exact_ext_runouts(self, queries, ext, law="reference", want_pairs=True):
@@ -563,48 +545,31 @@ class Engine:
         exact_ext_ways restricted to the table completions that hold the card (flop: the pair; the card rows are the sums
         of their pair rows).  The rows of what cannot come are zero; a turn record's pair rows are all zero.  Equity given
         that card c comes next: (win + tie) / runs of cards[i, c], or pot_share of that row."""
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
+        code = _law_code(law)
+        q, e = _records(queries, ext)
         cards = np.zeros((len(q), RUNOUT_CARD_ROWS), RESULT_WAYS_DTYPE)
         pairs = np.zeros((len(q), HAND_ROWS), RESULT_WAYS_DTYPE) if want_pairs else None
-        rc = self._lib.mcq_exact_batch_ext_runouts(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, cards.ctypes.data,
-                                                   pairs.ctypes.data if want_pairs else None)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_exact_batch_ext_runouts, self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, cards.ctypes.data,
+              _addr(pairs))
         return cards, pairs
 
     def eval_batch_ext_ways(self, queries, ext, seed, first_query_id=0, mode=MODE_PHILOX):
         """eval_batch_ext with the ties split by the hands that share the pot (mcq_eval_batch_ext_ways).  -> array of
         RESULT_WAYS_DTYPE: the fields of RESULT_DTYPE exactly as eval_batch_ext returns them, then tie_ways[9]."""
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
+        q, e = _records(queries, ext)
         out = np.zeros(len(q), RESULT_WAYS_DTYPE)
-        rc = self._lib.mcq_eval_batch_ext_ways(self._ctx, q.ctypes.data, e.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
-                                               int(first_query_id) & (2 ** 64 - 1), int(mode), out.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_eval_batch_ext_ways, self._ctx, q.ctypes.data, e.ctypes.data, len(q), _u64(seed),
+              _u64(first_query_id), int(mode), out.ctypes.data)
         return out
 
     def eval_batch_ext_seats(self, queries, ext, seed, first_query_id=0):
         """eval_batch_ext with one tally per SEAT (mcq_eval_batch_ext_seats; production mode): every hand's win, tie and
         pot share from the same iterations.  -> array of RESULT_SEATS_DTYPE; runs, passes and seat 0's win and tie are
         what eval_batch_ext_ways returns for the same arguments; seat_shares(rows) gives the pot shares."""
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
+        q, e = _records(queries, ext)
         out = np.zeros(len(q), RESULT_SEATS_DTYPE)
-        rc = self._lib.mcq_eval_batch_ext_seats(self._ctx, q.ctypes.data, e.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
-                                                int(first_query_id) & (2 ** 64 - 1), MODE_PHILOX, out.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_eval_batch_ext_seats, self._ctx, q.ctypes.data, e.ctypes.data, len(q), _u64(seed),
+              _u64(first_query_id), MODE_PHILOX, out.ctypes.data)
         return out
 
     def eval_batch_ranges(self, queries, seat_table, tables, seed, first_query_id=0):
@@ -614,7 +579,7 @@ class Engine:
         jointly, proportional to the product of the seats' weights over the disjoint deals clear of the table cards; `hole`
         of the records is not read.  -> array of RESULT_SEATS_DTYPE (passes counts whole trials); seat_shares(rows) gives
         the pot shares.  A wrong shape or dtype raises ValueError before the engine is touched."""
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        q = _queries(queries)
         if not isinstance(tables, np.ndarray) or tables.dtype != np.uint16 or tables.ndim != 2 or tables.shape[1] != HAND_ROWS \
                 or tables.shape[0] == 0:
             raise ValueError("tables is a uint16 array of shape [n_tables >= 1, HAND_ROWS = %d]" % HAND_ROWS)
@@ -622,27 +587,18 @@ class Engine:
             raise ValueError("seat_table is a uint32 array of shape [n, 10] = (%d, 10)" % len(q))
         tb, st = np.ascontiguousarray(tables), np.ascontiguousarray(seat_table)
         out = np.zeros(len(q), RESULT_SEATS_DTYPE)
-        rc = self._lib.mcq_eval_batch_ranges(self._ctx, q.ctypes.data, st.ctypes.data, tb.ctypes.data, len(tb), len(q),
-                                             int(seed) & (2 ** 64 - 1), int(first_query_id) & (2 ** 64 - 1), out.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_eval_batch_ranges, self._ctx, q.ctypes.data, st.ctypes.data, tb.ctypes.data, len(tb), len(q),
+              _u64(seed), _u64(first_query_id), out.ctypes.data)
         return out
 
     def exact_seats(self, queries, ext, law="reference"):
         """Exact per-seat enumeration of the all-in case (mcq_exact_batch_seats): every hand known, no random opponent.
         -> RESULT_SEATS_DTYPE rows of integer weights: runs = total weight, seat[s].share / (SHARE_UNIT * runs) is the
         exact pot share of seat s (seat_shares(rows))."""
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
+        code = _law_code(law)
+        q, e = _records(queries, ext)
         out = np.zeros(len(q), RESULT_SEATS_DTYPE)
-        rc = self._lib.mcq_exact_batch_seats(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, out.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_exact_batch_seats, self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, out.ctypes.data)
         return out
 
     def exact_ext_seats(self, queries, ext, law="reference"):
@@ -650,17 +606,10 @@ class Engine:
         1 + n_known is that opponent.  -> RESULT_SEATS_DTYPE rows of integer weights as exact_seats returns them (and the
         same rows bit for bit for a record without a random opponent); seat_shares(rows) gives the exact pot shares.  Two
         random opponents raise ValueError."""
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
+        code = _law_code(law)
+        q, e = _records(queries, ext)
         out = np.zeros(len(q), RESULT_SEATS_DTYPE)
-        rc = self._lib.mcq_exact_batch_ext_seats(self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, out.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_exact_batch_ext_seats, self._ctx, q.ctypes.data, e.ctypes.data, len(q), code, out.ctypes.data)
         return out
 
     def exact_matrix(self, queries, want_tie=True):
@@ -668,16 +617,13 @@ class Engine:
         3 to 5 table cards.  -> (win, tie, total): win[i, hand_index(h), hand_index(g)] = the table completions on which
         hand h beats hand g, tie likewise (None without want_tie), both uint16 [n, HAND_ROWS, HAND_ROWS] and zero where the
         two hands cannot meet; total[i] = the completions of a pair of hands, win[h][g] + win[g][h] + tie[h][g]."""
-        q = np.ascontiguousarray(queries, dtype=MATRIX_QUERY_DTYPE).reshape(-1)
+        q = _queries(queries, MATRIX_QUERY_DTYPE)
         if not 1 <= len(q) <= MATRIX_MAX_BATCH:
             raise ValueError("1 to MATRIX_MAX_BATCH = %d records per call" % MATRIX_MAX_BATCH)
         win = np.zeros((len(q), HAND_ROWS, HAND_ROWS), np.uint16)
         tie = np.zeros((len(q), HAND_ROWS, HAND_ROWS), np.uint16) if want_tie else None
         total = np.zeros(len(q), np.uint32)
-        rc = self._lib.mcq_exact_matrix(self._ctx, q.ctypes.data, len(q), win.ctypes.data,
-                                        tie.ctypes.data if want_tie else None, total.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_exact_matrix, self._ctx, q.ctypes.data, len(q), win.ctypes.data, _addr(tie), total.ctypes.data)
         return win, tie, total
 
     def exact_matrix_device(self, queries, d_win, d_tie, stream=0):
@@ -685,68 +631,49 @@ class Engine:
         pointers (ints) to n x HAND_ROWS x HAND_ROWS uint16 each, d_tie 0 or None for win alone, stream a hipStream_t handle
         (int) or 0.  The records are host memory and are validated before anything is launched.  Asynchronous.
         -> total (uint32 [n])."""
-        q = np.ascontiguousarray(queries, dtype=MATRIX_QUERY_DTYPE).reshape(-1)
+        q = _queries(queries, MATRIX_QUERY_DTYPE)
         total = np.zeros(len(q), np.uint32)
-        rc = self._lib.mcq_exact_matrix_device(self._ctx, q.ctypes.data, len(q), int(d_win) if d_win else None,
-                                               int(d_tie) if d_tie else None, total.ctypes.data,
-                                               int(stream) if stream else None)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_exact_matrix_device, self._ctx, q.ctypes.data, len(q), _opt(d_win), _opt(d_tie), total.ctypes.data,
+              _opt(stream))
         return total
 
     def eval_batch_ext(self, queries, ext, seed, first_query_id=0, mode=MODE_PHILOX):
         """queries with one QUERY_EXT_DTYPE record each (ranges, hero range, ghost cards, second known hand)."""
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
-        e = np.ascontiguousarray(ext, dtype=QUERY_EXT_DTYPE).reshape(-1)
-        if len(e) != len(q):
-            raise ValueError("one mcq_query_ext per query")
+        q, e = _records(queries, ext)
         out = np.zeros(len(q), RESULT_DTYPE)
-        rc = self._lib.mcq_eval_batch_ext(self._ctx, q.ctypes.data, e.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
-                                          int(first_query_id) & (2 ** 64 - 1), int(mode), out.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_eval_batch_ext, self._ctx, q.ctypes.data, e.ctypes.data, len(q), _u64(seed), _u64(first_query_id),
+              int(mode), out.ctypes.data)
         return out
 
     def eval_batch_numpy_stream(self, queries):
         """Parity mode on numpy's GLOBAL random state: the queries consume np.random's MT19937 stream in order,
         exactly as consecutive reference calls do, and np.random is left where those calls would leave it."""
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        q = _queries(queries)
         out = np.zeros(len(q), RESULT_DTYPE)
         st = np.random.get_state()
         key = np.ascontiguousarray(st[1], dtype=np.uint32).copy()
         pos = C.c_uint32(int(st[2]))
-        rc = self._lib.mcq_eval_batch_numpy_stream(self._ctx, q.ctypes.data, len(q), key.ctypes.data, C.byref(pos),
-                                                   out.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_eval_batch_numpy_stream, self._ctx, q.ctypes.data, len(q), key.ctypes.data, C.byref(pos),
+              out.ctypes.data)
         np.random.set_state((st[0], key, int(pos.value), st[3], st[4]))
         return out
 
     def eval_batch_device(self, d_queries, n, seed, d_results, first_query_id=0, stream=None):
         """Device-resident entry: d_queries / d_results are raw device pointers (ints), stream a hipStream_t
         handle (int) or None.  Asynchronous."""
-        rc = self._lib.mcq_eval_batch_device(self._ctx, int(d_queries), int(n), int(seed) & (2 ** 64 - 1),
-                                             int(first_query_id) & (2 ** 64 - 1), int(d_results),
-                                             int(stream) if stream else None)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_eval_batch_device, self._ctx, int(d_queries), int(n), _u64(seed), _u64(first_query_id),
+              int(d_results), _opt(stream))
 
     def eval_batch_device_ways(self, d_queries, n, seed, d_results, first_query_id=0, stream=None):
         """eval_batch_device writing mcq_result_ways rows: d_results -> n x 22 uint64 (176 bytes per query)."""
-        rc = self._lib.mcq_eval_batch_device_ways(self._ctx, int(d_queries), int(n), int(seed) & (2 ** 64 - 1),
-                                                  int(first_query_id) & (2 ** 64 - 1), int(d_results),
-                                                  int(stream) if stream else None)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_eval_batch_device_ways, self._ctx, int(d_queries), int(n), _u64(seed), _u64(first_query_id),
+              int(d_results), _opt(stream))
 
     def eval_batch_device_small(self, d_queries, n, seed, d_results, first_query_id=0, stream=None):
         """eval_batch_device for queries of at most 8192 iterations each: ONE kernel launch, no pricing kernel, no
         atomics (a longer query gets runs = 0, passes = 2**64 - 1 like an invalid one)."""
-        rc = self._lib.mcq_eval_batch_device_small(self._ctx, int(d_queries), int(n), int(seed) & (2 ** 64 - 1),
-                                                   int(first_query_id) & (2 ** 64 - 1), int(d_results),
-                                                   int(stream) if stream else None)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_eval_batch_device_small, self._ctx, int(d_queries), int(n), _u64(seed), _u64(first_query_id),
+              int(d_results), _opt(stream))
 
     def showdown(self, hands, want_keys=False):
         """hands [T, P, 7] card ids -> (winner[T], winner_type[T][, keys[T, P]])."""
@@ -757,10 +684,7 @@ class Engine:
         win = np.zeros(T, np.uint8)
         wt = np.zeros(T, np.uint8)
         keys = np.zeros((T, P), np.uint32) if want_keys else None
-        rc = self._lib.mcq_showdown(self._ctx, h.ctypes.data, T, P, win.ctypes.data, wt.ctypes.data,
-                                    keys.ctypes.data if want_keys else None)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_showdown, self._ctx, h.ctypes.data, T, P, win.ctypes.data, wt.ctypes.data, _addr(keys))
         return (win, wt, keys) if want_keys else (win, wt)
 
     def kernel_times(self, max_n=64):
@@ -780,56 +704,39 @@ PARTITION_AUTO, PARTITION_QUERIES, PARTITION_ITERATIONS = 0, 1, 2
 _PARTITIONS = {None: 0, "auto": 0, "queries": 1, "iterations": 2, 0: 0, 1: 1, 2: 2}
 
 
-class MultiEngine:
+class MultiEngine(_Handle):
     """mcq_multi: one process driving several GPUs of a node (include/mcq.h).  The batch is partitioned over
     shards, ONE RCCL all-reduce of the integer tally matrix joins them; results are bit-identical to Engine.eval_batch.
 
     devices: one HIP device ordinal per shard (a device may repeat); None = every visible device once."""
+    _handle, _destroy = "_m", "mcq_multi_destroy"
 
     def __init__(self, devices=None):
         self._lib = load_library()
         if devices is None:
             n = self._lib.mcq_device_count()
             if n <= 0:
-                raise McqError("no HIP device visible: " + (self._lib.mcq_last_error() or b"").decode("utf-8", "replace"))
+                raise McqError("no HIP device visible: " + _last_error())
             devices = list(range(n))
         devs = np.ascontiguousarray(devices, dtype=np.int32)
         self._m = self._lib.mcq_multi_create(devs.ctypes.data, len(devs), 0)
         if not self._m:
-            msg = (self._lib.mcq_last_error() or b"").decode("utf-8", "replace")
-            raise McqError("mcq_multi_create(%s) failed: %s" % ([int(d) for d in devs], msg))
+            raise McqError("mcq_multi_create(%s) failed: %s" % ([int(d) for d in devs], _last_error()))
         self.devices = [int(d) for d in devs]
         self.lock = threading.Lock()   # the shim's shared MultiEngines serialise their callers on it
 
-    def close(self):
-        if getattr(self, "_m", None):
-            self._lib.mcq_multi_destroy(self._m)
-            self._m = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_dealing_law(self, law):
-        code = {"reference": 0, "uniform": 1, 0: 0, 1: 1}.get(law)
-        if code is None:
-            raise ValueError("law must be 'reference' or 'uniform'")
-        rc = self._lib.mcq_multi_set_dealing_law(self._m, code)
-        if rc:
-            _raise(rc)
+        code = _law_code(law)
+        _call(self._lib.mcq_multi_set_dealing_law, self._m, code)
 
     def eval_batch(self, queries, seed, first_query_id=0, partition=None):
         """queries: array of QUERY_DTYPE (host) -> array of RESULT_DTYPE; partition 'auto' | 'queries' | 'iterations'."""
         if partition not in _PARTITIONS:
             raise ValueError("partition must be 'auto', 'queries' or 'iterations'")
-        q = np.ascontiguousarray(queries, dtype=QUERY_DTYPE).reshape(-1)
+        q = _queries(queries)
         out = np.zeros(len(q), RESULT_DTYPE)
-        rc = self._lib.mcq_multi_eval_batch(self._m, q.ctypes.data, len(q), int(seed) & (2 ** 64 - 1),
-                                            int(first_query_id) & (2 ** 64 - 1), _PARTITIONS[partition], out.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_multi_eval_batch, self._m, q.ctypes.data, len(q), _u64(seed), _u64(first_query_id),
+              _PARTITIONS[partition], out.ctypes.data)
         return out
 
     def eval_batch_device(self, d_queries, n, seed, d_results, first_query_id=0, partition="auto"):
@@ -839,37 +746,32 @@ class MultiEngine:
         k = len(self.devices)
         if len(d_queries) != k or len(d_results) != k:
             raise ValueError("one device pointer pair per shard")
-        qp = (C.c_void_p * k)(*[int(p) if p else None for p in d_queries])
-        rp = (C.c_void_p * k)(*[int(p) if p else None for p in d_results])
-        rc = self._lib.mcq_multi_eval_batch_device(self._m, qp, int(n), int(seed) & (2 ** 64 - 1),
-                                                   int(first_query_id) & (2 ** 64 - 1), _PARTITIONS[partition], rp)
-        if rc:
-            _raise(rc)
+        qp = (C.c_void_p * k)(*[_opt(p) for p in d_queries])
+        rp = (C.c_void_p * k)(*[_opt(p) for p in d_results])
+        _call(self._lib.mcq_multi_eval_batch_device, self._m, qp, int(n), _u64(seed), _u64(first_query_id),
+              _PARTITIONS[partition], rp)
 
     @property
     def info(self):
         v = np.zeros(4, np.int32)
-        rc = self._lib.mcq_multi_info(self._m, v.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_multi_info, self._m, v.ctypes.data)
         return {"shards": int(v[0]), "devices": int(v[1]), "rccl_version": int(v[2]),
                 "last_partition": {0: "auto", 1: "queries", 2: "iterations"}[int(v[3])]}
 
     @property
     def last_times_ms(self):
         v = np.zeros(3, np.float32)
-        rc = self._lib.mcq_multi_times(self._m, v.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_multi_times, self._m, v.ctypes.data)
         return {"kernel_max": float(v[0]), "all_reduce": float(v[1]), "call": float(v[2])}
 
 
-class Tables:
+class Tables(_Handle):
     """mcq_tables: T Hold'em tables advanced in lock-step by the native driver (include/mcq.h, BASELINE configs[4]).
 
     seats: one entry per seat -- ("equity", min_call_equity, min_bet_equity) or ("random",).
     engine=None gives a driver without GPU: only begin()/resume() work (used to pin the rules on the CPU).
     The tables are independent (own generator each): results do not depend on `threads`."""
+    _handle, _destroy = "_t", "mcq_tables_destroy"
 
     def __init__(self, engine, n_tables, seats, runs=1000, initial_stacks=100, small_blind=1, big_blind=2,
                  max_raises=2, seed=0, threads=0, overlap=True, calculate_equity=False):
@@ -878,7 +780,7 @@ class Tables:
         cfg = np.zeros(1, TABLES_CONFIG_DTYPE)
         cfg["n_tables"], cfg["n_seats"], cfg["runs"], cfg["max_raises"] = n_tables, len(seats), runs, max_raises
         cfg["initial_stacks"], cfg["small_blind"], cfg["big_blind"] = initial_stacks, small_blind, big_blind
-        cfg["seed"] = int(seed) & (2 ** 64 - 1)
+        cfg["seed"] = _u64(seed)
         cfg["reserved"][0, 0] = threads          # host threads stepping the tables; 0 = automatic
         cfg["reserved"][0, 1] = 0 if overlap else 1   # run(): groups of tables on streams of their own (same results either way)
         cfg["reserved"][0, 2] = 1 if calculate_equity else 0   # three more queries per observation (env.py:248-256)
@@ -894,18 +796,7 @@ class Tables:
         self.n_tables, self.n_seats = int(n_tables), len(seats)
         self._t = self._lib.mcq_tables_create(engine._ctx if engine is not None else None, cfg.ctypes.data)
         if not self._t:
-            raise ValueError((self._lib.mcq_last_error() or b"").decode("utf-8", "replace"))
-
-    def close(self):
-        if getattr(self, "_t", None):
-            self._lib.mcq_tables_destroy(self._t)
-            self._t = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            raise ValueError(_last_error())
 
     def begin(self):
         """-> the pending query of every table (QUERY_DTYPE[n_tables])."""
@@ -917,16 +808,12 @@ class Tables:
         e = np.ascontiguousarray(equity, np.float64)
         if e.shape != (self.n_tables,):
             raise ValueError("one equity per table")
-        rc = self._lib.mcq_tables_resume(self._t, e.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_tables_resume, self._t, e.ctypes.data)
 
     def run(self, lock_steps):
         """lock_steps rounds of (queries of all tables -> ONE GPU batch -> every table acts).  -> stats()."""
         st = np.zeros(3, np.uint64)
-        rc = self._lib.mcq_tables_run(self._t, int(lock_steps), st.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_tables_run, self._t, int(lock_steps), st.ctypes.data)
         return {"env_steps": int(st[0]), "queries": int(st[1]), "episodes": int(st[2])}
 
     def stats(self):
@@ -937,9 +824,7 @@ class Tables:
     def state(self, table):
         stacks = np.zeros(self.n_seats, np.float64)
         info = np.zeros(8, np.int32)
-        rc = self._lib.mcq_tables_state(self._t, int(table), stacks.ctypes.data, info.ctypes.data)
-        if rc:
-            _raise(rc)
+        _call(self._lib.mcq_tables_state, self._t, int(table), stacks.ctypes.data, info.ctypes.data)
         keys = ["stage", "current", "winner", "episodes", "env_steps", "queries", "legal", "phase"]
         d = dict(zip(keys, (int(x) for x in info)))
         d["stacks"] = stacks
@@ -960,8 +845,7 @@ def default_engine():
         dev = int(os.environ.get("MCQ_DEVICE", os.environ.get("LOCAL_RANK", "0")))
         n = load_library().mcq_device_count()
         if n <= 0:
-            raise McqError("no HIP device visible: neuron_poker_amd needs an AMD GPU (no CPU fallback). " +
-                           (load_library().mcq_last_error() or b"").decode("utf-8", "replace"))
+            raise McqError("no HIP device visible: neuron_poker_amd needs an AMD GPU (no CPU fallback). " + _last_error())
         eng = Engine(dev % n)
         import weakref
         with _lock:

@@ -134,9 +134,7 @@ def _ext_record(hero, hero_is_range, known_hands, ghost_cards, opponent_range, o
     except TypeError:  # something unhashable inside: build it afresh
         key, ext = None, None
     if ext is None:
-        ghost = None
-        if ghost_cards != '' and ghost_cards is not None:
-            ghost = [card_id(ghost_cards[0]), card_id(ghost_cards[1])]
+        ghost = _ghost_ids(ghost_cards)
         known = [_lib.range_bits(h) if isinstance(h, (set, frozenset)) else [card_id(c) for c in h] for h in known_hands]
         ext = _lib.pack_query_ext(1, ghost=ghost, known=known,
                                   hero_range=_lib.range_bits(hero) if hero_is_range else None, opp_range=opp_bits)
@@ -167,6 +165,38 @@ def _query(player_cards, table_cards, players, runs):
     return _lib.pack_query_one(hole, board, players, runs)
 
 
+def _hero_query(hero, table_cards, players, runs):
+    """_query for a hero given as two cards or as a range (a set of classes): a range's record is made with two
+    placeholder cards that pass _query's checks, and its hole, which the library does not read, is then zeroed."""
+    if not isinstance(hero, (set, frozenset)):
+        return _query(list(hero), table_cards, players, runs)
+    q = _query(["2C", "2D"], table_cards, players, runs)
+    q["hole"] = 0
+    return q
+
+
+def _split_ties(ties, whole="credited"):
+    """The `ties` argument: `whole` (a tied pot counts for hero in full) or 'split'.  -> whether it is 'split'."""
+    if ties not in (whole, "split"):
+        raise ValueError("ties must be '%s' or 'split'" % whole)
+    return ties == "split"
+
+
+def _ghost_ids(ghost_cards, exactly_two=False):
+    """run_montecarlo's ghost_cards ('' or None: none) -> the two card ids or None."""
+    if ghost_cards == '' or ghost_cards is None:
+        return None
+    if exactly_two and len(ghost_cards) != 2:
+        raise ValueError("ghost_cards is two cards or ''")
+    return [card_id(ghost_cards[0]), card_id(ghost_cards[1])]
+
+
+def _two_cards_each(hands, message="a known hand is two cards here (ranged known hands are not enumerated)"):
+    """Known hands that an enumeration takes as two cards each: a range or another length raises ValueError(message)."""
+    if any(isinstance(h, (set, frozenset)) or len(h) != 2 for h in hands):
+        raise ValueError(message)
+
+
 class MonteCarlo(object):
     """Mirror of tools/montecarlo_python.py:22 MonteCarlo for the path gym_env/env.py uses."""
 
@@ -186,9 +216,7 @@ class MonteCarlo(object):
         ties="credited" (default): a tied pot counts for hero in full, as the reference does.  ties="split": `equity`
         is hero's expected SHARE of the pot (a tie among k hands counts 1/k) and `result` the 22-word row
         (RESULT_WAYS_DTYPE); winnerCardTypeList stays on the credited counts.  Same streams, same query ids."""
-        if ties not in ("credited", "split"):
-            raise ValueError("ties must be 'credited' or 'split'")
-        split = ties == "split"
+        split = _split_ties(ties)
         eng = self._engine or _lib.default_engine()
         if mode == "exact":
             return self._run_exact(eng, original_player_card_list, original_table_card_list, player_amount, ghost_cards,
@@ -201,7 +229,7 @@ class MonteCarlo(object):
         hero_is_range = isinstance(hero, (set, frozenset))
         opp_bits = _opponent_range_bits(opponent_range)
         plain = not hero_is_range and len(players) == 1 and opp_bits is None and (ghost_cards == '' or ghost_cards is None)
-        q = _query(["2C", "2D"] if hero_is_range else list(hero), list(original_table_card_list), player_amount, maxRuns)
+        q = _hero_query(hero, list(original_table_card_list), player_amount, maxRuns)
         if plain:
             if m == _lib.MODE_REPLAY_MT19937 and _state["couple_numpy"] and seed is None:
                 if split:
@@ -211,8 +239,6 @@ class MonteCarlo(object):
                 s, first = _take_ids(1) if seed is None else (int(seed), 0)
                 res = (eng.eval_batch_ways if split else eng.eval_batch)(q, s, first_query_id=first, mode=m)[0]
         else:
-            if hero_is_range:
-                q["hole"] = 0
             ext = _ext_record(hero, hero_is_range, players[1:], ghost_cards, opponent_range, opp_bits)
             s, first = _take_ids(1) if seed is None else (int(seed), 0)
             # (straight to the C ABI: Engine.eval_batch_ext's conversions of arrays that are already right cost 8 us)
@@ -248,9 +274,7 @@ class MonteCarlo(object):
             raise ValueError("between one and ten known hands")
         if isinstance(players[0], (set, frozenset)):
             raise ValueError("mode='exact' needs the hero's two cards, not a range")
-        for h in players[1:]:
-            if isinstance(h, (set, frozenset)) or len(h) != 2:
-                raise ValueError("mode='exact' needs every known hand as two cards")
+        _two_cards_each(players[1:], "mode='exact' needs every known hand as two cards")
         opp_bits = _opponent_range_bits(opponent_range)
         q = _query(list(players[0]), list(original_table_card_list), player_amount, 1)
         ext = _ext_record(list(players[0]), False, players[1:], ghost_cards, opponent_range, opp_bits)
@@ -353,12 +377,10 @@ def get_seat_equities(hands, table_cards, players=None, runs=10000, *, ghost_car
         raise ValueError("the Monte-Carlo form deals the reference's law only (exact=True has dealing='uniform')")
     hero = hands[0]
     hero_is_range = isinstance(hero, (set, frozenset))
-    if exact and any(isinstance(h, (set, frozenset)) or len(h) != 2 for h in hands):
-        raise ValueError("exact=True needs every hand as two cards")
+    if exact:
+        _two_cards_each(hands, "exact=True needs every hand as two cards")
     opp_range = 1 if opponent_range is None else opponent_range
-    q = _query(["2C", "2D"] if hero_is_range else hero, list(table_cards), players, 1 if exact else runs)
-    if hero_is_range:
-        q["hole"] = 0
+    q = _hero_query(hero, list(table_cards), players, 1 if exact else runs)
     ext = _ext_record(hero, hero_is_range, hands[1:], ghost_cards or '', opp_range, _opponent_range_bits(opp_range))
     eng = _lib.default_engine()
     if exact:
@@ -382,8 +404,7 @@ def get_seat_equities_exact(hands, table_cards, players=None, ghost_cards=None, 
     players = len(hands) if players is None else int(players)
     if not len(hands) <= players <= len(hands) + 1:
         raise ValueError("the per-seat enumeration takes at most one random opponent: players is len(hands) or len(hands) + 1")
-    if any(isinstance(h, (set, frozenset)) or len(h) != 2 for h in hands):
-        raise ValueError("every hand is two cards here (ranged hands are not enumerated)")
+    _two_cards_each(hands, "every hand is two cards here (ranged hands are not enumerated)")
     if dealing not in ("reference", "uniform"):
         raise ValueError("dealing must be 'reference' or 'uniform'")
     opp_range = 1 if opponent_range is None else opponent_range
@@ -414,11 +435,10 @@ def get_equity_batch(hole, board, n_players, runs, seed=None, first_query_id=0, 
     STATUS of n_gpus > 1: untested on more than one distinct device (no multi-GPU node was reachable; the partitions,
     the same-device add and a one-rank RCCL communicator are tested on one GPU with devices=[0, 0, ...]).
     """
-    if ties not in ("hero", "split"):
-        raise ValueError("ties must be 'hero' or 'split'")
+    split = _split_ties(ties, "hero")
     q = _lib.pack_queries(hole, board, n_players, runs)
     m = _state["mode"] if mode is None else _MODES[mode]
-    if ties == "split" and (devices is not None or (n_gpus is not None and int(n_gpus) > 1)):
+    if split and (devices is not None or (n_gpus is not None and int(n_gpus) > 1)):
         raise ValueError("ties='split' runs on one GPU (the multi-GPU entry has no split-pot rows)")
     if seed is None:
         s, base = _take_ids(len(q))
@@ -445,7 +465,7 @@ def get_equity_batch(hole, board, n_players, runs, seed=None, first_query_id=0, 
             res = me.eval_batch(q, s, first_query_id=first_query_id)
     else:
         eng = engine or _lib.default_engine()
-        if ties == "split":
+        if split:
             res = eng.eval_batch_ways(q, s, first_query_id=first_query_id, mode=m)
             tallies = res.view(np.uint64).reshape(len(q), 22)
             return _lib.pot_share(tallies), tallies
@@ -470,25 +490,20 @@ def get_equity_exact(player_cards, table_cards, players, dealing="reference", en
     have no common integer total, the equity is exact all the same.
     ties="split": the equity is hero's exact pot share and the row a RESULT_WAYS_DTYPE row of weights
     (mcq_exact_batch_ext_ways: at most ONE random opponent)."""
-    if ties not in ("credited", "split"):
-        raise ValueError("ties must be 'credited' or 'split'")
+    split = _split_ties(ties)
     opp_bits = _opponent_range_bits(opponent_range)
     known_hands = [list(h) for h in known_hands]
     q = _query(list(player_cards), list(table_cards), players, 1)
     eng = engine or _lib.default_engine()
-    if ties == "split":
-        for h in known_hands:
-            if len(h) != 2:
-                raise ValueError("a known hand is two cards here (ranged known hands are not enumerated)")
+    if split:
+        _two_cards_each(known_hands)
         ext = _ext_record(list(player_cards), False, known_hands, ghost_cards, opponent_range, opp_bits)
         _, weights = eng.exact_ext_ways(q, ext, dealing)
         return float(_lib.pot_share(weights)[0]), weights[0]
     if not known_hands and opp_bits is None and (ghost_cards == '' or ghost_cards is None):
         res = eng.exact(q, dealing)[0]
         return (int(res["win"]) + int(res["tie"])) / int(res["runs"]), res
-    for h in known_hands:
-        if isinstance(h, (set, frozenset)) or len(h) != 2:
-            raise ValueError("a known hand is two cards here (ranged known hands are not enumerated)")
+    _two_cards_each(known_hands)
     ext = _ext_record(list(player_cards), False, known_hands, ghost_cards, opponent_range, opp_bits)
     prob, weights = eng.exact_ext(q, ext, dealing)
     return float(prob[0]["win"] + prob[0]["tie"]), weights[0]
@@ -508,8 +523,7 @@ def get_range_equity_exact(hero_range, table_cards, opponent_range=1, dealing="r
     runs as the reference credits a tie; ties="split": the heads-up pot share (win + tie / 2) / runs -- and how often
     `dealing` deals hero that hand in proportion; `equity` is their weighted mean, what run_montecarlo with a hero range
     converges to under dealing='reference'.  Preflop, further players and known hands raise ValueError."""
-    if ties not in ("credited", "split"):
-        raise ValueError("ties must be 'credited' or 'split'")
+    _split_ties(ties)
     hero_bits = _opponent_range_bits(hero_range)
     if hero_bits is None:
         hero_bits = _lib.ALL_CLASSES
@@ -517,9 +531,7 @@ def get_range_equity_exact(hero_range, table_cards, opponent_range=1, dealing="r
     board = [card_id(c) for c in table_cards]
     if len(board) > 5:
         raise ValueError("table_cards holds more than five cards")
-    ghost = None
-    if ghost_cards != '' and ghost_cards is not None:
-        ghost = [card_id(ghost_cards[0]), card_id(ghost_cards[1])]
+    ghost = _ghost_ids(ghost_cards)
     q = _lib.pack_query_one([0, 0], board, 2, 1)
     ext = _lib.pack_query_ext(1, ghost=ghost, hero_range=hero_bits, opp_range=opp_bits)
     eng = engine or _lib.default_engine()
@@ -636,8 +648,7 @@ def get_range_equity_exact_weighted(hero, table_cards, opponent, ghost_cards='',
     its exact equity against the weighted opponent -- ties as in get_range_equity_exact -- and its weight (the quantised
     one / 65535; 1.0 in a plain range); `equity` is their weighted mean.  Preflop raises ValueError, and so does a hero
     hand against which no opponent hand of positive weight is left."""
-    if ties not in ("credited", "split"):
-        raise ValueError("ties must be 'credited' or 'split'")
+    _split_ties(ties)
     hero_bits, hero_w = _weighted_range(hero, "hero")
     opp_bits, opp_w = _weighted_range(opponent, "opponent")
     if opp_w is None:
@@ -645,9 +656,7 @@ def get_range_equity_exact_weighted(hero, table_cards, opponent, ghost_cards='',
     board = [card_id(c) for c in table_cards]
     if len(board) > 5:
         raise ValueError("table_cards holds more than five cards")
-    ghost = None
-    if ghost_cards != '' and ghost_cards is not None:
-        ghost = [card_id(ghost_cards[0]), card_id(ghost_cards[1])]
+    ghost = _ghost_ids(ghost_cards)
     q = _lib.pack_query_one([0, 0], board, 2, 1)
     ext = _lib.pack_query_ext(1, ghost=ghost, hero_range=hero_bits, opp_range=opp_bits)
     eng = engine or _lib.default_engine()
@@ -676,11 +685,10 @@ def matrix_equity(win, tie, total, ties="split"):
     """get_equity_matrix's counts as a float64 matrix of the row hand's equity against the column hand: ties="split" the
     heads-up pot share (win + tie / 2) / total, ties="credited" (win + tie) / total as the reference credits a tie; NaN where
     the two hands cannot both be dealt."""
-    if ties not in ("credited", "split"):
-        raise ValueError("ties must be 'credited' or 'split'")
+    split = _split_ties(ties)
     w, t = np.asarray(win, np.float64), np.asarray(tie, np.float64)
     dealt = (w + w.T + t) == float(total)
-    eq = (w + (t / 2.0 if ties == "split" else t)) / float(total)
+    eq = (w + (t / 2.0 if split else t)) / float(total)
     return np.where(dealt, eq, np.nan)
 
 
@@ -746,8 +754,7 @@ def get_preflop_range_equity_exact(hero_range, opponent_range=1, dealing="refere
     The arguments and the result are get_range_equity_exact's without table cards: -> (equity, {(card, card): (equity_h,
     weight_h)}).  by_class=True adds a third value, the 169-class table {class string: (equity, weight)}: per class of
     the range its hands' weighted mean equity and total weight under `dealing` (preflop_class_table)."""
-    if ties not in ("credited", "split"):
-        raise ValueError("ties must be 'credited' or 'split'")
+    _split_ties(ties)
     if dealing not in ("reference", "uniform", 0, 1):
         raise ValueError("dealing must be 'reference' or 'uniform'")
     hero_bits = _opponent_range_bits(hero_range)
@@ -756,11 +763,7 @@ def get_preflop_range_equity_exact(hero_range, opponent_range=1, dealing="refere
     if not np.asarray(hero_bits).any():
         raise ValueError("hero_range names no preflop class")
     opp_bits = _opponent_range_bits(opponent_range)
-    ghost = None
-    if ghost_cards != '' and ghost_cards is not None:
-        if len(ghost_cards) != 2:
-            raise ValueError("ghost_cards is two cards or ''")
-        ghost = [card_id(ghost_cards[0]), card_id(ghost_cards[1])]
+    ghost = _ghost_ids(ghost_cards, exactly_two=True)
     q = _lib.pack_query_one([0, 0], [], 2, 1)
     ext = _lib.pack_query_ext(1, ghost=ghost, hero_range=hero_bits, opp_range=opp_bits)
     eng = engine or _lib.default_engine()
@@ -781,19 +784,14 @@ def get_preflop_range_equity_exact_weighted(hero, opponent, ghost_cards='', engi
     (('AH', 'KH'): 1.0), quantised by quantise_weight.  -> (equity, {(card, card): (equity_h, weight_h)}) as that function
     returns it; by_class=True adds the class table {class string: (equity, weight)} of preflop_class_table.  A hero hand
     against which no opponent hand of positive weight is left raises ValueError."""
-    if ties not in ("credited", "split"):
-        raise ValueError("ties must be 'credited' or 'split'")
+    _split_ties(ties)
     hero_bits, hero_w = _weighted_range(hero, "hero")
     opp_bits, opp_w = _weighted_range(opponent, "opponent")
     if not np.asarray(hero_bits).any():
         raise ValueError("hero names no preflop class")
     if opp_w is None:
         opp_w = np.ones((1, _lib.HAND_ROWS), np.uint16)
-    ghost = None
-    if ghost_cards != '' and ghost_cards is not None:
-        if len(ghost_cards) != 2:
-            raise ValueError("ghost_cards is two cards or ''")
-        ghost = [card_id(ghost_cards[0]), card_id(ghost_cards[1])]
+    ghost = _ghost_ids(ghost_cards, exactly_two=True)
     q = _lib.pack_query_one([0, 0], [], 2, 1)
     ext = _lib.pack_query_ext(1, ghost=ghost, hero_range=hero_bits, opp_range=opp_bits)
     eng = engine or _lib.default_engine()
@@ -818,16 +816,13 @@ def get_runout_equities(player_cards, table_cards, players, dealing="reference",
     credits a tie; ties="split": hero's exact pot share.  Under dealing='reference' a card that would be the highest card
     left never comes (montecarlo_python.py:188) and is not listed.  Preflop, the river, two random opponents and ranged
     hands raise ValueError."""
-    if ties not in ("credited", "split"):
-        raise ValueError("ties must be 'credited' or 'split'")
+    split = _split_ties(ties)
     if opponent_range is None:
         opponent_range = 1
     if ghost_cards is None:
         ghost_cards = ''
     known_hands = [list(h) for h in known_hands]
-    for h in known_hands:
-        if len(h) != 2:
-            raise ValueError("a known hand is two cards here (ranged known hands are not enumerated)")
+    _two_cards_each(known_hands)
     opp_bits = _opponent_range_bits(opponent_range)
     q = _query(list(player_cards), list(table_cards), players, 1)
     k = 5 - int(q["n_board"][0])
@@ -838,7 +833,7 @@ def get_runout_equities(player_cards, table_cards, players, dealing="reference",
 
     def value(rows):
         """Equity of every weight row, exactly: the reference's credit or the pot share."""
-        if ties == "split":
+        if split:
             return [float(v) for v in _lib.pot_share(rows, exact=True)]
         return [(int(r[2]) + int(r[3])) / max(int(r[0]), 1) for r in rows]
 
