@@ -5,6 +5,7 @@
 
 #include "../../include/mcq.h"
 #include "mcq_plan.hpp"
+#include "mcq_tally.hpp" /* MCQ_DIRECT_TASKS_LIMIT */
 
 struct McqTables;
 
@@ -131,7 +132,6 @@ struct McqDirectKarg {
     uint32_t rec[MCQ_DIRECT_KARG_SLOTS][4]; /* per wave slot: the query record (16 B) */
     uint32_t qi[MCQ_DIRECT_KARG_SLOTS];     /* per wave slot: the query index or MCQ_DIRECT_IDLE */
 };
-#define MCQ_DIRECT_TASKS_LIMIT 32u /* most tasks of a query on the one-launch path: its row sums add two counters per word */
 hipError_t mcq_launch_eval_direct(int mode, const void *work_rec, const uint32_t *work_qi, uint32_t rounds, uint32_t merge,
                                   mcq_result *res, uint64_t seed, uint64_t first_qid, const McqTables *d_luts, uint32_t grid,
                                   uint32_t *d_done, uint32_t *done_flag, uint32_t ticket, hipStream_t s, hipEvent_t t0,

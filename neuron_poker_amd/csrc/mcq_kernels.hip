@@ -31,6 +31,7 @@
 #include "mcq_mt_ext.hpp"
 #include "mcq_mt_blocks.hpp"
 #include "mcq_ranges.hpp"
+#include "mcq_tally.hpp"
 
 namespace {
 
@@ -822,201 +823,35 @@ __global__ __launch_bounds__(256) void mcq_publish_kernel(ulonglong2 *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------- eval
-struct WaveTally { /* per-lane running sums of the current (wave, query) pair */
-    uint32_t code[MCQ_N_CODES], tie, passes;
-    bool dirty;
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int c = 0; c < MCQ_N_CODES; c++) code[c] = 0;
-        tie = passes = 0;
-        dirty = false;
-    }
-    __device__ __forceinline__ void add(const McqLaneAcc &a) {
-#pragma unroll
-        for (int c = 0; c < MCQ_N_CODES; c++)
-            if (c != 5) code[c] += (uint32_t)(a.types >> (6 * c)) & 63u;
-        tie += a.tie;
-        passes += a.passes;
-        dirty = true;
-    }
-    /* lanes -> wave: lane k < 12 returns word k + 1 of the result row (passes, win, tie, by_type[9]).  For the
-     * one-launch path: the whole wave is active and a lane has added at most MCQ_DIRECT_TASKS_LIMIT tasks of 16
-     * iterations, so a counter's wave sum is below 2^16 and two counters share a reduction. */
-    __device__ __forceinline__ unsigned long long row_words(uint32_t lane) {
-        static_assert(64u * 16u * MCQ_DIRECT_TASKS_LIMIT < 65536u, "two counters per 32-bit reduction");
-        uint32_t sums[MCQ_N_CODES + 1]; /* the codes (5 unused), then the ties */
-#pragma unroll
-        for (uint32_t c = 0; c < MCQ_N_CODES; c += 2) {
-            const uint32_t hi = c + 1 < MCQ_N_CODES ? code[c + 1] : 0u;
-            const uint32_t v = wave_sum_dpp(code[c] | (hi << 16));
-            sums[c] = v & 0xFFFFu;
-            sums[c + 1] = v >> 16;
-        }
-        const uint32_t ties = wave_sum_dpp(tie);
-        const uint32_t pass = wave_sum_dpp(passes);
-        uint32_t wins = 0;
-        unsigned long long mine = 0;
-#pragma unroll
-        for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-            if (c == 5) continue;
-            wins += sums[c];
-            if (lane == 3u + mcq_code_to_type(c)) mine = sums[c];
-        }
-        if (lane == 0) mine = pass;
-        if (lane == 1) mine = wins - ties;
-        if (lane == 2) mine = ties;
-        return mine;
-    }
-    /* lanes -> wave (shuffles): lane l < 12 holds word 1 + l of the row (passes, win, tie, by_type[9]) */
-    __device__ __forceinline__ uint64_t row_value(uint32_t lane) {
-        uint32_t wins = 0;
-        uint64_t mine = 0;
-#pragma unroll
-        for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-            if (c == 5) continue;
-            const uint32_t v = wave_sum(code[c]);
-            wins += v;
-            if (lane == 3u + mcq_code_to_type(c)) mine = v;
-        }
-        const uint32_t ties = wave_sum(tie);
-        const uint32_t pass = wave_sum(passes);
-        if (lane == 0) mine = pass;
-        if (lane == 1) mine = wins - ties;
-        if (lane == 2) mine = ties;
-        return mine;
-    }
-    /* ... -> one 64-bit atomic per counter */
-    __device__ __forceinline__ void flush(mcq_result *row, uint32_t lane) {
-        if (!dirty) return;
+/* The wave tallies (mcq_tally.hpp: lane states, counter-to-word table, lanes -> row step) wired to this wave's reductions --
+ * shuffles for a flush in the middle of the work, DPP where the whole wave is active -- and to the row's atomics. */
+struct WaveSum {
+    __device__ __forceinline__ uint32_t operator()(uint32_t v) const { return wave_sum(v); }
+};
+struct WaveSumDpp {
+    __device__ __forceinline__ uint32_t operator()(uint32_t v) const { return wave_sum_dpp(v); }
+};
+struct RowAtomicAdd {
+    __device__ __forceinline__ void operator()(unsigned long long *word, unsigned long long v) const { atomicAdd(word, v); }
+};
+template <class State> struct WaveTallyOf : State {
+    __device__ __forceinline__ uint64_t row_value(uint32_t lane) const { return State::row_value(lane, WaveSum()); }
+    __device__ __forceinline__ uint64_t row_words(uint32_t lane) const { return State::row_words(lane, WaveSumDpp()); }
+    /* ... -> one 64-bit atomic per counter that is not zero.  (Written out here and not behind a functor for the atomic,
+     * as the per-seat flush is: that form changed the instruction order of the sliced kernels.) */
+    template <class Row> __device__ __forceinline__ void flush(Row *row, uint32_t lane) {
+        if (!this->dirty) return;
         const uint64_t mine = row_value(lane);
-        if (lane < 12 && mine != 0)
+        if (lane < State::kLanes && mine != 0)
             atomicAdd(reinterpret_cast<unsigned long long *>(row) + 1 + lane, (unsigned long long)mine);
-        clear();
+        this->clear();
     }
 };
-
-/* The split-pot rows (mcq_result_ways): tie_ways[k - 2] in lane 12 + (k - 2) = word 13 + (k - 2) of the 22-word row, the
- * same reductions and, on the one-launch path, the same two-per-word packing.  The evaluation kernels run at the register
- * limit, so the nine counters cost two registers, not nine: a lane keeps them as 10-bit fields, three per register -- a
- * task adds at most 16 to a field, so the tally is flushed after MCQ_WAYS_TALLY_TASKS tasks (the row's counters are
- * atomic sums: a flush in the middle of a query changes nothing) -- and `tie` is not kept at all: it is their sum. */
-#define MCQ_WAYS_TALLY_TASKS 63u
-struct WaveTallyWays {
-    uint32_t code[MCQ_N_CODES], passes, way3[3];
-    uint32_t n_add; /* tasks added since the last flush (wave-uniform) */
-    bool dirty;
-    static_assert(16u * MCQ_WAYS_TALLY_TASKS < 1024u && MCQ_DIRECT_TASKS_LIMIT <= MCQ_WAYS_TALLY_TASKS, "10-bit fields");
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int c = 0; c < MCQ_N_CODES; c++) code[c] = 0;
-        way3[0] = way3[1] = way3[2] = 0;
-        passes = 0;
-        n_add = 0;
-        dirty = false;
-    }
-    __device__ __forceinline__ void add(const McqLaneAccWays &a) {
-#pragma unroll
-        for (int c = 0; c < MCQ_N_CODES; c++)
-            if (c != 5) code[c] += (uint32_t)(a.types >> (6 * c)) & 63u;
-#pragma unroll
-        for (uint32_t k = 0; k < MCQ_N_WAYS; k++)
-            way3[k / 3u] += ((uint32_t)(a.ways >> (6u * (k + 1u))) & 63u) << (10u * (k % 3u));
-        passes += a.passes;
-        n_add++;
-        dirty = true;
-    }
-    __device__ __forceinline__ bool full() const { return n_add >= MCQ_WAYS_TALLY_TASKS; }
-    __device__ __forceinline__ uint32_t way(uint32_t k) const { return (way3[k / 3u] >> (10u * (k % 3u))) & 1023u; }
-    /* as WaveTally::row_words, lanes 12..20: tie_ways */
-    __device__ __forceinline__ unsigned long long row_words(uint32_t lane) {
-        static_assert(64u * 16u * MCQ_DIRECT_TASKS_LIMIT < 65536u, "two counters per 32-bit reduction");
-        uint32_t wins = 0, ties = 0;
-        unsigned long long mine = 0;
-#pragma unroll
-        for (uint32_t c = 0; c < MCQ_N_CODES; c += 2) {
-            const uint32_t hi = c + 1 < MCQ_N_CODES ? code[c + 1] : 0u;
-            const uint32_t v = wave_sum_dpp(code[c] | (hi << 16));
-            const uint32_t s0 = v & 0xFFFFu, s1 = v >> 16;
-            wins += s0 + s1; /* (code 5 is never counted: zero) */
-            if (c != 5 && lane == 3u + mcq_code_to_type(c)) mine = s0;
-            if (c + 1 != 5 && c + 1 < MCQ_N_CODES && lane == 3u + mcq_code_to_type(c + 1)) mine = s1;
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < MCQ_N_WAYS; k += 2) {
-            const uint32_t hi = k + 1 < MCQ_N_WAYS ? way(k + 1) : 0u;
-            const uint32_t v = wave_sum_dpp(way(k) | (hi << 16));
-            ties += (v & 0xFFFFu) + (v >> 16);
-            if (lane == 12u + k) mine = v & 0xFFFFu;
-            if (k + 1 < MCQ_N_WAYS && lane == 13u + k) mine = v >> 16;
-        }
-        const uint32_t pass = wave_sum_dpp(passes);
-        if (lane == 0) mine = pass;
-        if (lane == 1) mine = wins - ties;
-        if (lane == 2) mine = ties;
-        return mine;
-    }
-    __device__ __forceinline__ uint64_t row_value(uint32_t lane) {
-        uint32_t wins = 0, ties = 0;
-        uint64_t mine = 0;
-#pragma unroll
-        for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-            if (c == 5) continue;
-            const uint32_t v = wave_sum(code[c]);
-            wins += v;
-            if (lane == 3u + mcq_code_to_type(c)) mine = v;
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < MCQ_N_WAYS; k++) {
-            const uint32_t v = wave_sum(way(k));
-            ties += v;
-            if (lane == 12u + k) mine = v;
-        }
-        const uint32_t pass = wave_sum(passes);
-        if (lane == 0) mine = pass;
-        if (lane == 1) mine = wins - ties;
-        if (lane == 2) mine = ties;
-        return mine;
-    }
-    __device__ __forceinline__ void flush(unsigned long long *row, uint32_t lane) {
-        if (!dirty) return;
-        const uint64_t mine = row_value(lane);
-        if (lane < 12u + MCQ_N_WAYS && mine != 0) atomicAdd(row + 1 + lane, (unsigned long long)mine);
-        clear();
-    }
-};
-/* The per-seat rows (mcq_result_seats, extended queries): word 1 passes, then win, tie, share of seat 0..9 -- lane l holds
- * word 1 + l, lanes 0..30.  Thirty running counters per lane would not fit beside the iteration's state, so nothing is
- * kept per lane between tasks: a task's lane words (McqLaneAccSeats: one packed word per seat) are summed over the wave
- * at once -- the share field on its own (64 lanes x 16 x 2520 < 2^22), win and tie together as 16-bit halves (<= 1024
- * each) -- and every lane adds the sum of ITS word to one 64-bit register, which goes to the row as one atomic per lane
- * when the wave leaves the query. */
-struct WaveTallySeats {
-    unsigned long long mine;
-    bool dirty;
-    __device__ __forceinline__ void clear() {
-        mine = 0;
-        dirty = false;
-    }
-    __device__ __forceinline__ void add(const McqLaneAccSeats &a, uint32_t lane) { /* whole wave */
-        const uint32_t pass = wave_sum_dpp(a.passes);
-        uint32_t v = lane == 0u ? pass : 0u;
-#pragma unroll
-        for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) {
-            const uint32_t w = a.seat[s];
-            const uint32_t share = wave_sum_dpp(w & 0xFFFFu);
-            const uint32_t wt = wave_sum_dpp(((w >> MCQ_SEAT_WIN_SHIFT) & 31u) | (((w >> MCQ_SEAT_TIE_SHIFT) & 31u) << 16));
-            v = lane == 1u + 3u * s ? wt & 0xFFFFu : v;
-            v = lane == 2u + 3u * s ? wt >> 16 : v;
-            v = lane == 3u + 3u * s ? share : v;
-        }
-        mine += v;
-        dirty = true;
-    }
-    __device__ __forceinline__ void flush(unsigned long long *row, uint32_t lane) {
-        if (!dirty) return;
-        if (lane < 1u + 3u * MCQ_MAX_SEATS && mine != 0ull) atomicAdd(row + 1 + lane, mine);
-        clear();
-    }
+typedef WaveTallyOf<McqTally> WaveTally;
+typedef WaveTallyOf<McqTallyWays> WaveTallyWays;
+struct WaveTallySeats : McqTallySeats {
+    __device__ __forceinline__ void add(const McqLaneAccSeats &a, uint32_t lane) { McqTallySeats::add(a, lane, WaveSumDpp()); }
+    __device__ __forceinline__ void flush(unsigned long long *row, uint32_t lane) { McqTallySeats::flush(row, lane, RowAtomicAdd()); }
 };
 /* what a kernel instantiation works with: the lane accumulator, the wave tally, the row's length in 64-bit words and the
  * lanes that hold one word of it each (every word but `runs`).  KIND: MCQ_ROW_PLAIN (0 = false), MCQ_ROW_WAYS (1 = true),
@@ -1027,13 +862,13 @@ struct WaveTallySeats {
 template <int KIND> struct McqRowKind {
     typedef McqLaneAcc Acc;
     typedef WaveTally Tally;
-    static constexpr uint32_t kWords = 13u, kLanes = 12u;
+    static constexpr uint32_t kWords = Tally::kWords, kLanes = Tally::kLanes;
     static __device__ __forceinline__ mcq_result *row(mcq_result *res, uint32_t i) { return res + i; }
 };
 template <> struct McqRowKind<MCQ_ROW_WAYS> {
     typedef McqLaneAccWays Acc;
     typedef WaveTallyWays Tally;
-    static constexpr uint32_t kWords = 13u + MCQ_N_WAYS, kLanes = 12u + MCQ_N_WAYS;
+    static constexpr uint32_t kWords = Tally::kWords, kLanes = Tally::kLanes;
     static __device__ __forceinline__ unsigned long long *row(mcq_result *res, uint32_t i) {
         return reinterpret_cast<unsigned long long *>(res) + (size_t)i * kWords;
     }
@@ -1041,13 +876,11 @@ template <> struct McqRowKind<MCQ_ROW_WAYS> {
 template <> struct McqRowKind<MCQ_ROW_SEATS> {
     typedef McqLaneAccSeats Acc;
     typedef WaveTallySeats Tally;
-    static constexpr uint32_t kWords = 2u + 3u * MCQ_MAX_SEATS; /* lanes 0..30 hold words 1..31 */
+    static constexpr uint32_t kWords = Tally::kWords; /* lanes 0..30 hold words 1..31 */
     static __device__ __forceinline__ unsigned long long *row(mcq_result *res, uint32_t i) {
         return reinterpret_cast<unsigned long long *>(res) + (size_t)i * kWords;
     }
 };
-static_assert(McqRowKind<MCQ_ROW_WAYS>::kWords * 8u == sizeof(mcq_result_ways), "row of mcq_result_ways");
-static_assert(McqRowKind<MCQ_ROW_SEATS>::kWords * 8u == sizeof(mcq_result_seats) && sizeof(mcq_seat) == 24u, "row of mcq_result_seats");
 
 template <int MODE, bool SPLIT, bool WAYS>
 __global__ __launch_bounds__(kMaxBlock) void mcq_eval_kernel(const mcq_query *__restrict__ queries, uint32_t n,

@@ -18,6 +18,7 @@
 #include "../../neuron_poker_amd/csrc/mcq_mt_ext.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_mt_blocks.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_replay.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace {
 McqTables g_tab;
@@ -29,18 +30,6 @@ const McqTables &luts() {
 // the iteration takes the base-deck pointer biased by -128 entries: keep 128 unused entries in front
 void make_base(const McqQueryCtx &qc, const McqTables &t, McqCard *store) {
     for (uint32_t l = 0; l < 64; l++) store[128 + l] = mcq_base_entry(qc, l, t.sel8);
-}
-void fold(const McqLaneAcc &a, mcq_result *r) {
-    uint64_t wins = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue;
-        uint64_t v = (a.types >> (6 * c)) & 63;
-        r->by_type[mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    r->tie += a.tie;
-    r->win += wins - a.tie;
-    r->passes += a.passes;
 }
 }  // namespace
 
@@ -135,7 +124,7 @@ static int run_ctr_t(const mcq_query *q, uint64_t seed, uint64_t qid, mcq_result
         if (STRAIGHT) mcq_iterations<true>(qc, dr, base, t.tf, t.tops, t.sd, acc, cnt); /* as the bulk kernel runs them */
         else for (uint32_t j = 0; j < cnt; j++) mcq_iteration(qc, dr, base, t.tf, t.tops, t.sd, acc);
         acc.passes += cnt * qc.n_opp; /* MCQ-CTR v5: one attempt per opponent, never re-drawn */
-        fold(acc, out);
+        mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
     }
     return MCQ_OK;
 }
@@ -174,7 +163,7 @@ int hs_run_replay(const mcq_query *q, uint32_t seed32, mcq_result *out) {
             McqLaneAcc acc = {0, 0, 0};
             mcq_iteration(qc, dr, base, t.tf, t.tops, t.sd, acc);
             acc.passes = 0;
-            fold(acc, out);
+            mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
         }
     }
     return MCQ_OK;
@@ -203,7 +192,7 @@ int hs_run_replay_stream(const mcq_query *q, uint32_t *key, uint32_t *pos, mcq_r
         McqLaneAcc acc = {0, 0, 0};
         mcq_iteration(qc, dr, base, t.tf, t.tops, t.sd, acc);
         acc.passes = 0;
-        fold(acc, out);
+        mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
     }
     return MCQ_OK;
 }
@@ -259,7 +248,7 @@ extern "C" int hs_run_ext(int replay, const mcq_query *q, const mcq_query_ext *e
             McqLaneAcc acc = {0, 0, 0};
             mcq_iteration_ext(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc);
             acc.passes = 0;
-            fold(acc, out);
+            mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
         }
         return MCQ_OK;
     }
@@ -275,7 +264,7 @@ extern "C" int hs_run_ext(int replay, const mcq_query *q, const mcq_query_ext *e
                           : mcq_iteration_ext(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc)))
                 return MCQ_EINVAL;
         }
-        fold(acc, out);
+        mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
     }
     return MCQ_OK;
 }

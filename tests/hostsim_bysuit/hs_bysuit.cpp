@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace {
 // HS_BYSUIT_LEAN (hs_main.cpp, the stand-alone program under the sanitizers): a few forms -- heads-up with one card to
@@ -34,33 +35,6 @@ typedef McqDeckBySuit<kY, 5u, 8u> DeckPos;                        /* position-ma
 typedef McqDeckBySuit<kY, 3u, 8u * MCQ_HOLE_POSITIONS> DeckSuit;  /* suit-major */
 typedef McqDeckSplit<kY> DeckSplit;
 
-void fold(const McqLaneAcc &a, uint64_t *row) {
-    uint64_t wins = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue; /* the gap in the codes */
-        const uint64_t v = (a.types >> (6 * c)) & 63;
-        row[4 + mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    row[2] += wins - a.tie;
-    row[3] += a.tie;
-}
-void fold(const McqLaneAccWays &a, uint64_t *row) { /* as WaveTallyWays: tie is the sum of the ways */
-    uint64_t wins = 0, ties = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue;
-        const uint64_t v = (a.types >> (6 * c)) & 63;
-        row[4 + mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    for (uint32_t k = 0; k < MCQ_N_WAYS; k++) {
-        const uint64_t v = (a.ways >> (6u * (k + 1u))) & 63;
-        row[13 + k] += v;
-        ties += v;
-    }
-    row[2] += wins - ties;
-    row[3] += ties;
-}
 
 // a query's base deck behind every accessor: the array of cards, the two arrays of halves, and a hole table per layout.
 // A table's 1600 bytes END its heap block (a read or write behind position 49 is the sanitizer's); in front of it lie the
@@ -108,7 +82,7 @@ int run(const Decks &dk, const Deck &deck, const mcq_query *q, uint64_t seed, ui
         for (uint32_t j = 0; j < cnt; j++)
             mcq_iteration_sum<Draws, NOPP, NDEAL, Acc, Deck, MCQ_DEAL_RULE, BYSUIT>(qc, dr, deck, tabs, acc);
         row[1] += (uint64_t)cnt * qc.n_opp; /* passes: one attempt per opponent, never re-drawn */
-        fold(acc, row);
+        mcq_tally_fold(acc, row);
     }
     return MCQ_OK;
 }

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace {
 McqTables g_tab;
@@ -33,16 +34,8 @@ int run(const mcq_query *q, uint64_t seed, uint64_t qid, uint64_t *row) {
         const uint64_t left = (uint64_t)q->runs - (uint64_t)s * MCQ_STREAM_ITERS;
         const uint32_t cnt = left < MCQ_STREAM_ITERS ? (uint32_t)left : MCQ_STREAM_ITERS;
         mcq_iterations<STRAIGHT>(qc, dr, base, t.tf, t.tops, t.sd, acc, cnt);
-        uint64_t wins = 0;
-        for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-            if (c == 5) continue; /* the gap in the codes */
-            const uint64_t v = (acc.types >> (6 * c)) & 63;
-            row[4 + mcq_code_to_type(c)] += v;
-            wins += v;
-        }
-        row[1] += (uint64_t)cnt * qc.n_opp; /* passes: one attempt per opponent, never re-drawn */
-        row[2] += wins - acc.tie;
-        row[3] += acc.tie;
+        acc.passes = cnt * qc.n_opp; /* one attempt per opponent, never re-drawn */
+        mcq_tally_fold(acc, row);
     }
     return MCQ_OK;
 }

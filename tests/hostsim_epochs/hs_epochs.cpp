@@ -17,6 +17,7 @@
 
 #include "../../neuron_poker_amd/csrc/mcq_device.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_replay.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace {
 // HS_EPOCHS_LEAN (hs_main.cpp, the stand-alone program under the sanitizers): the plans of 3, 7, 12, 15 and 23 draws, and of
@@ -33,33 +34,6 @@ bool g_init = false;
 const McqTables &luts() {
     if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
     return g_tab;
-}
-void fold(const McqLaneAcc &a, uint64_t *row) {
-    uint64_t wins = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue; /* the gap in the codes */
-        const uint64_t v = (a.types >> (6 * c)) & 63;
-        row[4 + mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    row[2] += wins - a.tie;
-    row[3] += a.tie;
-}
-void fold(const McqLaneAccWays &a, uint64_t *row) { /* as WaveTallyWays: tie is the sum of the ways */
-    uint64_t wins = 0, ties = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue;
-        const uint64_t v = (a.types >> (6 * c)) & 63;
-        row[4 + mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    for (uint32_t k = 0; k < MCQ_N_WAYS; k++) {
-        const uint64_t v = (a.ways >> (6u * (k + 1u))) & 63;
-        row[13 + k] += v;
-        ties += v;
-    }
-    row[2] += wins - ties;
-    row[3] += ties;
 }
 
 // ---- positions
@@ -130,7 +104,7 @@ int run(const mcq_query *q, uint64_t seed, uint64_t qid, uint64_t *row) {
         const uint32_t cnt = left < MCQ_STREAM_ITERS ? (uint32_t)left : MCQ_STREAM_ITERS;
         for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, NOPP, NDEAL, Acc, McqDeckAoS, RULE>(qc, dr, deck, tabs, acc);
         row[1] += (uint64_t)cnt * qc.n_opp; /* passes: one attempt per opponent, never re-drawn */
-        fold(acc, row);
+        mcq_tally_fold(acc, row);
     }
     return MCQ_OK;
 }
@@ -242,7 +216,7 @@ int hs_epochs_replay(const mcq_query *q, uint32_t seed32, uint64_t *row) {
         dr.load(draws.data() + it4, stride, qc.n_opp, qc.n_deal);
         McqLaneAcc acc = {};
         mcq_iterations_replay4(qc, dr, deck, tabs, acc, q->runs - it4 < 4u ? q->runs - it4 : 4u);
-        fold(acc, row);
+        mcq_tally_fold(acc, row);
     }
     return MCQ_OK;
 }

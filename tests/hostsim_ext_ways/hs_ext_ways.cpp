@@ -25,6 +25,7 @@ inline void hs_dealt(uint32_t h, uint32_t c1, uint32_t c2) {
 #include "../../neuron_poker_amd/csrc/mcq_device.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_replay.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact_ext.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace {
 McqTables g_tab;
@@ -32,23 +33,6 @@ bool g_init = false;
 const McqTables &luts() {
     if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
     return g_tab;
-}
-void fold(const McqLaneAccWays &a, mcq_result_ways *o) { /* as WaveTallyWays: `tie` is the sum of the ways */
-    uint64_t wins = 0, ties = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue;
-        const uint64_t v = (a.types >> (6 * c)) & 63;
-        o->r.by_type[mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    for (uint32_t k = 0; k < MCQ_N_WAYS; k++) {
-        const uint64_t v = (a.ways >> (6u * (k + 1u))) & 63;
-        o->tie_ways[k] += v;
-        ties += v;
-    }
-    o->r.tie += ties;
-    o->r.win += wins - ties;
-    o->r.passes += a.passes;
 }
 }  // namespace
 
@@ -110,7 +94,7 @@ int hs_ext_ways_run(int replay, const mcq_query *q, const mcq_query_ext *e, uint
             begin(it);
             mcq_iteration_ext<McqExtReplayDraws, false, McqLaneAccWays>(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc);
             acc.passes = 0;
-            fold(acc, out);
+            mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
         }
         return MCQ_OK;
     }
@@ -129,7 +113,7 @@ int hs_ext_ways_run(int replay, const mcq_query *q, const mcq_query_ext *e, uint
                 : mcq_iteration_ext<McqExtCtrDraws, false, McqLaneAccWays>(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc);
             if (!ok) return MCQ_EINVAL;
         }
-        fold(acc, out);
+        mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
     }
     return MCQ_OK;
 }

@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace {
 McqTables g_tab;
@@ -18,33 +19,6 @@ bool g_init = false;
 const McqTables &luts() {
     if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
     return g_tab;
-}
-void fold(const McqLaneAcc &a, uint64_t *row) {
-    uint64_t wins = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue; /* the gap in the codes */
-        const uint64_t v = (a.types >> (6 * c)) & 63;
-        row[4 + mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    row[2] += wins - a.tie;
-    row[3] += a.tie;
-}
-void fold(const McqLaneAccWays &a, uint64_t *row) { /* as WaveTallyWays: tie is the sum of the ways */
-    uint64_t wins = 0, ties = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue;
-        const uint64_t v = (a.types >> (6 * c)) & 63;
-        row[4 + mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    for (uint32_t k = 0; k < MCQ_N_WAYS; k++) {
-        const uint64_t v = (a.ways >> (6u * (k + 1u))) & 63;
-        row[13 + k] += v;
-        ties += v;
-    }
-    row[2] += wins - ties;
-    row[3] += ties;
 }
 
 template <class Draws, class Acc, int NOPP, int NDEAL>
@@ -69,7 +43,7 @@ int run(const mcq_query *q, uint64_t seed, uint64_t qid, uint64_t *row) {
         const uint32_t cnt = left < MCQ_STREAM_ITERS ? (uint32_t)left : MCQ_STREAM_ITERS;
         for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, NOPP, NDEAL, Acc>(qc, dr, deck, tabs, acc);
         row[1] += (uint64_t)cnt * qc.n_opp; /* passes: one attempt per opponent, never re-drawn */
-        fold(acc, row);
+        mcq_tally_fold(acc, row);
     }
     return MCQ_OK;
 }

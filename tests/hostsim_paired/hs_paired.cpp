@@ -16,6 +16,7 @@
 
 #include "../../neuron_poker_amd/csrc/mcq_device.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_replay.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace {
 // HS_PAIRED_LEAN (hs_main.cpp, the stand-alone program under the sanitizers): the plans of 7, 12, 15, 19 and 23 draws, and
@@ -31,33 +32,6 @@ bool g_init = false;
 const McqTables &luts() {
     if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
     return g_tab;
-}
-void fold(const McqLaneAcc &a, uint64_t *row) {
-    uint64_t wins = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue; /* the gap in the codes */
-        const uint64_t v = (a.types >> (6 * c)) & 63;
-        row[4 + mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    row[2] += wins - a.tie;
-    row[3] += a.tie;
-}
-[[maybe_unused]] void fold(const McqLaneAccWays &a, uint64_t *row) { /* (a lean build has no split-pot rows)  as WaveTallyWays: tie is the sum of the ways */
-    uint64_t wins = 0, ties = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue;
-        const uint64_t v = (a.types >> (6 * c)) & 63;
-        row[4 + mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    for (uint32_t k = 0; k < MCQ_N_WAYS; k++) {
-        const uint64_t v = (a.ways >> (6u * (k + 1u))) & 63;
-        row[13 + k] += v;
-        ties += v;
-    }
-    row[2] += wins - ties;
-    row[3] += ties;
 }
 
 // ---- positions
@@ -145,7 +119,7 @@ int run(const mcq_query *q, uint64_t seed, uint64_t qid, uint64_t *row) {
         for (uint32_t j = 0; j < cnt; j++)
             mcq_iteration_sum<Draws, NOPP, NDEAL, Acc, McqDeckAoS, MCQ_DEAL_RULE, (MCQ_HOLE_BY_SUIT != 0), PAIRED>(qc, dr, deck, tabs, acc);
         row[1] += (uint64_t)cnt * qc.n_opp; /* passes: one attempt per opponent, never re-drawn */
-        fold(acc, row);
+        mcq_tally_fold(acc, row);
     }
     return MCQ_OK;
 }
@@ -264,7 +238,7 @@ int hs_paired_replay(const mcq_query *q, uint32_t seed32, uint64_t *row) {
         dr.load(draws.data() + it4, stride, qc.n_opp, qc.n_deal);
         McqLaneAcc acc = {};
         mcq_iterations_replay4(qc, dr, deck, tabs, acc, q->runs - it4 < 4u ? q->runs - it4 : 4u);
-        fold(acc, row);
+        mcq_tally_fold(acc, row);
     }
     return MCQ_OK;
 }

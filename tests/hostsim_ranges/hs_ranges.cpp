@@ -22,6 +22,7 @@ inline void hs_dealt(uint32_t h, uint32_t c1, uint32_t c2) {
 #define MCQ_RANGES_DEAL_HOOK(h, c1, c2) hs_dealt(h, c1, c2)
 
 #include "../../neuron_poker_amd/csrc/mcq_ranges.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace {
 McqTables g_tab;
@@ -85,12 +86,7 @@ int hs_ranges_run(const mcq_query *q, const uint32_t *seat_table, const uint16_t
             failed = !mcq_iteration_ranges<McqExtCtrDraws, false, McqLaneAccSeats>(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc);
         }
         if (failed) return 2;
-        out->passes += acc.passes;
-        for (uint32_t k = 0; k < MCQ_MAX_SEATS; k++) {
-            out->seat[k].share += acc.seat[k] & 0xFFFFu;
-            out->seat[k].win += (acc.seat[k] >> MCQ_SEAT_WIN_SHIFT) & 31u;
-            out->seat[k].tie += (acc.seat[k] >> MCQ_SEAT_TIE_SHIFT) & 31u;
-        }
+        mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
     }
     return MCQ_OK;
 }

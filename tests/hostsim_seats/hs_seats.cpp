@@ -24,6 +24,7 @@ inline void hs_dealt(uint32_t h, uint32_t c1, uint32_t c2) {
 
 #include "../../neuron_poker_amd/csrc/mcq_device.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact_ext.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace {
 McqTables g_tab;
@@ -31,14 +32,6 @@ bool g_init = false;
 const McqTables &luts() {
     if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
     return g_tab;
-}
-void fold(const McqLaneAccSeats &a, mcq_result_seats *o) {
-    o->passes += a.passes;
-    for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) {
-        o->seat[s].share += a.seat[s] & 0xFFFFu;
-        o->seat[s].win += (a.seat[s] >> MCQ_SEAT_WIN_SHIFT) & 31u;
-        o->seat[s].tie += (a.seat[s] >> MCQ_SEAT_TIE_SHIFT) & 31u;
-    }
 }
 }  // namespace
 
@@ -93,7 +86,7 @@ int hs_seats_run(const mcq_query *q, const mcq_query_ext *e, uint64_t seed, uint
             if (!mcq_iteration_ext<McqExtCtrDraws, false, McqLaneAccSeats>(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc))
                 return MCQ_EINVAL;
         }
-        fold(acc, out);
+        mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
     }
     return MCQ_OK;
 }

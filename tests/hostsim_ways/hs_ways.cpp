@@ -11,6 +11,7 @@
 
 #include "../../neuron_poker_amd/csrc/mcq_device.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_replay.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace {
 McqTables g_tab;
@@ -21,23 +22,6 @@ const McqTables &luts() {
 }
 void make_base(const McqQueryCtx &qc, const McqTables &t, McqCard *store) {
     for (uint32_t l = 0; l < 64; l++) store[128 + l] = mcq_base_entry(qc, l, t.sel8);
-}
-void fold(const McqLaneAccWays &a, mcq_result_ways *o) {
-    uint64_t wins = 0, ties = 0;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) {
-        if (c == 5) continue;
-        const uint64_t v = (a.types >> (6 * c)) & 63;
-        o->r.by_type[mcq_code_to_type(c)] += v;
-        wins += v;
-    }
-    for (uint32_t k = 0; k < MCQ_N_WAYS; k++) {
-        const uint64_t v = (a.ways >> (6u * (k + 1u))) & 63;
-        o->tie_ways[k] += v;
-        ties += v;
-    }
-    o->r.tie += ties;
-    o->r.win += wins - ties;
-    o->r.passes += a.passes;
 }
 
 template <class Draws, bool STRAIGHT>
@@ -60,7 +44,7 @@ int run_ctr_t(const mcq_query *q, uint64_t seed, uint64_t qid, mcq_result_ways *
         if (STRAIGHT) mcq_iterations<true>(qc, dr, base, t.tf, t.tops, t.sd, acc, cnt); /* as the bulk kernel runs them */
         else for (uint32_t j = 0; j < cnt; j++) mcq_iteration(qc, dr, base, t.tf, t.tops, t.sd, acc); /* the one-launch kernel */
         acc.passes += cnt * qc.n_opp;
-        fold(acc, out);
+        mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
     }
     return MCQ_OK;
 }
@@ -94,7 +78,7 @@ int hs_ways_run(int mode, const mcq_query *q, uint64_t seed, uint64_t qid, int g
             McqLaneAccWays acc = {};
             mcq_iteration(qc, dr, base, t.tf, t.tops, t.sd, acc);
             acc.passes = 0;
-            fold(acc, out);
+            mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
         }
     }
     return MCQ_OK;

@@ -12,7 +12,9 @@ and 1 150 000 iterations are 224 or 225 tasks per wave: three flushes, then a ta
 The saturating board: hero 2C 3D on KC KD KH KS AS.  The reference scores quads on the table by the two highest distinct
 ranks of all seven cards, so every hand ties in every iteration: each iteration adds to exactly one field, k =
 n_players, and a lane's field stands at exactly 16 x 63 = 1008 of its 1023 when the flush comes.  k = 4, 7, 10 are the
-top fields of the three registers, k = 2, 5, 8 the bottom ones.
+top fields of the three registers, k = 2, 5, 8 the bottom ones.  (The packing itself -- why 63 and not 64, what a field
+holds after every task -- is pinned without a GPU by tests/test_tally_host.py on csrc/mcq_tally.hpp; here the shipped
+kernels run into it.)
 
 Part C -- run counts at the top of the 32-bit range at the full geometry: single tasks (windows) against the oracle, and
 whole queries of 2^32 - 1 iterations against identities that need no oracle.
