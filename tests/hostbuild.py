@@ -63,3 +63,17 @@ def first_bytes(a, n):
 def record(query16, ext):
     """(the query's 16 bytes, the extension's 304 bytes)"""
     return first_bytes(query16, 16), first_bytes(ext, 304)
+
+
+def rows(entry, queries, width, *args, qid_at=None):
+    """One 16-byte record of `queries` at a time through entry(record, *args, row) -> uint64 [n, width].  qid_at: the
+    place in args of the first query's id; query i gets that id + i.  ValueError on a return other than 0."""
+    q = np.ascontiguousarray(queries).view(np.uint8).reshape(-1, 16)
+    out = np.zeros((len(q), width), np.uint64)
+    for i in range(len(q)):
+        rec = q[i].copy()
+        a = [v + i if k == qid_at else v for k, v in enumerate(args)]
+        rc = entry(rec.ctypes.data_as(ctypes.c_void_p), *a, out[i].ctypes.data_as(ctypes.c_void_p))
+        if rc:
+            raise ValueError("%s: %d (arguments %s, query %s)" % (entry.__name__, rc, a, rec.tolist()))
+    return out

@@ -4,34 +4,15 @@
 // HOST compiler and walks the kernels' task/lane decomposition sequentially, so that the lane code can be
 // checked against the oracle and the golden fixtures in a container that has no GPU.  It is not a CPU
 // backend: libmcq_hip.so contains none of this and fails loudly without a GPU.
-#include <stdint.h>
-#include <string.h>
-
 #include <atomic>
 #include <thread>
-#include <vector>
 
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "hs_walk.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_layout.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_mt.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_mt_ext.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_mt_blocks.hpp"
-#include "../../neuron_poker_amd/csrc/mcq_replay.hpp"
-#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
-
-namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
-// the iteration takes the base-deck pointer biased by -128 entries: keep 128 unused entries in front
-void make_base(const McqQueryCtx &qc, const McqTables &t, McqCard *store) {
-    for (uint32_t l = 0; l < 64; l++) store[128 + l] = mcq_base_entry(qc, l, t.sel8);
-}
-}  // namespace
 
 extern "C" {
 
@@ -39,7 +20,7 @@ int hs_query_valid(const mcq_query *q) { return mcq_query_valid(mcq_query_words(
 
 // keys of 7-card hands: cards 0,1 = hole, 2..6 = table (the split does not matter for the key)
 void hs_eval7(const uint8_t *cards, size_t n, uint32_t *keys) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     for (size_t i = 0; i < n; i++) {
         McqBoard b;
         b.clear();
@@ -57,7 +38,7 @@ uint32_t hs_key_type(uint32_t key) { return mcq_key_type(key); }
 // hs_eval7 takes (hole = cards 0 and 1).  Returns the index of the first hand one of whose other twenty splits gives
 // a different key, n when there is none.  `threads` host threads (1..16) over contiguous shares.
 size_t hs_eval7_splits(const uint8_t *cards, size_t n, uint32_t *keys, int threads) {
-    const McqTables &t = luts(); /* filled before the threads start */
+    const McqTables &t = hs::luts(); /* filled before the threads start */
     if (threads < 1) threads = 1;
     if (threads > 16) threads = 16;
     std::atomic<size_t> bad(n);
@@ -95,7 +76,7 @@ size_t hs_eval7_splits(const uint8_t *cards, size_t n, uint32_t *keys, int threa
     return bad.load();
 }
 
-uint32_t hs_select_pop(uint32_t *dlo, uint32_t *dhi, uint32_t k) { return mcq_select_pop(*dlo, *dhi, k, luts().sel8); }
+uint32_t hs_select_pop(uint32_t *dlo, uint32_t *dhi, uint32_t k) { return mcq_select_pop(*dlo, *dhi, k, hs::luts().sel8); }
 
 void hs_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out) {
     mcq_philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], out);
@@ -107,25 +88,12 @@ void hs_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out) {
 template <class Draws, bool STRAIGHT = true>
 static int run_ctr_t(const mcq_query *q, uint64_t seed, uint64_t qid, mcq_result *out) {
     if (!mcq_query_valid(mcq_query_words(*q))) return MCQ_EINVAL;
-    const McqTables &t = luts();
-    McqQueryCtx qc;
-    mcq_query_ctx(mcq_query_words(*q), qc);
-    static thread_local McqCard base[192];
-    make_base(qc, t, base);
-    memset(out, 0, sizeof(*out));
-    out->runs = q->runs;
-    uint32_t n_streams = (q->runs + MCQ_STREAM_ITERS - 1) / MCQ_STREAM_ITERS;
-    for (uint32_t s = 0; s < n_streams; s++) {
-        Draws dr;
-        dr.start(seed, qid, s);
-        McqLaneAcc acc = {0, 0, 0};
-        const uint64_t left = (uint64_t)q->runs - (uint64_t)s * MCQ_STREAM_ITERS;
-        const uint32_t cnt = left < MCQ_STREAM_ITERS ? (uint32_t)left : MCQ_STREAM_ITERS;
-        if (STRAIGHT) mcq_iterations<true>(qc, dr, base, t.tf, t.tops, t.sd, acc, cnt); /* as the bulk kernel runs them */
-        else for (uint32_t j = 0; j < cnt; j++) mcq_iteration(qc, dr, base, t.tf, t.tops, t.sd, acc);
-        acc.passes += cnt * qc.n_opp; /* MCQ-CTR v5: one attempt per opponent, never re-drawn */
-        mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
-    }
+    const McqTables &t = hs::luts();
+    const hs::BaseDeck bd(*q);
+    hs::walk_streams<Draws, McqLaneAcc>(bd.qc, q->runs, seed, qid, reinterpret_cast<uint64_t *>(out), [&](Draws &dr, McqLaneAcc &acc, uint32_t cnt) {
+        if (STRAIGHT) mcq_iterations<true>(bd.qc, dr, bd.card, t.tf, t.tops, t.sd, acc, cnt); /* as the bulk kernel runs them */
+        else for (uint32_t j = 0; j < cnt; j++) mcq_iteration(bd.qc, dr, bd.card, t.tf, t.tops, t.sd, acc);
+    });
     return MCQ_OK;
 }
 
@@ -143,42 +111,16 @@ int hs_run_ctr_general(const mcq_query *q, uint64_t seed, uint64_t qid, mcq_resu
 
 // parity mode: host parse of the MT19937 stream + the same lane arithmetic
 int hs_run_replay(const mcq_query *q, uint32_t seed32, mcq_result *out) {
-    if (!mcq_query_valid(mcq_query_words(*q))) return MCQ_EINVAL;
-    const McqTables &t = luts();
-    McqQueryCtx qc;
-    mcq_query_ctx(mcq_query_words(*q), qc);
-    static thread_local McqCard base[192];
-    make_base(qc, t, base);
-    memset(out, 0, sizeof(*out));
-    out->runs = q->runs;
-    size_t stride = q->runs ? q->runs : 1;
-    std::vector<uint8_t> draws((size_t)mcq_draws_per_iteration(*q) * stride + 4);
-    out->passes = mcq_replay_parse(*q, seed32, draws.data(), stride);
-    /* as the kernel reads them: four iterations per 32-bit load of every draw row (McqReplayDraws4) */
-    for (uint32_t it4 = 0; it4 < q->runs; it4 += 4) {
-        McqReplayDraws4 dr;
-        dr.load(draws.data() + it4, stride, qc.n_opp, qc.n_deal);
-        for (uint32_t k = 0; k < 4 && it4 + k < q->runs; k++) {
-            dr.sh = 8u * k;
-            McqLaneAcc acc = {0, 0, 0};
-            mcq_iteration(qc, dr, base, t.tf, t.tops, t.sd, acc);
-            acc.passes = 0;
-            mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
-        }
-    }
-    return MCQ_OK;
+    return hs::replay_row<McqLaneAcc, true>(q, seed32, reinterpret_cast<uint64_t *>(out));
 }
 
-// parity mode continuing an MT19937 stream given as numpy state (key[624], pos); state updated in place
+// parity mode continuing an MT19937 stream given as numpy state (key[624], pos); state updated in place, the draws read
+// one iteration at a time (McqReplayDraws)
 int hs_run_replay_stream(const mcq_query *q, uint32_t *key, uint32_t *pos, mcq_result *out) {
     if (!mcq_query_valid(mcq_query_words(*q))) return MCQ_EINVAL;
-    const McqTables &t = luts();
-    McqQueryCtx qc;
-    mcq_query_ctx(mcq_query_words(*q), qc);
-    static thread_local McqCard base[192];
-    make_base(qc, t, base);
-    memset(out, 0, sizeof(*out));
-    out->runs = q->runs;
+    const McqTables &t = hs::luts();
+    const hs::BaseDeck bd(*q);
+    hs::start_row<McqLaneAcc>(reinterpret_cast<uint64_t *>(out), q->runs);
     size_t stride = q->runs ? q->runs : 1;
     std::vector<uint8_t> draws((size_t)mcq_draws_per_iteration(*q) * stride + 1);
     McqMt19937 g;
@@ -190,7 +132,7 @@ int hs_run_replay_stream(const mcq_query *q, uint32_t *key, uint32_t *pos, mcq_r
     for (uint32_t it = 0; it < q->runs; it++) {
         McqReplayDraws dr = {draws.data() + it, stride};
         McqLaneAcc acc = {0, 0, 0};
-        mcq_iteration(qc, dr, base, t.tf, t.tops, t.sd, acc);
+        mcq_iteration(bd.qc, dr, bd.card, t.tf, t.tops, t.sd, acc);
         acc.passes = 0;
         mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
     }
@@ -208,72 +150,25 @@ void hs_mt_words(uint32_t seed, uint32_t n, uint32_t *out) {
 
 extern "C" int hs_run_ext(int replay, const mcq_query *q, const mcq_query_ext *e, uint64_t seed, uint64_t qid,
                           mcq_result *out) {
-    const McqExtRec er = {reinterpret_cast<const uint32_t *>(e)};
-    const McqQueryWords qw = mcq_query_words(*q);
-    if (!mcq_query_ext_valid(qw, er)) return MCQ_EINVAL;
-    const McqTables &t = luts();
-    McqExtCtx qc;
-    mcq_ext_ctx(qw, er, qc);
-    McqExtWaveCtx wc;
-    memset(&wc, 0, sizeof wc);
-    for (uint32_t h = 0; h < qc.n_hands; h++) wc.hand[h] = mcq_ext_hand(qw, er, h);
-    /* the candidate lists, as mcq_ext_lists_kernel lays them out */
-    const uint32_t n_lists = mcq_ext_n_lists(qw, er);
-    std::vector<uint16_t> lists((size_t)(n_lists ? n_lists : 1) * MCQ_EXT_LIST_STRIDE);
-    for (uint32_t li = 0; li < n_lists; li++) {
-        uint64_t U;
-        uint32_t set_off, cnt = 0;
-        mcq_ext_list_plan(qw, er, li, U, set_off);
-        for (uint32_t c = 0; c < 2704u; c++)
-            if (mcq_ext_candidate(U, er.w + set_off, c)) lists[(size_t)li * MCQ_EXT_LIST_STRIDE + cnt++] = (uint16_t)((c / 52u) | ((c % 52u) << 8));
-        wc.cnt[li] = cnt;
-        wc.list[li] = lists.data() + (size_t)li * MCQ_EXT_LIST_STRIDE;
-        if (cnt == 0 && !replay) return MCQ_EINVAL;
-    }
-    McqCard cards[64];
-    for (uint32_t c = 0; c < 64; c++) cards[c] = mcq_card(c < 52 ? c : 0);
-    memset(out, 0, sizeof(*out));
-    out->runs = q->runs;
-    uint16_t ids[MCQ_MAX_OPP + 1];
-    if (replay) {
-        size_t stride = q->runs ? q->runs : 1;
-        std::vector<uint8_t> draws((size_t)mcq_ext_draws_per_iteration(*q, *e) * stride + 1);
-        McqMt19937 g;
-        g.seed((uint32_t)seed);
-        uint64_t passes = mcq_replay_parse_ext(*q, *e, g, draws.data(), stride, 1000000u);
-        if (passes == ~0ull) return MCQ_EINVAL;
-        out->passes = passes;
-        for (uint32_t it = 0; it < q->runs; it++) {
-            McqExtReplayDraws dr = {draws.data() + it, stride};
-            McqLaneAcc acc = {0, 0, 0};
-            mcq_iteration_ext(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc);
-            acc.passes = 0;
-            mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
-        }
-        return MCQ_OK;
-    }
-    const uint32_t s_iters = mcq_ext_stream_iters(qw, er);
-    uint32_t n_streams = (q->runs + s_iters - 1) / s_iters;
-    for (uint32_t s = 0; s < n_streams; s++) {
-        McqExtCtrDraws dr;
-        dr.start(seed, qid, s);
-        McqLaneAcc acc = {0, 0, 0};
-        for (uint32_t j = 0; j < s_iters; j++) {
-            if ((uint64_t)s * s_iters + j >= q->runs) break;
-            if (!(qc.fast ? mcq_iteration_ext_fast(qc, wc, dr, cards, t.sel8, t.tf, t.tops, t.sd, acc)   /* as the kernel picks */
-                          : mcq_iteration_ext(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc)))
-                return MCQ_EINVAL;
-        }
-        mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
-    }
-    return MCQ_OK;
+    hs::ExtQuery x(q, e);
+    if (!x.valid || (x.empty_list && !replay)) return MCQ_EINVAL;
+    const McqTables &t = hs::luts();
+    uint64_t *row = reinterpret_cast<uint64_t *>(out);
+    if (replay)
+        return x.replay<McqLaneAcc>((uint32_t)seed, row, [&](McqExtReplayDraws &dr, McqLaneAcc &acc, uint64_t) {
+            mcq_iteration_ext(x.qc, x.wc, dr, x.cards, t.sel8, x.ids, 1, t.tf, t.tops, t.sd, acc);
+        });
+    return x.walk<McqLaneAcc>(seed, qid, row, [&](McqExtCtrDraws &dr, McqLaneAcc &acc, uint64_t) {
+        return x.qc.fast ? mcq_iteration_ext_fast(x.qc, x.wc, dr, x.cards, t.sel8, t.tf, t.tops, t.sd, acc)   /* as the kernel picks */
+                         : mcq_iteration_ext(x.qc, x.wc, dr, x.cards, t.sel8, x.ids, 1, t.tf, t.tops, t.sd, acc);
+    });
 }
 
 
 // exact enumeration (mcq_exact.hpp) walked like mcq_exact_kernel: completion by completion, pass A then pass B,
 // the 64 lanes one after the other
 extern "C" int hs_exact(const mcq_query *q, int law, uint64_t *out13) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     McqExactQuery e;
     if (!mcq_exact_query(mcq_query_words(*q), law, e)) return -1;
     std::vector<uint16_t> pair_xy(MCQ_EXACT_PAIRS), rec(MCQ_EXACT_PAIRS);

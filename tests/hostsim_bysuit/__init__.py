@@ -52,13 +52,5 @@ def entries(query):
 
 def rows(queries, seed, first_qid, nopp, ndeal, accessor, uniform=False, ways=False):
     """Query i (16-byte records) with id first_qid + i through mcq_iteration_sum<.., nopp, ndeal, ..> -> uint64 [n, 13 or 22]."""
-    L = lib()
-    q = np.ascontiguousarray(queries).view(np.uint8).reshape(-1, 16)
-    out = np.zeros((len(q), 22 if ways else 13), np.uint64)
-    for i in range(len(q)):
-        rec = q[i].copy()
-        rc = L.hs_bysuit_run(rec.ctypes.data_as(C.c_void_p), seed, first_qid + i, nopp, ndeal, int(uniform), int(ways),
-                             accessor, out[i].ctypes.data_as(C.c_void_p))
-        if rc:
-            raise ValueError("hs_bysuit_run: %d (nopp %d, ndeal %d, accessor %d, query %s)" % (rc, nopp, ndeal, accessor, rec.tolist()))
-    return out
+    return hostbuild.rows(lib().hs_bysuit_run, queries, 22 if ways else 13, seed, first_qid, nopp, ndeal, int(uniform), int(ways),
+                          accessor, qid_at=1)

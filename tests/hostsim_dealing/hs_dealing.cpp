@@ -4,19 +4,9 @@
 // scan and inserts it stands for (mcq_hole_put, mcq_hole_reg), and of the plain path's iteration walked lane by lane as
 // the bulk kernel walks it, with a draw policy that hands McqCtrDraws' draws through and counts the cases the single-hole
 // step can get wrong.
-#include <stdint.h>
-#include <string.h>
-
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
-#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
+#include "../hostsim/hs_walk.hpp"
 
 namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
 
 // the register's second draw by the generic path: insert of the first at slot J - 1, scan, insert at slot J
 template <int J>
@@ -65,26 +55,14 @@ struct CountingDraws {
 template <bool STRAIGHT, bool UNIFORM>
 int run(const mcq_query *q, uint64_t seed, uint64_t qid, uint64_t *row, uint64_t *hits) {
     if (!mcq_query_valid(mcq_query_words(*q))) return MCQ_EINVAL;
-    const McqTables &t = luts();
-    McqQueryCtx qc;
-    mcq_query_ctx(mcq_query_words(*q), qc);
-    McqCard base[192]; /* the iteration's deck pointer is biased by -128 entries */
-    for (uint32_t l = 0; l < 64; l++) base[128 + l] = mcq_base_entry(qc, l, t.sel8);
-    memset(row, 0, 13 * sizeof(uint64_t));
-    row[0] = q->runs;
-    const uint32_t n_streams = (q->runs + MCQ_STREAM_ITERS - 1) / MCQ_STREAM_ITERS;
-    for (uint32_t s = 0; s < n_streams; s++) {
-        CountingDraws<UNIFORM> dr;
-        dr.hits = hits;
-        dr.t0 = 0;
-        dr.start(seed, qid, s);
-        McqLaneAcc acc = {0, 0, 0};
-        const uint64_t left = (uint64_t)q->runs - (uint64_t)s * MCQ_STREAM_ITERS;
-        const uint32_t cnt = left < MCQ_STREAM_ITERS ? (uint32_t)left : MCQ_STREAM_ITERS;
-        mcq_iterations<STRAIGHT>(qc, dr, base, t.tf, t.tops, t.sd, acc, cnt);
-        acc.passes = cnt * qc.n_opp; /* one attempt per opponent, never re-drawn */
-        mcq_tally_fold(acc, row);
-    }
+    typedef CountingDraws<UNIFORM> Draws;
+    const McqTables &t = hs::luts();
+    const hs::BaseDeck bd(*q);
+    Draws proto = {};
+    proto.hits = hits;
+    hs::walk_streams<Draws, McqLaneAcc>(bd.qc, q->runs, seed, qid, row, [&](Draws &dr, McqLaneAcc &acc, uint32_t cnt) {
+        mcq_iterations<STRAIGHT>(bd.qc, dr, bd.card, t.tf, t.tops, t.sd, acc, cnt);
+    }, proto);
     return MCQ_OK;
 }
 }  // namespace

@@ -3,20 +3,9 @@
 // Host build of two pieces of the plain path's lane code (neuron_poker_amd/csrc/mcq_device.hpp): the position arithmetic
 // of the dealing (mcq_draw_opp, mcq_draw_table) and the two deck accessors of the
 // iteration (McqDeckAoS, McqDeckSplit), run side by side on the same streams.
-#include <stdint.h>
-#include <string.h>
-
-#include <vector>
-
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../hostsim/hs_walk.hpp"
 
 namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
 constexpr uint32_t kY = 1024u + 1u; /* as the kernels lay it out: no multiple of 64, beyond 255 entries */
 typedef McqDeckSplit<kY> Split;
 
@@ -26,30 +15,21 @@ uint32_t draw(uint32_t r, const uint32_t (&H)[5], uint32_t &hb) { return mcq_dra
 template <class Draws, class Acc, bool STRAIGHT, class Deck>
 void run(const McqQueryCtx &qc, const McqTables &t, const Deck &deck, uint64_t seed, uint64_t qid, uint32_t runs, std::vector<Acc> &out) {
     const McqSumTabs tabs = mcq_sum_tabs_of(t.tf);
-    const uint32_t n_streams = (runs + MCQ_STREAM_ITERS - 1) / MCQ_STREAM_ITERS;
-    for (uint32_t s = 0; s < n_streams; s++) {
-        Draws dr;
-        dr.start(seed, qid, s);
-        Acc acc = {};
-        const uint32_t left = runs - s * MCQ_STREAM_ITERS, cnt = left < MCQ_STREAM_ITERS ? left : MCQ_STREAM_ITERS;
+    hs::each_stream<Draws, Acc>(runs, seed, qid, [&](Draws &dr, Acc &acc, uint32_t cnt) { /* the lanes' own sums, not a row */
         if (STRAIGHT) mcq_iterations_sum<true>(qc, dr, deck, tabs, acc, cnt);
         else for (uint32_t j = 0; j < cnt; j++) mcq_iteration_sum<Draws, -1, -1, Acc>(qc, dr, deck, tabs, acc);
         out.push_back(acc);
-    }
+    });
 }
 template <class Draws, class Acc, bool STRAIGHT>
 int64_t both(const mcq_query *q, uint64_t seed, uint64_t qid) {
     if (!mcq_query_valid(mcq_query_words(*q))) return -1;
-    const McqTables &t = luts();
-    McqQueryCtx qc;
-    mcq_query_ctx(mcq_query_words(*q), qc);
-    std::vector<McqCard> aos(192);
+    const McqTables &t = hs::luts();
+    const hs::BaseDeck bd(*q);
+    const McqQueryCtx &qc = bd.qc;
     std::vector<McqPair> split(128 + 64 + kY + 64);
-    for (uint32_t l = 0; l < 64; l++) {
-        aos[128 + l] = mcq_base_entry(qc, l, t.sel8);
-        Split::put(split.data() + 128, l, aos[128 + l]);
-    }
-    const McqDeckAoS da = {aos.data()};
+    for (uint32_t l = 0; l < 64; l++) Split::put(split.data() + 128, l, bd.card[128 + l]);
+    const McqDeckAoS da = bd.aos();
     const Split ds = {split.data()};
     std::vector<Acc> a, b;
     run<Draws, Acc, STRAIGHT>(qc, t, da, seed, qid, q->runs, a);

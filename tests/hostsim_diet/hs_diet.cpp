@@ -3,40 +3,17 @@
 // Host build of the plain path's iteration (neuron_poker_amd/csrc/mcq_device.hpp: mcq_iterations) walked lane by lane as
 // the bulk kernel walks it -- one stream of MCQ_STREAM_ITERS iterations per lane -- and folded into the thirteen words of
 // an mcq_result row, so that the lane code can be compared with the oracle's CTR mode where no GPU exists.
-#include <stdint.h>
-#include <string.h>
-
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
-#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
+#include "../hostsim/hs_walk.hpp"
 
 namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
 template <bool STRAIGHT>
 int run(const mcq_query *q, uint64_t seed, uint64_t qid, uint64_t *row) {
     if (!mcq_query_valid(mcq_query_words(*q))) return MCQ_EINVAL;
-    const McqTables &t = luts();
-    McqQueryCtx qc;
-    mcq_query_ctx(mcq_query_words(*q), qc);
-    McqCard base[192]; /* the iteration's deck pointer is biased by -128 entries */
-    for (uint32_t l = 0; l < 64; l++) base[128 + l] = mcq_base_entry(qc, l, t.sel8);
-    memset(row, 0, 13 * sizeof(uint64_t));
-    row[0] = q->runs;
-    const uint32_t n_streams = (q->runs + MCQ_STREAM_ITERS - 1) / MCQ_STREAM_ITERS;
-    for (uint32_t s = 0; s < n_streams; s++) {
-        McqCtrDraws dr;
-        dr.start(seed, qid, s);
-        McqLaneAcc acc = {0, 0, 0};
-        const uint64_t left = (uint64_t)q->runs - (uint64_t)s * MCQ_STREAM_ITERS;
-        const uint32_t cnt = left < MCQ_STREAM_ITERS ? (uint32_t)left : MCQ_STREAM_ITERS;
-        mcq_iterations<STRAIGHT>(qc, dr, base, t.tf, t.tops, t.sd, acc, cnt);
-        acc.passes = cnt * qc.n_opp; /* one attempt per opponent, never re-drawn */
-        mcq_tally_fold(acc, row);
-    }
+    const McqTables &t = hs::luts();
+    const hs::BaseDeck bd(*q);
+    hs::walk_streams<McqCtrDraws, McqLaneAcc>(bd.qc, q->runs, seed, qid, row, [&](McqCtrDraws &dr, McqLaneAcc &acc, uint32_t cnt) {
+        mcq_iterations<STRAIGHT>(bd.qc, dr, bd.card, t.tf, t.tops, t.sd, acc, cnt);
+    });
     return MCQ_OK;
 }
 }  // namespace

@@ -9,21 +9,12 @@
 
 #include <vector>
 
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../hostsim/hs_walk.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact_ext.hpp"
-
-namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
-}  // namespace
 
 // -> 0, or the refusal: MCQ_XX_* (1..4), 5 = the range cannot be dealt.  prob: 11 doubles, weights: 13 words.
 extern "C" int hs_exact_ext(const mcq_query *q, const mcq_query_ext *x, int law, double *prob, uint64_t *weights) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     McqExactExtQuery e;
     const McqExtRec er = {reinterpret_cast<const uint32_t *>(x)};
     const int why = mcq_exact_ext_query(mcq_query_words(*q), er, law, e);

@@ -22,19 +22,8 @@ inline void hs_dealt(uint32_t h, uint32_t c1, uint32_t c2) {
 }  // namespace
 #define MCQ_EXT_DEAL_HOOK(h, c1, c2) hs_dealt(h, c1, c2)
 
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
-#include "../../neuron_poker_amd/csrc/mcq_replay.hpp"
+#include "../hostsim/hs_walk.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact_ext.hpp"
-#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
-
-namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
-}  // namespace
 
 extern "C" {
 
@@ -43,32 +32,10 @@ extern "C" {
 // hands (may be null): runs x (2 n_players + 5) card ids.
 int hs_ext_ways_run(int replay, const mcq_query *q, const mcq_query_ext *e, uint64_t seed, uint64_t qid, int general,
                     mcq_result_ways *out, uint8_t *hands) {
-    const McqExtRec er = {reinterpret_cast<const uint32_t *>(e)};
-    const McqQueryWords qw = mcq_query_words(*q);
-    if (!mcq_query_ext_valid(qw, er)) return MCQ_EINVAL;
-    const McqTables &t = luts();
-    McqExtCtx qc;
-    mcq_ext_ctx(qw, er, qc);
-    McqExtWaveCtx wc;
-    memset(&wc, 0, sizeof wc);
-    for (uint32_t h = 0; h < qc.n_hands; h++) wc.hand[h] = mcq_ext_hand(qw, er, h);
-    const uint32_t n_lists = mcq_ext_n_lists(qw, er);
-    std::vector<uint16_t> lists((size_t)(n_lists ? n_lists : 1) * MCQ_EXT_LIST_STRIDE);
-    for (uint32_t li = 0; li < n_lists; li++) { /* as mcq_ext_lists_kernel lays them out */
-        uint64_t U;
-        uint32_t set_off, cnt = 0;
-        mcq_ext_list_plan(qw, er, li, U, set_off);
-        for (uint32_t c = 0; c < 2704u; c++)
-            if (mcq_ext_candidate(U, er.w + set_off, c)) lists[(size_t)li * MCQ_EXT_LIST_STRIDE + cnt++] = (uint16_t)((c / 52u) | ((c % 52u) << 8));
-        wc.cnt[li] = cnt;
-        wc.list[li] = lists.data() + (size_t)li * MCQ_EXT_LIST_STRIDE;
-        if (cnt == 0 && !replay) return MCQ_EINVAL;
-    }
-    McqCard cards[64];
-    for (uint32_t c = 0; c < 64; c++) cards[c] = mcq_card(c < 52 ? c : 0);
-    memset(out, 0, sizeof(*out));
-    out->r.runs = q->runs;
-    uint16_t ids[MCQ_MAX_OPP + 1];
+    hs::ExtQuery x(q, e);
+    if (!x.valid || (x.empty_list && !replay)) return MCQ_EINVAL;
+    const McqTables &t = hs::luts();
+    uint64_t *row = reinterpret_cast<uint64_t *>(out);
     const uint32_t rec = 2u * q->n_players + 5u;
     g_players = q->n_players;
     g_board = q->n_board;
@@ -80,42 +47,17 @@ int hs_ext_ways_run(int replay, const mcq_query *q, const mcq_query_ext *e, uint
         g_hands[1] = q->hole[1];
         for (uint32_t k = 0; k < q->n_board; k++) g_hands[2u * q->n_players + k] = q->board[k];
     };
-    if (replay) {
-        size_t stride = q->runs ? q->runs : 1;
-        std::vector<uint8_t> draws((size_t)mcq_ext_draws_per_iteration(*q, *e) * stride + 1);
-        McqMt19937 g;
-        g.seed((uint32_t)seed);
-        uint64_t passes = mcq_replay_parse_ext(*q, *e, g, draws.data(), stride, 1000000u);
-        if (passes == ~0ull) return MCQ_EINVAL;
-        out->r.passes = passes;
-        for (uint32_t it = 0; it < q->runs; it++) {
-            McqExtReplayDraws dr = {draws.data() + it, stride};
-            McqLaneAccWays acc = {};
+    if (replay)
+        return x.replay<McqLaneAccWays>((uint32_t)seed, row, [&](McqExtReplayDraws &dr, McqLaneAccWays &acc, uint64_t it) {
             begin(it);
-            mcq_iteration_ext<McqExtReplayDraws, false, McqLaneAccWays>(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc);
-            acc.passes = 0;
-            mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
-        }
-        return MCQ_OK;
-    }
-    const uint32_t s_iters = mcq_ext_stream_iters(qw, er);
-    const uint32_t n_streams = (q->runs + s_iters - 1) / s_iters;
-    for (uint32_t s = 0; s < n_streams; s++) {
-        McqExtCtrDraws dr;
-        dr.start(seed, qid, s);
-        McqLaneAccWays acc = {};
-        for (uint32_t j = 0; j < s_iters; j++) {
-            const uint64_t it = (uint64_t)s * s_iters + j;
-            if (it >= q->runs) break;
-            begin(it);
-            const bool ok = qc.fast && !general
-                ? mcq_iteration_ext_fast<McqExtCtrDraws, true, false, McqLaneAccWays>(qc, wc, dr, cards, t.sel8, t.tf, t.tops, t.sd, acc)
-                : mcq_iteration_ext<McqExtCtrDraws, false, McqLaneAccWays>(qc, wc, dr, cards, t.sel8, ids, 1, t.tf, t.tops, t.sd, acc);
-            if (!ok) return MCQ_EINVAL;
-        }
-        mcq_tally_fold(acc, reinterpret_cast<uint64_t *>(out));
-    }
-    return MCQ_OK;
+            mcq_iteration_ext<McqExtReplayDraws, false, McqLaneAccWays>(x.qc, x.wc, dr, x.cards, t.sel8, x.ids, 1, t.tf, t.tops, t.sd, acc);
+        });
+    return x.walk<McqLaneAccWays>(seed, qid, row, [&](McqExtCtrDraws &dr, McqLaneAccWays &acc, uint64_t it) {
+        begin(it);
+        return x.qc.fast && !general
+            ? mcq_iteration_ext_fast<McqExtCtrDraws, true, false, McqLaneAccWays>(x.qc, x.wc, dr, x.cards, t.sel8, t.tf, t.tops, t.sd, acc)
+            : mcq_iteration_ext<McqExtCtrDraws, false, McqLaneAccWays>(x.qc, x.wc, dr, x.cards, t.sel8, x.ids, 1, t.tf, t.tops, t.sd, acc);
+    });
 }
 
 // 1 if the kernels take the fast form for this query
@@ -161,7 +103,7 @@ uint32_t hs_ext_list_len(const mcq_query *q, const mcq_query_ext *e, uint32_t li
 // The exact enumeration's split-pot lane code, kinds 0 and 1, walked as mcq_exact_ext_kernel<KIND, true> walks it.
 // -> 0, MCQ_XX_* (1..4), 5 = cannot be dealt, 6 = two random opponents.  weights: 22 words.
 int hs_exact_ext_ways(const mcq_query *q, const mcq_query_ext *x, int law, uint64_t *weights) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     McqExactExtQuery e;
     const McqExtRec er = {reinterpret_cast<const uint32_t *>(x)};
     const int why = mcq_exact_ext_query(mcq_query_words(*q), er, law, e);

@@ -11,16 +11,10 @@
 #include <thread>
 #include <vector>
 
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../hostsim/hs_walk.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact_hero_pre.hpp"
 
 namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
 uint32_t host_threads(uint32_t most) {
     uint32_t n = std::thread::hardware_concurrency();
     n = n < 1u ? 1u : n > 8u ? 8u : n;
@@ -34,7 +28,7 @@ uint32_t host_threads(uint32_t most) {
 // allowed, live, ranked, C(|D|, k).  Everything is untouched by a refusal.
 extern "C" int hs_hero_pre(const mcq_query *q, const mcq_query_ext *x, int law, uint32_t lo, uint32_t hi, uint64_t *rows_out,
                            double *agg, uint32_t *counts) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     McqExactHeroQuery e;
     const McqExtRec er = {reinterpret_cast<const uint32_t *>(x)};
     if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return -1;
@@ -172,7 +166,7 @@ extern "C" uint32_t hs_pre_share(uint32_t n_g) { return mcq_exact_hero_pre_share
 // hands: n_hands x 2 card ids (a < b, both in D); rows_out: n_hands x 13 words (runs, 0, win, tie, by_type[9]).
 extern "C" int hs_slow_ref(const uint8_t *deck, uint32_t Ld, const uint32_t *opp_bits, int law, const uint32_t *start,
                            uint32_t count, const uint8_t *hands, uint32_t n_hands, uint64_t *rows_out) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     const bool ref = law == MCQ_LAW_REFERENCE;
     auto one = [&](uint32_t hi_) {
         const uint32_t ha = hands[2u * hi_], hb = hands[2u * hi_ + 1u];

@@ -14,16 +14,10 @@
 #include <thread>
 #include <vector>
 
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../hostsim/hs_walk.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact_hero_pre.hpp"
 
 namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
 uint32_t host_threads(uint32_t most) {
     uint32_t n = std::thread::hardware_concurrency();
     n = n < 1u ? 1u : n > 8u ? 8u : n;
@@ -42,7 +36,7 @@ extern "C" uint64_t hs_hero_pre_w_walked(void) { return g_walked.load(); }
 // Everything is untouched by a refusal; MCQ_XH_UNDEALABLE comes from mcq_exact_hero_pre_w_undealable, before any completion.
 extern "C" int hs_hero_pre_w(const mcq_query *q, const mcq_query_ext *x, const uint16_t *opp_w, const uint16_t *hero_w, uint32_t lo,
                              uint32_t hi, uint64_t *rows_out, double *agg, uint32_t *counts) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     McqExactHeroQuery e;
     const McqExtRec er = {reinterpret_cast<const uint32_t *>(x)};
     if (!opp_w) return -3;

@@ -10,21 +10,12 @@
 #include <thread>
 #include <vector>
 
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../hostsim/hs_walk.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact_hero.hpp"
-
-namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
-}  // namespace
 
 // -> 0, or the refusal MCQ_XH_* (1..7).  rows: MCQ_XH_ROWS x 13 words, agg: 11 doubles; both untouched by a refusal.
 extern "C" int hs_hero_range(const mcq_query *q, const mcq_query_ext *x, int law, uint64_t *rows_out, double *agg) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     McqExactHeroQuery e;
     const McqExtRec er = {reinterpret_cast<const uint32_t *>(x)};
     if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return -1;

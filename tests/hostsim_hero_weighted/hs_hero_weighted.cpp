@@ -11,23 +11,14 @@
 #include <thread>
 #include <vector>
 
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../hostsim/hs_walk.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact_hero.hpp"
-
-namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
-}  // namespace
 
 // -> 0, the refusal MCQ_XH_* (1..7), or -2 (no opponent table).  opp_w, hero_w: MCQ_XH_ROWS uint16 each, hero_w may be
 // null.  rows: MCQ_XH_ROWS x 13 words, agg: 11 doubles; both untouched by a refusal.
 extern "C" int hs_hero_weighted(const mcq_query *q, const mcq_query_ext *x, const uint16_t *opp_w, const uint16_t *hero_w,
                                 uint64_t *rows_out, double *agg) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     McqExactHeroQuery e;
     const McqExtRec er = {reinterpret_cast<const uint32_t *>(x)};
     if (!opp_w) return -2;

@@ -2,8 +2,6 @@
 import ctypes as C
 import functools
 
-import numpy as np
-
 from tests import hostbuild
 
 
@@ -17,13 +15,5 @@ def lib():
 
 def rows(queries, seed, first_qid, nopp, ndeal, uniform=False, ways=False):
     """Query i (16-byte records) with id first_qid + i through mcq_iteration_sum<.., nopp, ndeal, ..>: -> uint64 [n, 13 or 22]."""
-    L = lib()
-    q = np.ascontiguousarray(queries).view(np.uint8).reshape(-1, 16)
-    out = np.zeros((len(q), 22 if ways else 13), np.uint64)
-    for i in range(len(q)):
-        rec = q[i].copy()
-        rc = L.hs_join_run(rec.ctypes.data_as(C.c_void_p), seed, first_qid + i, nopp, ndeal, int(uniform), int(ways),
-                           out[i].ctypes.data_as(C.c_void_p))
-        if rc:
-            raise ValueError("hs_join_run: %d (nopp %d, ndeal %d, query %s)" % (rc, nopp, ndeal, rec.tolist()))
-    return out
+    return hostbuild.rows(lib().hs_join_run, queries, 22 if ways else 13, seed, first_qid, nopp, ndeal, int(uniform), int(ways),
+                          qid_at=1)

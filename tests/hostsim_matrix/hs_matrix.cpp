@@ -11,22 +11,13 @@
 #include <thread>
 #include <vector>
 
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../hostsim/hs_walk.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact_matrix.hpp"
-
-namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
-}  // namespace
 
 // -> 0, the refusal MCQ_XM_* (1..7), or -2 (no win matrix).  win, tie: [1326][1326] uint16 (tie may be null), total: one
 // word (may be null); all untouched by a refusal.
 extern "C" int hs_matrix(const mcq_matrix_query *q, uint16_t *win, uint16_t *tie, uint32_t *total) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     if (!win) return -2;
     McqMatrixQuery e;
     const int why = mcq_matrix_query_build(*q, e);

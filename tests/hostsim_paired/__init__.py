@@ -65,26 +65,10 @@ def positions(n_plan, rule, draws, paired=True):
 
 def rows(queries, seed, first_qid, nopp, ndeal, uniform=False, ways=False, paired=True):
     """Query i (16-byte records) with id first_qid + i through mcq_iteration_sum<.., nopp, ndeal, ..>: -> uint64 [n, 13 or 22]."""
-    L = lib()
-    q = np.ascontiguousarray(queries).view(np.uint8).reshape(-1, 16)
-    out = np.zeros((len(q), 22 if ways else 13), np.uint64)
-    for i in range(len(q)):
-        rec = q[i].copy()
-        rc = L.hs_paired_run(rec.ctypes.data_as(C.c_void_p), seed, first_qid + i, nopp, ndeal, int(uniform), int(ways),
-                             int(paired), out[i].ctypes.data_as(C.c_void_p))
-        if rc:
-            raise ValueError("hs_paired_run: %d (nopp %d, ndeal %d, query %s)" % (rc, nopp, ndeal, rec.tolist()))
-    return out
+    return hostbuild.rows(lib().hs_paired_run, queries, 22 if ways else 13, seed, first_qid, nopp, ndeal, int(uniform), int(ways),
+                          int(paired), qid_at=1)
 
 
 def replay_rows(queries, seed32):
     """Parity mode: query i from the start of the MT19937 stream of seed32 -> uint64 [n, 13]."""
-    L = lib()
-    q = np.ascontiguousarray(queries).view(np.uint8).reshape(-1, 16)
-    out = np.zeros((len(q), 13), np.uint64)
-    for i in range(len(q)):
-        rec = q[i].copy()
-        rc = L.hs_paired_replay(rec.ctypes.data_as(C.c_void_p), seed32, out[i].ctypes.data_as(C.c_void_p))
-        if rc:
-            raise ValueError("hs_paired_replay: %d (query %s)" % (rc, rec.tolist()))
-    return out
+    return hostbuild.rows(lib().hs_paired_replay, queries, 13, seed32)

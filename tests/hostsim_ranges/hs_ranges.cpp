@@ -22,16 +22,7 @@ inline void hs_dealt(uint32_t h, uint32_t c1, uint32_t c2) {
 #define MCQ_RANGES_DEAL_HOOK(h, c1, c2) hs_dealt(h, c1, c2)
 
 #include "../../neuron_poker_amd/csrc/mcq_ranges.hpp"
-#include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
-
-namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
-}  // namespace
+#include "../hostsim/hs_walk.hpp"
 
 extern "C" {
 
@@ -60,7 +51,7 @@ int hs_ranges_run(const mcq_query *q, const uint32_t *seat_table, const uint16_t
         wc.cum[s] = cum.data() + (size_t)seat_table[s] * MCQ_RG_CUM_STRIDE;
         wc.total[s] = mcq_ranges_seat_total(wc.cum[s]);
     }
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     McqCard cards[64];
     for (uint32_t c = 0; c < 64; c++) cards[c] = mcq_card(c < 52 ? c : 0);
     memset(out, 0, sizeof(*out));

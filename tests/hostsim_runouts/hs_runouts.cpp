@@ -10,22 +10,13 @@
 
 #include <vector>
 
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../hostsim/hs_walk.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_exact_runout.hpp"
-
-namespace {
-McqTables g_tab;
-bool g_init = false;
-const McqTables &luts() {
-    if (!g_init) { mcq_fill_tables(&g_tab); g_init = true; }
-    return g_tab;
-}
-}  // namespace
 
 // -> 0, -1 (bad law), the refusal MCQ_XX_* / MCQ_XR_* (1..7) or 8 = the range cannot be dealt.  cards: 52 x 22 words,
 // pairs: 1326 x 22 words; both untouched by a refusal.
 extern "C" int hs_runouts(const mcq_query *q, const mcq_query_ext *x, int law, uint64_t *cards_out, uint64_t *pairs_out) {
-    const McqTables &t = luts();
+    const McqTables &t = hs::luts();
     McqExactExtQuery e;
     const McqExtRec er = {reinterpret_cast<const uint32_t *>(x)};
     if (law != MCQ_LAW_REFERENCE && law != MCQ_LAW_UNIFORM) return -1;

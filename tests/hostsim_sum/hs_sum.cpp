@@ -2,38 +2,33 @@
 //
 // Compiles neuron_poker_amd/csrc/mcq_device.hpp for the HOST compiler and exposes the sum-form tables, the rank
 // multisets they are built from, and a sweep of the sum-form key beside mcq_eval_key over all 7-card hands.
-#include <stdint.h>
-#include <string.h>
-
 #include <thread>
-#include <vector>
 
-#include "../../neuron_poker_amd/csrc/mcq_device.hpp"
+#include "../hostsim/hs_walk.hpp"
 
 namespace {
-McqTables g_tab;
-bool g_init = false, g_ok = false;
-uint32_t g_n_ids[MCQ_N_CODES];
-const McqTables &luts() {
-    if (!g_init) {
-        mcq_fill_tables(&g_tab);
-        g_ok = mcq_fill_sum_tables_checked(&g_tab, g_n_ids); /* the same tables again, with the verdict */
-        g_init = true;
-    }
-    return g_tab;
+struct Checked { /* the filled tables with the sum form built again, for the verdict */
+    McqTables t;
+    uint32_t n_ids[MCQ_N_CODES];
+    bool ok;
+    Checked() : t(hs::luts()) { ok = mcq_fill_sum_tables_checked(&t, n_ids); }
+};
+const Checked &checked() {
+    static const Checked c;
+    return c;
 }
+const McqTables &checked_tables() { return checked().t; }
 }  // namespace
 
 extern "C" {
 // sizes: rows, slots, shift, bytes of the LDS image, 1 if the tables fit, then the ids per type code (MCQ_N_CODES)
 void hs_sum_info(uint32_t *out) {
-    luts();
     out[0] = MCQ_SUM_ROWS; out[1] = MCQ_SUM_SLOTS; out[2] = MCQ_SUM_SHIFT; out[3] = (uint32_t)sizeof(McqSumImage);
-    out[4] = g_ok ? 1u : 0u;
-    for (uint32_t c = 0; c < MCQ_N_CODES; c++) out[5 + c] = g_n_ids[c];
+    out[4] = checked().ok ? 1u : 0u;
+    for (uint32_t c = 0; c < MCQ_N_CODES; c++) out[5 + c] = checked().n_ids[c];
 }
 void hs_sum_tables(uint16_t *hoff, uint16_t *hrank, uint32_t *tfid, uint32_t *tf) {
-    const McqTables &t = luts();
+    const McqTables &t = checked_tables();
     memcpy(hoff, t.sum.hoff, sizeof(t.sum.hoff));
     memcpy(hrank, t.sum.hrank, sizeof(t.sum.hrank));
     memcpy(tfid, t.tfid, sizeof(t.tfid));
@@ -45,7 +40,7 @@ void hs_sum_weights(uint32_t *w) {
 // Every rank multiset (seven cards, at most four of a rank), enumerated here by seven nested rank choices, not by the
 // product's walk: its weight sum and its key by mcq_eval_key without a flush.  Returns their number (cap: 65536).
 uint32_t hs_sum_multisets(uint32_t *sums, uint32_t *keys) {
-    const McqTables &t = luts();
+    const McqTables &t = checked_tables();
     uint32_t n = 0, r[7];
     for (r[0] = 0; r[0] < 13; r[0]++) for (r[1] = r[0]; r[1] < 13; r[1]++) for (r[2] = r[1]; r[2] < 13; r[2]++)
     for (r[3] = r[2]; r[3] < 13; r[3]++) for (r[4] = r[3]; r[4] < 13; r[4]++) for (r[5] = r[4]; r[5] < 13; r[5]++)
@@ -78,7 +73,7 @@ uint32_t hs_sum_multisets(uint32_t *sums, uint32_t *keys) {
 // id.  Returns the number of hands seen; *bad counts hands whose id maps to two different keys or whose type
 // (mcq_id_type) differs from mcq_key_type of the key.
 uint64_t hs_sum_sweep(uint32_t threads, uint32_t stride, uint32_t phase, uint32_t *key_of_id /* 65536 */, uint64_t *bad) {
-    const McqTables &t = luts();
+    const McqTables &t = checked_tables();
     const McqSumTabs st = mcq_sum_tabs_of(t.tf);
     if (threads < 1) threads = 1;
     std::vector<std::vector<uint32_t>> maps(threads, std::vector<uint32_t>(65536, 0u));
