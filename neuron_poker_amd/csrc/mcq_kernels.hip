@@ -31,6 +31,7 @@
 #include "mcq_mt_ext.hpp"
 #include "mcq_mt_blocks.hpp"
 #include "mcq_ranges.hpp"
+#include "mcq_stage.hpp"
 #include "mcq_tally.hpp"
 
 namespace {
@@ -121,29 +122,31 @@ __device__ __forceinline__ void load_sum_tables(McqSumImage &dst, const McqTable
     __syncthreads();
 }
 
-// Exclusive prefix sum of one 64-bit value per thread over a 1024-thread block (two barriers): wave-level scan by
-// shuffles, the 16 wave totals through LDS.  Returns the sum of the values of all lower threads; *total = block sum.
-__device__ __forceinline__ uint64_t block_exclusive_scan_1024(uint64_t v, uint64_t *wave_tot /* LDS, 16 entries */,
-                                                               uint64_t *total) {
+// Exclusive prefix sum of one value per thread (T: uint32_t or uint64_t) over a block of WAVES waves (two barriers):
+// wave-level scan by shuffles, the wave totals through LDS.  Returns the sum of the values of all lower threads;
+// *total = block sum.
+template <class T, uint32_t WAVES>
+__device__ __forceinline__ T block_exclusive_scan(T v, T *wave_tot /* LDS, WAVES entries */, T *total) {
+    typedef std::conditional_t<sizeof(T) == 8, unsigned long long, unsigned int> Shfl;
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    uint64_t inc = v;
+    T inc = v;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t o = __shfl_up((unsigned long long)inc, off, 64);
+        const T o = (T)__shfl_up((Shfl)inc, off, 64);
         if (lane >= (uint32_t)off) inc += o;
     }
     __syncthreads(); /* wave_tot may still be read from the previous call */
     if (lane == 63u) wave_tot[wv] = inc;
     __syncthreads();
-    uint64_t before = 0, all = 0;
+    T at = inc - v, all = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < 16; k++) {
-        const uint64_t t = wave_tot[k];
-        before += k < wv ? t : 0ull;
+    for (uint32_t k = 0; k < WAVES; k++) {
+        const T t = wave_tot[k];
+        at += k < wv ? t : (T)0;
         all += t;
     }
     *total = all;
-    return before + inc - v;
+    return at;
 }
 
 // ---------------------------------------------------------------------------------------------- prep
@@ -173,7 +176,7 @@ __device__ __forceinline__ void mcq_prep_rows(uint32_t n, mcq_result *__restrict
             for (int k = 2; k < (int)ROW_WORDS; k++) r[k] = 0;
         }
         uint64_t chunk_total;
-        const uint64_t before = block_exclusive_scan_1024(cost, wave_tot, &chunk_total);
+        const uint64_t before = block_exclusive_scan<uint64_t, 16>(cost, wave_tot, &chunk_total);
         if (i < n) prefix[i] = carry + before;
         carry += chunk_total;
     }
@@ -234,7 +237,7 @@ __global__ __launch_bounds__(1024) void mcq_prep_kernel(const mcq_query *__restr
             }
         }
         uint64_t chunk_total;
-        const uint64_t before = block_exclusive_scan_1024(cost, wave_tot, &chunk_total);
+        const uint64_t before = block_exclusive_scan<uint64_t, 16>(cost, wave_tot, &chunk_total);
         if (i < n) prefix[i] = carry + before;
         carry += chunk_total;
     }
@@ -1339,13 +1342,15 @@ __global__ __launch_bounds__(1024) void mcq_prep_ext_kernel(const mcq_query *__r
 // The candidate lists of the production mode: one block per query; list li of the query = all ordered pairs (a, b) of
 // cards of U_li whose class its range allows, in the order of 52 * a + b (the specification's order: the oracle builds
 // the same list).  Every thread looks at eleven consecutive candidates; a block scan of the counts puts the survivors
-// in order.  cnts[query * lists_stride + li] = the list's length (0 for a query that is invalid).
+// in order (the steps: mcq_stage.hpp).  cnts[query * lists_stride + li] = the list's length (0 for a query that is
+// invalid).  The second launch bound is there to keep the occupancy at five waves per SIMD (96 VGPRs): what a thread holds
+// per candidate stays in registers across the lists, and without the bound the compiler takes 100.
 constexpr int kListBlock = 256;
-__global__ __launch_bounds__(kListBlock) void mcq_ext_lists_kernel(const mcq_query *__restrict__ q,
+__global__ __launch_bounds__(kListBlock, 5) void mcq_ext_lists_kernel(const mcq_query *__restrict__ q,
                                                                    const mcq_query_ext *__restrict__ ext, uint32_t lists_stride,
                                                                    uint16_t *__restrict__ lists, uint32_t *__restrict__ cnts) {
     __shared__ uint32_t wave_tot[kListBlock / 64];
-    const uint32_t qi = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t qi = blockIdx.x, tid = threadIdx.x;
     const uint4 raw = reinterpret_cast<const uint4 *>(q)[qi];
     const McqQueryWords qq = {raw.x, raw.y, raw.z, raw.w};
     const McqExtRec er = {reinterpret_cast<const uint32_t *>(ext + qi)};
@@ -1360,30 +1365,10 @@ __global__ __launch_bounds__(kListBlock) void mcq_ext_lists_kernel(const mcq_que
         uint32_t set_off;
         mcq_ext_list_plan(qq, er, li, U, set_off);
         constexpr uint32_t kPer = (2704u + kListBlock - 1) / kListBlock; /* 11 */
-        uint32_t mask = 0;
-        for (uint32_t k = 0; k < kPer; k++)
-            if (mcq_ext_candidate(U, er.w + set_off, tid * kPer + k)) mask |= 1u << k;
-        const uint32_t mine = (uint32_t)__popc(mask);
-        uint32_t inc = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= (uint32_t)off) inc += o;
-        }
-        __syncthreads(); /* wave_tot of the previous list has been read */
-        if (lane == 63u) wave_tot[wv] = inc;
-        __syncthreads();
-        uint32_t at = inc - mine, total = 0;
-        for (uint32_t k = 0; k < kListBlock / 64; k++) {
-            at += k < wv ? wave_tot[k] : 0u;
-            total += wave_tot[k];
-        }
-        uint16_t *dst = lists + ((size_t)qi * lists_stride + li) * MCQ_EXT_LIST_STRIDE;
-        for (uint32_t k = 0; k < kPer; k++)
-            if ((mask >> k) & 1u) {
-                const uint32_t c = tid * kPer + k, a = c / 52u;
-                dst[at++] = (uint16_t)(a | ((c - 52u * a) << 8));
-            }
+        const uint32_t mask = mcq_ext_list_mask<kPer>(U, er.w + set_off, tid);
+        uint32_t total;
+        const uint32_t at = block_exclusive_scan<uint32_t, kListBlock / 64>((uint32_t)__popc(mask), wave_tot, &total);
+        mcq_ext_list_scatter<kPer>(mask, tid, at, lists + ((size_t)qi * lists_stride + li) * MCQ_EXT_LIST_STRIDE);
         if (tid == 0) cnts[(size_t)qi * lists_stride + li] = total;
     }
 }
@@ -1412,9 +1397,8 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
      * (34 000 cycles per wave-iteration at the top quarter of the classes).  So a block first brings the lists of ITS
      * queries -- a block's waves cover a contiguous piece of the cost axis, hence consecutive queries -- into LDS when
      * they fit (36 KB beside the tables; 2 B per ordered card pair), and the trials read them there. */
-    constexpr uint32_t kStageEntries = 18u * 1024u, kStageLists = 96u;
-    __shared__ __attribute__((aligned(16))) uint16_t s_lists[kStageEntries];
-    __shared__ uint32_t s_list_off[kStageLists + 1];
+    __shared__ __attribute__((aligned(16))) uint16_t s_lists[MCQ_EXT_STAGE_ENTRIES];
+    __shared__ uint32_t s_list_off[MCQ_EXT_STAGE_LISTS + 1];
     __shared__ uint32_t s_stage[3]; /* first query, number of queries, staged? */
     if (threadIdx.x < 64) cards[threadIdx.x] = mcq_card(threadIdx.x < 52 ? threadIdx.x : 0u);
     load_tables(tab, g_tab);
@@ -1430,17 +1414,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_kernel(const mcq_query
         if (threadIdx.x == 0) { /* the block's queries: those whose cost interval meets the block's piece of the axis */
             const McqAxisRecords mine = mcq_axis_block_records(prefix, n, blockIdx.x, waves_per_block, gridDim.x);
             const uint32_t qa = mine.first, nq = mine.count;
-            uint32_t staged = 0;
-            if (nq != 0u && (uint64_t)nq * lists_stride <= kStageLists) {
-                uint32_t at = 0;
-                for (uint32_t k = 0; k < nq * lists_stride; k++) {
-                    s_list_off[k] = at;
-                    at += (cnts[(size_t)qa * lists_stride + k] + 1u) & ~1u; /* whole 32-bit words */
-                    if (at > kStageEntries) break;
-                }
-                s_list_off[nq * lists_stride] = at;
-                staged = at <= kStageEntries ? 1u : 0u;
-            }
+            const uint32_t staged = mcq_ext_stage_lists(qa, nq, lists_stride, cnts, s_list_off) ? 1u : 0u;
             s_stage[0] = qa;
             s_stage[1] = nq;
             s_stage[2] = staged;
@@ -1583,7 +1557,7 @@ __global__ __launch_bounds__(kRgTabBlock) void mcq_ranges_tables_kernel(const ui
                                                                         uint32_t *__restrict__ cum) {
     __shared__ uint32_t wave_tot[kRgTabBlock / 64];
     __shared__ uint32_t s_nnz, s_last;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     constexpr uint32_t kPer = (MCQ_HAND_ROWS + kRgTabBlock - 1) / kRgTabBlock; /* 6 */
     const uint16_t *src = tables + (size_t)blockIdx.x * MCQ_HAND_ROWS;
     uint32_t v[kPer], mine = 0, nnz = 0, last = 0;
@@ -1601,16 +1575,8 @@ __global__ __launch_bounds__(kRgTabBlock) void mcq_ranges_tables_kernel(const ui
         atomicAdd(&s_nnz, nnz);
         atomicMax(&s_last, last);
     }
-    uint32_t inc = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += o;
-    }
-    if (lane == 63u) wave_tot[wv] = inc;
-    __syncthreads();
-    uint32_t at = inc - mine;
-    for (uint32_t k = 0; k < kRgTabBlock / 64; k++) at += k < wv ? wave_tot[k] : 0u;
+    uint32_t total; /* not used: the last hand's inclusive sum, stored by the loop below, is the table's total */
+    uint32_t at = block_exclusive_scan<uint32_t, kRgTabBlock / 64>(mine, wave_tot, &total);
     uint32_t *dst = cum + (size_t)blockIdx.x * MCQ_RG_CUM_STRIDE;
 #pragma unroll
     for (uint32_t k = 0; k < kPer; k++) {
@@ -1618,7 +1584,7 @@ __global__ __launch_bounds__(kRgTabBlock) void mcq_ranges_tables_kernel(const ui
         at += v[k];
         if (i < MCQ_HAND_ROWS) dst[i] = at;
     }
-    if (tid == 0) { /* (behind the barrier above: every thread's atomics have landed) */
+    if (tid == 0) { /* (behind the scan's barriers: every thread's atomics have landed) */
         dst[MCQ_RG_NNZ_WORD] = s_nnz;
         dst[MCQ_RG_LAST_WORD] = s_last;
     }
@@ -1672,7 +1638,8 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ranges_kernel(const mcq_qu
     const uint64_t n_waves = (uint64_t)gridDim.x * waves_per_block;
     const uint64_t total = prefix[n];
     const uint64_t lo = total * wave / n_waves, hi = total * (wave + 1ull) / n_waves;
-    if (threadIdx.x == 0) { /* the block's records: those whose cost interval meets the block's piece of the axis */
+    if (threadIdx.x == 0) { /* the block's records: those whose cost interval meets the block's piece of the axis
+                             * (mcq_axis_block_records written out: profiles/block_steps_ab.txt) */
         const uint64_t blo = total * ((uint64_t)blockIdx.x * waves_per_block) / n_waves;
         const uint64_t bhi = total * ((uint64_t)(blockIdx.x + 1u) * waves_per_block) / n_waves;
         uint32_t qa = 0, nq = 0, n_tab = 0;
@@ -1689,20 +1656,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ranges_kernel(const mcq_qu
                 if (prefix[mid] < bhi) a = mid; else b = mid;
             }
             nq = a - qa + 1u;
-            bool fits = nq <= MCQ_RG_STAGE_QUERIES;
-            for (uint32_t j = 0; j < nq && fits; j++) {
-                const uint32_t p = reinterpret_cast<const uint32_t *>(queries)[(size_t)(qa + j) * 4u + 2u] & 0xFFu;
-                for (uint32_t s = 0; s < p && s < MCQ_MAX_SEATS && fits; s++) {
-                    const uint32_t t = seat_table[(size_t)(qa + j) * MCQ_MAX_SEATS + s];
-                    if (cum[(size_t)t * MCQ_RG_CUM_STRIDE + MCQ_RG_NNZ_WORD] == 1u) continue; /* a known hand reads no table */
-                    uint32_t k = 0;
-                    while (k < n_tab && s_tab_id[k] != t) k++;
-                    if (k < n_tab) continue;
-                    if (n_tab == MCQ_RG_STAGE_TABLES) fits = false;
-                    else s_tab_id[n_tab++] = t;
-                }
-            }
-            if (!fits) n_tab = 0;
+            n_tab = mcq_ranges_stage_tables(reinterpret_cast<const uint32_t *>(queries), seat_table, cum, qa, nq, s_tab_id);
         }
         s_stage[0] = qa;
         s_stage[1] = nq;
@@ -1755,9 +1709,7 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ranges_kernel(const mcq_qu
                     const uint32_t tot = mcq_ranges_seat_total(cp);
                     wc.total[lane] = tot;
                     if (tab_in_lds && !(tot & MCQ_RG_KNOWN)) { /* every table of a staged record is among the staged ones */
-                        uint32_t k = 0;
-                        while (k + 1u < n_staged && s_tab_id[k] != t) k++;
-                        cp = s_cum + k * MCQ_RG_CUM_STRIDE;
+                        cp = s_cum + mcq_ranges_stage_slot(s_tab_id, n_staged, t) * MCQ_RG_CUM_STRIDE;
                     }
                     wc.cum[lane] = cp;
                 }
@@ -1844,38 +1796,18 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ext_small_kernel(McqExtSma
     const uint32_t n_lists = __builtin_amdgcn_readfirstlane(valid ? mcq_ext_n_lists(q, er) : 0u);
     bool ok = valid && n_lists <= MCQ_EXT_SMALL_LISTS;
     /* the candidate lists, in the order of 52 * a + b: every thread looks at three consecutive candidates, a block scan
-     * of the counts puts the survivors in order */
+     * of the counts puts the survivors in order (the steps: mcq_stage.hpp) */
     uint32_t list_at = 0;
     for (uint32_t li = 0; li < n_lists && ok; li++) { /* (block-uniform) */
         uint64_t U;
         uint32_t set_off;
         mcq_ext_list_plan(q, er, li, U, set_off);
         constexpr uint32_t kPer = (2704u + kExtBlock - 1) / kExtBlock; /* 3 */
-        uint32_t mask = 0;
-        for (uint32_t k = 0; k < kPer; k++)
-            if (mcq_ext_candidate(U, er.w + set_off, tid * kPer + k)) mask |= 1u << k;
-        const uint32_t mine = (uint32_t)__popc(mask);
-        uint32_t inc = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= (uint32_t)off) inc += o;
-        }
-        __syncthreads(); /* wave_tot of the previous list has been read */
-        if (lane == 63u) wave_tot[wv] = inc;
-        __syncthreads();
-        uint32_t at = inc - mine, total = 0;
-        for (uint32_t k = 0; k < kWaves; k++) {
-            at += k < wv ? wave_tot[k] : 0u;
-            total += wave_tot[k];
-        }
+        const uint32_t mask = mcq_ext_list_mask<kPer>(U, er.w + set_off, tid);
+        uint32_t total;
+        const uint32_t at = block_exclusive_scan<uint32_t, kWaves>((uint32_t)__popc(mask), wave_tot, &total);
         total = __builtin_amdgcn_readfirstlane(total);
-        uint16_t *dst = s_lists + list_at;
-        for (uint32_t k = 0; k < kPer; k++)
-            if ((mask >> k) & 1u) {
-                const uint32_t c = tid * kPer + k, a = c / 52u;
-                dst[at++] = (uint16_t)(a | ((c - 52u * a) << 8));
-            }
+        mcq_ext_list_scatter<kPer>(mask, tid, at, s_lists + list_at);
         if (tid == 0) {
             wave_ctx.cnt[li] = total;
             wave_ctx.list[li] = s_lists + list_at;

@@ -237,7 +237,7 @@ def expect(recs, fq, seed=SEED, seats=True):
 
 # ---- mirrors of the host layer's and the kernels' choices
 SMALL_Q, SMALL_LISTS, SMALL_TASKS, SMALL_BLOCKS = 8, 6, 64, 32   # MCQ_EXT_SMALL_* (csrc/mcq_plan.hpp)
-STAGE_ENTRIES, STAGE_LISTS = 18 * 1024, 96                        # kStageEntries, kStageLists of mcq_eval_ext_kernel
+STAGE_ENTRIES, STAGE_LISTS = 18 * 1024, 96                        # MCQ_EXT_STAGE_ENTRIES, _LISTS (csrc/mcq_stage.hpp)
 BLOCK_WAVES = 16                                                   # kBlock / 64
 
 
@@ -290,36 +290,52 @@ def block_records(prefix, n, blk, wpb, grid):
     return qa, a - qa + 1
 
 
-def staging(recs, n_cu, occ):
+_list_len = {}
+
+
+def list_counts(recs, stride):
+    """cnts[query * stride + li] as mcq_ext_lists_kernel leaves them: the lists' lengths, 0 behind a query's last list."""
+    out = np.zeros(len(recs) * stride, np.uint32)
+    for qi, r in enumerate(recs):
+        if r.key not in _list_len:
+            _list_len[r.key] = [H.list_len(r.q, r.ext, li) for li in range(r.lists)]
+        out[qi * stride:qi * stride + r.lists] = _list_len[r.key]
+    return out
+
+
+def stage_lists(cnts, stride, qa, nq):
+    """What a block of mcq_eval_ext_kernel decides about the candidate lists of its queries qa .. qa + nq - 1 -> ("staged"
+    | "count" | "entries", {list: the offset the block stores for it}).  "count": more than 96 lists; "entries": the lists
+    hold more than 18 432 entries.  The mirror of mcq_ext_stage_lists (csrc/mcq_stage.hpp); tests/test_stage_host.py holds
+    the two together, limits included."""
+    if nq * stride > STAGE_LISTS:
+        return "count", {}
+    at, off = 0, {}
+    for k in range(nq * stride):
+        off[k] = at
+        at += (int(cnts[qa * stride + k]) + 1) & ~1     # whole 32-bit words
+        if at > STAGE_ENTRIES:
+            break
+    off[nq * stride] = at
+    return "staged" if at <= STAGE_ENTRIES else "entries", off
+
+
+def staging(recs, n_cu, occ, offsets=False):
     """What every block of mcq_eval_ext_kernel decides about its queries' candidate lists, for a batch on the general
-    path: a list, one entry per block with work, of ("staged" | "count" | "entries", first query, queries).  "count": more
-    than 96 lists; "entries": the lists hold more than 18 432 entries."""
+    path: a list, one entry per block with work, of (verdict of stage_lists, first query, queries), with `offsets` also
+    the offsets."""
     n = len(recs)
     stride = max(max(r.lists for r in recs), 1)
     prefix = np.concatenate([[0], np.cumsum([r.tasks * r.weight for r in recs], dtype=np.uint64)]).astype(object)
     grid, wpb = geometry(sum(r.tasks for r in recs), n_cu, occ)
-    cnts = {}
-
-    def cnt(k):   # cnts[query * stride + li]
-        if k not in cnts:
-            qi, li = divmod(k, stride)
-            cnts[k] = H.list_len(recs[qi].q, recs[qi].ext, li)
-        return cnts[k]
+    cnts = list_counts(recs, stride)
     out = []
     for blk in range(grid):
         mine = block_records(prefix, n, blk, wpb, grid)
         if mine is None:
             continue
-        qa, nq = mine
-        if nq * stride > STAGE_LISTS:
-            out.append(("count", qa, nq))
-            continue
-        at = 0
-        for k in range(nq * stride):
-            at += (cnt(qa * stride + k) + 1) & ~1
-            if at > STAGE_ENTRIES:
-                break
-        out.append(("staged" if at <= STAGE_ENTRIES else "entries", qa, nq))
+        verdict, off = stage_lists(cnts, stride, *mine)
+        out.append((verdict, *mine, off) if offsets else (verdict, *mine))
     return out
 
 

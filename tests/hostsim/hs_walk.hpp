@@ -19,6 +19,7 @@
 
 #include "../../neuron_poker_amd/csrc/mcq_device.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_replay.hpp"
+#include "../../neuron_poker_amd/csrc/mcq_stage.hpp"
 #include "../../neuron_poker_amd/csrc/mcq_tally.hpp"
 
 namespace hs {
@@ -244,8 +245,8 @@ struct ExtQuery {
             uint32_t set_off, cnt = 0;
             uint16_t *list = lists.data() + (size_t)li * MCQ_EXT_LIST_STRIDE;
             mcq_ext_list_plan(qw, er, li, U, set_off);
-            for (uint32_t c = 0; c < 2704u; c++)
-                if (mcq_ext_candidate(U, er.w + set_off, c)) list[cnt++] = (uint16_t)((c / 52u) | ((c % 52u) << 8));
+            for (uint32_t c = 0; c < 2704u; c++) /* one candidate per "thread", the offsets summed on the way */
+                cnt = mcq_ext_list_scatter<1>(mcq_ext_list_mask<1>(U, er.w + set_off, c), c, cnt, list);
             wc.cnt[li] = cnt;
             wc.list[li] = list;
             empty_list = empty_list || cnt == 0;

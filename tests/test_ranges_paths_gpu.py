@@ -1,7 +1,8 @@
 """The parts of mcq_eval_batch_ranges that exist only in mcq_kernels.hip -- the parallel table scan, the decision what a
 block stages in LDS, the chunked cost prefix -- bit for bit against the host build of the lane code (tests/hostsim_ranges,
 which prepares its tables with the serial mcq_ranges_prefix and knows neither blocks nor staging).  Which path ran cannot
-be observed from outside: every docstring states, from the kernel's rule, which path its shape takes.  A sample of every
+be observed from outside: every docstring states which path its shape takes, and tests/test_stage_host.py asks the kernel's
+own rule (csrc/mcq_stage.hpp) the same of the same constructions (tests/ranges_paths.py).  A sample of every
 batch is sent again record by record at the matching first_query_id, where a record is alone in its block."""
 from concurrent.futures import ThreadPoolExecutor
 
@@ -9,14 +10,12 @@ import numpy as np
 import pytest
 
 import neuron_poker_amd as npa
-from neuron_poker_amd import _lib
 from tests import hostsim_ranges as H
 from tests import seats_expect as SE
+from tests.ranges_paths import BOARD, STREETS, THRESHOLD_SHAPES, batch, mixed_batch, narrow_tables, threshold_shape
 
 pytestmark = pytest.mark.gpu
 SEED = 20261021
-BOARD = [10, 17, 34, 3, 21]   # 4H 6D TH 2S 7D: clear of every hand the scan tables name
-STREETS = (3, 0, 4, 5)
 FULL = 65535
 
 
@@ -44,15 +43,6 @@ def w32(rows):
     return np.ascontiguousarray(rows).view(np.uint64).reshape(-1, 32)
 
 
-def batch(recs):
-    """recs: [(table cards, seats' table numbers, runs)] -> (queries, seat_table [n, 10])"""
-    q = np.concatenate([_lib.pack_query_one([0, 0], BOARD[:nb], len(st), runs) for nb, st, runs in recs])
-    seat_table = np.full((len(recs), 10), 0xFFFFFFFF, np.uint32)   # entries at or above n_players are not read
-    for i, (_, st, _) in enumerate(recs):
-        seat_table[i, :len(st)] = st
-    return q, seat_table
-
-
 def check(e, recs, tables, qid, alone):
     """The batch equals the host build row by row; rows `alone` equal the same record sent on its own."""
     q, seat_table = batch(recs)
@@ -73,25 +63,6 @@ def check(e, recs, tables, qid, alone):
     for r, rec in zip(got, recs):
         SE.check_invariants(r, len(rec[1]))
     return got
-
-
-def narrow_tables(n, seed):
-    """n distinct tables of about 300 hands, weights 1..9."""
-    g = np.random.default_rng(seed)
-    t = np.zeros((n, 1326), np.uint16)
-    for k in range(n):
-        on = g.random(1326) < 0.23
-        t[k, on] = g.integers(1, 10, int(on.sum()))
-    assert len({x.tobytes() for x in t}) == n
-    return t
-
-
-def one_hot_tables(hands):
-    t = np.zeros((len(hands), 1326), np.uint16)
-    for k, (a, b) in enumerate(hands):
-        assert a not in BOARD and b not in BOARD
-        t[k, _lib.hand_index(a, b)] = 1 + 7 * k
-    return t
 
 
 # ------------------------------------------------------------------------------------------------------- the table scan
@@ -139,26 +110,7 @@ def test_table_scan_against_the_serial_prefix(eng):
 
 
 # ------------------------------------------------------------------------------------------- what a block stages in LDS
-ONE_HOT = [(0, 1), (4, 5), (8, 9), (12, 13), (16, 18), (20, 22), (24, 25), (28, 29), (32, 33), (36, 37)]
-
-
-def threshold_records(n, n_tables, known=False):
-    """n records of 2 to 6 seats over every street, runs 1 .. 200, seat s of record i on table (i + s) % n_tables; with
-    `known`, one seat of every record (two of every third) holds one of the four known hands behind the tables."""
-    recs = []
-    for i in range(n):
-        p = 2 + i % 5
-        st = [(i + s) % n_tables for s in range(p)]
-        if known:
-            st[i % p] = n_tables + i % 4
-            if i % 3 == 0:
-                st[(i + 1) % p] = n_tables + (i + 1) % 4
-        recs.append((STREETS[i % 4], st, (1, 17, 64, 200, 130)[i % 5]))
-    return recs
-
-
-@pytest.mark.parametrize("shape", ["32 records, 6 tables", "32 records, 7 tables", "33 records, 6 tables",
-                                   "32 records, 6 tables and 4 known hands", "known hands only"])
+@pytest.mark.parametrize("shape", THRESHOLD_SHAPES)
 def test_staging_thresholds_in_one_block(eng_one_block, shape):
     """One block sees every record of the call.  It stages when its records are at most MCQ_RG_STAGE_QUERIES = 32 and
     name at most MCQ_RG_STAGE_TABLES = 6 distinct tables, tables with one entry not counted:
@@ -167,52 +119,23 @@ def test_staging_thresholds_in_one_block(eng_one_block, shape):
       33 records, 6 tables                     -> one record too many: HBM;
       32 records, 6 tables and 4 known hands   -> ten distinct tables, four of them known hands: staged;
       known hands only                         -> no table to stage, no draw at all: passes == runs."""
-    if shape == "known hands only":
-        tables = one_hot_tables(ONE_HOT)
-        recs = [(STREETS[i % 4], [(i + 3 * s) % 10 for s in range(2 + i % 3)], (1, 17, 64, 200)[i % 4]) for i in range(32)]
-        for _, st, _ in recs:
-            assert len(set(st)) == len(st)
-    else:
-        n, nt = (33 if shape.startswith("33") else 32), (7 if "7 tables" in shape else 6)
-        known = "known" in shape
-        tables = narrow_tables(nt, 23)
-        if known:
-            tables = np.concatenate([tables, one_hot_tables(ONE_HOT[:4])])
-        recs = threshold_records(n, nt, known)
-        named = {t for _, st, _ in recs for t in st}
-        assert named == set(range(len(tables)))
+    recs, tables = threshold_shape(shape)
     got = check(eng_one_block, recs, tables, 4000, alone=[0, 5, len(recs) - 1])
     if shape == "known hands only":
         assert all(int(r[0]) == int(r[1]) for r in got)
 
 
 # ------------------------------------------------------------------------------------------------------- mixed blocks
-def full_width_tables():
-    """Ten distinct tables with all 1326 entries non-zero (weights 1..7), each with most of its weight on the six pairs of
-    one rank that is not on the flop: ten seats then collide seldom, and the host build of the reference stays cheap."""
-    g = np.random.default_rng(29)
-    t = g.integers(1, 8, (10, 1326)).astype(np.uint16)
-    ranks = [r for r in range(13) if r not in {c >> 2 for c in BOARD[:3]}]
-    for k in range(10):
-        for a in range(4):
-            for b in range(a + 1, 4):
-                t[k, _lib.hand_index(4 * ranks[k] + a, 4 * ranks[k] + b)] = 60000
-    assert (t != 0).all()
-    return t
-
-
 def test_blocks_that_stage_beside_blocks_that_do_not(eng):
     """48 flop records of 2500 runs (three wave tasks each) on the default grid: 144 tasks, one block of four waves per
     task.  Records 0..23 (2 to 6 seats) name tables 0..5 only, records 24..47 seat ten players on ten distinct full-width
     tables each.  A block whose piece of the cost axis lies inside the first 24 records finds at most six tables and
     stages them; one inside the last 24 finds ten and reads HBM; the block whose piece holds the end of record 23 and the
-    start of record 24 finds sixteen, and its waves run BOTH kinds of record from HBM.  The cost axis is cut by price
+    start of record 24 names fifteen, and its waves run BOTH kinds of record from HBM.  The cost axis is cut by price
     (seats, street, estimated trials), not by record: with the host's prices for these tables blocks 0..67 lie among the
     first 24 records (one to three records each, so fewer than six tables are staged in most), block 68 holds the change
     and blocks 69..143 lie among the last 24."""
-    tables = np.concatenate([narrow_tables(6, 31), full_width_tables()])
-    recs = [(3, [(i + s) % 6 for s in range(2 + i % 5)], 2500) for i in range(24)]
-    recs += [(3, [6 + (i + s) % 10 for s in range(10)], 2500) for i in range(24)]
+    recs, tables = mixed_batch()
     check(eng, recs, tables, 5000, alone=[0, 23, 24, 47])
 
 
