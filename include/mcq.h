@@ -481,11 +481,44 @@ MCQ_API int mcq_exact_batch_hero_range_preflop_weighted(mcq_ctx *ctx, const mcq_
  * 1.1 at two seats, 1.3 at three, 3.6 at six and 55 at ten before the flop, and 75 at ten on a flop (a table hit is re-drawn
  * by its seat alone and abandons nothing, but three cards fewer are left to be disjoint on).  Ten wide ranges are expensive,
  * and narrow ranges crowded on the same cards can be worse (nine opponents on the top quarter of the classes: refused).  Device memory: 8 KB per distinct table.
- * Not covered: dead or ghost cards, a per-hero-hand breakdown multiway, the one-launch path for small queries, a
- * device-resident or torch entry, the parity mode (the reference has nothing to match), mcq_multi_*. */
+ * Not covered: dead or ghost cards, the one-launch path for small queries, a device-resident or torch entry, the parity
+ * mode (the reference has nothing to match), mcq_multi_*.  The breakdown by the hands of one seat:
+ * mcq_eval_batch_ranges_hands. */
 MCQ_API int mcq_eval_batch_ranges(mcq_ctx *ctx, const mcq_query *q, const uint32_t *seat_table /* [n][10] */,
                                   const uint16_t *tables /* [n_tables][MCQ_HAND_ROWS] */, size_t n_tables, size_t n,
                                   uint64_t seed, uint64_t first_query_id, mcq_result_seats *out);
+
+/* mcq_eval_batch_ranges with the BREAKDOWN BY HAND of one seat: which hands of the range carry its equity -- how often each
+ * is dealt, how often it wins or ties, what pot share it takes against these other ranges.  The records, the tables, the law
+ * (MCQ-RG v1), the streams (keyed by (seed, first_query_id + i, task * 64 + lane), sixteen iterations each) and the refusals
+ * are those of mcq_eval_batch_ranges, word for word.  `seat` is the watched seat, one value per call, 0..9.
+ *  1. out[i] is bit for bit the row mcq_eval_batch_ranges writes for the same arguments (the schedule differs, the streams
+ *     do not).
+ *  2. hands[i * MCQ_HAND_ROWS + MCQ_HAND_INDEX(a, b)] describes the iterations in which the watched seat held {a < b}: runs
+ *     counts them; win, tie and share are that seat's increments in them, exactly as mcq_seat defines them.  A hand the
+ *     seat cannot hold -- zero weight, or a table card in it -- has a zero row.
+ *  3. Summed over the MCQ_HAND_ROWS rows: runs == out[i].runs, and win, tie, share == out[i].seat[seat].win, .tie, .share,
+ *     exactly.
+ *  4. The conditional equity of a hand is (win + tie) / runs, its pot share is share / (MCQ_SHARE_UNIT * runs).
+ *  5. A row depends on (record, tables, seed, query id, seat) only -- not on the batch, the launch shape or MCQ_GRID_CAP --
+ *     and a batch split into calls with the matching first_query_id gives the same rows.
+ *  6. A watched seat whose table is one-hot (a known hand) is legal: its one row equals the seat's whole row.
+ * Refused with MCQ_EINVAL, nothing launched, out and hands untouched: whatever mcq_eval_batch_ranges refuses, hands == NULL,
+ * seat >= n_players of any record, n > MCQ_RANGES_HANDS_MAX_BATCH.  A record whose seats block each other is seen on the
+ * device, as there: MCQ_EINVAL with both outputs untouched.  MCQ_EBUSY as everywhere; n == 0 returns MCQ_OK.
+ * Device memory: 42 KB of rows per record, beside what mcq_eval_batch_ranges takes.  Runs up to 2^32 - 1 stay exact.
+ * Not covered: several watched seats in one call, and what mcq_eval_batch_ranges does not cover. */
+typedef struct mcq_hand_row {
+    uint64_t runs;  /* iterations in which the watched seat held this hand */
+    uint64_t win;   /* ... and was the only best hand */
+    uint64_t tie;   /* ... and was one of several best hands */
+    uint64_t share; /* sum of MCQ_SHARE_UNIT / k over those two */
+} mcq_hand_row;     /* 32 bytes */
+#define MCQ_RANGES_HANDS_MAX_BATCH 1024u
+MCQ_API int mcq_eval_batch_ranges_hands(mcq_ctx *ctx, const mcq_query *q, const uint32_t *seat_table /* [n][10] */,
+                                        const uint16_t *tables /* [n_tables][MCQ_HAND_ROWS] */, size_t n_tables, size_t n,
+                                        uint64_t seed, uint64_t first_query_id, uint32_t seat,
+                                        mcq_result_seats *out /* [n] */, mcq_hand_row *hands /* [n][MCQ_HAND_ROWS] */);
 
 /* Exact equity PER RUNOUT, on the flop and the turn: which cards help and how much, from ONE enumeration per record.
  * Accepted: whatever mcq_exact_batch_ext_ways accepts -- hero given as two cards, 0..9 known hands each given as two cards,

@@ -11,8 +11,8 @@ from .cards import card_id, card_str, key_type, TYPES  # noqa: F401
 from ._lib import (Engine, MODE_PHILOX, MODE_REPLAY_MT19937, QUERY_DTYPE, QUERY_EXT_DTYPE, RESULT_DTYPE, RESULT_WAYS_DTYPE, EXACT_PROB_WAYS_DTYPE, McqError,  # noqa: F401
                    RESULT_SEATS, RESULT_SEATS_DTYPE, SHARE_UNIT, seat_shares,
                    McqBusyError, pot_share, load_library, library_path, pack_queries, pack_query_ext, range_bits, class_bit, default_engine, Tables, hand_index, HAND_ROWS,
-                   MultiEngine, MATRIX_QUERY_DTYPE, pack_matrix_query)
-from .montecarlo_hip import get_seat_equities, get_seat_equities_exact, get_range_equity_exact, get_runout_equities, get_preflop_range_equity_exact, preflop_class_table, get_range_equity_exact_weighted, get_preflop_range_equity_exact_weighted, get_range_equities, get_equity_matrix, matrix_equity  # noqa: F401
+                   MultiEngine, MATRIX_QUERY_DTYPE, pack_matrix_query, HAND_ROW_DTYPE)
+from .montecarlo_hip import get_seat_equities, get_seat_equities_exact, get_range_equity_exact, get_runout_equities, get_preflop_range_equity_exact, preflop_class_table, get_range_equity_exact_weighted, get_preflop_range_equity_exact_weighted, get_range_equities, get_equity_matrix, matrix_equity, get_range_hand_equities  # noqa: F401
 
 __all__ = ["card_id", "card_str", "key_type", "TYPES", "Engine", "MODE_PHILOX", "MODE_REPLAY_MT19937", "QUERY_DTYPE",
            "QUERY_EXT_DTYPE", "RESULT_DTYPE", "RESULT_WAYS_DTYPE", "EXACT_PROB_WAYS_DTYPE", "RESULT_SEATS", "RESULT_SEATS_DTYPE", "SHARE_UNIT", "pot_share", "seat_shares", "get_seat_equities", "get_seat_equities_exact",
@@ -20,4 +20,5 @@ __all__ = ["card_id", "card_str", "key_type", "TYPES", "Engine", "MODE_PHILOX", 
            "range_bits", "class_bit", "default_engine", "Tables", "MultiEngine", "hand_index", "HAND_ROWS",
            "get_range_equity_exact", "get_runout_equities", "get_preflop_range_equity_exact", "preflop_class_table",
            "get_range_equity_exact_weighted", "get_preflop_range_equity_exact_weighted", "get_range_equities",
-           "MATRIX_QUERY_DTYPE", "pack_matrix_query", "get_equity_matrix", "matrix_equity"]
+           "MATRIX_QUERY_DTYPE", "pack_matrix_query", "get_equity_matrix", "matrix_equity", "HAND_ROW_DTYPE",
+           "get_range_hand_equities"]

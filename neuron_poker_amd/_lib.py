@@ -28,6 +28,9 @@ SHARE_UNIT = 2520
 SEAT_DTYPE = np.dtype([("win", "<u8"), ("tie", "<u8"), ("share", "<u8")])
 RESULT_SEATS_DTYPE = np.dtype([("runs", "<u8"), ("passes", "<u8"), ("seat", SEAT_DTYPE, (10,))])
 RESULT_SEATS = RESULT_SEATS_DTYPE
+# mcq_hand_row: the iterations in which the watched seat of eval_batch_ranges_hands held one hand, and its increments in them
+HAND_ROW_DTYPE = np.dtype([("runs", "<u8"), ("win", "<u8"), ("tie", "<u8"), ("share", "<u8")])
+RANGES_HANDS_MAX_BATCH = 1024
 KNOWN_HAND_DTYPE = np.dtype([("cards", "u1", (2,)), ("is_range", "u1"), ("reserved", "u1"), ("range", "<u4", (6,))])
 MAX_KNOWN = 9
 QUERY_EXT_DTYPE = np.dtype([("ghost", "u1", (2,)), ("hero_is_range", "u1"), ("n_known", "u1"), ("opp_range", "<u4", (6,)),
@@ -111,6 +114,7 @@ _PROTOTYPES = (
     ("mcq_exact_batch_hero_range_preflop", _I, _P, _P, _P, _SZ, _I, _P, _P),
     ("mcq_exact_batch_hero_range_preflop_weighted", _I, _P, _P, _P, _SZ, _P, _P, _P, _P),
     ("mcq_eval_batch_ranges", _I, _P, _P, _P, _P, _SZ, _SZ, _U64, _U64, _P),
+    ("mcq_eval_batch_ranges_hands", _I, _P, _P, _P, _P, _SZ, _SZ, _U64, _U64, _U32, _P, _P),
     ("mcq_exact_batch_ext_runouts", _I, _P, _P, _P, _SZ, _I, _P, _P),
     ("mcq_exact_matrix", _I, _P, _P, _SZ, _P, _P, _P),
     ("mcq_exact_matrix_device", _I, _P, _P, _SZ, _P, _P, _P, _P),
@@ -590,6 +594,27 @@ class Engine(_Handle):
         _call(self._lib.mcq_eval_batch_ranges, self._ctx, q.ctypes.data, st.ctypes.data, tb.ctypes.data, len(tb), len(q),
               _u64(seed), _u64(first_query_id), out.ctypes.data)
         return out
+
+    def eval_batch_ranges_hands(self, queries, seat_table, tables, seed, first_query_id=0, seat=0):
+        """eval_batch_ranges with the breakdown by hand of seat `seat` (mcq_eval_batch_ranges_hands): the same arguments,
+        streams and rows, and for every record the HAND_ROWS rows of HAND_ROW_DTYPE, indexed by hand_index(a, b): the
+        iterations in which the seat held that hand and its win, tie and share in them (zero rows for hands it cannot hold).
+        -> (rows [n], hands [n, HAND_ROWS]); at most RANGES_HANDS_MAX_BATCH records per call, seat below every record's
+        n_players."""
+        q = _queries(queries)
+        if not isinstance(tables, np.ndarray) or tables.dtype != np.uint16 or tables.ndim != 2 or tables.shape[1] != HAND_ROWS \
+                or tables.shape[0] == 0:
+            raise ValueError("tables is a uint16 array of shape [n_tables >= 1, HAND_ROWS = %d]" % HAND_ROWS)
+        if not isinstance(seat_table, np.ndarray) or seat_table.dtype != np.uint32 or seat_table.shape != (len(q), 10):
+            raise ValueError("seat_table is a uint32 array of shape [n, 10] = (%d, 10)" % len(q))
+        if not 0 <= int(seat) <= 9:
+            raise ValueError("seat is 0..9")
+        tb, st = np.ascontiguousarray(tables), np.ascontiguousarray(seat_table)
+        out = np.zeros(len(q), RESULT_SEATS_DTYPE)
+        hands = np.zeros((len(q), HAND_ROWS), HAND_ROW_DTYPE)
+        _call(self._lib.mcq_eval_batch_ranges_hands, self._ctx, q.ctypes.data, st.ctypes.data, tb.ctypes.data, len(tb), len(q),
+              _u64(seed), _u64(first_query_id), int(seat), out.ctypes.data, hands.ctypes.data)
+        return out, hands
 
     def exact_seats(self, queries, ext, law="reference"):
         """Exact per-seat enumeration of the all-in case (mcq_exact_batch_seats): every hand known, no random opponent.

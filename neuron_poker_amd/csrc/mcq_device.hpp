@@ -1067,6 +1067,9 @@ struct McqLaneAccSeats {
     static constexpr bool kWays = false, kSeats = true;
     uint32_t passes;
     uint32_t seat[MCQ_MAX_SEATS];
+    /* what mcq_iteration_ranges has at the end of an accepted iteration (the seats' hands as card ids, the seats level with
+     * the best, their increment): nothing to do here; the per-hand accumulator (mcq_hands.hpp) counts the watched seat's hand */
+    MCQ_HDM void dealt(const uint16_t *, uint32_t, uint32_t, uint32_t) {}
 };
 static_assert(MCQ_STREAM_ITERS * MCQ_SHARE_UNIT < (1u << MCQ_SEAT_WIN_SHIFT) && MCQ_STREAM_ITERS < 32u, "fields of McqLaneAccSeats");
 MCQ_HD uint32_t mcq_seat_increment(uint32_t k) { /* k = 1..10 hands share the pot */

@@ -1116,17 +1116,21 @@ int mcq_eval_batch_ext_seats(mcq_ctx *c, const mcq_query *q, const mcq_query_ext
     ABI_GUARD_END("mcq_eval_batch_ext_seats")
 }
 
-/* A weighted range per seat (mcq_ranges.hpp).  Everything that can be refused is refused here, before a launch; what is
- * left for the device is the record whose seats block each other. */
-int mcq_eval_batch_ranges(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_table, const uint16_t *tables, size_t n_tables,
-                          size_t n, uint64_t seed, uint64_t first_query_id, mcq_result_seats *out) {
-    ABI_GUARD_BEGIN
+}  // extern "C"
+
+/* A weighted range per seat (mcq_ranges.hpp): mcq_eval_batch_ranges and, per_hand, mcq_eval_batch_ranges_hands with the
+ * watched seat's tally per hand (mcq_hands.hpp).  Everything that can be refused is refused here, before a launch; what
+ * is left for the device is the record whose seats block each other. */
+static int eval_batch_ranges_impl(const char *who, mcq_ctx *c, const mcq_query *q, const uint32_t *seat_table,
+                                  const uint16_t *tables, size_t n_tables, size_t n, uint64_t seed, uint64_t first_query_id,
+                                  mcq_result_seats *out, bool per_hand, uint32_t seat, mcq_hand_row *hands) {
     if (n == 0) return MCQ_OK;
-    if (!c) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: null context");
-    if (!q || !seat_table || !tables || !out) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: null buffer");
-    if (n > 0x7fffffffu) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: n too large");
+    if (!c) return mcq_fail(MCQ_EINVAL, who, "null context");
+    if (!q || !seat_table || !tables || !out || (per_hand && !hands)) return mcq_fail(MCQ_EINVAL, who, "null buffer");
+    if (n > 0x7fffffffu) return mcq_fail(MCQ_EINVAL, who, "n too large");
+    if (per_hand && n > MCQ_RANGES_HANDS_MAX_BATCH) return mcq_fail(MCQ_EINVAL, who, "n above MCQ_RANGES_HANDS_MAX_BATCH (split the batch)");
     if (n_tables == 0 || n_tables > 0x7fffffffu / MCQ_RG_CUM_STRIDE)
-        return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: n_tables must be 1 .. 2^31 / 1328");
+        return mcq_fail(MCQ_EINVAL, who, "n_tables must be 1 .. 2^31 / 1328");
     std::vector<uint32_t> with_card(n_tables * MCQ_RG_WITH_CARD_STRIDE);
     for (size_t t = 0; t < n_tables; t++) mcq_ranges_with_card(tables + t * MCQ_HAND_ROWS, with_card.data() + t * MCQ_RG_WITH_CARD_STRIDE);
     uint64_t total_tasks = 0;
@@ -1135,28 +1139,32 @@ int mcq_eval_batch_ranges(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_t
     for (size_t i = 0; i < n; i++) {
         const McqQueryWords qw = mcq_query_words(q[i]);
         if (!mcq_ranges_query_valid(qw)) {
-            snprintf(buf, sizeof buf, "mcq_eval_batch_ranges: record %zu invalid (0, 3, 4 or 5 distinct table cards < 52, "
+            snprintf(buf, sizeof buf, "record %zu invalid (0, 3, 4 or 5 distinct table cards < 52, "
                      "n_players 2..10, reserved 0, runs >= 1)", i);
-            return mcq_fail(MCQ_EINVAL, buf);
+            return mcq_fail(MCQ_EINVAL, who, buf);
         }
         const McqRangesPrice pr = mcq_ranges_price(tables, n_tables, with_card.data(), qw, seat_table + i * 10u);
         if (pr.refused == MCQ_RG_REFUSED_TABLE) {
-            snprintf(buf, sizeof buf, "mcq_eval_batch_ranges: record %zu, seat %u names table %u of %zu", i, pr.seat, pr.table, n_tables);
-            return mcq_fail(MCQ_EINVAL, buf);
+            snprintf(buf, sizeof buf, "record %zu, seat %u names table %u of %zu", i, pr.seat, pr.table, n_tables);
+            return mcq_fail(MCQ_EINVAL, who, buf);
         }
         if (pr.refused) {
-            snprintf(buf, sizeof buf, "mcq_eval_batch_ranges: record %zu, seat %u: table %u has no hand of positive weight "
+            snprintf(buf, sizeof buf, "record %zu, seat %u: table %u has no hand of positive weight "
                      "clear of the table cards", i, pr.seat, pr.table);
-            return mcq_fail(MCQ_EINVAL, buf);
+            return mcq_fail(MCQ_EINVAL, who, buf);
+        }
+        if (per_hand && seat >= qw.n_players()) {
+            snprintf(buf, sizeof buf, "record %zu has %u seats: no seat %u to watch", i, qw.n_players(), seat);
+            return mcq_fail(MCQ_EINVAL, who, buf);
         }
         price[i] = pr.price;
         total_tasks += mcq_ranges_task_count(qw);
     }
-    if (total_tasks > 0xfffffff0ull) return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: too many iterations in one call");
-    MCQ_ENTER(c, "mcq_eval_batch_ranges");
+    if (total_tasks > 0xfffffff0ull) return mcq_fail(MCQ_EINVAL, who, "too many iterations in one call");
+    MCQ_ENTER(c, who);
     McqDeviceScope dev_(c->device);
     HIP_TRY(dev_.err);
-    const size_t row_bytes = sizeof(mcq_result_seats);
+    const size_t row_bytes = sizeof(mcq_result_seats), hand_bytes = n * MCQ_HAND_ROWS * sizeof(mcq_hand_row);
     HIP_TRY(c->h_res.reserve(n * row_bytes));
     HIP_TRY(c->d_q.reserve(n * sizeof(mcq_query)));
     HIP_TRY(c->d_res.reserve(n * row_bytes));
@@ -1166,6 +1174,7 @@ int mcq_eval_batch_ranges(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_t
     HIP_TRY(c->d_lists.reserve(n_tables * MCQ_HAND_ROWS * sizeof(uint16_t)));
     HIP_TRY(c->d_draws.reserve(n_tables * MCQ_RG_CUM_STRIDE * sizeof(uint32_t)));
     HIP_TRY(c->d_cnts.reserve(n * 11u * sizeof(uint32_t))); /* ... and behind them the records' prices */
+    if (per_hand) HIP_TRY(c->d_ext.reserve(hand_bytes)); /* ... the rows per hand: 42 KB per record */
     HIP_TRY(hipMemcpyAsync(c->d_q.p, q, n * sizeof(mcq_query), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_lists.p, tables, n_tables * MCQ_HAND_ROWS * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_cnts.p, seat_table, n * 10u * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
@@ -1173,11 +1182,19 @@ int mcq_eval_batch_ranges(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_t
     c->last_ms = 0.f;
     const McqGeometry geo = mcq_plan_geometry(c->knobs, MCQ_MODE_PHILOX, total_tasks);
     const int slot = (int)(c->n_timed % mcq_ctx::kRing);
-    HIP_TRY(mcq_launch_eval_ranges((const mcq_query *)c->d_q.p, (const uint32_t *)c->d_cnts.p,
-                                   (const uint32_t *)c->d_cnts.p + n * 10u, (const uint16_t *)c->d_lists.p,
-                                   (uint32_t)n_tables, (uint32_t *)c->d_draws.p, (uint32_t)n, (uint64_t *)c->scratch[0].prefix.p,
-                                   (mcq_result *)c->d_res.p, seed, first_query_id, c->d_luts, geo.grid, geo.block, c->stream,
-                                   c->timing ? c->ev0[slot] : nullptr, c->timing ? c->ev1[slot] : nullptr));
+    if (per_hand)
+        HIP_TRY(mcq_launch_eval_ranges_hands((const mcq_query *)c->d_q.p, (const uint32_t *)c->d_cnts.p,
+                                             (const uint32_t *)c->d_cnts.p + n * 10u, (const uint16_t *)c->d_lists.p,
+                                             (uint32_t)n_tables, (uint32_t *)c->d_draws.p, (uint32_t)n,
+                                             (uint64_t *)c->scratch[0].prefix.p, (mcq_result *)c->d_res.p, (mcq_hand_row *)c->d_ext.p,
+                                             seat, seed, first_query_id, c->d_luts, geo.grid, geo.block, c->stream,
+                                             c->timing ? c->ev0[slot] : nullptr, c->timing ? c->ev1[slot] : nullptr));
+    else
+        HIP_TRY(mcq_launch_eval_ranges((const mcq_query *)c->d_q.p, (const uint32_t *)c->d_cnts.p,
+                                       (const uint32_t *)c->d_cnts.p + n * 10u, (const uint16_t *)c->d_lists.p,
+                                       (uint32_t)n_tables, (uint32_t *)c->d_draws.p, (uint32_t)n, (uint64_t *)c->scratch[0].prefix.p,
+                                       (mcq_result *)c->d_res.p, seed, first_query_id, c->d_luts, geo.grid, geo.block, c->stream,
+                                       c->timing ? c->ev0[slot] : nullptr, c->timing ? c->ev1[slot] : nullptr));
     if (c->timing) c->n_timed++;
     HIP_TRY(hipMemcpyAsync(c->h_res.p, c->d_res.p, n * row_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1185,11 +1202,33 @@ int mcq_eval_batch_ranges(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_t
     const uint64_t *hr = (const uint64_t *)c->h_res.p;
     for (size_t i = 0; i < n; i++)
         if (hr[(size_t)kSeatsWords * i] != q[i].runs)
-            return mcq_fail(MCQ_EINVAL, "mcq_eval_batch_ranges: the seats' ranges block each other: an iteration found no "
-                                        "trial in which their hands are disjoint");
+            return mcq_fail(MCQ_EINVAL, who, "the seats' ranges block each other: an iteration found no "
+                                             "trial in which their hands are disjoint");
+    if (per_hand) { /* (behind the check: a refused call leaves both outputs untouched) */
+        HIP_TRY(hipMemcpyAsync(hands, c->d_ext.p, hand_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
     memcpy(out, hr, n * row_bytes);
     return MCQ_OK;
+}
+
+extern "C" {
+
+int mcq_eval_batch_ranges(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_table, const uint16_t *tables, size_t n_tables,
+                          size_t n, uint64_t seed, uint64_t first_query_id, mcq_result_seats *out) {
+    ABI_GUARD_BEGIN
+    return eval_batch_ranges_impl("mcq_eval_batch_ranges", c, q, seat_table, tables, n_tables, n, seed, first_query_id, out,
+                                  false, 0u, nullptr);
     ABI_GUARD_END("mcq_eval_batch_ranges")
+}
+
+int mcq_eval_batch_ranges_hands(mcq_ctx *c, const mcq_query *q, const uint32_t *seat_table, const uint16_t *tables,
+                                size_t n_tables, size_t n, uint64_t seed, uint64_t first_query_id, uint32_t seat,
+                                mcq_result_seats *out, mcq_hand_row *hands) {
+    ABI_GUARD_BEGIN
+    return eval_batch_ranges_impl("mcq_eval_batch_ranges_hands", c, q, seat_table, tables, n_tables, n, seed, first_query_id,
+                                  out, true, seat, hands);
+    ABI_GUARD_END("mcq_eval_batch_ranges_hands")
 }
 
 int mcq_eval_batch_numpy_stream(mcq_ctx *c, const mcq_query *q, size_t n, uint32_t *mt_key, uint32_t *mt_pos,

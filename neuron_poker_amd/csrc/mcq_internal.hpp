@@ -96,6 +96,13 @@ hipError_t mcq_launch_eval_ranges(const mcq_query *d_q, const uint32_t *d_seat_t
                                   const uint16_t *d_tables, uint32_t n_tables, uint32_t *d_cum, uint32_t n, uint64_t *d_prefix, mcq_result *d_res, uint64_t seed,
                                   uint64_t first_qid, const McqTables *d_luts, uint32_t grid, uint32_t block, hipStream_t s,
                                   hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+/* ... with the watched seat's tally per hand (mcq_hands.hpp; mcq_eval_ranges_hands_kernel): d_hands, n x MCQ_HAND_ROWS
+ * rows, is zeroed on the stream first; seat < n_players of every record */
+hipError_t mcq_launch_eval_ranges_hands(const mcq_query *d_q, const uint32_t *d_seat_table, const uint32_t *d_trials,
+                                        const uint16_t *d_tables, uint32_t n_tables, uint32_t *d_cum, uint32_t n, uint64_t *d_prefix,
+                                        mcq_result *d_res, mcq_hand_row *d_hands, uint32_t seat, uint64_t seed, uint64_t first_qid,
+                                        const McqTables *d_luts, uint32_t grid, uint32_t block, hipStream_t s,
+                                        hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 /* host-buffer calls with few rows: d_rows[0..n_rows) -> pinned host memory (device address h_rows_dev), d_rows zeroed,
  * then *done_flag = ticket; n_rows even (buffers hold the odd row's neighbour), d_done a zeroed device word */
 hipError_t mcq_launch_publish(mcq_result *d_rows, mcq_result *h_rows_dev, uint64_t n_rows, uint32_t *d_done,

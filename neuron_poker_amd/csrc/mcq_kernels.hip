@@ -26,6 +26,7 @@
 #include "mcq_exact_hero_pre.hpp"
 #include "mcq_exact_matrix.hpp"
 #include "mcq_exact_runout.hpp"
+#include "mcq_hands.hpp"
 #include "mcq_internal.hpp"
 #include "mcq_mt.hpp"
 #include "mcq_mt_ext.hpp"
@@ -1753,6 +1754,162 @@ __global__ __launch_bounds__(kExtBlock) void mcq_eval_ranges_kernel(const mcq_qu
     }
 }
 
+// mcq_eval_batch_ranges_hands: the same records, streams and per-seat rows, and beside them the watched seat's tally PER
+// HAND (mcq_hands.hpp).  The kernel above lets every wave walk its own piece of the cost axis, so the waves of a block may
+// be on different records at once; a table keyed by hand alone needs the whole block on ONE record.  So the axis is cut per
+// BLOCK here -- block b owns [total b / grid, total (b + 1) / grid) -- and the block walks its records one after the other,
+// the tasks of a record's piece going to the waves in rounds (task = first + round * waves + wave).  The cut only decides
+// which block runs which task: the tasks of a record are numbered as above, so the rows are those of the kernel above.
+// Every accepted iteration adds the watched seat's hand to the block's table in LDS (one LDS atomic, three when the seat is
+// level with the best); at the end of a record's piece, and every MCQ_HT_FLUSH_ROUNDS rounds within it (a uint32 word holds
+// 104 rounds of shares), the block meets, every thread adds its non-zero words to the record's rows in HBM with 64-bit
+// atomics -- other blocks hold other pieces of the record -- and clears them, and the block meets again.  No global atomic
+// per lane and iteration: a one-hot watched seat would put a thousand lanes on one address.
+// Barriers: each sits under conditions computed from blockIdx, the prefix and the round counter alone -- never under a
+// lane's or a wave's progress (`failed`, a stream's iteration count, a wave without a task in its last round).  Between two
+// flushes the waves do not meet: a wave may run ahead of the others, but by no more than the rounds between two flushes.
+// LDS: the evaluator's tables 97 KB, the hands' card ids 20 KB, the table of hands 21 KB, which leaves room for
+// MCQ_RG_HANDS_STAGE_TABLES = 3 staged tables (16 KB) instead of six: 156 KB of 160.  Records that name more read them
+// from HBM, the form the kernel above has as well.
+struct LdsHandAdd { /* table[word] += v in LDS, nothing returned */
+    __attribute__((address_space(3))) uint32_t *table;
+    __device__ __forceinline__ void operator()(uint32_t word, uint32_t v) const {
+        __hip_atomic_fetch_add(table + word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+};
+__global__ __launch_bounds__(kExtBlock) void mcq_eval_ranges_hands_kernel(const mcq_query *__restrict__ queries,
+                                                                          const uint32_t *__restrict__ seat_table,
+                                                                          const uint32_t *__restrict__ cum,
+                                                                          const uint32_t *__restrict__ trials, uint32_t n,
+                                                                          const uint64_t *__restrict__ prefix,
+                                                                          mcq_result *__restrict__ res,
+                                                                          unsigned long long *__restrict__ hand_rows,
+                                                                          uint32_t seat, uint64_t seed, uint64_t first_qid,
+                                                                          const McqTables *__restrict__ g_tab) {
+    typedef McqRowKind<MCQ_ROW_SEATS> Row;
+    typedef McqLaneAccSeatsHands<LdsHandAdd> Acc;
+    static_assert(kExtBlock / 64 == MCQ_HT_BLOCK_WAVES, "the flush bound counts a round of sixteen waves");
+    __shared__ __attribute__((aligned(16))) LdsTablesEval tab;
+    __shared__ McqCard cards[64];
+    __shared__ McqRangesWaveCtx wave_ctx[kExtBlock / 64];
+    __shared__ uint16_t ids[MCQ_MAX_SEATS * kExtBlock];
+    __shared__ __attribute__((aligned(16))) uint32_t s_cum[MCQ_RG_HANDS_STAGE_TABLES * MCQ_RG_CUM_STRIDE];
+    __shared__ uint32_t s_tab_id[MCQ_RG_HANDS_STAGE_TABLES];
+    __shared__ uint32_t s_stage[3]; /* first record, number of records, staged tables (0: nothing staged) */
+    __shared__ uint32_t s_hands[MCQ_HT_TABLE_WORDS];
+    if (threadIdx.x < 64) cards[threadIdx.x] = mcq_card(threadIdx.x < 52 ? threadIdx.x : 0u);
+    for (uint32_t w = threadIdx.x; w < MCQ_HT_TABLE_WORDS; w += blockDim.x) s_hands[w] = 0u;
+    load_tables(tab, g_tab);
+
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t waves = blockDim.x >> 6;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t total = prefix[n];
+    const uint64_t blo = total * blockIdx.x / gridDim.x, bhi = total * (blockIdx.x + 1ull) / gridDim.x; /* the BLOCK's piece */
+    if (threadIdx.x == 0) { /* the block's records, as above, and which of their tables it stages */
+        uint32_t qa = 0, nq = 0, n_tab = 0;
+        if (blo < bhi) {
+            uint32_t a = 0, b = n;
+            while (b - a > 1) {
+                const uint32_t mid = (a + b) >> 1;
+                if (prefix[mid] <= blo) a = mid; else b = mid;
+            }
+            qa = a;
+            b = n;
+            while (b - a > 1) { /* last record that starts before the block's end */
+                const uint32_t mid = (a + b) >> 1;
+                if (prefix[mid] < bhi) a = mid; else b = mid;
+            }
+            nq = a - qa + 1u;
+            n_tab = mcq_ranges_stage_tables<MCQ_RG_HANDS_STAGE_TABLES>(reinterpret_cast<const uint32_t *>(queries), seat_table, cum,
+                                                                       qa, nq, s_tab_id);
+        }
+        s_stage[0] = qa;
+        s_stage[1] = nq;
+        s_stage[2] = n_tab;
+    }
+    __syncthreads();
+    {
+        const uint32_t words = s_stage[2] * MCQ_RG_CUM_STRIDE; /* (at most MCQ_RG_HANDS_STAGE_TABLES tables: inside s_cum) */
+        for (uint32_t w = threadIdx.x; w < words; w += blockDim.x) {
+            const uint32_t k = w / MCQ_RG_CUM_STRIDE;
+            s_cum[w] = cum[(size_t)s_tab_id[k] * MCQ_RG_CUM_STRIDE + (w - k * MCQ_RG_CUM_STRIDE)];
+        }
+    }
+    __syncthreads();
+    McqRangesWaveCtx &wc = wave_ctx[threadIdx.x >> 6];
+    uint16_t *my_ids = ids + threadIdx.x;
+    const uint32_t q_first = __builtin_amdgcn_readfirstlane(s_stage[0]);
+    const uint32_t q_end = q_first + __builtin_amdgcn_readfirstlane(s_stage[1]); /* (no record: the loop does not run) */
+    const uint32_t n_staged = __builtin_amdgcn_readfirstlane(s_stage[2]);
+    const bool tab_in_lds = n_staged != 0u; /* every table of the block's records is staged, or none */
+    typename Row::Tally tally;
+    tally.clear();
+    /* block-uniform from here to the end: qi, the piece, the rounds and `since` come from the prefix and blockIdx alone */
+    for (uint32_t qi = q_first; qi < q_end; qi++) {
+        const uint4 raw = reinterpret_cast<const uint4 *>(queries)[qi];
+        const McqQueryWords q = {raw.x, raw.y, raw.z, raw.w};
+        const uint64_t pfx = prefix[qi];
+        const bool ok = prefix[qi + 1] > pfx;
+        const uint32_t weight = mcq_ranges_task_weight(q) * trials[qi]; /* (as mcq_prep_ranges_kernel priced it) */
+        McqHandsPiece piece = mcq_hands_piece(pfx, weight, ok ? mcq_ranges_task_count(q) : 0u, blo, bhi);
+        piece.first = __builtin_amdgcn_readfirstlane(piece.first);
+        piece.end = __builtin_amdgcn_readfirstlane(piece.end);
+        const uint32_t rounds = __builtin_amdgcn_readfirstlane(mcq_hands_rounds(piece, waves));
+        if (rounds == 0u) continue; /* (nothing added: the table is clear, no barrier is owed) */
+        McqRangesCtx qc;
+        mcq_ranges_ctx(q, qc);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        if (lane < MCQ_MAX_SEATS) { /* (entries at or above n_players are not read: they may name anything) */
+            const uint32_t t = seat_table[(size_t)qi * MCQ_MAX_SEATS + (lane < qc.n_players ? lane : 0u)];
+            const uint32_t *cp = cum + (size_t)t * MCQ_RG_CUM_STRIDE;
+            const uint32_t tot = mcq_ranges_seat_total(cp);
+            wc.total[lane] = tot;
+            if (tab_in_lds && !(tot & MCQ_RG_KNOWN)) cp = s_cum + mcq_ranges_stage_slot(s_tab_id, n_staged, t) * MCQ_RG_CUM_STRIDE;
+            wc.cum[lane] = cp;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        unsigned long long *rows = hand_rows + (size_t)qi * MCQ_HT_TABLE_WORDS;
+        bool failed = false;
+        uint32_t since = 0;
+        for (uint32_t round = 0; round < rounds; round++) {
+            const uint32_t task = piece.first + round * waves + wv;
+            if (task < piece.end) { /* (wave-uniform; a wave without a task goes on to the round's end) */
+                Acc acc = {};
+                acc.add.table = (__attribute__((address_space(3))) uint32_t *)s_hands;
+                acc.watched = seat;
+                const uint32_t stream = task * MCQ_WAVE + lane;
+                const uint64_t it0 = (uint64_t)stream * MCQ_STREAM_ITERS;
+                if (it0 < qc.runs) {
+                    McqExtCtrDraws dr;
+                    dr.start(seed, first_qid + qi, stream);
+                    const uint32_t cnt = (uint32_t)min((uint64_t)MCQ_STREAM_ITERS, (uint64_t)qc.runs - it0);
+                    if (tab_in_lds) /* (block-uniform) */
+                        for (uint32_t j = 0; j < cnt && !failed; j++)
+                            failed = !mcq_iteration_ranges<McqExtCtrDraws, true, Acc>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
+                    else
+                        for (uint32_t j = 0; j < cnt && !failed; j++)
+                            failed = !mcq_iteration_ranges<McqExtCtrDraws, false, Acc>(qc, wc, dr, cards, tab.sel8, my_ids, kExtBlock, g_tab->tf, tab.tops, tab.sd, acc);
+                }
+                tally.add(acc, lane);
+            }
+            since++;
+            if (mcq_hands_flush_due(since, rounds - 1u - round)) { /* (block-uniform: the round counter and the piece) */
+                __syncthreads();
+                mcq_hands_flush(s_hands, threadIdx.x, blockDim.x, rows, RowAtomicAdd());
+                __syncthreads();
+                since = 0;
+            }
+        }
+        if (__any(failed) && lane == 0) atomicExch(reinterpret_cast<unsigned long long *>(Row::row(res, qi)), 0ull); /* runs := 0 */
+        tally.flush(Row::row(res, qi), lane);
+        __syncthreads(); /* the end of the record's piece: the table goes to its rows and is clear for the next record */
+        mcq_hands_flush(s_hands, threadIdx.x, blockDim.x, rows, RowAtomicAdd());
+        __syncthreads();
+    }
+}
+
 // A FEW extended queries in ONE launch (production mode; what a decision of the reference's agents asks for: ONE ranged
 // query of a thousand iterations, agent_*.py -> get_equity -> run_montecarlo).  The general path above is six stream
 // operations (two copies, prep, lists, evaluation, copy back: 140 us for such a query); here the queries travel in the
@@ -2864,6 +3021,22 @@ hipError_t mcq_launch_eval_ranges(const mcq_query *d_q, const uint32_t *d_seat_t
     hipLaunchKernelGGL(mcq_prep_ranges_kernel, dim3(1), dim3(1024), 0, s, d_q, d_trials, n, d_res, d_prefix);
     MCQ_LAUNCH_TIMED(mcq_eval_ranges_kernel, grid, block, d_q, d_seat_table, (const uint32_t *)d_cum, d_trials, n,
                      (const uint64_t *)d_prefix, d_res, seed, first_qid, d_luts);
+    return hipGetLastError();
+}
+
+hipError_t mcq_launch_eval_ranges_hands(const mcq_query *d_q, const uint32_t *d_seat_table, const uint32_t *d_trials,
+                                        const uint16_t *d_tables, uint32_t n_tables, uint32_t *d_cum, uint32_t n, uint64_t *d_prefix,
+                                        mcq_result *d_res, mcq_hand_row *d_hands, uint32_t seat, uint64_t seed, uint64_t first_qid,
+                                        const McqTables *d_luts, uint32_t grid, uint32_t block, hipStream_t s, hipEvent_t t0,
+                                        hipEvent_t t1) {
+    if (n == 0 || n_tables == 0 || block > (uint32_t)kExtBlock || !d_hands || seat >= MCQ_MAX_SEATS) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(d_hands, 0, (size_t)n * MCQ_HAND_ROWS * sizeof(mcq_hand_row), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(mcq_ranges_tables_kernel, dim3(n_tables), dim3(kRgTabBlock), 0, s, d_tables, d_cum);
+    hipLaunchKernelGGL(mcq_prep_ranges_kernel, dim3(1), dim3(1024), 0, s, d_q, d_trials, n, d_res, d_prefix);
+    MCQ_LAUNCH_TIMED(mcq_eval_ranges_hands_kernel, grid, block, d_q, d_seat_table, (const uint32_t *)d_cum, d_trials, n,
+                     (const uint64_t *)d_prefix, d_res, reinterpret_cast<unsigned long long *>(d_hands), seat, seed, first_qid,
+                     d_luts);
     return hipGetLastError();
 }
 

@@ -35,7 +35,8 @@
 #define MCQ_RG_LAST_WORD 1327u    /* the index of the last of them */
 #define MCQ_RG_KNOWN 0x80000000u  /* McqRangesWaveCtx::total of a known hand: this flag | a | b << 8 */
 #define MCQ_RG_STAGE_TABLES 6u    /* prepared tables a block keeps in LDS beside the evaluator's (6 x 5312 B) */
-#define MCQ_RG_STAGE_QUERIES 32u  /* a block looks at no more records than this when it decides what to stage */
+#define MCQ_RG_HANDS_STAGE_TABLES 3u /* ... the per-hand kernel: 21 KB of its LDS hold the table of hands (mcq_hands.hpp) */
+#define MCQ_RG_STAGE_QUERIES 32u /* a block looks at no more records than this when it decides what to stage */
 
 /* the record: a valid table, 0/3/4/5 of its cards, 2..10 seats, at least one iteration; hole is not read */
 MCQ_HD bool mcq_ranges_query_valid(const McqQueryWords &q) {
@@ -201,5 +202,6 @@ MCQ_HD bool mcq_iteration_ranges(const McqRangesCtx &qc, const McqRangesWaveCtx 
     const uint32_t inc = mcq_seat_increment(mcq_popc(level));
 #pragma unroll
     for (uint32_t s = 0; s < MCQ_MAX_SEATS; s++) acc.seat[s] += ((level >> s) & 1u) ? inc : 0u;
+    acc.dealt(ids, ids_stride, level, inc); /* (McqLaneAccSeats: empty; mcq_hands.hpp: the watched seat's hand) */
     return true;
 }

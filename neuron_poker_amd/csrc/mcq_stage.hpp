@@ -31,9 +31,11 @@ MCQ_HD bool mcq_ext_stage_lists(uint32_t first, uint32_t nq, uint32_t lists_stri
 /* The distinct tables that records first .. first + nq - 1 draw from -> tab_id[0 .. the number returned), in the order
  * the seats name them; 0: nothing is staged (no record, more than MCQ_RG_STAGE_QUERIES of them, a table beyond
  * MCQ_RG_STAGE_TABLES, or known hands only).  query_words: the records, four words each; seats at or above a record's
- * n_players are not read; a table with one entry is a known hand, which reads no table. */
+ * n_players are not read; a table with one entry is a known hand, which reads no table.  MAX_TABLES: the room of the
+ * kernel that asks (mcq_eval_ranges_hands_kernel keeps MCQ_RG_HANDS_STAGE_TABLES beside its table of hands). */
+template <uint32_t MAX_TABLES = MCQ_RG_STAGE_TABLES>
 MCQ_HD uint32_t mcq_ranges_stage_tables(const uint32_t *query_words, const uint32_t *seat_table, const uint32_t *cum,
-                                        uint32_t first, uint32_t nq, uint32_t *tab_id /* MCQ_RG_STAGE_TABLES entries */) {
+                                        uint32_t first, uint32_t nq, uint32_t *tab_id /* MAX_TABLES entries */) {
     uint32_t n_tab = 0;
     bool fits = nq <= MCQ_RG_STAGE_QUERIES;
     for (uint32_t j = 0; j < nq && fits; j++) {
@@ -44,7 +46,7 @@ MCQ_HD uint32_t mcq_ranges_stage_tables(const uint32_t *query_words, const uint3
             uint32_t k = 0;
             while (k < n_tab && tab_id[k] != t) k++;
             if (k < n_tab) continue;
-            if (n_tab == MCQ_RG_STAGE_TABLES) fits = false;
+            if (n_tab == MAX_TABLES) fits = false;
             else tab_id[n_tab++] = t;
         }
     }

@@ -34,7 +34,7 @@ import numpy as np
 from . import _lib
 from .cards import TYPES, card_id, card_str
 
-__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_range_equity_exact_weighted", "get_range_equities", "quantise_weight", "get_preflop_range_equity_exact", "get_preflop_range_equity_exact_weighted", "preflop_class_table", "get_runout_equities", "MonteCarlo", "seed",
+__all__ = ["get_equity", "get_pot_equity", "get_seat_equities", "get_seat_equities_exact", "get_equity_batch", "get_equity_exact", "get_range_equity_exact", "get_range_equity_exact_weighted", "get_range_equities", "get_range_hand_equities", "quantise_weight", "get_preflop_range_equity_exact", "get_preflop_range_equity_exact_weighted", "preflop_class_table", "get_runout_equities", "MonteCarlo", "seed",
            "configure", "get_equity_matrix", "matrix_equity"]
 
 _state = {"couple_numpy": False,
@@ -634,6 +634,36 @@ def get_range_equities(ranges, table_cards, runs=100000, *, engine=None):
     n = float(r["runs"])
     return ([(float(r["seat"][k]["win"]) / n, float(r["seat"][k]["tie"]) / n, float(share[k])) for k in range(len(ranges))],
             float(r["passes"]) / n)
+
+
+def get_range_hand_equities(ranges, table_cards, runs=100000, *, seat=0, engine=None):
+    """get_range_equities with the breakdown by hand of one seat (mcq_eval_batch_ranges_hands): which hands of the range
+    of seat `seat` carry its equity against these other ranges.  `ranges`, `table_cards`, `runs` and the seeding are those
+    of get_range_equities: the same seed gives the same iterations.
+    -> (seats, trials, per_hand): seats and trials as get_range_equities returns them, per_hand = {(card, card):
+    (frequency, win, tie, pot_share)} for the hands the seat held at least once, lower card id first: frequency is the
+    part of the iterations in which it held the hand; win, tie and pot_share are conditional on the hand."""
+    ranges = list(ranges)
+    tables, seat_table = _range_tables(ranges)
+    if not 0 <= int(seat) < len(ranges):
+        raise ValueError("seat %r: the seats are 0 .. %d" % (seat, len(ranges) - 1))
+    board = [card_id(c) for c in table_cards]
+    if len(board) > 5:
+        raise ValueError("table_cards holds more than five cards")
+    q = _lib.pack_query_one([0, 0], board, len(ranges), runs)
+    eng = engine or _lib.default_engine()
+    s, first = _take_ids(1)
+    rows, hands = eng.eval_batch_ranges_hands(q, seat_table, tables, s, first_query_id=first, seat=int(seat))
+    r, share, h = rows[0], _lib.seat_shares(rows)[0], hands[0]
+    n = float(r["runs"])
+    per_hand = {}
+    for i in np.flatnonzero(h["runs"]):
+        a, b = _ROW_HANDS[i]
+        k = float(h["runs"][i])
+        per_hand[(card_str(a), card_str(b))] = (k / n, float(h["win"][i]) / k, float(h["tie"][i]) / k,
+                                                float(h["share"][i]) / (_lib.SHARE_UNIT * k))
+    return ([(float(r["seat"][k]["win"]) / n, float(r["seat"][k]["tie"]) / n, float(share[k])) for k in range(len(ranges))],
+            float(r["passes"]) / n, per_hand)
 
 
 def get_range_equity_exact_weighted(hero, table_cards, opponent, ghost_cards='', engine=None, ties="credited"):
